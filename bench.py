@@ -7,7 +7,11 @@ buffers: the reference's __getitem__/collate_fn/H2D) → ResNet18(audio) ‖
 ResNet34(image) forward → fusion head → cross-entropy → backward → [RCCL all-reduce] → Adam,
 all in fp32 on the libtspm HIP kernels (graph-replayed).
 
-Prints ONE JSON line on rank 0 (contract in the task statement), including:
+A plain run (``--gpus N --steps K --warmup W``) sets up, warms up, times the K steps and prints ONE JSON line
+on rank 0 (metric, value, unit, higher_is_better, dtype, ms_per_step, ...).  ``--dump-outputs DIR`` also
+writes what the last timed step computed (loss, logits, a fixed sample of the updated parameters) as
+DIR/<name>.npy; inputs and weights are seeded, so two builds can be compared output for output.  ``--full``
+adds the secondary measurements, all after the timed region:
   roofline     — the conv implicit-GEMM kernel family (dominant: ~90 % of step FLOPs): valid-tap
                  FLOPs of every conv launch of one step ÷ the summed DEVICE duration of those kernels
                  (torch.profiler = rocprofiler timestamps) over replays of the step re-captured on one
@@ -411,6 +415,8 @@ def mmimdb_bench(args) -> None:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         el = t.item()
     value = args.steps * B * world / el
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, model, loss=st.eng.loss)
     fps = mmimdb_flops_per_sample()
     tf = fps * value / 1e12
     nparam = sum(p.numel() for p in model.parameters())
@@ -568,25 +574,26 @@ def input_stage_bench(args) -> None:
                        "unit": "GB/s", "frac": round(k["achieved_GBps"] / 8000.0, 4),
                        "traffic": pmc_traffic("gather")[0], "traffic_unit": "HBM bytes per 128-sample launch (PMC)",
                        "bytes_per_sample": INPUT_BYTES_PER_SAMPLE, "batch": 128}
-    # CPU baseline: the reference's host path on a bounded sample of files
-    from oracle import avmnist_data_ref as dref
-    torch.set_num_threads(1)
-    root = tempfile.mkdtemp(prefix="tspm_ref_corpus_")
-    m = args.cpu_input_samples
-    small = corpus.subset(range(m))
-    csv = dref.write_reference_files(root, small.audio, small.image, small.labels)
-    for _ in dref.reference_host_batches(csv, B, dev):  # warm-up: matplotlib / PIL / file cache
-        break
-    t0 = time.perf_counter()
-    cnt = 0
-    for b in dref.reference_host_batches(csv, B, dev):
-        cnt += b["labels"].numel()
-    torch.cuda.synchronize()
-    el = time.perf_counter() - t0
-    res["cpu_baseline"] = {"value": round(cnt / el, 1), "unit": "samples/sec", "cores": 1, "kind": "port",
-                           "sample": f"{cnt} samples in the reference file layout through the reference's "
-                                     f"per-sample host path (torch.load x2, cm.gist_earth, PIL convert L, "
-                                     f"ToDtype scale, mask, stack, .to(cuda)), batch {B}, 1 thread, {el:.1f}s"}
+    # CPU baseline (--full): the reference's host path on a bounded sample of files
+    if not args.no_cpu_baseline:
+        from oracle import avmnist_data_ref as dref
+        torch.set_num_threads(1)
+        root = tempfile.mkdtemp(prefix="tspm_ref_corpus_")
+        m = args.cpu_input_samples
+        small = corpus.subset(range(m))
+        csv = dref.write_reference_files(root, small.audio, small.image, small.labels)
+        for _ in dref.reference_host_batches(csv, B, dev):  # warm-up: matplotlib / PIL / file cache
+            break
+        t0 = time.perf_counter()
+        cnt = 0
+        for b in dref.reference_host_batches(csv, B, dev):
+            cnt += b["labels"].numel()
+        torch.cuda.synchronize()
+        el = time.perf_counter() - t0
+        res["cpu_baseline"] = {"value": round(cnt / el, 1), "unit": "samples/sec", "cores": 1, "kind": "port",
+                               "sample": f"{cnt} samples in the reference file layout through the reference's "
+                                         f"per-sample host path (torch.load x2, cm.gist_earth, PIL convert L, "
+                                         f"ToDtype scale, mask, stack, .to(cuda)), batch {B}, 1 thread, {el:.1f}s"}
     emit(res)
 
 
@@ -647,25 +654,27 @@ def eval_bench(args) -> None:
                         "achieved": round(tflops, 3), "peak": FP32_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
                         "frac": round(tflops / FP32_MFMA_PEAK_TFLOPS, 4), "traffic": None,
                         "valid_tap_flop_per_sample": valid}}
-    # whole epochs through the harness (metrics computed at the end of each)
-    opt = tspm_amd.FusedAdam(model.parameters(), lr=5e-4, weight_decay=1e-4)
-    runner = EpochRunner(model, opt, None)
-    vl = ds.device_loader(B)
-    runner.validate_epoch(vl)  # capture
-    t0 = time.perf_counter()
-    _, _, metrics, nb = runner.validate_epoch(vl)
-    el = time.perf_counter() - t0
-    res["validate_epoch"] = {"samples": len(ds), "batches": nb, "seconds": round(el, 4),
-                             "samples_per_s": round(len(ds) / el, 1), "accuracy_AI": float(metrics["accuracy_AI"])}
-    tr = AVMNIST(None, "train", "multimodal", selected_patterns=["ai"], corpus=synthetic_corpus(args.eval_corpus, 99),
-                 device=dev)
-    tl = tr.device_loader(B, shuffle=True, drop_last=True)
-    runner.train_epoch(tl)
-    t0 = time.perf_counter()
-    _, _, _, nb = runner.train_epoch(tl)
-    el = time.perf_counter() - t0
-    res["train_epoch"] = {"samples": nb * B, "batches": nb, "seconds": round(el, 4),
-                          "samples_per_s": round(nb * B / el, 1)}
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, loss=st.loss, logits=st.logits, preds=st.preds)
+    if args.full:  # whole epochs through the harness (metrics computed at the end of each)
+        opt = tspm_amd.FusedAdam(model.parameters(), lr=5e-4, weight_decay=1e-4)
+        runner = EpochRunner(model, opt, None)
+        vl = ds.device_loader(B)
+        runner.validate_epoch(vl)  # capture
+        t0 = time.perf_counter()
+        _, _, metrics, nb = runner.validate_epoch(vl)
+        el = time.perf_counter() - t0
+        res["validate_epoch"] = {"samples": len(ds), "batches": nb, "seconds": round(el, 4),
+                                 "samples_per_s": round(len(ds) / el, 1), "accuracy_AI": float(metrics["accuracy_AI"])}
+        tr = AVMNIST(None, "train", "multimodal", selected_patterns=["ai"],
+                     corpus=synthetic_corpus(args.eval_corpus, 99), device=dev)
+        tl = tr.device_loader(B, shuffle=True, drop_last=True)
+        runner.train_epoch(tl)
+        t0 = time.perf_counter()
+        _, _, _, nb = runner.train_epoch(tl)
+        el = time.perf_counter() - t0
+        res["train_epoch"] = {"samples": nb * B, "batches": nb, "seconds": round(el, 4),
+                              "samples_per_s": round(nb * B / el, 1)}
     if not args.no_cpu_baseline:
         from oracle import avmnist_eval_ref as eref
         from oracle import avmnist_ref as orc
@@ -726,6 +735,8 @@ def mono_bench(args) -> None:
     torch.cuda.synchronize()
     el = time.perf_counter() - t0
     value = args.steps * B / el
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, model, loss=st.loss, logits=st.logits)
     # roofline: device kernel durations of further graph replays (outside the timed region); the graph
     # is re-captured once with a recorder on the engine so every conv launch maps to its shape
     roof = None
@@ -852,6 +863,8 @@ def mosi_bench(args) -> None:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         el = t.item()
     value = args.steps * B * world / el
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, model, loss=st.eng.loss, logits=st.eng.logits)
     heights, C, Ft = netT.heights, netT.out_channels, netT.input_size
     conv_flops = sum(2 * B * (T - h + 1) * h * Ft * C for h in heights)  # valid MACs x 2, one launch per height
     roof = {"bound": "mfma", "kernel": "TextCNN convolutions: (h x 768) kernels over [B, T, 768] as implicit GEMM "
@@ -925,6 +938,30 @@ def mosi_bench(args) -> None:
         emit(res)
     if world > 1:
         dist.destroy_process_group()
+
+
+DUMP_PARAM_SAMPLE = 1 << 20  # parameters written by --dump-outputs (4 MB as float32)
+
+
+def dump_outputs(path: str, model=None, **tensors) -> None:
+    """--dump-outputs: what the timed path's last step left for its caller, as ``path/<name>.npy`` (float32
+    or float64): the step's output tensors and, for a train step, ``params_sample`` — the updated parameters
+    (all of them concatenated in ``model.parameters()`` order) at DUMP_PARAM_SAMPLE fixed positions drawn
+    with seed 0, or every parameter of a smaller model.  Call right after the timed region, before any
+    further step runs."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {}
+    for name, t in tensors.items():
+        t = t.detach()
+        arrays[name] = (t if t.dtype in (torch.float32, torch.float64) else t.double()).cpu().numpy()
+    if model is not None:
+        flat = torch.cat([p.detach().reshape(-1) for p in model.parameters()]).float().cpu().numpy()
+        if flat.size > DUMP_PARAM_SAMPLE:
+            flat = flat[np.sort(np.random.default_rng(0).integers(0, flat.size, DUMP_PARAM_SAMPLE))]
+        arrays["params_sample"] = flat
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def process_group_info():
@@ -1118,7 +1155,23 @@ def main() -> None:
     ap.add_argument("--kernel-table", default=None, help="write the per-launch conv durations (JSON) here")
     ap.add_argument("--dry-run", action="store_true",
                     help="multi-rank plumbing only (gloo, no GPU, empty step): launch, barriers, max over ranks")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary measurements after the timed steps: CPU baseline, conv roofline "
+                         "replays, DP exchange probe, PCIe-inclusive step (each still has its own switch)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the last step's outputs (loss, logits, a fixed sample of the "
+                         "updated parameters) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:
+        # a plain run does only what the headline figure needs: set up, warm up, time the steps, print the line
+        if args.kernel_table:
+            ap.error("--kernel-table needs --full (the table comes from the roofline replays)")
+        args.no_cpu_baseline = True
+        args.profile_steps = args.exchange_steps = args.pcie_steps = 0
+    if args.dump_outputs and (args.dry_run or args.input_stage):
+        ap.error("--dump-outputs: --dry-run and --input-stage run no step whose outputs could be written")
     check_world(args.gpus)
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         if args.input_stage or args.eval or args.mono:
@@ -1192,7 +1245,10 @@ def main() -> None:
         elapsed = t.item()
     ms_per_step = elapsed / args.steps * 1e3
     value = world * B * args.steps / elapsed
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, model, loss=step.loss, logits=step.logits)
 
+    # the exchange, roofline, PCIe and CPU legs below run with --full only (their step counts are 0 on a plain run)
     # ---- after the timed region: how much of the DP exchange the step hides (every rank) -----------
     exchange = None
     if isinstance(step.allreduce, ddp.PhasedGradAllReduce) and step.use_graph and args.exchange_steps > 0:
@@ -1277,7 +1333,9 @@ def main() -> None:
                         "under rocprofv3 kernel tracing); conv_ms_per_step = summed conv-kernel durations per step; "
                         "r34_3x3 = the ResNet34 3x3 launches of the same replays (single stream: exact launch "
                         "attribution)"}
-        if roof is not None:
+        if roof is None:
+            rl["timing"] = "not measured: the roofline replays run with --full (and --profile-steps > 0)"
+        else:
             ach = roof["achieved"]
             rl.update({"achieved": round(ach, 3), "frac": round(ach / FP32_MFMA_PEAK_TFLOPS, 4),
                        "conv_ms_per_step": round(roof["conv_kernel_ms_per_step"], 4),

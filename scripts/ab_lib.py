@@ -28,7 +28,7 @@ def main():
     ap.add_argument("rest", nargs=argparse.REMAINDER)
     a = ap.parse_args()
     rest = a.rest[1:] if a.rest and a.rest[0] == "--" else a.rest
-    base = ["--no-cpu-baseline", "--pcie-steps", "0", "--exchange-steps", "0"]
+    base = ["--full", "--no-cpu-baseline", "--pcie-steps", "0", "--exchange-steps", "0"]
     res = {"A": [], "B": []}
     lines = {"A": None, "B": None}
     for r in range(a.rounds):

@@ -82,8 +82,9 @@ def test_failing_rank_fails_the_launch():
 def test_gpus2_line_carries_roofline_cpu_baseline_and_exchange():
     """the N > 1 line has the same post-timed-region keys as N = 1 — roofline (rank 0
     profiles its local step), cpu_baseline (rank 0 while the other ranks sleep in a gloo barrier) and the
-    exchange block (per-phase host wait, exposed tail, local step time, RCCL world size)."""
-    p = _run(["--gpus", "2", "--dry-run", "--steps", "2", "--cpu-budget", "1", "--exchange-steps", "3"],
+    exchange block (per-phase host wait, exposed tail, local step time, RCCL world size).  These legs run
+    with ``--full``."""
+    p = _run(["--gpus", "2", "--dry-run", "--full", "--steps", "2", "--cpu-budget", "1", "--exchange-steps", "3"],
              timeout=300)
     assert p.returncode == 0, p.stderr[-3000:]
     res = _one_json(p.stdout)
@@ -95,3 +96,38 @@ def test_gpus2_line_carries_roofline_cpu_baseline_and_exchange():
     assert ex["rccl_world_size"] == 2 and ex["phases"] == 3 and ex["steps_probed"] == 3
     assert {"exposed_tail_ms_per_step", "host_wait_ms_per_step", "local_step_ms",
             "exchange_exposed_ms_per_step", "late_phase_window_ms_per_step"} <= set(ex)
+
+
+def test_plain_run_skips_the_secondary_legs():
+    """Without ``--full`` the line carries the headline only: no CPU baseline is timed even when a budget
+    is given, and the per-kernel table (it needs the roofline replays) is refused."""
+    p = _run(["--gpus", "1", "--dry-run", "--steps", "2", "--cpu-budget", "1"])
+    assert p.returncode == 0, p.stderr[-3000:]
+    res = _one_json(p.stdout)
+    assert res["steps"] == 2 and "cpu_baseline" not in res and res["exchange"] is None
+    p = _run(["--gpus", "1", "--dry-run", "--kernel-table", os.devnull])
+    assert p.returncode != 0 and "--full" in p.stderr
+
+
+def test_dump_outputs_writes_float_arrays(tmp_path, monkeypatch):
+    """``--dump-outputs``: every tensor lands as <name>.npy in float32 / float64 (integers widened), and
+    the parameters as the same seeded sample on every call."""
+    import numpy as np
+    import torch
+    import bench  # the repository root is on sys.path (tests/conftest.py)
+    torch.manual_seed(0)
+    model = torch.nn.Linear(7, 5)
+    logits = torch.randn(4, 5)
+    preds = torch.arange(4)
+    bench.dump_outputs(str(tmp_path / "a"), model, loss=torch.tensor([0.5]), logits=logits, preds=preds)
+    got = {f[:-4]: np.load(tmp_path / "a" / f) for f in sorted(os.listdir(tmp_path / "a"))}
+    assert sorted(got) == ["logits", "loss", "params_sample", "preds"]
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert np.array_equal(got["logits"], logits.numpy()) and np.array_equal(got["preds"], np.arange(4.0))
+    flat = torch.cat([p.detach().reshape(-1) for p in model.parameters()]).numpy()
+    assert np.array_equal(got["params_sample"], flat)  # smaller than the sample: all of it
+    monkeypatch.setattr(bench, "DUMP_PARAM_SAMPLE", 8)
+    bench.dump_outputs(str(tmp_path / "b"), model)
+    bench.dump_outputs(str(tmp_path / "c"), model)
+    b, c = np.load(tmp_path / "b" / "params_sample.npy"), np.load(tmp_path / "c" / "params_sample.npy")
+    assert b.shape == (8,) and np.array_equal(b, c) and np.isin(b, flat).all()
