@@ -46,8 +46,10 @@ enum {
  * and tspm_head_desc.adam_step; 21 = round 6: no mutable global state and no environment reads inside the library —
  * tspm_set_conv_lds_floor removed, the floor and the hand-off mode are per-call tspm_conv_algo fields, and the
  * head's row block is tspm_head_desc.rows_per_block); 22 = round 6: tspm_conv_algo.variant 4, the LDS-staged kernels with
- * every fp32 product formed from an exact three-piece bf16 split on the bf16 MFMA (same structs and entry points). */
-#define TSPM_ABI_VERSION 22
+ * every fp32 product formed from an exact three-piece bf16 split on the bf16 MFMA (same structs and entry points);
+ * 23 = tspm_mono_head_step, the monomodal pre-training head (classifier, cross-entropy, predictions, backward) in
+ * one launch. */
+#define TSPM_ABI_VERSION 23
 int tspm_abi_version(void);  /* returns TSPM_ABI_VERSION */
 /* Static string for a status code. */
 const char* tspm_status_string(int status);
@@ -795,6 +797,36 @@ int tspm_seq_gather(int32_t count, const int64_t* index, int64_t n_samples, cons
                     const int64_t* offsets, const int32_t* lengths, int32_t feat, int32_t steps_pad, float* out,
                     int64_t stride_t, int64_t stride_b, const float* row_mask, const int64_t* labels,
                     int64_t* labels_out, tspm_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Monomodal pre-training head (ABI 23) — train_monomodal.MonomodalEncoder's `classifier = nn.Linear(hid,
+ * classes)` forward, the loss group's weighted cross-entropy, the argmax(logits, 1) predictions
+ * (train_monomodal.py:236,394) and the Linear's whole backward in ONE launch, for the launch-bound MOSI / MOSEI
+ * encoder pre-training step ([128,64] x [64,3]).  Semantics of tspm_linear_fwd + tspm_cross_entropy +
+ * tspm_linear_bwd up to summation order: logits = emb w^T + b; loss[0] = loss_weight * mean CE;
+ * dlogits = (softmax - onehot)/n * loss_weight; dw = dlogits^T emb, db = column sums of dlogits,
+ * demb = dlogits w (all overwritten); an out-of-range label gives NaN loss and gradients (no out-of-bounds read).
+ * One workgroup walks the rows in chunks of 64 with the embeddings staged in LDS and reduces in a fixed order:
+ * no atomics, no workspace, two runs on the same input are bitwise equal; forward-only mode (dw, db and demb all
+ * NULL) gives bitwise the training mode's logits, loss and preds.
+ * Limits: 1 <= n <= 1024; hid <= 128 and a multiple of 4; classes <= 16; ld_emb, ld_demb >= hid and multiples of
+ * 4 with emb / demb 16-byte aligned; dw, db, demb all given or all NULL; otherwise TSPM_ERR_INVALID. */
+typedef struct tspm_mono_head_desc {
+  int32_t n, hid, classes, ld_emb, ld_demb;
+  float loss_weight;     /* the cross-entropy term's weight (tspm_cross_entropy's grad_scale) */
+  const float* emb;      /* [n, ld_emb] */
+  const float* w;        /* [classes, hid] */
+  const float* b;        /* [classes] */
+  const int64_t* labels; /* [n] */
+  float* logits;         /* [n, classes] */
+  float* loss;           /* loss[0] */
+  int64_t* preds;        /* nullable: first maximum of the logits (TSPM_ARGMAX_LOGITS) */
+  float* dw;             /* [classes, hid] */
+  float* db;             /* [classes] */
+  float* demb;           /* [n, ld_demb] */
+  float* stats;          /* nullable: the three accumulators of tspm_cross_entropy */
+} tspm_mono_head_desc;
+int tspm_mono_head_step(const tspm_mono_head_desc* desc, tspm_stream_t stream);
 
 #ifdef __cplusplus
 }

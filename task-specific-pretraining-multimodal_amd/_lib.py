@@ -17,7 +17,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("TSPM_LIB", os.path.join(_HERE, "libtspm.so"))
-ABI_VERSION = 22
+ABI_VERSION = 23
 COUNTER_BYTES = 65536     # TSPM_COUNTER_BYTES: arrival-counter header of a split wgrad workspace
 
 
@@ -121,6 +121,12 @@ class LstmBwdDesc(Structure):
     """tspm_lstm_bwd_desc (ABI 12; argmax ABI 14)."""
     _fields_ = [(n, c_int32) for n in ("batch", "steps", "hidden", "ld_dh")] + \
         [(n, c_void_p) for n in ("w_hh", "gates", "cs", "dh", "dgates", "argmax")]
+
+
+class MonoHeadDesc(Structure):
+    """tspm_mono_head_desc (ABI 23): the monomodal head (classifier, CE, predictions, backward) in one launch."""
+    _fields_ = [(n, c_int32) for n in ("n", "hid", "classes", "ld_emb", "ld_demb")] + [("loss_weight", c_float)] + \
+        [(n, c_void_p) for n in ("emb", "w", "b", "labels", "logits", "loss", "preds", "dw", "db", "demb", "stats")]
 
 
 _SIGS = {
@@ -240,6 +246,8 @@ _SIGS = {
     "tspm_grad_clip_coef": (c_int32, [c_int64, _P, c_float, c_float, _P, _P, _P, c_size_t, _P]),
     "tspm_seq_gather": (c_int32, [c_int32, _P, c_int64, _P, _P, _P, c_int32, c_int32, _P, c_int64, c_int64, _P, _P, _P,
                                   _P]),
+    # ABI 23: the monomodal pre-training head in one launch
+    "tspm_mono_head_step": (c_int32, [POINTER(MonoHeadDesc), _P]),
 }
 
 EXPORTED = tuple(_SIGS)

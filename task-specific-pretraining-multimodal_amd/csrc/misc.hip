@@ -1161,3 +1161,147 @@ extern "C" int tspm_head_train_step(const tspm_head_desc* desc, tspm_stream_t st
   TSPM_LAUNCH_CHECK();
   return TSPM_OK;
 }
+
+// ------------------------------------------------------------------------------------------------
+// Monomodal head step (ABI 23): classifier Linear forward, weighted cross-entropy, argmax(logits) and the
+// Linear's whole backward in ONE launch of ONE workgroup.  The problem is launch-bound ([128,64] x [64,3] at
+// the MOSI shapes), so the rows are not spread over workgroups: the workgroup walks the batch in chunks of
+// MH_ROWS rows with the chunk's embeddings staged in LDS, every thread keeps its dw elements in registers
+// across the chunks, and every sum runs in a fixed order (no atomics, no workspace) — two runs are bitwise equal.
+// ------------------------------------------------------------------------------------------------
+namespace {
+constexpr int MH_THREADS = 256, MH_ROWS = 64, MH_MAXH = 128, MH_MAXC = 16, MH_MAXN = 1024;
+constexpr int MH_LDE = MH_MAXH + 4;                      // LDS row stride of emb / w (16-byte rows, bank offset 4)
+constexpr int MH_LDL = MH_MAXC + 1;                      // LDS row stride of the chunk's logits / dlogits
+constexpr int MH_ACC = MH_MAXH * MH_MAXC / MH_THREADS;   // dw elements per thread (8)
+
+__global__ __launch_bounds__(MH_THREADS) void k_mono_head(tspm_mono_head_desc d) {
+  __shared__ __attribute__((aligned(16))) float emb_s[MH_ROWS * MH_LDE];
+  __shared__ __attribute__((aligned(16))) float w_s[MH_MAXC * MH_LDE];
+  __shared__ float b_s[MH_MAXC];
+  __shared__ float z_s[MH_ROWS * MH_LDL];
+  const int t = threadIdx.x, N = d.n, H = d.hid, K = d.classes, H4 = H >> 2;
+  const bool train = d.dw != nullptr;
+  for (int e = t; e < K * H; e += MH_THREADS) w_s[(e / H) * MH_LDE + e % H] = d.w[e];
+  if (t < K) b_s[t] = d.b[t];
+  float acc[MH_ACC];
+#pragma unroll
+  for (int u = 0; u < MH_ACC; ++u) acc[u] = 0.f;
+  float dbacc = 0.f;     // thread c < K: db[c]
+  double lsum = 0.0;     // thread r < MH_ROWS: CE of rows r, r + MH_ROWS, ...
+  int correct = 0;
+  const float invn = 1.0f / (float)N;
+  for (int r0 = 0; r0 < N; r0 += MH_ROWS) {
+    const int rows = min(MH_ROWS, N - r0);
+    __syncthreads();  // the previous chunk's readers are done (and w_s / b_s are written)
+    for (int i = t; i < rows * H4; i += MH_THREADS) {
+      const int r = i / H4, j = (i % H4) * 4;
+      st4(emb_s + r * MH_LDE + j, ld4(d.emb + (long long)(r0 + r) * d.ld_emb + j));
+    }
+    __syncthreads();
+    // logits of the chunk: one (row, class) dot product per thread and pass
+    for (int p = t; p < rows * K; p += MH_THREADS) {
+      const int r = p / K, c = p % K;
+      const float* er = emb_s + r * MH_LDE;
+      const float* wr = w_s + c * MH_LDE;
+      float s = 0.f;
+      for (int j = 0; j < H; j += 4) {
+        const f32x4 a = ld4(er + j), b = ld4(wr + j);
+        s += a[0] * b[0];
+        s += a[1] * b[1];
+        s += a[2] * b[2];
+        s += a[3] * b[3];
+      }
+      s += b_s[c];
+      z_s[r * MH_LDL + c] = s;
+      d.logits[(long long)(r0 + r) * K + c] = s;
+    }
+    __syncthreads();
+    // softmax / CE / argmax per row (k_cross_entropy's arithmetic); dlogits overwrite the row's logits in LDS
+    if (t < rows) {
+      float* z = z_s + t * MH_LDL;
+      float mx = z[0];
+      int am = 0;
+      for (int k = 1; k < K; ++k)
+        if (z[k] > mx) { mx = z[k]; am = k; }
+      float se = 0.f;
+      for (int k = 0; k < K; ++k) se += expf(z[k] - mx);
+      const float lse = logf(se);
+      const long long lab64 = d.labels[r0 + t];
+      const bool lok = lab64 >= 0 && lab64 < K;  // out-of-range label: NaN loss / gradients, no out-of-bounds read
+      const int lab = lok ? (int)lab64 : 0;
+      lsum += lok ? (double)(lse - (z[lab] - mx)) : (double)__builtin_nanf("");
+      correct += (am == lab) ? 1 : 0;
+      if (d.preds) d.preds[r0 + t] = am;
+      if (train)
+        for (int k = 0; k < K; ++k) {
+          const float pk = expf(z[k] - mx) / se;
+          z[k] = lok ? (pk - (k == lab ? 1.f : 0.f)) * invn * d.loss_weight : __builtin_nanf("");
+        }
+    }
+    if (!train) continue;  // uniform: forward only
+    __syncthreads();
+    // demb = dlogits @ w for the chunk's rows
+    for (int i = t; i < rows * H4; i += MH_THREADS) {
+      const int r = i / H4, j = (i % H4) * 4;
+      f32x4 s = {0.f, 0.f, 0.f, 0.f};
+      for (int c = 0; c < K; ++c) s += z_s[r * MH_LDL + c] * ld4(w_s + c * MH_LDE + j);
+      st4(d.demb + (long long)(r0 + r) * d.ld_demb + j, s);
+    }
+    // dw[c][j] += sum_r dlogits[r][c] emb[r][j] (rows in order), db[c] += sum_r dlogits[r][c]
+#pragma unroll
+    for (int u = 0; u < MH_ACC; ++u) {
+      const int e = t + u * MH_THREADS;
+      if (e < K * H) {
+        const int c = e / H, j = e % H;
+        float s = acc[u];
+        for (int r = 0; r < rows; ++r) s += z_s[r * MH_LDL + c] * emb_s[r * MH_LDE + j];
+        acc[u] = s;
+      }
+    }
+    if (t < K)
+      for (int r = 0; r < rows; ++r) dbacc += z_s[r * MH_LDL + t];
+  }
+  if (train) {
+#pragma unroll
+    for (int u = 0; u < MH_ACC; ++u) {
+      const int e = t + u * MH_THREADS;
+      if (e < K * H) d.dw[e] = acc[u];
+    }
+    if (t < K) d.db[t] = dbacc;
+  }
+  if (t < 64) {  // wave 0 holds every row's loss (MH_ROWS == 64): xor butterfly, the same order in every run
+    static_assert(MH_ROWS == 64, "the loss reduction is one wave");
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      lsum += __shfl_xor(lsum, o, 64);
+      correct += __shfl_xor(correct, o, 64);
+    }
+    if (t == 0) {
+      d.loss[0] = (float)(lsum / (double)N) * d.loss_weight;
+      if (d.stats) {
+        d.stats[0] += (float)lsum;
+        d.stats[1] += (float)correct;
+        d.stats[2] += (float)N;
+      }
+    }
+  }
+}
+}  // namespace
+
+extern "C" int tspm_mono_head_step(const tspm_mono_head_desc* desc, tspm_stream_t stream) {
+  if (!desc) return TSPM_ERR_INVALID;
+  const tspm_mono_head_desc& d = *desc;
+  if (d.n < 1 || d.n > MH_MAXN || d.hid < 4 || d.hid > MH_MAXH || d.hid % 4 || d.classes < 1 || d.classes > MH_MAXC)
+    return TSPM_ERR_INVALID;
+  if (!d.emb || !d.w || !d.b || !d.labels || !d.logits || !d.loss) return TSPM_ERR_INVALID;
+  if (d.ld_emb < d.hid || d.ld_emb % 4 || !aligned16(d.emb)) return TSPM_ERR_INVALID;
+  const bool train = d.dw || d.db || d.demb;
+  if (train) {  // the whole backward or none of it
+    if (!d.dw || !d.db || !d.demb) return TSPM_ERR_INVALID;
+    if (d.ld_demb < d.hid || d.ld_demb % 4 || !aligned16(d.demb)) return TSPM_ERR_INVALID;
+  }
+  hipLaunchKernelGGL(k_mono_head, dim3(1), dim3(MH_THREADS), 0, static_cast<hipStream_t>(stream), d);
+  TSPM_LAUNCH_CHECK();
+  return TSPM_OK;
+}

@@ -14,12 +14,19 @@ pretrained late-fusion config loads (train_monomodal.py:789-802, train_multimoda
   classifier → cross-entropy → classifier backward → encoder backward → FusedAdam, with the
   ``argmax(logits, 1)`` predictions written on the device (``tspm_classify_update_ex``, logits mode).
 * :class:`FusedMonoEvalStep` — ``validation_step`` as one HIP graph (eval-mode BatchNorm).
+* :class:`FusedMosiMonoStep` / :class:`FusedMosiMonoEvalStep` — the same two steps around a MOSI / MOSEI
+  encoder (``mosi.LSTMEncoder`` "last" / "maxpool", ``mosi.TextCNN``; the reference's ``configs/mosi/mono/``
+  pre-training): encoder forward (``mosi.MosiEncoderEngine``) → ``tspm_mono_head_step`` (classifier, CE,
+  predictions and the classifier's backward in one launch; ``fused_head=False`` keeps the four separate
+  launches) → encoder backward → FusedAdam.  Learning rate, weight decay and batch size are the caller's
+  optimizer and loader arguments.
 * :func:`select_modality_key` — the reference's choice of the batch key (train_monomodal.py:103-128).
 * :class:`MonoEpochRunner` / :func:`fit_monomodal` — the epoch loop of ``train_monomodal``
   (train_monomodal.py:536-884) on those steps, one host read per epoch.
 """
 from __future__ import annotations
 
+import ctypes
 import math
 import os
 import time
@@ -38,8 +45,13 @@ from .optim import FusedAdam
 from .step import _ce_weight, shared_batches_tracked
 
 ARGMAX_LOGITS = 1  # TSPM_ARGMAX_LOGITS (include/tspm.h)
-# keys train_monomodal.py:110-112 never treats as a modality (+ this package's device pattern index)
-_RESERVED = ("labels", "label", "genres", "imdb_ids", "pattern_name", "missing_masks", "sample_idx", "pattern_ids")
+# keys train_monomodal.py:110-112 never treats as a modality (+ this package's device pattern index
+# and mosi_data's loader bookkeeping)
+_RESERVED = ("labels", "label", "genres", "imdb_ids", "pattern_name", "missing_masks", "sample_idx", "pattern_ids",
+             "steps", "time_major", "pattern_names")
+# MonomodalEncoder(fused_head=...) default for MOSI encoders: tspm_mono_head_step against the four separate launches,
+# graph-replayed at B=128, T=50 (scripts/bench_mosi_mono.py, profiles/mosi_mono_head_ab.json)
+FUSED_HEAD_DEFAULT = True
 
 
 def _exp_name(config) -> str:
@@ -140,15 +152,16 @@ class _LinearFn(torch.autograd.Function):
 class _MonoBuffers:
     """Static device buffers + graph bookkeeping shared by the fused train and eval steps."""
 
-    def _init_buffers(self, model, x_shape: Tuple[int, ...], log) -> None:
+    def _init_buffers(self, model, x_shape: Tuple[int, ...], log, batch: Optional[int] = None) -> None:
         enc, cls = model.encoder, model.classifier
         self.model, self.log = model, log
         dev = next(model.parameters()).device
         self.device = dev
-        self.N = int(x_shape[0])
+        self.N = int(x_shape[0] if batch is None else batch)  # batch: the input buffer is time-major [T, B, F]
         self.hid, self.K = cls.in_features, cls.out_features
-        if self.hid != enc.hidden_dim:
-            raise L.TspmError(f"classifier input {self.hid} != encoder hidden_dim {enc.hidden_dim}")
+        hidden = enc.hidden_dim if hasattr(enc, "hidden_dim") else enc.hidden_size
+        if self.hid != hidden:
+            raise L.TspmError(f"classifier input {self.hid} != encoder hidden_dim {hidden}")
         f32 = dict(device=dev, dtype=torch.float32)
         self.X = torch.zeros(x_shape, **f32)
         self.labels = torch.zeros(self.N, dtype=torch.int64, device=dev)
@@ -295,19 +308,228 @@ class FusedMonoEvalStep(_MonoBuffers):
         return {"loss": self.loss, "logits": self.logits, "preds": self.preds}
 
 
+class _MosiMonoBuffers(_MonoBuffers):
+    """What the MOSI-encoder train and eval steps share: the single-encoder engine on the step's time-major
+    input buffer, and the head — ``tspm_mono_head_step`` or the separate launches."""
+
+    def _init_mosi(self, model, x_shape, log, fused_head: Optional[bool]) -> None:
+        from .mosi import MosiEncoderEngine
+        b, t, f = (int(v) for v in x_shape)
+        if f != model.encoder.input_size:
+            raise L.TspmError(f"input features {f} != encoder input_size {model.encoder.input_size}")
+        self._init_buffers(model, (t, b, f), log, batch=b)
+        self.T = t
+        self.fused_head = bool(model.fused_head if fused_head is None else fused_head)
+        self.eng = MosiEncoderEngine(model.encoder, b, t, self.device, seed=model._rng_seed, x=self.X, emb=self.emb)
+        self.demb = self.eng.demb
+        model._by_buffer[self.X.data_ptr()] = self
+
+    @property
+    def keep_override(self):
+        return self.eng.keep_override
+
+    @keep_override.setter
+    def keep_override(self, v):
+        self.eng.keep_override = v
+
+    def load_batch(self, x: torch.Tensor, labels: torch.Tensor) -> None:
+        """x: a batch-first [B, T, F] batch (one tspm_seq_gather into the time-major buffer), or the step's own
+        input buffer (mosi_data.MOSI.device_loader(step_for=...) gathered into it: no copy)."""
+        if x.data_ptr() != self.X.data_ptr():
+            self.eng.load(x)
+        if labels.data_ptr() != self.labels.data_ptr():
+            self.labels.copy_(labels.reshape(-1), non_blocking=True)
+
+    def _head(self, lib, sh: int, train: bool) -> None:
+        n, hid, K = self.N, self.hid, self.K
+        cls = self.model.classifier
+        if self.fused_head:
+            d = L.MonoHeadDesc()
+            d.n, d.hid, d.classes, d.ld_emb, d.ld_demb, d.loss_weight = n, hid, K, hid, hid, self.ce_weight
+            d.emb, d.w, d.b = self.emb.data_ptr(), cls.weight.data_ptr(), cls.bias.data_ptr()
+            d.labels, d.logits, d.loss = self.labels.data_ptr(), self.logits.data_ptr(), self.loss.data_ptr()
+            d.preds = self.preds.data_ptr()
+            if train:
+                d.dw, d.db, d.demb = cls.weight.grad.data_ptr(), cls.bias.grad.data_ptr(), self.demb.data_ptr()
+                d.stats = self.stats.data_ptr()
+            L.check(lib.tspm_mono_head_step(ctypes.byref(d), sh), "mono_head_step")
+            if self.log is not None:  # the epoch's confusion counts and loss log
+                self._classify(lib, sh)
+            return
+        L.check(lib.tspm_linear_fwd(n, hid, K, self.emb.data_ptr(), hid, cls.weight.data_ptr(), cls.bias.data_ptr(), 0,
+                                    None, 1.0, self.logits.data_ptr(), K, sh), "classifier fwd")
+        L.check(lib.tspm_cross_entropy(n, K, self.logits.data_ptr(), self.labels.data_ptr(), self.loss.data_ptr(),
+                                       self.dlogits.data_ptr() if train else None, self.ce_weight,
+                                       self.stats.data_ptr() if train else None, sh), "cross_entropy")
+        self._classify(lib, sh)
+        if train:
+            linear_bwd(n, hid, K, self.emb.data_ptr(), hid, self.dlogits.data_ptr(), K, cls.weight.data_ptr(),
+                       cls.weight.grad.data_ptr(), cls.bias.grad.data_ptr(), self.demb.data_ptr(), hid, sh)
+
+    def matches_shape(self, x: torch.Tensor) -> bool:
+        return x.data_ptr() == self.X.data_ptr() or tuple(x.shape) == (self.N, self.T, self.X.shape[2])
+
+
+class FusedMosiMonoStep(_MosiMonoBuffers):
+    """MonomodalEncoder.train_step around a MOSI encoder as one HIP graph:
+
+        encoder fwd → tspm_mono_head_step (classifier, CE, argmax, classifier bwd) → encoder bwd → FusedAdam
+
+    ``x_shape`` is the batch-first (B, T, F).  Gradients go straight into FusedAdam's flat views (overwritten);
+    no gradient clip (MonomodalEncoder.train_step has none).  The TextCNN's dropout masks are drawn by
+    ``tspm_dropout_mask`` on the optimizer's step counter (``keep_override = {"text": mask}`` injects one).  First
+    call eager, second captures, later calls replay."""
+
+    def __init__(self, model, optimizer: FusedAdam, loss_functions, x_shape, use_graph: bool = True, log=None,
+                 fused_head: Optional[bool] = None):
+        self.ce_weight = _ce_weight(loss_functions)
+        if self.ce_weight is None:
+            raise L.TspmError("FusedMosiMonoStep: the loss group must be a single cross-entropy term")
+        if not isinstance(optimizer, FusedAdam):
+            raise L.TspmError("FusedMosiMonoStep needs tspm_amd.FusedAdam")
+        model.train()
+        for p in model.parameters():
+            if p.requires_grad and p.grad is None:
+                raise L.TspmError("FusedMosiMonoStep: parameter without a FusedAdam gradient view")
+        self._init_mosi(model, x_shape, log, fused_head)
+        self.opt = optimizer
+        self.use_graph = use_graph and not os.environ.get("TSPM_NO_GRAPH")
+        self.eng.rng_ctr_ptr = optimizer.flat_groups()[0].hyper.data_ptr() + L.HYPER_STEP_OFFSET
+        f32 = dict(device=self.device, dtype=torch.float32)
+        self.dlogits = torch.empty(self.N, self.K, **f32)
+        self.stats = torch.zeros(4, **f32)
+        self._sig = (id(optimizer), id(loss_functions), self.fused_head)
+
+    def matches(self, x: torch.Tensor, optimizer, loss_functions, fused_head: Optional[bool] = None) -> bool:
+        fh = bool(self.model.fused_head if fused_head is None else fused_head)
+        return self._sig == (id(optimizer), id(loss_functions), fh) and self.matches_shape(x)
+
+    def _enqueue(self) -> None:
+        lib = L.lib()
+        sh = torch.cuda.current_stream().cuda_stream
+        self.eng.forward(sh, True)
+        self._head(lib, sh, True)
+        self.eng.backward(sh)
+        self.opt.launch(sh)
+
+    def run(self) -> None:
+        """One training step on the batch in the static input buffers."""
+        self.model.train()
+        self.opt.sync_hyper()
+        self.eng.apply_keep_override()
+        self._replay_or_enqueue()
+        self.opt.note_steps(1)
+
+    def step(self, x: torch.Tensor, labels: torch.Tensor) -> Dict[str, torch.Tensor]:
+        self.load_batch(x, labels)
+        self.run()
+        return {"loss": self.loss, "logits": self.logits, "preds": self.preds}
+
+
+class FusedMosiMonoEvalStep(_MosiMonoBuffers):
+    """MonomodalEncoder.validation_step around a MOSI encoder as one HIP graph: eval-mode encoder forward (no
+    dropout) and the head in forward-only mode (logits, weighted CE, argmax)."""
+
+    def __init__(self, model, loss_functions, x_shape, log=None, use_graph: bool = True,
+                 fused_head: Optional[bool] = None):
+        self.ce_weight = _ce_weight(loss_functions)
+        if self.ce_weight is None:
+            raise L.TspmError("FusedMosiMonoEvalStep: the loss group must be a single cross-entropy term")
+        self._init_mosi(model, x_shape, log, fused_head)
+        self.use_graph = use_graph and not os.environ.get("TSPM_NO_GRAPH")
+
+    def _enqueue(self) -> None:
+        sh = torch.cuda.current_stream().cuda_stream
+        self.eng.forward(sh, False)
+        self._head(L.lib(), sh, False)
+
+    def run(self) -> None:
+        self.model.eval()
+        self._replay_or_enqueue()
+
+    def step(self, x: torch.Tensor, labels: torch.Tensor) -> Dict[str, torch.Tensor]:
+        self.load_batch(x, labels)
+        self.run()
+        return {"loss": self.loss, "logits": self.logits, "preds": self.preds}
+
+
+class _MosiMonoFn(torch.autograd.Function):
+    """MonomodalEncoder.forward around a MOSI encoder as one autograd node (encoder + classifier on the HIP
+    schedule, forward and backward), for the reference's own train_step sequence with a torch optimizer."""
+
+    @staticmethod
+    def forward(ctx, x, model: "MonomodalEncoder", *params):
+        eng = model._mosi_engine(x.shape[0], x.shape[1], x.device)
+        eng.load(x)
+        eng.apply_keep_override()
+        sh = L.stream_handle()
+        eng.forward(sh, True)
+        cls = model.classifier
+        n, hid, K = x.shape[0], cls.in_features, cls.out_features
+        logits = torch.empty(n, K, device=x.device, dtype=torch.float32)
+        L.check(L.lib().tspm_linear_fwd(n, hid, K, eng.emb.data_ptr(), hid, cls.weight.data_ptr(), cls.bias.data_ptr(),
+                                        0, None, 1.0, logits.data_ptr(), K, sh), "classifier fwd")
+        model._fwd_generation += 1
+        ctx.model, ctx.eng, ctx.gen = model, eng, model._fwd_generation
+        return logits
+
+    @staticmethod
+    def backward(ctx, g):
+        model, eng = ctx.model, ctx.eng
+        if model._fwd_generation != ctx.gen:
+            raise L.TspmError("MonomodalEncoder: another training forward ran before this backward")
+        g = g.contiguous().float()
+        grads = {id(p): torch.empty_like(p) for p in model.parameters()}
+        cls, sh = model.classifier, L.stream_handle()
+        n, hid, K = g.shape[0], cls.in_features, cls.out_features
+        linear_bwd(n, hid, K, eng.emb.data_ptr(), hid, g.data_ptr(), K, cls.weight.data_ptr(),
+                   grads[id(cls.weight)].data_ptr(), grads[id(cls.bias)].data_ptr(), eng.demb.data_ptr(), hid, sh)
+        eng.grad_of = lambda p: grads[id(p)]  # noqa: E731
+        try:
+            eng.backward(sh)
+        finally:
+            eng.grad_of = lambda p: p.grad  # noqa: E731
+        return (None, None, *[grads[id(p)] for p in model.parameters()])
+
+
 class MonomodalEncoder(nn.Module):
     """train_monomodal.py:64-95 drop-in: ``encoder`` + ``classifier``, executed on libtspm."""
 
-    def __init__(self, encoder: nn.Module, output_dim: int, num_classes: int):
+    def __init__(self, encoder: nn.Module, output_dim: int, num_classes: int, fused_head: bool = FUSED_HEAD_DEFAULT):
         super().__init__()
         self.encoder = encoder
         self.classifier = nn.Linear(output_dim, num_classes)
         self._fused: Optional[FusedMonoStep] = None
         self._eval_steps: Dict[Tuple, FusedMonoEvalStep] = {}
+        # MOSI / MOSEI encoders (mosi.LSTMEncoder / mosi.TextCNN): the head in one launch (tspm_mono_head_step)
+        # or, fused_head=False, the separate classifier / CE / classify / classifier-backward launches
+        self.fused_head = bool(fused_head)
+        self._rng_seed = int(torch.initial_seed()) & ((1 << 63) - 1)  # the TextCNN dropout masks' seed
+        self._mosi_engines: Dict[Tuple, Any] = {}
+        self._by_buffer: Dict[int, Any] = {}  # input buffer address -> the MOSI step that owns it
+        self._fwd_generation = 0
+
+    def _apply(self, fn, *args, **kwargs):
+        out = super()._apply(fn, *args, **kwargs)
+        self._mosi_engines = {}
+        return out
+
+    def _mosi_engine(self, b: int, t: int, device):
+        from .mosi import MosiEncoderEngine
+        key = (int(b), int(t), device)
+        eng = self._mosi_engines.get(key)
+        if eng is None:
+            eng = self._mosi_engines[key] = MosiEncoderEngine(self.encoder, b, t, device, seed=self._rng_seed)
+        return eng
 
     def forward(self, x):
         if isinstance(x, list):
             x = torch.stack(x)
+        if self._mosi_encoder() and self.training and torch.is_grad_enabled():
+            x = x.float()
+            if not x.is_cuda:
+                raise L.TspmError("MonomodalEncoder (tspm_amd) runs on the MI355X only (there is no CPU fallback)")
+            return _MosiMonoFn.apply(x, self, *self.parameters())
         encoded = self.encoder(x)
         if encoded.dim() > 2:  # train_monomodal.py:83-86
             encoded = encoded.reshape(encoded.shape[0], -1)
@@ -330,11 +552,20 @@ class MonomodalEncoder(nn.Module):
         from .modules import ResNetEncoder
         return isinstance(self.encoder, ResNetEncoder)
 
+    def _mosi_encoder(self) -> bool:
+        from .mosi import LSTMEncoder, TextCNN
+        return isinstance(self.encoder, (LSTMEncoder, TextCNN))
+
     def train_step_fused(self, x: torch.Tensor, labels: torch.Tensor, optimizer, loss_functions,
                          log: Optional[ClassificationLog] = None) -> FusedMonoStep:
         """Run one fused step on device tensors and return the step (its loss / logits / preds buffers)."""
         if self._fused is None or not self._fused.matches(x, optimizer, loss_functions):
-            self._fused = FusedMonoStep(self, optimizer, loss_functions, tuple(x.shape))
+            own = self._by_buffer.get(x.data_ptr())
+            if self._mosi_encoder():
+                self._fused = own if isinstance(own, FusedMosiMonoStep) and own.matches(x, optimizer, loss_functions) \
+                    else FusedMosiMonoStep(self, optimizer, loss_functions, tuple(x.shape))
+            else:
+                self._fused = FusedMonoStep(self, optimizer, loss_functions, tuple(x.shape))
         self._fused.log = log
         self._fused.step(x, labels)
         return self._fused
@@ -342,11 +573,21 @@ class MonomodalEncoder(nn.Module):
     def eval_step_for(self, loss_functions, x_shape, log=None) -> FusedMonoEvalStep:
         key = tuple(x_shape)
         st = self._eval_steps.get(key)
-        if st is None or st.ce_weight != _ce_weight(loss_functions):
-            st = FusedMonoEvalStep(self, loss_functions, key, log)
+        if st is None or st.ce_weight != _ce_weight(loss_functions) or \
+                getattr(st, "fused_head", self.fused_head) != self.fused_head:
+            cls = FusedMosiMonoEvalStep if self._mosi_encoder() else FusedMonoEvalStep
+            st = cls(self, loss_functions, key, log)
             self._eval_steps[key] = st
         st.log = log
         return st
+
+    def _eval_step_of(self, x: torch.Tensor, loss_functions, log=None):
+        """The eval step for batch x: the step whose input buffer x is (a loader gathered into it), else by shape."""
+        own = self._by_buffer.get(x.data_ptr())
+        if isinstance(own, FusedMosiMonoEvalStep) and own.ce_weight == _ce_weight(loss_functions):
+            own.log = log
+            return own
+        return self.eval_step_for(loss_functions, tuple(x.shape), log)
 
     def train_step(self, batch, optimizer, loss_functions, device, metric_recorder, config=None, **kwargs):
         """train_monomodal.py:97-260.  Fused HIP graph with FusedAdam and the single cross-entropy loss
@@ -354,8 +595,8 @@ class MonomodalEncoder(nn.Module):
         key, x, labels = self._inputs(batch, config, device)
         dlog = _device_log(metric_recorder)
         fused = (not os.environ.get("TSPM_DISABLE_FUSED_STEP") and isinstance(optimizer, FusedAdam)
-                 and self._hip_encoder() and _ce_weight(loss_functions) is not None and x.is_cuda
-                 and labels.dim() == 1 and x.dim() in (3, 4))
+                 and _ce_weight(loss_functions) is not None and x.is_cuda and labels.dim() == 1
+                 and ((self._hip_encoder() and x.dim() in (3, 4)) or (self._mosi_encoder() and x.dim() == 3)))
         if fused:
             st = self.train_step_fused(x, labels, optimizer, loss_functions, dlog)
             loss_t, preds = st.loss, st.preds
@@ -374,9 +615,9 @@ class MonomodalEncoder(nn.Module):
         with torch.no_grad():
             key, x, labels = self._inputs(batch, config, device)
             dlog = _device_log(metric_recorder)
-            if (not self.training and self._hip_encoder() and _ce_weight(loss_functions) is not None and x.is_cuda
-                    and labels.dim() == 1 and x.dim() in (3, 4)):
-                st = self.eval_step_for(loss_functions, tuple(x.shape), dlog)
+            if (not self.training and _ce_weight(loss_functions) is not None and x.is_cuda and labels.dim() == 1
+                    and ((self._hip_encoder() and x.dim() in (3, 4)) or (self._mosi_encoder() and x.dim() == 3))):
+                st = self._eval_step_of(x, loss_functions, dlog)
                 st.step(x, labels)
                 loss_t, preds = st.loss, st.preds
             else:
@@ -429,6 +670,25 @@ class MonoEpochRunner:
         self.log: Optional[ClassificationLog] = None
         self.recorder: Optional[DeviceMetricRecorder] = None
         self.train_steps: Dict[Tuple, FusedMonoStep] = {}
+        self._mosi = model._mosi_encoder()
+
+    # MOSI encoders: ``mosi_data.MOSI.loader(...)``'s ``step_for`` hooks — the loader gathers each batch time-major
+    # straight into the step's input buffer (set on every loader that has the attribute, as harness.MosiHarness does)
+    def train_step_for(self, b: int, t: int):
+        shape = (int(b), int(t), int(self.model.encoder.input_size))
+        st = self.train_steps.get(shape)
+        if st is None or (self._mosi and st.fused_head != self.model.fused_head):
+            cls = FusedMosiMonoStep if self._mosi else FusedMonoStep
+            st = self.train_steps[shape] = cls(self.model, self.optimizer, self.loss_functions, shape)
+        return st
+
+    def eval_step_for(self, b: int, t: int):
+        return self.model.eval_step_for(self.loss_functions, (int(b), int(t), int(self.model.encoder.input_size)),
+                                        self.log)
+
+    def _hook(self, loader, train: bool) -> None:
+        if self._mosi and hasattr(loader, "step_for"):
+            loader.step_for = self.train_step_for if train else self.eval_step_for
 
     def _ensure_log(self, key) -> None:
         if self.log is None:
@@ -463,12 +723,15 @@ class MonoEpochRunner:
         t0 = time.time()
         accs: List[torch.Tensor] = []
         self.model.train()
+        self._hook(loader, True)
         for x, lab in self._batches(loader):
-            shape = tuple(x.shape)
-            st = self.train_steps.get(shape)
-            if st is None:
-                st = FusedMonoStep(self.model, self.optimizer, self.loss_functions, shape)
-                self.train_steps[shape] = st
+            st = self.model._by_buffer.get(x.data_ptr()) if self._mosi else None
+            if not isinstance(st, FusedMosiMonoStep):
+                shape = tuple(x.shape)
+                st = self.train_step_for(*shape[:2]) if self._mosi else self.train_steps.get(shape)
+                if st is None:
+                    st = FusedMonoStep(self.model, self.optimizer, self.loss_functions, shape)
+                    self.train_steps[shape] = st
             st.log = self.log
             st.step(x, lab)
             accs.append(st.batch_accuracy())
@@ -479,8 +742,9 @@ class MonoEpochRunner:
         t0 = time.time()
         accs: List[torch.Tensor] = []
         self.model.eval()
+        self._hook(loader, False)
         for x, lab in self._batches(loader):
-            st = self.model.eval_step_for(self.loss_functions, tuple(x.shape), self.log)
+            st = self.model._eval_step_of(x, self.loss_functions, self.log)
             st.step(x, lab)
             accs.append(st.batch_accuracy())
         return self._finish(t0, accs)

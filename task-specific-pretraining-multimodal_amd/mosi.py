@@ -113,9 +113,30 @@ class TextCNN(nn.Module):
         self.heights = [int(k) for k in kernel_heights]
         self.out_channels = out_channels
         self.input_size = input_size
+        self._engines: Dict[Any, "MosiEncoderEngine"] = {}
 
     def convs(self):
         return [self.conv1, self.conv2, self.conv3]
+
+    def _apply(self, fn, *args, **kwargs):
+        out = super()._apply(fn, *args, **kwargs)
+        self._engines = {}
+        return out
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        """Inference embedding of x [B, T, input] (no dropout; gradients flow through UttFusionModel or
+        MonomodalEncoder only)."""
+        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()) and x.requires_grad:
+            raise L.TspmError("TextCNN: train it inside UttFusionModel or MonomodalEncoder (the fused HIP step / its "
+                              "autograd node)")
+        L.require_cuda_f32(x, "TextCNN input")
+        key = (x.shape[0], x.shape[1], x.device)
+        eng = self._engines.get(key)
+        if eng is None:
+            eng = self._engines[key] = MosiEncoderEngine(self, x.shape[0], x.shape[1], x.device)
+        eng.load(x)
+        eng.forward(L.stream_handle(), False)
+        return eng.emb.clone()
 
 
 class FcClassifier(nn.Module):
@@ -175,6 +196,151 @@ def _conv_algo(n: int) -> L.ConvAlgo:
     return L.ConvAlgo()
 
 
+def _lstm_alloc(enc: "LSTMEncoder", B: int, T: int, device, backward: bool = True) -> Dict[str, Optional[torch.Tensor]]:
+    """One LSTM's saved activations for a fixed (batch, steps): xg / gates [T*B, 4H], cs [T*B, H], hs [(T+1)*B, H],
+    the gate gradients dg [T*B, 4H] (``backward``) and, for the "maxpool" embedding, the time index of each unit's
+    maximum (uint8 [B][H])."""
+    if enc.hidden_size != 64:
+        raise NotImplementedError("MOSI HIP path: LSTM hidden size 64 (tspm_lstm_fwd)")
+    f, H = dict(device=device, dtype=torch.float32), enc.hidden_size
+    bufs = dict(xg=torch.empty(T * B, 4 * H, **f), gates=torch.empty(T * B, 4 * H, **f),
+                cs=torch.empty(T * B, H, **f), hs=torch.empty((T + 1) * B, H, **f),
+                dg=torch.empty(T * B, 4 * H, **f) if backward else None)
+    bufs["arg"] = torch.zeros(B, H, dtype=torch.uint8, device=device) if enc.embd_method == "maxpool" else None
+    return bufs
+
+
+def _lstm_fwd_prepare(d, enc: "LSTMEncoder", x: torch.Tensor, bufs, B: int, T: int, h_out: int, ld_out: int,
+                      sh: int) -> None:
+    """The input projection over all T*B rows (launched) and the recurrence's descriptor `d` (filled)."""
+    rnn, fin = enc.rnn, enc.input_size
+    L.check(L.lib().tspm_linear_fwd(T * B, fin, 4 * enc.hidden_size, x.data_ptr(), fin, rnn.weight_ih_l0.data_ptr(),
+                                    rnn.bias_ih_l0.data_ptr(), 0, None, 1.0, bufs["xg"].data_ptr(),
+                                    4 * enc.hidden_size, sh), "lstm input projection")
+    d.batch, d.steps, d.hidden, d.ld_out = B, T, enc.hidden_size, ld_out
+    d.xg, d.w_hh, d.b_hh = bufs["xg"].data_ptr(), rnn.weight_hh_l0.data_ptr(), rnn.bias_hh_l0.data_ptr()
+    d.gates, d.cs, d.hs = bufs["gates"].data_ptr(), bufs["cs"].data_ptr(), bufs["hs"].data_ptr()
+    d.h_out = h_out
+    d.argmax = L.ptr(bufs["arg"])
+
+
+def _lstm_bwd_desc(d, enc: "LSTMEncoder", bufs, B: int, T: int, dh: int, ld_dh: int) -> None:
+    rnn = enc.rnn
+    d.batch, d.steps, d.hidden, d.ld_dh = B, T, enc.hidden_size, ld_dh
+    d.w_hh, d.gates, d.cs = rnn.weight_hh_l0.data_ptr(), bufs["gates"].data_ptr(), bufs["cs"].data_ptr()
+    d.dh, d.dgates = dh, bufs["dg"].data_ptr()
+    d.argmax = L.ptr(bufs["arg"])
+
+
+def _lstm_wgrad(enc: "LSTMEncoder", x: torch.Tensor, bufs, B: int, T: int, splits: Dict[int, int],
+                wg_ws: torch.Tensor, g, sh: int) -> None:
+    """The LSTM weight gradients as GEMMs over the T*B rows of dgates (after tspm_lstm_bwd)."""
+    lib, rnn, H, fin = L.lib(), enc.rnn, enc.hidden_size, enc.input_size
+    ws, wsb = wg_ws.data_ptr(), wg_ws.numel() * 4
+    # dW_hh = dgates^T h_{t-1} (rows (t, b) of hs[0:T]); db_hh = column sums of dgates
+    L.check(lib.tspm_linear_bwd_weight_splitk(T * B, H, 4 * H, bufs["hs"].data_ptr(), H, bufs["dg"].data_ptr(),
+                                              4 * H, g(rnn.weight_hh_l0).data_ptr(),
+                                              g(rnn.bias_hh_l0).data_ptr(), splits[H], ws, wsb, sh),
+            "lstm dW_hh")
+    # dW_ih = dgates^T x; db_ih = the same column sums (same split and order: bitwise db_hh)
+    L.check(lib.tspm_linear_bwd_weight_splitk(T * B, fin, 4 * H, x.data_ptr(), fin, bufs["dg"].data_ptr(),
+                                              4 * H, g(rnn.weight_ih_l0).data_ptr(),
+                                              g(rnn.bias_ih_l0).data_ptr(), splits[fin], ws, wsb, sh),
+            "lstm dW_ih")
+
+
+def _lstm_wgrad_plan(B: int, T: int, fins, device):
+    """LSTM weight gradients reduce over T*B rows into 256 x {in, 64} outputs (8-16 output tiles): split the
+    reduction so the launch fills the chip (tspm_linear_bwd_weight_splitk) — one split for every product
+    (db_ih and db_hh come from two calls and must stay bitwise equal).  → (splits by fan-in, workspace)."""
+    lib, H = L.lib(), 64
+    sp = max(1, min(32, (T * B) // 128))
+    splits = {fin: sp for fin in tuple(fins) + (H,)}
+    wsb = max(int(lib.tspm_linear_bwd_weight_splitk_workspace(T * B, fin, 4 * H, sp)) for fin in splits)
+    return splits, torch.empty(max(wsb // 4, 1), device=device, dtype=torch.float32)
+
+
+def _text_alloc(o, t: "TextCNN", B: int, T: int, device) -> None:
+    """The TextCNN half's plan for a fixed (batch, steps), set as attributes of its owner `o` (MosiEngine or
+    MosiEncoderEngine): conv shapes / tiles / outputs / workspace, pooled values and their argmax, the embedding
+    Linear's input and the backward's work buffers."""
+    if T > 255 or min(t.heights) > T or max(t.heights) > 5:
+        raise L.TspmError("MOSI HIP path: 1 <= kernel heights <= min(5, steps) and steps <= 255")
+    f = dict(device=device, dtype=torch.float32)
+    o.ft = t.input_size
+    C, nc = t.out_channels, 3 * t.out_channels
+    o.C, o.nc = C, nc
+    o.conv_shapes = [L.ConvShape(B, T, 1, o.ft, C, k, 1, 1, 0, T - k + 1, 1) for k in t.heights]
+    o.conv_algo = _conv_algo(B)
+    from .engine import tuned_table
+    tab = tuned_table()
+    o.conv_algos = []
+    for s in o.conv_shapes:
+        e = tab.get(("fwd", s.n, s.h, s.w, s.c, s.k, s.r, s.s, s.stride))
+        o.conv_algos.append(L.ConvAlgo(*e) if e is not None else o.conv_algo)
+    o.conv_out = [torch.empty((T - k + 1) * B, C, **f) for k in t.heights]
+    lib = L.lib()
+    ws = max(lib.tspm_conv_fwd_workspace(ctypes.byref(s), ctypes.byref(al))
+             for s, al in zip(o.conv_shapes, o.conv_algos))
+    o.conv_ws = torch.zeros(max(int(ws), 256), dtype=torch.uint8, device=device)
+    o.pooled = torch.empty(B, nc, **f)
+    o.argmax = torch.empty(B, nc, dtype=torch.uint8, device=device)
+    o.fc_in = torch.empty(B, nc, **f)
+    o.dfc_in = torch.empty(B, nc, **f)
+    o.g_work = torch.empty(B, nc, **f)
+
+
+def _text_forward(o, t: "TextCNN", sh: int, keep: Optional[int], out: int, ld_out: int) -> None:
+    """TextCNN forward on owner `o`'s plan: three convolutions (implicit GEMM), pooling + dropout (keep: the
+    uint8 mask's pointer or None), embedding Linear + ReLU written to `out` (row stride ld_out)."""
+    lib, B, T = L.lib(), o.B, o.T
+    for conv, s, al, y in zip(t.convs(), o.conv_shapes, o.conv_algos, o.conv_out):
+        L.check(lib.tspm_conv_fwd(ctypes.byref(s), ctypes.byref(al), o.X.data_ptr(), None,
+                                  conv.weight.data_ptr(), y.data_ptr(), None, o.conv_ws.data_ptr(),
+                                  o.conv_ws.numel(), sh), "textcnn conv")
+    heights = (ctypes.c_int32 * 3)(*t.heights)
+    outs = (ctypes.c_void_p * 3)(*[y.data_ptr() for y in o.conv_out])
+    biases = (ctypes.c_void_p * 3)(*[cv.bias.data_ptr() for cv in t.convs()])
+    tp = t.dropout.p
+    L.check(lib.tspm_textcnn_pool_fwd(B, T, 3, heights, o.C, outs, biases, keep,
+                                      1.0 / (1.0 - tp) if tp < 1 else 0.0, o.pooled.data_ptr(),
+                                      o.argmax.data_ptr(), o.fc_in.data_ptr(), o.nc, sh), "textcnn pool")
+    emb = t.embd[0]
+    L.check(lib.tspm_linear_fwd(B, o.nc, emb.out_features, o.fc_in.data_ptr(), o.nc, emb.weight.data_ptr(),
+                                emb.bias.data_ptr(), 1, None, 1.0, out, ld_out, sh),
+            "textcnn embd")
+
+
+def _text_backward(o, t: "TextCNN", sh: int, keep: Optional[int], dout: int, ld_d: int, out: int, ld_out: int,
+                   g) -> None:
+    """TextCNN backward from `dout` (the embedding's gradient, masked in place through the ReLU of `out`):
+    embedding Linear, then pooling / dropout and the sparse conv weight gradients."""
+    lib, B, T = L.lib(), o.B, o.T
+    emb = t.embd[0]
+    L.check(lib.tspm_act_bwd(B, emb.out_features, dout, ld_d, out, ld_out, 1.0, sh), "textcnn embd relu")
+    linear_bwd(B, o.nc, emb.out_features, o.fc_in.data_ptr(), o.nc, dout, ld_d, emb.weight.data_ptr(),
+               g(emb.weight).data_ptr(), g(emb.bias).data_ptr(), o.dfc_in.data_ptr(), o.nc, sh)
+    heights = (ctypes.c_int32 * 3)(*t.heights)
+    dws = (ctypes.c_void_p * 3)(*[g(cv.weight).data_ptr() for cv in t.convs()])
+    dbs = (ctypes.c_void_p * 3)(*[g(cv.bias).data_ptr() for cv in t.convs()])
+    tp = t.dropout.p
+    L.check(lib.tspm_textcnn_bwd(B, T, o.ft, 3, heights, o.C, o.X.data_ptr(), o.dfc_in.data_ptr(),
+                                 o.nc, keep, 1.0 / (1.0 - tp) if 0 < tp < 1 else 1.0, o.pooled.data_ptr(),
+                                 o.argmax.data_ptr(), dws, dbs, o.g_work.data_ptr(), sh), "textcnn bwd")
+
+
+def _seq_load(src: torch.Tensor, dst: torch.Tensor, B: int, T: int, index, offs, lens, nm: str, sh: int) -> None:
+    """A batch-first [B, T, F] tensor → the time-major buffer `dst` (one tspm_seq_gather: the dense batch seen
+    as B sequences of length T)."""
+    L.require_cuda_f32(src, nm)
+    if tuple(src.shape) != (B, T, dst.shape[2]):
+        raise L.TspmError(f"{nm} batch shape {tuple(src.shape)} != planned {(B, T, dst.shape[2])}")
+    src = src.contiguous()
+    L.check(L.lib().tspm_seq_gather(B, index.data_ptr(), B, src.data_ptr(), offs.data_ptr(), lens.data_ptr(),
+                                    dst.shape[2], T, dst.data_ptr(), B * dst.shape[2], dst.shape[2], None, None, None,
+                                    sh), "seq_gather")
+
+
 class MosiEngine:
     """Execution plan of UttFusionModel for a fixed (batch, steps): pre-allocated time-major buffers, one
     fixed sequence of libtspm launches on the caller's stream (graph-capturable)."""
@@ -182,10 +348,6 @@ class MosiEngine:
     def __init__(self, model: "UttFusionModel", batch: int, steps: int, device: torch.device):
         self.m, self.B, self.T, self.device = model, batch, steps, device
         a, v, t, c = model.netA, model.netV, model.netT, model.netC
-        if a.hidden_size != 64 or v.hidden_size != 64:
-            raise NotImplementedError("MOSI HIP path: LSTM hidden size 64 (tspm_lstm_fwd)")
-        if steps > 255 or min(t.heights) > steps or max(t.heights) > 5:
-            raise L.TspmError("MOSI HIP path: 1 <= kernel heights <= min(5, steps) and steps <= 255")
         f = dict(device=device, dtype=torch.float32)
         B, T, H = batch, steps, 64
         self.fa, self.fv, self.ft = a.input_size, v.input_size, t.input_size
@@ -198,32 +360,10 @@ class MosiEngine:
         if c.linears()[0].in_features != self.E:
             raise L.TspmError("FcClassifier input_dim must equal the sum of the three embedding sizes")
         self.fused = torch.zeros(B, self.E, **f)
-        self.lstm = {}
-        for name, enc in (("a", a), ("v", v)):
-            self.lstm[name] = dict(xg=torch.empty(T * B, 4 * H, **f), gates=torch.empty(T * B, 4 * H, **f),
-                                   cs=torch.empty(T * B, H, **f), hs=torch.empty((T + 1) * B, H, **f),
-                                   dg=torch.empty(T * B, 4 * H, **f))
-            # "maxpool" embedding: the time index of each unit's maximum (uint8 [B][H])
-            self.lstm[name]["arg"] = (torch.zeros(B, H, dtype=torch.uint8, device=device)
-                                      if enc.embd_method == "maxpool" else None)
-        C, nc = t.out_channels, 3 * t.out_channels
-        self.C, self.nc = C, nc
-        self.conv_shapes = [L.ConvShape(B, T, 1, self.ft, C, k, 1, 1, 0, T - k + 1, 1) for k in t.heights]
-        self.conv_algo = _conv_algo(B)
-        from .engine import tuned_table
-        tab = tuned_table()
-        self.conv_algos = []
-        for s in self.conv_shapes:
-            e = tab.get(("fwd", s.n, s.h, s.w, s.c, s.k, s.r, s.s, s.stride))
-            self.conv_algos.append(L.ConvAlgo(*e) if e is not None else self.conv_algo)
-        self.conv_out = [torch.empty((T - k + 1) * B, C, **f) for k in t.heights]
+        self.lstm = {name: _lstm_alloc(enc, B, T, device) for name, enc in (("a", a), ("v", v))}
+        _text_alloc(self, t, B, T, device)
+        nc = self.nc
         lib = L.lib()
-        ws = max(lib.tspm_conv_fwd_workspace(ctypes.byref(s), ctypes.byref(al))
-                 for s, al in zip(self.conv_shapes, self.conv_algos))
-        self.conv_ws = torch.zeros(max(int(ws), 256), dtype=torch.uint8, device=device)
-        self.pooled = torch.empty(B, nc, **f)
-        self.argmax = torch.empty(B, nc, dtype=torch.uint8, device=device)
-        self.fc_in = torch.empty(B, nc, **f)
         self.widths = c.widths
         self.h = [torch.empty(B, w, **f) for w in self.widths]
         self.logits = torch.empty(B, c.fc_out.out_features, **f)
@@ -238,8 +378,6 @@ class MosiEngine:
             self.bn_inv = [torch.empty(w, **f) for w in self.widths]
             self.dr = [torch.empty(B, w, **f) for w in self.widths]
         self.dfused = torch.empty(B, self.E, **f)
-        self.dfc_in = torch.empty(B, nc, **f)
-        self.g_work = torch.empty(B, nc, **f)
         self.loss = torch.zeros(1, **f)
         self.stats = torch.zeros(4, **f)
         # dropout keep masks: TextCNN (before the embedding Linear) + one per classifier layer
@@ -252,13 +390,7 @@ class MosiEngine:
         self.keep_override: Optional[Dict[str, torch.Tensor]] = None
         self.rng_ctr_ptr: Optional[int] = None
         self._host_ctr: Optional[torch.Tensor] = None
-        # LSTM weight gradients reduce over T*B rows into 256 x {in, 64} outputs (8-16 output tiles): split
-        # the reduction so the launch fills the chip (tspm_linear_bwd_weight_splitk)
-        # — one split for all four (db_ih and db_hh come from two calls and must stay bitwise equal)
-        sp = max(1, min(32, (T * B) // 128))
-        self.wg_splits = {fin: sp for fin in (self.fa, self.fv, H)}
-        wsb = max(int(lib.tspm_linear_bwd_weight_splitk_workspace(T * B, fin, 4 * H, sp)) for fin in (self.fa, self.fv, H))
-        self.wg_ws = torch.empty(max(wsb // 4, 1), **f)
+        self.wg_splits, self.wg_ws = _lstm_wgrad_plan(B, T, (self.fa, self.fv), device)
         self.concurrent = os.environ.get("TSPM_MOSI_SERIAL", "0") != "1"
         self.side: Optional[torch.cuda.Stream] = None
         self.clip_coef = torch.ones(1, **f)
@@ -273,15 +405,9 @@ class MosiEngine:
     def load(self, A: torch.Tensor, V: torch.Tensor, T: torch.Tensor, labels: Optional[torch.Tensor] = None) -> None:
         """Batch-first [B, T, F] reference tensors → the time-major buffers (tspm_seq_gather: one launch per
         modality, the dense batch seen as B sequences of length T)."""
-        lib, sh = L.lib(), L.stream_handle()
+        sh = L.stream_handle()
         for src, dst, nm in ((A, self.A, "audio"), (V, self.V, "video"), (T, self.X, "text")):
-            L.require_cuda_f32(src, nm)
-            if tuple(src.shape) != (self.B, self.T, dst.shape[2]):
-                raise L.TspmError(f"{nm} batch shape {tuple(src.shape)} != planned {(self.B, self.T, dst.shape[2])}")
-            src = src.contiguous()
-            L.check(lib.tspm_seq_gather(self.B, self._index.data_ptr(), self.B, src.data_ptr(), self._offs.data_ptr(),
-                                        self._lens.data_ptr(), dst.shape[2], self.T, dst.data_ptr(),
-                                        self.B * dst.shape[2], dst.shape[2], None, None, None, sh), "seq_gather")
+            _seq_load(src, dst, self.B, self.T, self._index, self._offs, self._lens, nm, sh)
         if labels is not None:
             self.labels.copy_(labels.reshape(-1).to(self.labels.dtype), non_blocking=True)
 
@@ -351,42 +477,15 @@ class MosiEngine:
         B, T = self.B, self.T
         # LSTM input projections over all T*B rows, then both recurrences in one launch
         descs = (L.LstmFwdDesc * 2)()
-        for i, (name, enc, x, fin, col) in enumerate((("a", m.netA, self.A, self.fa, 0),
-                                                      ("v", m.netV, self.V, self.fv, m.netA.hidden_size))):
-            bufs, rnn = self.lstm[name], enc.rnn
-            L.check(lib.tspm_linear_fwd(T * B, fin, 4 * enc.hidden_size, x.data_ptr(), fin, rnn.weight_ih_l0.data_ptr(),
-                                        rnn.bias_ih_l0.data_ptr(), 0, None, 1.0, bufs["xg"].data_ptr(),
-                                        4 * enc.hidden_size, sh), "lstm input projection")
-            d = descs[i]
-            d.batch, d.steps, d.hidden, d.ld_out = B, T, enc.hidden_size, self.E
-            d.xg, d.w_hh, d.b_hh = bufs["xg"].data_ptr(), rnn.weight_hh_l0.data_ptr(), rnn.bias_hh_l0.data_ptr()
-            d.gates, d.cs, d.hs = bufs["gates"].data_ptr(), bufs["cs"].data_ptr(), bufs["hs"].data_ptr()
-            d.h_out = self.fused.data_ptr() + col * 4
-            d.argmax = L.ptr(bufs["arg"])
+        for i, (name, enc, x, col) in enumerate((("a", m.netA, self.A, 0), ("v", m.netV, self.V, m.netA.hidden_size))):
+            _lstm_fwd_prepare(descs[i], enc, x, self.lstm[name], B, T, self.fused.data_ptr() + col * 4, self.E, sh)
         L.check(lib.tspm_lstm_fwd(2, descs, sh), "lstm_fwd")
 
     def _forward_text(self, sh: int, train: bool) -> None:
-        lib, m = L.lib(), self.m
-        B, T = self.B, self.T
-        # TextCNN: three convolutions (implicit GEMM), pooling + dropout, embedding Linear + ReLU
-        t = m.netT
-        for conv, s, al, y in zip(t.convs(), self.conv_shapes, self.conv_algos, self.conv_out):
-            L.check(lib.tspm_conv_fwd(ctypes.byref(s), ctypes.byref(al), self.X.data_ptr(), None,
-                                      conv.weight.data_ptr(), y.data_ptr(), None, self.conv_ws.data_ptr(),
-                                      self.conv_ws.numel(), sh), "textcnn conv")
-        heights = (ctypes.c_int32 * 3)(*t.heights)
-        outs = (ctypes.c_void_p * 3)(*[y.data_ptr() for y in self.conv_out])
-        biases = (ctypes.c_void_p * 3)(*[cv.bias.data_ptr() for cv in t.convs()])
-        tp = t.dropout.p
-        keep_t = self.keeps[0].data_ptr() if (train and tp > 0) else None
-        L.check(lib.tspm_textcnn_pool_fwd(B, T, 3, heights, self.C, outs, biases, keep_t,
-                                          1.0 / (1.0 - tp) if tp < 1 else 0.0, self.pooled.data_ptr(),
-                                          self.argmax.data_ptr(), self.fc_in.data_ptr(), self.nc, sh), "textcnn pool")
+        m, t = self.m, self.m.netT
+        keep_t = self.keeps[0].data_ptr() if (train and t.dropout.p > 0) else None
         col_t = m.netA.hidden_size + m.netV.hidden_size
-        emb = t.embd[0]
-        L.check(lib.tspm_linear_fwd(B, self.nc, emb.out_features, self.fc_in.data_ptr(), self.nc, emb.weight.data_ptr(),
-                                    emb.bias.data_ptr(), 1, None, 1.0, self.fused.data_ptr() + col_t * 4, self.E, sh),
-                "textcnn embd")
+        _text_forward(self, t, sh, keep_t, self.fused.data_ptr() + col_t * 4, self.E)
 
     def _forward_classifier(self, sh: int, train: bool) -> None:
         lib, m, B = L.lib(), self.m, self.B
@@ -474,25 +573,11 @@ class MosiEngine:
             self._backward_lstm(sh)
 
     def _backward_text(self, sh: int) -> None:
-        lib, m, g = L.lib(), self.m, self.grad_of
-        B, T = self.B, self.T
-        # TextCNN: embedding ReLU, Linear, then pooling/dropout and the sparse conv weight gradients
-        t = m.netT
+        m, t = self.m, self.m.netT
         col_t = m.netA.hidden_size + m.netV.hidden_size
-        emb = t.embd[0]
-        dcol = self.dfused.data_ptr() + col_t * 4
-        L.check(lib.tspm_act_bwd(B, emb.out_features, dcol, self.E, self.fused.data_ptr() + col_t * 4, self.E, 1.0, sh),
-                "textcnn embd relu")
-        linear_bwd(B, self.nc, emb.out_features, self.fc_in.data_ptr(), self.nc, dcol, self.E, emb.weight.data_ptr(),
-                   g(emb.weight).data_ptr(), g(emb.bias).data_ptr(), self.dfc_in.data_ptr(), self.nc, sh)
-        heights = (ctypes.c_int32 * 3)(*t.heights)
-        dws = (ctypes.c_void_p * 3)(*[g(cv.weight).data_ptr() for cv in t.convs()])
-        dbs = (ctypes.c_void_p * 3)(*[g(cv.bias).data_ptr() for cv in t.convs()])
-        tp = t.dropout.p
-        L.check(lib.tspm_textcnn_bwd(B, T, self.ft, 3, heights, self.C, self.X.data_ptr(), self.dfc_in.data_ptr(),
-                                     self.nc, self.keeps[0].data_ptr() if tp > 0 else None,
-                                     1.0 / (1.0 - tp) if 0 < tp < 1 else 1.0, self.pooled.data_ptr(),
-                                     self.argmax.data_ptr(), dws, dbs, self.g_work.data_ptr(), sh), "textcnn bwd")
+        keep_t = self.keeps[0].data_ptr() if t.dropout.p > 0 else None
+        _text_backward(self, t, sh, keep_t, self.dfused.data_ptr() + col_t * 4, self.E,
+                       self.fused.data_ptr() + col_t * 4, self.E, self.grad_of)
 
     def _backward_lstm(self, sh: int) -> None:
         lib, m, g = L.lib(), self.m, self.grad_of
@@ -500,32 +585,106 @@ class MosiEngine:
         # LSTMs: backward through time (one launch for both), then the weight gradients as GEMMs over T*B rows
         descs = (L.LstmBwdDesc * 2)()
         for i, (name, enc, col) in enumerate((("a", m.netA, 0), ("v", m.netV, m.netA.hidden_size))):
-            bufs, rnn = self.lstm[name], enc.rnn
-            d = descs[i]
-            d.batch, d.steps, d.hidden, d.ld_dh = B, T, enc.hidden_size, self.E
-            d.w_hh, d.gates, d.cs = rnn.weight_hh_l0.data_ptr(), bufs["gates"].data_ptr(), bufs["cs"].data_ptr()
-            d.dh, d.dgates = self.dfused.data_ptr() + col * 4, bufs["dg"].data_ptr()
-            d.argmax = L.ptr(bufs["arg"])
+            _lstm_bwd_desc(descs[i], enc, self.lstm[name], B, T, self.dfused.data_ptr() + col * 4, self.E)
         L.check(lib.tspm_lstm_bwd(2, descs, sh), "lstm_bwd")
-        for name, enc, x, fin in (("a", m.netA, self.A, self.fa), ("v", m.netV, self.V, self.fv)):
-            bufs, rnn, H = self.lstm[name], enc.rnn, enc.hidden_size
-            # dW_hh = dgates^T h_{t-1} (rows (t, b) of hs[0:T]); db_hh = column sums of dgates
-            ws, wsb = self.wg_ws.data_ptr(), self.wg_ws.numel() * 4
-            L.check(lib.tspm_linear_bwd_weight_splitk(T * B, H, 4 * H, bufs["hs"].data_ptr(), H, bufs["dg"].data_ptr(),
-                                                      4 * H, g(rnn.weight_hh_l0).data_ptr(),
-                                                      g(rnn.bias_hh_l0).data_ptr(), self.wg_splits[H], ws, wsb, sh),
-                    "lstm dW_hh")
-            # dW_ih = dgates^T x; db_ih = the same column sums (same split and order: bitwise db_hh)
-            L.check(lib.tspm_linear_bwd_weight_splitk(T * B, fin, 4 * H, x.data_ptr(), fin, bufs["dg"].data_ptr(),
-                                                      4 * H, g(rnn.weight_ih_l0).data_ptr(),
-                                                      g(rnn.bias_ih_l0).data_ptr(), self.wg_splits[fin], ws, wsb, sh),
-                    "lstm dW_ih")
+        for name, enc, x in (("a", m.netA, self.A), ("v", m.netV, self.V)):
+            _lstm_wgrad(enc, x, self.lstm[name], B, T, self.wg_splits, self.wg_ws, g, sh)
 
     def clip(self, sh: int, flat_grad: torch.Tensor, grad_scale: float) -> None:
         """clip_grad_norm_(model.parameters(), clip) coefficient into ``clip_coef`` (utt_fusion.py:188-189)."""
         L.check(L.lib().tspm_grad_clip_coef(flat_grad.numel(), flat_grad.data_ptr(), grad_scale, float(self.m.clip),
                                             self.clip_coef.data_ptr(), self.total_norm.data_ptr(),
                                             self.clip_ws.data_ptr(), self.clip_ws.numel() * 4, sh), "grad_clip")
+
+
+class MosiEncoderEngine:
+    """Execution plan of ONE MOSI encoder (LSTMEncoder "last" / "maxpool", or TextCNN) for a fixed (batch,
+    steps), forward and backward on the caller's stream (graph-capturable) — the encoder pre-training step of
+    monomodal.MonomodalEncoder and TextCNN's standalone forward.  The input is time-major in ``X`` [T, B, F];
+    the embedding goes to ``emb`` [B, hidden]; ``backward`` consumes its gradient ``demb`` and writes the
+    parameter gradients to ``grad_of(p)``.  Same launches as the encoder's half of MosiEngine (shared code):
+    LSTM = input projection + tspm_lstm_fwd(count 1) / tspm_lstm_bwd(count 1) + the two split-K weight
+    gradients; TextCNN = three convs + pool/dropout + embedding Linear / act_bwd + linear_bwd + textcnn_bwd."""
+
+    def __init__(self, enc: nn.Module, batch: int, steps: int, device, seed: int = 0,
+                 x: Optional[torch.Tensor] = None, emb: Optional[torch.Tensor] = None):
+        if torch.device(device).type != "cuda":
+            raise L.TspmError("MOSI encoders (tspm_amd) run on the MI355X only (no CPU fallback)")
+        self.enc, self.B, self.T, self.device = enc, int(batch), int(steps), device
+        B, T = self.B, self.T
+        f = dict(device=device, dtype=torch.float32)
+        self.is_text = isinstance(enc, TextCNN)
+        if not self.is_text and not isinstance(enc, LSTMEncoder):
+            raise L.TspmError(f"MosiEncoderEngine: LSTMEncoder or TextCNN, not {type(enc).__name__}")
+        self.hidden = int(enc.hidden_size)
+        shape = (T, B, int(enc.input_size))
+        if x is not None and (tuple(x.shape) != shape or not x.is_contiguous()):
+            raise L.TspmError(f"input buffer {tuple(x.shape)} != time-major {shape}")
+        self.X = x if x is not None else torch.zeros(shape, **f)
+        self.emb = emb if emb is not None else torch.zeros(B, self.hidden, **f)
+        self.demb = torch.empty(B, self.hidden, **f)
+        self.keep_override: Optional[Dict[str, torch.Tensor]] = None
+        self.rng_ctr_ptr: Optional[int] = None
+        self._host_ctr: Optional[torch.Tensor] = None
+        self.seed = int(seed)
+        if self.is_text:
+            _text_alloc(self, enc, B, T, device)
+            self.keep = torch.ones(B, self.nc, dtype=torch.uint8, device=device)
+        else:
+            self.bufs = _lstm_alloc(enc, B, T, device)
+            self.wg_splits, self.wg_ws = _lstm_wgrad_plan(B, T, (enc.input_size,), device)
+        self.grad_of = lambda p: p.grad  # noqa: E731  (FusedAdam's flat gradient views)
+        self._index = torch.arange(B, dtype=torch.int64, device=device)
+        self._lens = torch.full((B,), T, dtype=torch.int32, device=device)
+        self._offs = torch.arange(B, dtype=torch.int64, device=device) * T
+
+    def load(self, x: torch.Tensor) -> None:
+        """A batch-first [B, T, F] tensor → the time-major input buffer."""
+        _seq_load(x, self.X, self.B, self.T, self._index, self._offs, self._lens, "input", L.stream_handle())
+
+    def apply_keep_override(self) -> None:
+        """Copy the injected TextCNN dropout mask (parity hook: {"text": uint8 [B, 3C]}) into the keep buffer;
+        called before the step runs, outside any captured graph."""
+        if self.keep_override is not None and self.is_text:
+            self.keep.copy_(self.keep_override["text"].reshape(self.keep.shape).to(torch.uint8), non_blocking=True)
+
+    def _keep_mask(self, train: bool, sh: int) -> Optional[int]:
+        """The TextCNN keep mask of this forward: None in eval / without dropout, the injected mask, or a fresh
+        draw of tspm_dropout_mask on the step counter (the optimizer's, or a host-advanced one)."""
+        p = float(self.enc.dropout.p) if self.is_text else 0.0
+        if not train or p <= 0:
+            return None
+        if self.keep_override is None:
+            if self.rng_ctr_ptr is None:
+                self._host_ctr = torch.zeros(1, dtype=torch.int64, device=self.device)
+                self.rng_ctr_ptr = self._host_ctr.data_ptr()
+            L.check(L.lib().tspm_dropout_mask(self.keep.numel(), p, self.seed, self.rng_ctr_ptr, self.keep.data_ptr(),
+                                              sh), "dropout_mask (text)")
+            if self._host_ctr is not None and self.rng_ctr_ptr == self._host_ctr.data_ptr():
+                self._host_ctr.add_(1)  # nothing else advances a host-owned counter: fresh masks per forward
+        return self.keep.data_ptr()
+
+    def forward(self, sh: int, train: bool) -> None:
+        B, T = self.B, self.T
+        if self.is_text:
+            _text_forward(self, self.enc, sh, self._keep_mask(train, sh), self.emb.data_ptr(), self.hidden)
+            return
+        d = (L.LstmFwdDesc * 1)()
+        _lstm_fwd_prepare(d[0], self.enc, self.X, self.bufs, B, T, self.emb.data_ptr(), self.hidden, sh)
+        L.check(L.lib().tspm_lstm_fwd(1, d, sh), "lstm_fwd")
+
+    def backward(self, sh: int) -> None:
+        """From ``demb`` (modified in place by the TextCNN's ReLU mask) to every parameter gradient."""
+        B, T = self.B, self.T
+        if self.is_text:
+            keep = self.keep.data_ptr() if self.enc.dropout.p > 0 else None
+            _text_backward(self, self.enc, sh, keep, self.demb.data_ptr(), self.hidden, self.emb.data_ptr(),
+                           self.hidden, self.grad_of)
+            return
+        d = (L.LstmBwdDesc * 1)()
+        _lstm_bwd_desc(d[0], self.enc, self.bufs, B, T, self.demb.data_ptr(), self.hidden)
+        L.check(L.lib().tspm_lstm_bwd(1, d, sh), "lstm_bwd")
+        _lstm_wgrad(self.enc, self.X, self.bufs, B, T, self.wg_splits, self.wg_ws, self.grad_of, sh)
 
 
 def _ce_weight(loss_functions) -> Optional[float]:
@@ -883,19 +1042,11 @@ def _encode_lstm(enc: LSTMEncoder, x: torch.Tensor) -> torch.Tensor:
     """Standalone LSTMEncoder embedding (inference): projection GEMM + one-problem tspm_lstm_fwd."""
     L.require_cuda_f32(x, "LSTMEncoder input")
     B, T, F = x.shape
-    dev, H = x.device, enc.hidden_size
-    f = dict(device=dev, dtype=torch.float32)
     xt = x.transpose(0, 1).contiguous() if T > 1 else x.reshape(1, B, F).contiguous()
-    xg, gates = torch.empty(T * B, 4 * H, **f), torch.empty(T * B, 4 * H, **f)
-    cs, hs, out = torch.empty(T * B, H, **f), torch.empty((T + 1) * B, H, **f), torch.empty(B, H, **f)
-    arg = torch.empty(B, H, dtype=torch.uint8, device=dev) if enc.embd_method == "maxpool" else None
-    lib, sh, rnn = L.lib(), L.stream_handle(), enc.rnn
-    L.check(lib.tspm_linear_fwd(T * B, F, 4 * H, xt.data_ptr(), F, rnn.weight_ih_l0.data_ptr(),
-                                rnn.bias_ih_l0.data_ptr(), 0, None, 1.0, xg.data_ptr(), 4 * H, sh), "lstm proj")
+    out = torch.empty(B, enc.hidden_size, device=x.device, dtype=torch.float32)
+    sh = L.stream_handle()
     d = (L.LstmFwdDesc * 1)()
-    d[0].batch, d[0].steps, d[0].hidden, d[0].ld_out = B, T, H, H
-    d[0].xg, d[0].w_hh, d[0].b_hh = xg.data_ptr(), rnn.weight_hh_l0.data_ptr(), rnn.bias_hh_l0.data_ptr()
-    d[0].gates, d[0].cs, d[0].hs, d[0].h_out = gates.data_ptr(), cs.data_ptr(), hs.data_ptr(), out.data_ptr()
-    d[0].argmax = L.ptr(arg)
-    L.check(lib.tspm_lstm_fwd(1, d, sh), "lstm_fwd")
+    _lstm_fwd_prepare(d[0], enc, xt, _lstm_alloc(enc, B, T, x.device, backward=False), B, T, out.data_ptr(),
+                      enc.hidden_size, sh)
+    L.check(L.lib().tspm_lstm_fwd(1, d, sh), "lstm_fwd")
     return out

@@ -113,24 +113,26 @@ class DeviceMosiCorpus:
         if self.labels.dtype != torch.int64:
             raise L.TspmError("device gather carries int64 class labels (classification_labels)")
 
-    def steps_for(self, index_host: np.ndarray, pad_to: int = 0) -> int:
+    def steps_for(self, index_host: np.ndarray, pad_to: int = 0, modalities: Sequence[str] = MODALITIES) -> int:
         """pad_sequence's padded length, the longest sequence of the batch — per modality in the reference
         (data/mosi.py:225-230); the HIP step runs the three modalities over one common length, so the
         per-modality maxima must agree (aligned data) or all be covered by ``pad_to``."""
         if not len(index_host):
             return pad_to
-        mx = [int(self.host_lengths[m][index_host].max()) for m in MODALITIES]
+        mx = [int(self.host_lengths[m][index_host].max()) for m in modalities]
         if max(mx) > pad_to and len(set(mx)) > 1:
-            raise L.TspmError(f"unaligned batch: per-modality longest sequences {dict(zip(MODALITIES, mx))} differ "
+            raise L.TspmError(f"unaligned batch: per-modality longest sequences {dict(zip(modalities, mx))} differ "
                               "(pad_sequence pads each to its own length); pass pad_to >= all of them")
         return max(max(mx), pad_to)
 
     def gather(self, index: torch.Tensor, steps_pad: int, out: Dict[str, torch.Tensor], time_major: bool,
                masks: Optional[Dict[str, torch.Tensor]] = None, labels_out: Optional[torch.Tensor] = None) -> None:
-        """Write the batch ``index`` (device int64) into ``out[m]``: [T, B, F] (time_major) or [B, T, F]."""
+        """Write the batch ``index`` (device int64) into ``out[m]``: [T, B, F] (time_major) or [B, T, F], for
+        the modalities ``out`` names (all three for the fusion step, one for encoder pre-training); the labels
+        ride on the first launch."""
         lib, sh = L.lib(), L.stream_handle()
         b = int(index.numel())
-        for j, m in enumerate(MODALITIES):
+        for j, m in enumerate([m for m in MODALITIES if m in out]):
             f, dst = self.feat[m], out[m]
             shape = (steps_pad, b, f) if time_major else (b, steps_pad, f)
             if tuple(dst.shape) != shape or not dst.is_contiguous() or dst.dtype != torch.float32:
@@ -164,8 +166,11 @@ class MOSI(torch.utils.data.Dataset):
         if num_classes is not None:
             self.NUM_CLASSES = num_classes
         tm = str(getattr(target_modality, "value", target_modality)).lower().split(".")[-1]
-        if tm != "multimodal":
-            raise NotImplementedError("MOSI HIP path: target_modality multimodal (the UTT-Fusion configs)")
+        if tm not in MODALITIES + ("multimodal",):
+            raise AssertionError(f"Invalid modality provided, must be one of {list(MODALITIES) + ['multimodal']}")
+        # "audio" / "video" / "text": encoder pre-training (train_monomodal) — only that modality is gathered and
+        # present in the batch, and batches are flat (the monomodal loop has no per-pattern sub-batches)
+        self.target_modality = tm
         self.selected_patterns = list(selected_patterns) if selected_patterns is not None else list(PATTERNS)
         bad = set(self.selected_patterns) - set(PATTERNS)
         if bad:
@@ -242,7 +247,7 @@ class MOSI(torch.utils.data.Dataset):
         tspm_seq_gather each), labels, pattern names; valid/test batches grouped by pattern."""
         items = np.concatenate([b[1] for b in batch])
         rows, pid = self._resolve(items)
-        if self.split == "train":
+        if self.split == "train" or self.target_modality != "multimodal":
             return self._collate(rows, pid)
         out = {}
         for p in dict.fromkeys(pid.tolist()):
@@ -256,7 +261,32 @@ class MOSI(torch.utils.data.Dataset):
         return {m: k[:, j].contiguous().to(self.device, non_blocking=True)
                 for j, m in enumerate(MODALITIES) if not bool((k[:, j] == 1.0).all())}
 
+    def _want(self) -> Sequence[str]:
+        """The modalities a batch carries (data.AVMNIST._want's rule)."""
+        return MODALITIES if self.target_modality == "multimodal" else (self.target_modality,)
+
+    def _collate_mono(self, rows: np.ndarray, pid: np.ndarray, step=None, pad_to: int = 0) -> Dict[str, Any]:
+        """A pre-training batch: the target modality's key, ``label`` and ``pattern_name`` only (the last
+        non-bookkeeping key is the modality, monomodal.select_modality_key).  With ``step`` (a monomodal
+        FusedMosiMonoStep / FusedMosiMonoEvalStep) the gather writes time-major straight into its input buffer."""
+        dc, m = self.device_corpus, self.target_modality
+        b, tpad = len(rows), dc.steps_for(rows, pad_to, (m,))
+        index = torch.from_numpy(rows).to(self.device, non_blocking=True)
+        masks = {k: v for k, v in self._masks(pid).items() if k == m}
+        names = [self.selected_patterns[p] for p in pid]
+        if step is not None:
+            if (step.N, step.T) != (b, tpad):
+                raise L.TspmError(f"step planned for (B={step.N}, T={step.T}), batch is (B={b}, T={tpad})")
+            dc.gather(index, tpad, {m: step.X}, True, masks, step.labels)
+            return {m: step.X, "label": step.labels, "pattern_name": names}
+        out = torch.empty(b, tpad, dc.feat[m], device=self.device)
+        lab = torch.empty(b, dtype=torch.int64, device=self.device)
+        dc.gather(index, tpad, {m: out}, False, masks, lab)
+        return {m: out, "label": lab, "pattern_name": names}
+
     def _collate(self, rows: np.ndarray, pid: np.ndarray, step=None, pad_to: int = 0) -> Dict[str, Any]:
+        if self.target_modality != "multimodal":
+            return self._collate_mono(rows, pid, step, pad_to)
         dc = self.device_corpus
         b, tpad = len(rows), dc.steps_for(rows, pad_to)
         index = torch.from_numpy(rows).to(self.device, non_blocking=True)
@@ -283,9 +313,11 @@ class MOSI(torch.utils.data.Dataset):
         ``pad_to``: pad every batch to at least this many steps (the aligned length, e.g. 50 for aligned_50:
         one captured step shape for the whole epoch; pad_sequence pads to the batch maximum, which equals it
         on the reference's dense data).  ``group_patterns`` (default: valid / test splits, as collate_fn):
-        each batch is ``{pattern: sub-batch}`` in first-seen order (data/mosi.py:236-251)."""
+        each batch is ``{pattern: sub-batch}`` in first-seen order (data/mosi.py:236-251); with a single target
+        modality the default is flat batches (``step_for`` then returns the monomodal train / eval step)."""
         n = len(self)
-        grouped = (self.split != "train") if group_patterns is None else bool(group_patterns)
+        grouped = ((self.split != "train" and self.target_modality == "multimodal") if group_patterns is None
+                   else bool(group_patterns))
         order = torch.randperm(n, generator=generator).numpy() if shuffle else np.arange(n)
         for s in range(0, n, batch_size):
             items = order[s:s + batch_size]
@@ -298,7 +330,7 @@ class MOSI(torch.utils.data.Dataset):
             for name, sel in parts:
                 r, q = rows[sel], pid[sel]
                 if step_for is not None:
-                    t = self.device_corpus.steps_for(r, pad_to)
+                    t = self.device_corpus.steps_for(r, pad_to, self._want())
                     out[name] = self._collate(r, q, step_for(len(r), t), pad_to)
                     if grouped:
                         yield {name: out[name]}  # the step's buffers are reused: hand each group over at once
