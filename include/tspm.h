@@ -401,7 +401,9 @@ int tspm_dropout_mask(int64_t count, float p, uint64_t seed, const uint64_t* cou
  * ----------------------------------------------------------------------------------------------*/
 /* loss[0] = grad_scale * mean_i CE(logits_i, labels_i) (the group's total: weight × CE, grad_scale =
  * the term's weight); dlogits = (softmax - onehot)/n * grad_scale;
- * if stats != NULL: stats[0] += loss*n, stats[1] += #correct (argmax == label), stats[2] += n. */
+ * if stats != NULL: stats[0] += loss*n, stats[1] += #correct (argmax == label, first maximum), stats[2] += n.
+ * A label outside [0, classes) gives a NaN loss and a NaN dlogits row (no out-of-bounds read) and never counts
+ * as correct, whatever the row's argmax. */
 int tspm_cross_entropy(int32_t n, int32_t classes, const float* logits, const int64_t* labels, float* loss,
                        float* dlogits, float grad_scale, float* stats, tspm_stream_t stream);
 
@@ -421,7 +423,7 @@ int tspm_cross_entropy(int32_t n, int32_t classes, const float* logits, const in
  *       loss[0] = weight * mean CE, stats[0] += sum CE, stats[1] += #(argmax == label), stats[2] += n.
  * Every buffer below is caller-owned device memory; row_ws holds 2*n floats.  Same semantics as
  * tspm_linear_fwd/_bwd + tspm_act_bwd + tspm_dropout_mask + tspm_cross_entropy (out-of-range label →
- * NaN loss and gradients), up to summation order.  Limits: in <= 256, hidden <= 256, hidden2 <= 128,
+ * NaN loss and gradients, never counted in stats[1]), up to summation order.  Limits: in <= 256, hidden <= 256, hidden2 <= 128,
  * classes <= 16; in, hidden, hidden2 multiples of 4; w0 / w3 / x rows 16-byte aligned; the three
  * weight matrices plus the row blocks within 160 KiB of LDS (floats, RB = rows per workgroup, logits rows
  * padded to a multiple of 4: hidden*(in+4) + hidden2*(hidden+4) + classes*(hidden2+4)
@@ -784,7 +786,9 @@ int tspm_textcnn_bwd(int32_t batch, int32_t steps, int32_t feat, int32_t nconv, 
                      float* const* db, float* g_work, tspm_stream_t stream);
 /* clip_grad_norm_(parameters, max_norm) coefficient (utt_fusion.py:189): total = ||grad * grad_scale||_2
  * (squares summed in double, fixed order), *coef = min(1, max_norm / (total + 1e-6)) for
- * tspm_adam_step_clip; *total_norm (nullable) = total.  workspace: tspm_grad_clip_workspace() bytes. */
+ * tspm_adam_step_clip, as torch.clamp(max=1): a NaN total gives a NaN coefficient (an inf total gives 0);
+ * *total_norm (nullable) = total.  workspace: tspm_grad_clip_workspace() bytes (a missing or shorter one, with
+ * the other arguments valid, is TSPM_ERR_WORKSPACE). */
 size_t tspm_grad_clip_workspace(void);
 int tspm_grad_clip_coef(int64_t count, const float* grad, float grad_scale, float max_norm, float* coef,
                         float* total_norm, void* workspace, size_t workspace_bytes, tspm_stream_t stream);
@@ -805,7 +809,8 @@ int tspm_seq_gather(int32_t count, const int64_t* index, int64_t n_samples, cons
  * encoder pre-training step ([128,64] x [64,3]).  Semantics of tspm_linear_fwd + tspm_cross_entropy +
  * tspm_linear_bwd up to summation order: logits = emb w^T + b; loss[0] = loss_weight * mean CE;
  * dlogits = (softmax - onehot)/n * loss_weight; dw = dlogits^T emb, db = column sums of dlogits,
- * demb = dlogits w (all overwritten); an out-of-range label gives NaN loss and gradients (no out-of-bounds read).
+ * demb = dlogits w (all overwritten); an out-of-range label gives NaN loss and gradients (no out-of-bounds read)
+ * and is never counted in stats[1].
  * One workgroup walks the rows in chunks of 64 with the embeddings staged in LDS and reduces in a fixed order:
  * no atomics, no workspace, two runs on the same input are bitwise equal; forward-only mode (dw, db and demb all
  * NULL) gives bitwise the training mode's logits, loss and preds.

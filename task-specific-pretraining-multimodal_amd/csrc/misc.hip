@@ -334,7 +334,7 @@ __global__ __launch_bounds__(256) void k_cross_entropy(int N, int K, const float
     const bool lok = lab64 >= 0 && lab64 < K;  // out-of-range label: NaN loss/grad, no OOB read
     const int lab = lok ? (int)lab64 : 0;
     lsum += lok ? (double)(lse - (z[lab] - mx)) : (double)__builtin_nanf("");
-    correct += (am == lab) ? 1 : 0;
+    correct += (lok && am == lab) ? 1 : 0;  // an out-of-range label is never correct
     if (dlogits) {
       float* d = dlogits + (long long)n * K;
       for (int k = 0; k < K; ++k) {
@@ -1025,7 +1025,7 @@ __global__ __launch_bounds__(THREADS) void k_head_rows(HeadArgs a) {
       if (k == 0) {
         const float lse = logf(se);
         d.row_ws[n0 + r] = lok ? lse - (z[lab] - mx) : __builtin_nanf("");
-        d.row_ws[d.n + n0 + r] = (am == lab) ? 1.f : 0.f;
+        d.row_ws[d.n + n0 + r] = (lok && am == lab) ? 1.f : 0.f;  // an out-of-range label is never correct
       }
       const float invn = 1.0f / (float)d.n;
       const float pk = e / se;
@@ -1231,7 +1231,7 @@ __global__ __launch_bounds__(MH_THREADS) void k_mono_head(tspm_mono_head_desc d)
       const bool lok = lab64 >= 0 && lab64 < K;  // out-of-range label: NaN loss / gradients, no out-of-bounds read
       const int lab = lok ? (int)lab64 : 0;
       lsum += lok ? (double)(lse - (z[lab] - mx)) : (double)__builtin_nanf("");
-      correct += (am == lab) ? 1 : 0;
+      correct += (lok && am == lab) ? 1 : 0;  // an out-of-range label is never correct
       if (d.preds) d.preds[r0 + t] = am;
       if (train)
         for (int k = 0; k < K; ++k) {

@@ -417,7 +417,7 @@ __global__ __launch_bounds__(256) void k_clip_coef(int nparts, const double* __r
   const double s = red[0];
   const float total = (float)sqrt(s);
   const float cf = max_norm / (total + 1e-6f);
-  coef[0] = cf < 1.f ? cf : 1.f;
+  coef[0] = cf > 1.f ? 1.f : cf;  // torch.clamp(max=1): a NaN total gives a NaN coefficient (inf gives 0)
   if (norm_out) norm_out[0] = total;
 }
 
@@ -568,8 +568,8 @@ extern "C" size_t tspm_grad_clip_workspace(void) { return (size_t)kClipBlocks * 
 
 extern "C" int tspm_grad_clip_coef(int64_t count, const float* grad, float grad_scale, float max_norm, float* coef,
                                    float* total_norm, void* workspace, size_t workspace_bytes, tspm_stream_t stream) {
-  if (count <= 0 || !grad || !coef || !workspace || workspace_bytes < tspm_grad_clip_workspace() || !(max_norm > 0.f))
-    return TSPM_ERR_INVALID;
+  if (count <= 0 || !grad || !coef || !(max_norm > 0.f)) return TSPM_ERR_INVALID;
+  if (!workspace || workspace_bytes < tspm_grad_clip_workspace()) return TSPM_ERR_WORKSPACE;
   hipStream_t st = static_cast<hipStream_t>(stream);
   double* part = static_cast<double*>(workspace);
   hipLaunchKernelGGL(k_sumsq, dim3(kClipBlocks), dim3(256), 0, st, (long long)count, grad, grad_scale, part);

@@ -234,3 +234,87 @@ def pair_from(ours: torch.nn.Module, builder) -> Tuple[torch.nn.Module, torch.nn
     o32 = builder()
     anchor(o32, ours)
     return o32, copy.deepcopy(o32).double()
+
+
+# ------------------------------------------------------------------------------------------------
+# Op-level tests (test_gpu_seq_ops.py, test_gpu_loss_ops.py): one entry point against a plain-torch
+# restatement in fp64, with the fp32 run of the same restatement as the yardstick
+# ------------------------------------------------------------------------------------------------
+GUARD = 64                    # sentinel elements after every guarded output
+_SENTINEL = {torch.float32: 0x7FA5A5A5, torch.uint8: 0xA5, torch.int64: 0x7FA5A5A5A5A5A5A5}  # fp32: a NaN pattern
+_BITS = {torch.float32: torch.int32, torch.uint8: torch.uint8, torch.int64: torch.int64}
+
+
+class Guarded:
+    """A device output of `rows` x `width` elements with row stride `ld`, followed by GUARD elements.  The whole
+    allocation starts as a sentinel bit pattern; ``intact()`` asserts that the tail and the padding columns
+    (ld > width) still hold it, i.e. the kernel wrote only its own elements."""
+
+    def __init__(self, dev, rows, width, ld=None, dtype=torch.float32):
+        self.rows, self.width, self.ld = rows, width, ld or width
+        assert self.ld >= width
+        self.flat = torch.empty(rows * self.ld + GUARD, dtype=dtype, device=dev)
+        self.flat.view(_BITS[dtype]).fill_(_SENTINEL[dtype])
+
+    @property
+    def t(self) -> torch.Tensor:
+        """[rows, width] view of the kernel's own elements."""
+        return self.flat[:self.rows * self.ld].view(self.rows, self.ld)[:, :self.width]
+
+    def ptr(self) -> int:
+        return self.flat.data_ptr()
+
+    def cpu(self) -> torch.Tensor:
+        return self.t.cpu().contiguous()
+
+    def intact(self, name="output"):
+        bits = self.flat.cpu().view(_BITS[self.flat.dtype])
+        s = _SENTINEL[self.flat.dtype]
+        assert bool((bits[self.rows * self.ld:] == s).all()), f"{name}: wrote past its last element"
+        pad = bits[:self.rows * self.ld].view(self.rows, self.ld)[:, self.width:]
+        assert bool((pad == s).all()), f"{name}: wrote into the padding columns of its rows"
+
+
+class Ratios:
+    """Worst err_ours / err_ref32 per name (printed by the tests; the bound is FACTOR with the floors above)."""
+
+    def __init__(self):
+        self.worst = {}
+
+    def note(self, name, e_ours, e_ref):
+        r = e_ours / e_ref if e_ref > 0 else (0.0 if e_ours == 0 else float("inf"))
+        if name not in self.worst or r > self.worst[name][0]:
+            self.worst[name] = (r, e_ours, e_ref)
+
+    def __str__(self):
+        return "; ".join(f"{k} {v[0]:.2f} ({v[1]:.1e}/{v[2]:.1e})" for k, v in self.worst.items())
+
+
+def op_check(name, ours, ref32, ref64, grad=False, ratios: Optional[Ratios] = None):
+    """err_ours <= FACTOR * err_ref32 + floor against fp64 (FLOOR_OUT, or FLOOR_GRAD and cosine >= GRAD_COS for a
+    gradient); both errors are printed before the assertion."""
+    e_ours, e_ref = rel_l2(ours, ref64), rel_l2(ref32, ref64)
+    floor = FLOOR_GRAD if grad else FLOOR_OUT
+    print(f"{name}: err_ours {e_ours:.3e} err_ref32 {e_ref:.3e}")
+    if ratios is not None:
+        ratios.note(name.split("[")[0], e_ours, e_ref)
+    assert e_ours <= FACTOR * e_ref + floor, f"{name}: ours {e_ours:.3e} vs fp32 reference {e_ref:.3e} (fp64 truth)"
+    if grad:
+        cos = cosine(ours, ref64)
+        assert cos >= GRAD_COS, f"{name}: cosine {cos:.7f}"
+    return e_ours, e_ref
+
+
+def near_tie_flips(name, ours_idx, ref_idx, values64, dim):
+    """Argmax decisions against the fp64 reference's own: a disagreement must be a near-tie (the two fp64 candidates
+    within NEAR x rms of the tensor) and rare (at most max(1, MAX_FLIP_FRAC x numel)).  Returns the flip count."""
+    flip = ours_idx != ref_idx
+    nf = int(flip.sum())
+    if nf:
+        v = values64.double()
+        rms = v.pow(2).mean().sqrt().item() or 1.0
+        dist = (v.gather(dim, ours_idx.unsqueeze(dim)) - v.gather(dim, ref_idx.unsqueeze(dim))).squeeze(dim).abs()[flip]
+        worst = dist.max().item() / rms
+        assert worst <= NEAR, f"{name}: a flipped decision is {worst:.2e} x rms from its tie"
+    assert nf <= max(1, MAX_FLIP_FRAC * ours_idx.numel()), f"{name}: {nf} of {ours_idx.numel()} decisions flipped"
+    return nf

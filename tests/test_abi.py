@@ -156,6 +156,73 @@ def test_library_sources_read_no_environment_and_keep_no_mutable_globals():
                 raise AssertionError(f"{f}: file-scope variable: {line.strip()}")
 
 
+def test_sequence_entry_points_validate_before_launch():
+    """tspm_lstm_fwd / _bwd, tspm_textcnn_pool_fwd / _bwd and tspm_grad_clip_coef refuse bad arguments before any
+    launch (no GPU here: an accepted call would answer TSPM_ERR_LAUNCH = 2).  A short clip workspace is
+    TSPM_ERR_WORKSPACE = 3 like every other entry point's, not TSPM_ERR_INVALID."""
+    lib = L.load()
+    INVALID, WORKSPACE = 1, 3
+    P = 4096  # a 16-byte aligned, non-NULL stand-in: never dereferenced, every call returns before a launch
+
+    def fwd(count=1, **kw):
+        f = dict(batch=2, steps=3, hidden=64, ld_out=64, xg=P, w_hh=P, b_hh=P, gates=P, cs=P, hs=P, h_out=P, argmax=None)
+        f.update(kw)
+        d = (L.LstmFwdDesc * 2)(L.LstmFwdDesc(**f), L.LstmFwdDesc(**f))
+        return lib.tspm_lstm_fwd(count, d, None)
+
+    def bwd(count=1, **kw):
+        f = dict(batch=2, steps=3, hidden=64, ld_dh=64, w_hh=P, gates=P, cs=P, dh=P, dgates=P, argmax=None)
+        f.update(kw)
+        d = (L.LstmBwdDesc * 2)(L.LstmBwdDesc(**f), L.LstmBwdDesc(**f))
+        return lib.tspm_lstm_bwd(count, d, None)
+
+    for call in (fwd, bwd):
+        assert call(count=0) == INVALID and call(count=3) == INVALID
+        assert call(hidden=32) == INVALID and call(hidden=128) == INVALID
+        assert call(batch=0) == INVALID and call(steps=0) == INVALID
+        assert call(steps=257, argmax=P) == INVALID  # uint8 time index
+    assert fwd(ld_out=63) == INVALID and bwd(ld_dh=63) == INVALID
+    assert fwd(w_hh=P + 4) == INVALID  # the float4 loads of W_hh need 16-byte alignment
+    assert fwd(hs=None) == INVALID and bwd(dgates=None) == INVALID
+    assert lib.tspm_lstm_fwd(1, None, None) == INVALID and lib.tspm_lstm_bwd(1, None, None) == INVALID
+
+    def pool(batch=2, steps=9, nconv=2, heights=(2, 5), channels=4, ld_out=None, conv=P):
+        hs = (ctypes.c_int32 * len(heights))(*heights)
+        ptrs = (ctypes.c_void_p * 5)(*([conv] * 5))
+        return lib.tspm_textcnn_pool_fwd(batch, steps, nconv, hs, channels, ptrs, None, None, 1.0, P, P, P,
+                                         nconv * channels if ld_out is None else ld_out, None)
+
+    assert pool(steps=257) == INVALID
+    assert pool(heights=(2, 10)) == INVALID  # taller than the sequence
+    assert pool(heights=(0, 5)) == INVALID
+    assert pool(nconv=5, heights=(1, 2, 3, 4, 5)) == INVALID and pool(nconv=0) == INVALID
+    assert pool(ld_out=7) == INVALID
+    assert pool(conv=None) == INVALID and pool(batch=0) == INVALID
+
+    def tbwd(batch=2, steps=9, feat=8, nconv=2, heights=(2, 5), channels=4, ld_dout=None):
+        hs = (ctypes.c_int32 * len(heights))(*heights)
+        ptrs = (ctypes.c_void_p * 4)(*([P] * 4))
+        return lib.tspm_textcnn_bwd(batch, steps, feat, nconv, hs, channels, P, P,
+                                    nconv * channels if ld_dout is None else ld_dout, None, 1.0, P, P, ptrs, None, P, None)
+
+    assert tbwd(feat=1025) == INVALID and tbwd(feat=0) == INVALID
+    assert tbwd(heights=(2, 6)) == INVALID  # the kernels hold at most 5 window rows
+    assert tbwd(heights=(2, 10), steps=9) == INVALID and tbwd(ld_dout=7) == INVALID
+
+    ws = lib.tspm_grad_clip_workspace()
+    assert ws == 512 * 8
+
+    def clip(count=10, max_norm=1.0, workspace=P, ws_bytes=ws, grad=P, coef=P):
+        return lib.tspm_grad_clip_coef(count, grad, 1.0, max_norm, coef, None, workspace, ws_bytes, None)
+
+    assert clip(count=0) == INVALID and clip(count=-1) == INVALID
+    for bad in (0.0, -1.0, float("nan")):
+        assert clip(max_norm=bad) == INVALID, bad
+    assert clip(grad=None) == INVALID and clip(coef=None) == INVALID
+    assert clip(ws_bytes=ws - 1) == WORKSPACE and clip(workspace=None) == WORKSPACE
+    assert clip(count=0, ws_bytes=0) == INVALID  # the other arguments are judged first
+
+
 def test_round6_entry_points_validate_before_launch():
     """The round-6 entry points refuse bad arguments before any launch (no GPU here: an accepted call would fail with
     TSPM_ERR_LAUNCH = 2, a refused one returns TSPM_ERR_INVALID = 1)."""

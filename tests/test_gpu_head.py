@@ -101,9 +101,16 @@ def test_head_loss_weight_and_bad_label(gpu):
     assert abs(out["loss"].item() - r["loss"].item()) <= 1e-6 * abs(r["loss"].item())
     assert _rel(out["gw0"], r["gw0"]) < 1e-5
     ws["labels"][5] = 11  # out of range: NaN loss and gradients, no out-of-bounds read
+    ws["labels"][6] = -1
+    ws["b5"][0] = 100.0   # every row predicts class 0, the class the bounds-safe read falls back to
     _, out2 = _buffers(n, F, H, H2, C, gpu, seed=3)
     _run(ws, out2, 0.0, 1.0, keep, 0)
     assert torch.isnan(out2["loss"]).all() and torch.isnan(out2["dlogits"][5]).all()
+    assert torch.isnan(out2["dlogits"][6]).all() and not torch.isnan(out2["dlogits"][7]).any()
+    # stats[1] = #(argmax == label): a row whose label is out of range never counts, whatever its argmax
+    assert bool((out2["logits"].argmax(1) == 0).all())
+    st = out2["stats"].cpu()
+    assert st[1].item() == float((ws["labels"] == 0).sum()) and st[2].item() == n
 
 
 def test_head_invalid_shapes_refused(gpu):

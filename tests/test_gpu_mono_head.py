@@ -154,7 +154,14 @@ def test_mono_head_out_of_range_label_gives_nan(gpu):
     emb, w, b, labels = _inputs(63, 64, 3)
     labels = labels.clone()
     labels[17] = 3  # == classes
-    o = _run(gpu, emb, w, b, labels)
+    labels[40] = -1
+    emb = emb.clone()
+    emb[17] = emb[40] = 50 * w[0]  # both rows predict class 0, the class the bounds-safe read falls back to
+    o = _run(gpu, emb, w, b, labels, stats=True)
     assert torch.isnan(o["loss"]).all()
     assert torch.isnan(o["dw"]).any() and torch.isnan(o["db"]).any() and torch.isnan(o["demb"][17]).all()
+    assert torch.isnan(o["demb"][40]).all()
     assert not torch.isnan(o["logits"]).any()
+    # stats[1] = #(argmax == label): a row whose label is out of range never counts, whatever its argmax
+    assert o["preds"][17].item() == 0 and o["preds"][40].item() == 0
+    assert o["stats"][1].item() == float((o["preds"] == labels).sum()) and o["stats"][2].item() == 63.0
