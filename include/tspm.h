@@ -48,7 +48,9 @@ enum {
  * head's row block is tspm_head_desc.rows_per_block); 22 = round 6: tspm_conv_algo.variant 4, the LDS-staged kernels with
  * every fp32 product formed from an exact three-piece bf16 split on the bf16 MFMA (same structs and entry points);
  * 23 = tspm_mono_head_step, the monomodal pre-training head (classifier, cross-entropy, predictions, backward) in
- * one launch. */
+ * one launch.  Added under 23 with no existing signature or struct changed (callers built against 23 keep working):
+ * tspm_mono_head_bce_step / tspm_mono_head_bce_workspace, the multi-label (BCEWithLogits, F1 counts) form of that
+ * head for the MMIMDb encoder pre-training step. */
 #define TSPM_ABI_VERSION 23
 int tspm_abi_version(void);  /* returns TSPM_ABI_VERSION */
 /* Static string for a status code. */
@@ -832,6 +834,44 @@ typedef struct tspm_mono_head_desc {
   float* stats;          /* nullable: the three accumulators of tspm_cross_entropy */
 } tspm_mono_head_desc;
 int tspm_mono_head_step(const tspm_mono_head_desc* desc, tspm_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Multi-label monomodal head (added under ABI 23) — the same head around an MMIMDbModalityEncoder (hid 512, 23 genres,
+ * float multi-hot targets): `classifier` forward, the loss group's weighted BCEWithLogits, the predictions
+ * sigmoid(x) > threshold, the F1 accumulators and the Linear's whole backward in ONE launch.  Semantics of
+ * tspm_linear_fwd + tspm_bce_logits + tspm_linear_bwd up to summation order: logits = emb w^T + b;
+ * loss[0] = loss_weight * mean((1-t)*x - logsigmoid(x)); dlogits = (sigmoid(x) - t) * loss_weight / (n*classes);
+ * dw = dlogits^T emb, db = column sums of dlogits, demb = dlogits w (all overwritten; padding columns of demb
+ * untouched).  stats (nullable) has tspm_bce_logits' layout and accumulate-into semantics (3 + 3*classes floats).
+ * Rows are spread over up to 16 workgroups (chunks of up to 16 rows staged in LDS); each publishes its partial dw / db /
+ * loss / counts in the workspace and the last arriver adds them in workgroup order: no float atomics, every sum
+ * in a fixed order, two runs on the same input are bitwise equal; forward-only mode (dw, db and demb all NULL)
+ * gives bitwise the training mode's logits, loss, preds and stats.
+ * workspace: tspm_mono_head_bce_workspace(n, hid, classes) bytes, 16-byte aligned, its first 64 bytes (the arrival
+ * counter) zero before the first launch that uses it (the kernel re-arms it); one workspace serves one stream.
+ * Limits: 1 <= n <= 1024; hid <= 512 and a multiple of 4; 1 <= classes <= 32; ld_emb, ld_demb >= hid and multiples
+ * of 4 with emb / demb 16-byte aligned; dw, db, demb all given or all NULL; otherwise TSPM_ERR_INVALID (a missing or
+ * short workspace with the other arguments valid: TSPM_ERR_WORKSPACE) with nothing written. */
+typedef struct tspm_mono_head_bce_desc {
+  int32_t n, hid, classes, ld_emb, ld_demb;
+  float loss_weight;    /* the bce_with_logits term's weight (tspm_bce_logits' grad_scale) */
+  float threshold;      /* prediction = sigmoid(x) > threshold */
+  const float* emb;     /* [n, ld_emb] */
+  const float* w;       /* [classes, hid] */
+  const float* b;       /* [classes] */
+  const float* targets; /* [n, classes] multi-hot */
+  float* logits;        /* [n, classes] */
+  float* loss;          /* loss[0] */
+  uint8_t* preds;       /* nullable: [n, classes] */
+  float* dw;            /* [classes, hid] */
+  float* db;            /* [classes] */
+  float* demb;          /* [n, ld_demb] */
+  float* stats;         /* nullable: tspm_bce_logits' accumulators */
+  void* workspace;
+  size_t workspace_bytes;
+} tspm_mono_head_bce_desc;
+size_t tspm_mono_head_bce_workspace(int32_t n, int32_t hid, int32_t classes);
+int tspm_mono_head_bce_step(const tspm_mono_head_bce_desc* desc, tspm_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -129,6 +129,15 @@ class MonoHeadDesc(Structure):
         [(n, c_void_p) for n in ("emb", "w", "b", "labels", "logits", "loss", "preds", "dw", "db", "demb", "stats")]
 
 
+class MonoHeadBceDesc(Structure):
+    """tspm_mono_head_bce_desc (added under ABI 23): the multi-label monomodal head (classifier, BCEWithLogits, predictions, F1
+    counts, backward) in one launch; ``workspace`` holds ``tspm_mono_head_bce_workspace`` bytes, zeroed once."""
+    _fields_ = [(n, c_int32) for n in ("n", "hid", "classes", "ld_emb", "ld_demb")] + \
+        [("loss_weight", c_float), ("threshold", c_float)] + \
+        [(n, c_void_p) for n in ("emb", "w", "b", "targets", "logits", "loss", "preds", "dw", "db", "demb", "stats",
+                                 "workspace")] + [("workspace_bytes", c_size_t)]
+
+
 _SIGS = {
     "tspm_abi_version": (c_int32, []),
     "tspm_status_string": (ctypes.c_char_p, [c_int32]),
@@ -248,6 +257,9 @@ _SIGS = {
                                   _P]),
     # ABI 23: the monomodal pre-training head in one launch
     "tspm_mono_head_step": (c_int32, [POINTER(MonoHeadDesc), _P]),
+    # added under ABI 23 (no existing signature changed): the multi-label (BCEWithLogits) form of that head, for the MMIMDb encoders
+    "tspm_mono_head_bce_workspace": (c_size_t, [c_int32, c_int32, c_int32]),
+    "tspm_mono_head_bce_step": (c_int32, [POINTER(MonoHeadBceDesc), _P]),
 }
 
 EXPORTED = tuple(_SIGS)

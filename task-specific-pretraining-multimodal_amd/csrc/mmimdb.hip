@@ -525,7 +525,333 @@ __global__ __launch_bounds__(256) void k_pool_act_bwd(long long total, const flo
   }
 }
 
+// ------------------------------------------------------------------------------------------------
+// Multi-label monomodal head (added under ABI 23): classifier Linear forward, weighted BCEWithLogits, predictions, F1 counts
+// and the Linear's whole backward in ONE launch.  At hid 512 x 23 classes the three products are too much for one
+// workgroup (≈ 1.5 M multiply-adds each at n = 128, 64 per clock and CU), so the ROWS are spread: workgroup g takes
+// rows [g*rpw, (g+1)*rpw) (at most HB_MAXG workgroups) in chunks of HB_CH rows staged in LDS next to the whole weight, computes their logits,
+// loss terms, predictions, dlogits and demb, and keeps its partial dw in registers across its chunks.  Each
+// workgroup publishes its partial dw / db / loss / counts in its own workspace record (write-through stores) and the
+// last arriver (common.h last_arriver: agent-scope acquire, counter re-armed) adds the records in workgroup order —
+// no float atomics, every sum in a fixed order, the same grid in forward-only mode.
+// ------------------------------------------------------------------------------------------------
+constexpr int HB_THREADS = 256, HB_CH = 16, HB_MAXH = 512, HB_MAXC = 32, HB_MAXN = 1024, HB_MAXG = 16;
+constexpr int HB_LDZ = HB_MAXC + 1;          // LDS row stride of the chunk's logits / dlogits
+constexpr int HB_SL = HB_THREADS / (HB_CH / 2);  // logits: threads that share two rows (half a wave)
+constexpr int HB_QPT = HB_MAXH / 4 / HB_SL;  // logits: column quads per thread
+static_assert(HB_SL <= 64 && (HB_SL & (HB_SL - 1)) == 0, "the logits' lane reduction is an xor butterfly in a wave");
+// rows per workgroup come in steps of HB_RG: 8 rows each up to n = 128 (16 workgroups; a half-filled chunk), which
+// measured 3 us per step faster at n = 128 than 16 rows in 8 workgroups, and one full 16-row chunk each at n = 256
+// (6 us faster than two 8-row chunks) — scripts/bench_mmimdb_mono.py
+constexpr int HB_RG = 8;
+constexpr int HB_CU = 4;                     // logits: classes whose lane reductions run together
+constexpr int HB_CPT = 16;                   // dw: classes per thread (hid/4 = 128 columns x 2 class groups)
+constexpr int HB_HDR = 16;                   // workspace floats ahead of the records (the arrival counter)
+
+struct HbPlan {
+  int rpw, groups, rec;  // rows per workgroup, workgroups, floats per workspace record
+};
+inline HbPlan hb_plan(int n, int hid, int classes) {
+  HbPlan p;
+  p.rpw = HB_RG * cdiv(n, HB_RG * HB_MAXG);
+  p.groups = cdiv(n, p.rpw);
+  // record: loss sum, F1 sum (two doubles) | db[classes] | tp, fp, fn [classes][3] | dw[classes][hid]
+  p.rec = (4 + 4 * classes + classes * hid + 3) & ~3;
+  return p;
+}
+
+TSPM_DEV void st_sc1_f64(double* p, double v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+TSPM_DEV double ld_sc1_f64(const double* p) {
+  return __hip_atomic_load((__attribute__((address_space(1))) double*)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// Sum of v over the workgroup's HB_THREADS threads in a fixed order (xor butterfly per wave, waves in index order).
+TSPM_DEV double hb_block_sum(double v, double* red) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  double s = red[0];
+#pragma unroll
+  for (int w = 1; w < HB_THREADS / 64; ++w) s += red[w];
+  return s;
+}
+
+__global__ __launch_bounds__(HB_THREADS) void k_mono_head_bce(tspm_mono_head_bce_desc d, int rpw, int rec) {
+  extern __shared__ float lds[];
+  const int t = threadIdx.x, N = d.n, H = d.hid, K = d.classes, H4 = H >> 2, LDE = H + 4;
+  float* w_s = lds;                                  // [K][LDE]
+  float* emb_s = w_s + K * LDE;                      // [HB_CH][LDE]
+  float* z_s = emb_s + HB_CH * LDE;                  // [HB_CH][HB_LDZ] logits, then dlogits
+  float* b_s = z_s + HB_CH * HB_LDZ;                 // [HB_MAXC]
+  double* red = reinterpret_cast<double*>(b_s + HB_MAXC);  // [4] (8-byte aligned: every size above is even)
+  int* flag = reinterpret_cast<int*>(red + 4);
+  uint8_t* p_s = reinterpret_cast<uint8_t*>(flag + 4);     // [HB_CH][HB_MAXC] predictions
+  uint8_t* y_s = p_s + HB_CH * HB_MAXC;                    // [HB_CH][HB_MAXC] targets > 0.5
+  const bool train = d.dw != nullptr;
+  if ((reinterpret_cast<uintptr_t>(d.w) & 15) == 0) {  // uniform; a parameter view need not be 16-byte aligned
+    for (int e = t; e < K * H4; e += HB_THREADS) st4(w_s + (e / H4) * LDE + (e % H4) * 4, ld4(d.w + 4 * e));
+  } else {
+    for (int e = t; e < K * H; e += HB_THREADS) w_s[(e / H) * LDE + e % H] = d.w[e];
+  }
+  if (t < K) b_s[t] = d.b[t];
+  // dw: thread (cg, q) owns column quad q of classes cg, cg + CG, ... (HB_CPT of them at most: CG >= 2)
+  const int CG = HB_THREADS / H4, dq = t % H4, dcg = t / H4;
+  const bool dw_thread = dcg < CG;
+  f32x4 acc[HB_CPT];
+#pragma unroll
+  for (int u = 0; u < HB_CPT; ++u) acc[u] = f32x4{0.f, 0.f, 0.f, 0.f};
+  float dbacc = 0.f;              // thread c < K: db[c]
+  int tp = 0, fp = 0, fn = 0;     // thread 64 + c: the counts of class c
+  double lsum = 0.0, f1sum = 0.0;
+  const float inv = 1.f / (float)((long long)N * K);
+  const int g = blockIdx.x, r_end = min(N, (g + 1) * rpw);
+  for (int r0 = g * rpw; r0 < r_end; r0 += HB_CH) {
+    const int rows = min(HB_CH, r_end - r0);
+    __syncthreads();  // the previous chunk's readers are done (and w_s / b_s are written)
+    for (int i = t; i < HB_CH * H4; i += HB_THREADS) {
+      const int r = i / H4, j = (i % H4) * 4;
+      st4(emb_s + r * LDE + j,
+          r < rows ? ld4(d.emb + (long long)(r0 + r) * d.ld_emb + j) : f32x4{0.f, 0.f, 0.f, 0.f});
+    }
+    __syncthreads();
+    {  // logits: HB_SL lanes share rows 2rp and 2rp + 1, each over column quads s, s + HB_SL, ...; xor butterfly
+      const int rp = t / HB_SL, s = t % HB_SL;
+      f32x4 e0[HB_QPT], e1[HB_QPT];
+#pragma unroll
+      for (int i = 0; i < HB_QPT; ++i) {
+        const int q = s + HB_SL * i;
+        const bool ok = q < H4;
+        e0[i] = ok ? ld4(emb_s + (2 * rp) * LDE + 4 * q) : f32x4{0.f, 0.f, 0.f, 0.f};
+        e1[i] = ok ? ld4(emb_s + (2 * rp + 1) * LDE + 4 * q) : f32x4{0.f, 0.f, 0.f, 0.f};
+      }
+      for (int c0 = 0; c0 < K; c0 += HB_CU) {  // HB_CU classes at a time: their butterflies overlap
+        float p0[HB_CU], p1[HB_CU];
+#pragma unroll
+        for (int u = 0; u < HB_CU; ++u) {
+          const int c = min(c0 + u, K - 1);  // a class past the last repeats it (never stored)
+          float a0 = 0.f, a1 = 0.f;
+#pragma unroll
+          for (int i = 0; i < HB_QPT; ++i) {
+            const int q = s + HB_SL * i;
+            if (q < H4) {
+              const f32x4 wv = ld4(w_s + c * LDE + 4 * q);
+              a0 += e0[i][0] * wv[0]; a0 += e0[i][1] * wv[1]; a0 += e0[i][2] * wv[2]; a0 += e0[i][3] * wv[3];
+              a1 += e1[i][0] * wv[0]; a1 += e1[i][1] * wv[1]; a1 += e1[i][2] * wv[2]; a1 += e1[i][3] * wv[3];
+            }
+          }
+          p0[u] = a0;
+          p1[u] = a1;
+        }
+#pragma unroll
+        for (int o = HB_SL / 2; o > 0; o >>= 1) {
+#pragma unroll
+          for (int u = 0; u < HB_CU; ++u) {
+            p0[u] += __shfl_xor(p0[u], o, 64);
+            p1[u] += __shfl_xor(p1[u], o, 64);
+          }
+        }
+#pragma unroll
+        for (int u = 0; u < HB_CU; ++u) {
+          const int c = c0 + u;
+          if (s == c && c < K) {  // K <= 32
+            z_s[(2 * rp) * HB_LDZ + c] = p0[u] + b_s[c];
+            z_s[(2 * rp + 1) * HB_LDZ + c] = p1[u] + b_s[c];
+          }
+        }
+      }
+    }
+    __syncthreads();
+    // BCEWithLogits per element (k_bce_logits' arithmetic); dlogits overwrite the logits in LDS
+    for (int p = t; p < rows * K; p += HB_THREADS) {
+      const int r = p / K, c = p % K;
+      const long long gi = (long long)(r0 + r) * K + c;
+      const float xv = z_s[r * HB_LDZ + c], tv = d.targets[gi];
+      d.logits[gi] = xv;
+      const float ls = fminf(xv, 0.f) - log1pf(expf(-fabsf(xv)));
+      lsum += (double)((1.f - tv) * xv - ls);
+      const float sg = 1.f / (1.f + expf(-xv));
+      const bool pr = sg > d.threshold;
+      if (d.preds) d.preds[gi] = pr ? 1 : 0;
+      p_s[r * HB_MAXC + c] = pr ? 1 : 0;
+      y_s[r * HB_MAXC + c] = tv > 0.5f ? 1 : 0;
+      z_s[r * HB_LDZ + c] = (sg - tv) * inv * d.loss_weight;
+    }
+    __syncthreads();
+    if (d.stats) {
+      if (t < rows) {  // per-sample F1 (zero_division = 0)
+        int a = 0, b = 0, c2 = 0;
+        for (int k = 0; k < K; ++k) {
+          const int p = p_s[t * HB_MAXC + k], y = y_s[t * HB_MAXC + k];
+          a += p & y;
+          b += p & (y ^ 1);
+          c2 += (p ^ 1) & y;
+        }
+        const int den = 2 * a + b + c2;
+        f1sum += den > 0 ? (double)((2.f * a) / (float)den) : 0.0;
+      } else if (t >= 64 && t < 64 + K) {  // per-class counts
+        const int k = t - 64;
+        for (int r = 0; r < rows; ++r) {
+          const int p = p_s[r * HB_MAXC + k], y = y_s[r * HB_MAXC + k];
+          tp += p & y;
+          fp += p & (y ^ 1);
+          fn += (p ^ 1) & y;
+        }
+      }
+    }
+    if (!train) continue;  // uniform: forward only
+    // demb = dlogits @ w for the chunk's rows
+    for (int i = t; i < rows * H4; i += HB_THREADS) {
+      const int r = i / H4, j = (i % H4) * 4;
+      f32x4 s4 = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll 4
+      for (int c = 0; c < K; ++c) s4 += z_s[r * HB_LDZ + c] * ld4(w_s + c * LDE + j);
+      st4(d.demb + (long long)(r0 + r) * d.ld_demb + j, s4);
+    }
+    // dw[c][4q..] += sum_r dlogits[r][c] emb[r][4q..] (rows in order), db[c] += sum_r dlogits[r][c]
+    if (dw_thread)
+      for (int r = 0; r < rows; ++r) {
+        const f32x4 ev = ld4(emb_s + r * LDE + 4 * dq);
+#pragma unroll
+        for (int u = 0; u < HB_CPT; ++u) {
+          const int c = dcg + u * CG;
+          if (c < K) acc[u] += z_s[r * HB_LDZ + c] * ev;
+        }
+      }
+    if (t < K)
+      for (int r = 0; r < rows; ++r) dbacc += z_s[r * HB_LDZ + t];
+  }
+  // publish this workgroup's record (write-through), then the last arriver adds the records in workgroup order
+  float* ws = static_cast<float*>(d.workspace);
+  float* my = ws + HB_HDR + (long long)g * rec;
+  const double lwg = hb_block_sum(lsum, red);
+  const double fwg = hb_block_sum(f1sum, red);
+  if (t == 0) {
+    st_sc1_f64(reinterpret_cast<double*>(my), lwg);
+    st_sc1_f64(reinterpret_cast<double*>(my) + 1, fwg);
+  }
+  if (t < K) st_sc1(my + 4 + t, dbacc);
+  if (t >= 64 && t < 64 + K) {
+    float* cnt = my + 4 + K + 3 * (t - 64);
+    st_sc1(cnt, (float)tp);
+    st_sc1(cnt + 1, (float)fp);
+    st_sc1(cnt + 2, (float)fn);
+  }
+  const int dw0 = 4 + 4 * K;
+  if (train && dw_thread) {
+#pragma unroll
+    for (int u = 0; u < HB_CPT; ++u) {
+      const int c = dcg + u * CG;
+      if (c < K) {
+        float* p = my + dw0 + c * H + 4 * dq;
+        st_sc1(p, acc[u][0]);
+        st_sc1(p + 1, acc[u][1]);
+        st_sc1(p + 2, acc[u][2]);
+        st_sc1(p + 3, acc[u][3]);
+      }
+    }
+  }
+  const int G = gridDim.x;
+  if (!last_arriver(reinterpret_cast<unsigned*>(ws), (unsigned)G, flag)) return;
+  const float* recs = ws + HB_HDR;
+  if (train) {
+    // behind last_arriver's agent-scope acquire: plain 16-byte loads, G of them in flight per column quad (one
+    // sc1 load per element left the last workgroup waiting on K*H/256 round trips in a row)
+    // two column quads per pass, so 2 G loads are in flight
+    for (int e = t; e < K * H4; e += 2 * HB_THREADS) {
+      const int e2 = e + HB_THREADS;
+      const bool two = e2 < K * H4;
+      f32x4 v[HB_MAXG], v2[HB_MAXG];
+#pragma unroll
+      for (int q = 0; q < HB_MAXG; ++q) {
+        const float* rq = recs + (long long)q * rec + dw0;
+        v[q] = q < G ? ld4(rq + 4 * e) : f32x4{0.f, 0.f, 0.f, 0.f};
+        v2[q] = q < G && two ? ld4(rq + 4 * e2) : f32x4{0.f, 0.f, 0.f, 0.f};
+      }
+      f32x4 s4 = v[0], s42 = v2[0];
+#pragma unroll
+      for (int q = 1; q < HB_MAXG; ++q)
+        if (q < G) {
+          s4 += v[q];
+          s42 += v2[q];
+        }
+      float* o = d.dw + 4 * e;
+      o[0] = s4[0]; o[1] = s4[1]; o[2] = s4[2]; o[3] = s4[3];
+      if (two) {
+        float* o2 = d.dw + 4 * e2;
+        o2[0] = s42[0]; o2[1] = s42[1]; o2[2] = s42[2]; o2[3] = s42[3];
+      }
+    }
+    if (t < K) {
+      float s = 0.f;
+      for (int q = 0; q < G; ++q) s += ld_sc1(recs + (long long)q * rec + 4 + t);
+      d.db[t] = s;
+    }
+  }
+  if (t == 0) {
+    double l = 0.0, f = 0.0;
+    for (int q = 0; q < G; ++q) {
+      const double* rq = reinterpret_cast<const double*>(recs + (long long)q * rec);
+      l += ld_sc1_f64(rq);
+      f += ld_sc1_f64(rq + 1);
+    }
+    const float mean = (float)(l / ((double)N * (double)K)) * d.loss_weight;
+    d.loss[0] = mean;
+    if (d.stats) {
+      d.stats[0] += mean * (float)N;
+      d.stats[1] += (float)N;
+      d.stats[2] += (float)f;
+    }
+  }
+  if (d.stats && t >= 64 && t < 64 + K) {
+    float a = 0.f, b = 0.f, c2 = 0.f;
+    for (int q = 0; q < G; ++q) {
+      const float* cnt = recs + (long long)q * rec + 4 + K + 3 * (t - 64);
+      a += ld_sc1(cnt);
+      b += ld_sc1(cnt + 1);
+      c2 += ld_sc1(cnt + 2);
+    }
+    float* out = d.stats + 3 + 3 * (t - 64);
+    out[0] += a;
+    out[1] += b;
+    out[2] += c2;
+  }
+}
+
 }  // namespace
+
+extern "C" size_t tspm_mono_head_bce_workspace(int32_t n, int32_t hid, int32_t classes) {
+  if (n < 1 || n > HB_MAXN || hid < 4 || hid > HB_MAXH || hid % 4 || classes < 1 || classes > HB_MAXC) return 0;
+  const HbPlan p = hb_plan(n, hid, classes);
+  return ((size_t)HB_HDR + (size_t)p.groups * p.rec) * sizeof(float);
+}
+
+extern "C" int tspm_mono_head_bce_step(const tspm_mono_head_bce_desc* desc, tspm_stream_t stream) {
+  if (!desc) return TSPM_ERR_INVALID;
+  const tspm_mono_head_bce_desc& d = *desc;
+  if (d.n < 1 || d.n > HB_MAXN || d.hid < 4 || d.hid > HB_MAXH || d.hid % 4 || d.classes < 1 || d.classes > HB_MAXC)
+    return TSPM_ERR_INVALID;
+  if (!d.emb || !d.w || !d.b || !d.targets || !d.logits || !d.loss) return TSPM_ERR_INVALID;
+  const auto aligned16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+  if (d.ld_emb < d.hid || d.ld_emb % 4 || !aligned16(d.emb)) return TSPM_ERR_INVALID;
+  const bool train = d.dw || d.db || d.demb;
+  if (train) {  // the whole backward or none of it
+    if (!d.dw || !d.db || !d.demb) return TSPM_ERR_INVALID;
+    if (d.ld_demb < d.hid || d.ld_demb % 4 || !aligned16(d.demb)) return TSPM_ERR_INVALID;
+  }
+  const HbPlan p = hb_plan(d.n, d.hid, d.classes);
+  if (d.workspace && !aligned16(d.workspace)) return TSPM_ERR_INVALID;
+  if (!d.workspace || d.workspace_bytes < ((size_t)HB_HDR + (size_t)p.groups * p.rec) * sizeof(float))
+    return TSPM_ERR_WORKSPACE;
+  const int LDE = d.hid + 4;
+  const size_t lds = (size_t)(d.classes * LDE + HB_CH * LDE + HB_CH * HB_LDZ + HB_MAXC) * sizeof(float) +
+                     4 * sizeof(double) + 4 * sizeof(int) + 2 * HB_CH * HB_MAXC;
+  hipLaunchKernelGGL(k_mono_head_bce, dim3(p.groups), dim3(HB_THREADS), lds, static_cast<hipStream_t>(stream), d, p.rpw,
+                     p.rec);
+  TSPM_LAUNCH_CHECK();
+  return TSPM_OK;
+}
 
 extern "C" int tspm_gmu_fwd(int32_t n, int32_t d, const float* u, int32_t ldu, const float* wz, float* h,
                             int32_t ldh, float* gate, float* z, int32_t ldz, tspm_stream_t stream) {

@@ -63,8 +63,30 @@ class MMIMDbModalityEncoder(nn.Module):
         super().__init__()
         self.net = nn.Sequential(nn.BatchNorm1d(input_dim), nn.Linear(input_dim, output_dim))
 
-    def forward(self, x):  # pragma: no cover
-        raise L.TspmError("MMIMDbModalityEncoder runs inside MMIMDb's HIP engine (call the MMIMDb model)")
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        """Inference embedding of x [n, input_dim] (eval mode or under ``torch.no_grad()``): BatchNorm1d on its
+        running statistics (``tspm_bn_apply_eval``) → Linear (``tspm_linear_fwd``).  Training runs inside
+        MMIMDb's engine or MonomodalEncoder's fused step, never through an autograd node here."""
+        if not torch.is_tensor(x) or not x.is_cuda:
+            raise L.TspmError("MMIMDbModalityEncoder (tspm_amd) runs on the MI355X only (there is no CPU fallback)")
+        if self.training and torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+            raise L.TspmError("MMIMDbModalityEncoder: train it inside MMIMDb or MonomodalEncoder (the fused HIP "
+                              "step with FusedAdam); this forward is inference only (eval() or torch.no_grad())")
+        bn, fc = self.net[0], self.net[1]
+        if x.dim() != 2 or x.shape[1] != bn.num_features:
+            raise L.TspmError(f"MMIMDbModalityEncoder: expected [n, {bn.num_features}] features, got {tuple(x.shape)}")
+        x = x.detach().float().contiguous()
+        n, fin, fout = x.shape[0], bn.num_features, fc.out_features
+        g, b, rm, rv, eps, _ = _bn(bn)
+        lib, sh = L.lib(), L.stream_handle()
+        xn = torch.empty_like(x)
+        emb = torch.empty(n, fout, device=x.device, dtype=torch.float32)
+        L.check(lib.tspm_bn_apply_eval(n, fin, x.data_ptr(), rm.data_ptr(), rv.data_ptr(), eps, g.data_ptr(),
+                                       b.data_ptr(), 0, None, None, None, None, None, 0, xn.data_ptr(), sh),
+                "bn_apply_eval")
+        L.check(lib.tspm_linear_fwd(n, fin, fout, xn.data_ptr(), fin, fc.weight.data_ptr(), fc.bias.data_ptr(), 0,
+                                    None, 1.0, emb.data_ptr(), fout, sh), "encoder fc")
+        return emb
 
 
 class GatedBiModalNetwork(nn.Module):
@@ -791,6 +813,56 @@ class MMIMDbCorpus:
                                   (self.labels, self.labels.shape[1], None, Y_out)):
             L.check(lib.tspm_avmnist_gather(n, index.data_ptr(), self.n, src.data_ptr(), w, None, 0, None, None,
                                             L.ptr(mask), None, out.data_ptr(), None, None, sh), "mmimdb gather")
+
+    def mono_loader(self, modality: str, batch: int, shuffle: bool = False, seed: int = 0,
+                    drop_last: bool = False) -> "MonoLoader":
+        """Single-modality batches ``{modality: [b, dim], "label": [b, genres]}`` for the encoder pre-training
+        (monomodal.MonomodalEncoder / fit_monomodal), gathered on the device with ``gather``'s kernel."""
+        return MonoLoader(self, modality, batch, shuffle, seed, drop_last)
+
+    def gather_rows(self, index: torch.Tensor, src: torch.Tensor, out: torch.Tensor, mask=None) -> None:
+        """out = src[index] (* mask per row): one ``tspm_avmnist_gather`` launch, as ``gather`` issues per tensor."""
+        L.check(L.lib().tspm_avmnist_gather(index.numel(), index.data_ptr(), self.n, src.data_ptr(), src.shape[1], None,
+                                            0, None, None, L.ptr(mask), None, out.data_ptr(), None, None,
+                                            L.stream_handle()), "mmimdb gather")
+
+
+class MonoLoader:
+    """Re-iterable loader over an MMIMDbCorpus for one modality ("image" | "text"): every epoch draws a new
+    permutation from its seeded generator (``shuffle``) and gathers each batch with ``MMIMDbCorpus.gather_rows`` into
+    per-batch-size device buffers (reused: consume a batch before taking the next).  Only the modality's features
+    and the labels are gathered."""
+
+    def __init__(self, corpus: MMIMDbCorpus, modality: str, batch: int, shuffle: bool, seed: int, drop_last: bool):
+        if modality not in ("image", "text"):
+            raise ValueError(f"Invalid modality: {modality}. Must be image or text")
+        if batch < 1:
+            raise ValueError("batch must be positive")
+        self.corpus, self.modality, self.batch = corpus, modality, int(batch)
+        self.shuffle, self.drop_last = shuffle, drop_last
+        self.gen = torch.Generator(device="cpu").manual_seed(seed)
+        self._bufs: Dict[int, Any] = {}
+
+    def __len__(self) -> int:
+        n, b = self.corpus.n, self.batch
+        return n // b if self.drop_last else -(-n // b)
+
+    def __iter__(self):
+        c = self.corpus
+        order = (torch.randperm(c.n, generator=self.gen) if self.shuffle else torch.arange(c.n)).to(c.device)
+        for s in range(0, c.n, self.batch):
+            rows = order[s:s + self.batch]
+            n = rows.numel()
+            if self.drop_last and n < self.batch:
+                break
+            src = c.image if self.modality == "image" else c.text
+            if n not in self._bufs:
+                f = dict(device=c.device, dtype=torch.float32)
+                self._bufs[n] = (torch.empty(n, src.shape[1], **f), torch.empty(n, c.labels.shape[1], **f))
+            X, Y = self._bufs[n]
+            c.gather_rows(rows, src, X)
+            c.gather_rows(rows, c.labels, Y)
+            yield {self.modality: X, "label": Y}
 
 
 def _evaluate(model: MMIMDb, corpus: MMIMDbCorpus, batch: int, weight: float, pattern: str) -> Dict[str, float]:

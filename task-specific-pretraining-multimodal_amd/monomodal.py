@@ -20,6 +20,10 @@ pretrained late-fusion config loads (train_monomodal.py:789-802, train_multimoda
   predictions and the classifier's backward in one launch; ``fused_head=False`` keeps the four separate
   launches) → encoder backward → FusedAdam.  Learning rate, weight decay and batch size are the caller's
   optimizer and loader arguments.
+* :class:`FusedMMIMDbMonoStep` / :class:`FusedMMIMDbMonoEvalStep` — the same two steps around an MMIMDb encoder
+  (``mmimdb.MMIMDbModalityEncoder``: BatchNorm1d → Linear) under the multi-label classifier: ``tspm_bn1d_fwd`` →
+  ``tspm_linear_fwd`` → the head (``tspm_mono_head_bce_step``, or ``fused_head=False``: ``tspm_linear_fwd``,
+  ``tspm_bce_logits``, ``tspm_linear_bwd``) → encoder Linear backward → ``tspm_bn1d_bwd`` → FusedAdam.
 * :func:`select_modality_key` — the reference's choice of the batch key (train_monomodal.py:103-128).
 * :class:`MonoEpochRunner` / :func:`fit_monomodal` — the epoch loop of ``train_monomodal``
   (train_monomodal.py:536-884) on those steps, one host read per epoch.
@@ -52,6 +56,11 @@ _RESERVED = ("labels", "label", "genres", "imdb_ids", "pattern_name", "missing_m
 # MonomodalEncoder(fused_head=...) default for MOSI encoders: tspm_mono_head_step against the four separate launches,
 # graph-replayed at B=128, T=50 (scripts/bench_mosi_mono.py, profiles/mosi_mono_head_ab.json)
 FUSED_HEAD_DEFAULT = True
+# ... and for MMIMDb encoders: tspm_mono_head_bce_step against tspm_linear_fwd + tspm_bce_logits + tspm_linear_bwd,
+# graph-replayed at B = 128 / 256, image and text (scripts/bench_mmimdb_mono.py, profiles/mmimdb_mono_head_ab.json;
+# DESIGN.md §7): faster beyond the spread at 256 in both cases, not at 128
+FUSED_BCE_HEAD_MIN_BATCH = 256  # fused_head=None: the head kernel from this batch size up, the separate launches below
+BCE_HEAD_MAX_N, BCE_HEAD_MAX_HID, BCE_HEAD_MAX_CLASSES = 1024, 512, 32  # tspm_mono_head_bce_step's limits
 
 
 def _exp_name(config) -> str:
@@ -453,6 +462,240 @@ class FusedMosiMonoEvalStep(_MosiMonoBuffers):
         return {"loss": self.loss, "logits": self.logits, "preds": self.preds}
 
 
+def _bce_weight_of(loss_functions, who: str) -> float:
+    """mmimdb._bce_weight, with anything that is not a loss group refused the same way."""
+    from .mmimdb import _bce_weight
+    try:
+        return _bce_weight(loss_functions)
+    except AttributeError:
+        raise L.TspmError(f"{who}: the loss group must be a single bce_with_logits term (got "
+                          f"{type(loss_functions).__name__})") from None
+
+
+def bce_head_supported(n: int, hid: int, classes: int) -> bool:
+    """tspm_mono_head_bce_step's shape limits (csrc/mmimdb.hip: HB_MAXN / HB_MAXH / HB_MAXC)."""
+    return 1 <= n <= BCE_HEAD_MAX_N and 4 <= hid <= BCE_HEAD_MAX_HID and hid % 4 == 0 and \
+        1 <= classes <= BCE_HEAD_MAX_CLASSES
+
+
+def bce_head_choice(requested: Optional[bool], n: int, hid: int, classes: int) -> bool:
+    """Whether a step of this shape runs tspm_mono_head_bce_step: ``requested`` (None = the measured default, from
+    FUSED_BCE_HEAD_MIN_BATCH rows up), and never outside the kernel's limits (the separate launches take those)."""
+    if requested is None:
+        requested = n >= FUSED_BCE_HEAD_MIN_BATCH
+    return bool(requested) and bce_head_supported(n, hid, classes)
+
+
+class _MMIMDbMonoBuffers:
+    """What the MMIMDb-encoder train and eval steps share: the static buffers for one (batch, in), the graph
+    bookkeeping and the multi-label head — ``tspm_mono_head_bce_step`` or the separate launches
+    (``tspm_linear_fwd``, ``tspm_bce_logits``, ``tspm_linear_bwd``)."""
+
+    THRESHOLD = 0.5  # train_monomodal.py: torch.sigmoid(logits) > 0.5
+
+    def _init_mmimdb(self, model, loss_functions, x_shape, fused_head: Optional[bool], who: str) -> None:
+        from .mmimdb import MMIMDbModalityEncoder
+        enc, cls = model.encoder, model.classifier
+        if not isinstance(enc, MMIMDbModalityEncoder):
+            raise L.TspmError(f"{who}: the encoder must be an MMIMDbModalityEncoder")
+        self.weight = _bce_weight_of(loss_functions, who)
+        dev = next(model.parameters()).device
+        if dev.type != "cuda":
+            raise L.TspmError(f"{who} runs on the MI355X: move the model to cuda first")
+        n, fin = (int(v) for v in x_shape)
+        self.bn, self.fc = enc.net[0], enc.net[1]
+        if fin != self.bn.num_features:
+            raise L.TspmError(f"input features {fin} != encoder input_dim {self.bn.num_features}")
+        if cls.in_features != self.fc.out_features:
+            raise L.TspmError(f"classifier input {cls.in_features} != encoder output_dim {self.fc.out_features}")
+        self.model, self.device, self.N, self.fin = model, dev, n, fin
+        self.hid, self.K = cls.in_features, cls.out_features
+        self.fused_head = bce_head_choice(model.fused_head if fused_head is None else fused_head, n, self.hid, self.K)
+        f32 = dict(device=dev, dtype=torch.float32)
+        self.X = torch.zeros(n, fin, **f32)
+        self.labels = torch.zeros(n, self.K, **f32)
+        self.Xn = torch.empty(n, fin, **f32)
+        self.emb = torch.empty(n, self.hid, **f32)
+        self.logits = torch.empty(n, self.K, **f32)
+        self.loss = torch.zeros(1, **f32)
+        self.stats = torch.zeros(3 + 3 * self.K, **f32)  # tspm_bce_logits' accumulators (mmimdb.f1_metrics)
+        self._preds = torch.zeros(n, self.K, dtype=torch.uint8, device=dev) if self.fused_head else None
+        lib = L.lib()
+        if self.fused_head:
+            self.head_ws_bytes = int(lib.tspm_mono_head_bce_workspace(n, self.hid, self.K))
+            self.head_ws = torch.zeros(self.head_ws_bytes // 4, **f32)  # the arrival counter starts at zero
+        # split-K for the long (image) Linear when its output tiles cannot fill the chip, as MMIMDbEngine does
+        tiles = -(-n // 32) * -(-self.hid // 32)
+        self.splits = 4 if (fin >= 2048 and tiles < 256) else 1
+        wsb = lib.tspm_linear_fwd_splitk_workspace(n, fin, self.hid, self.splits) if self.splits > 1 else 0
+        self.ws = torch.zeros(max(int(wsb) // 4, 4), **f32)
+        self.graph: Optional[torch.cuda.CUDAGraph] = None
+        self.calls = 0
+        self.log = None  # the multi-label counts live in ``stats``; no ClassificationLog on this path
+
+    @property
+    def preds(self) -> torch.Tensor:
+        """bool [n, classes]: the head kernel's predictions, or (separate launches) sigmoid(logits) > 0.5."""
+        if self._preds is not None:
+            return self._preds.bool()
+        return torch.sigmoid(self.logits) > self.THRESHOLD
+
+    def _encoder_fc(self, lib, sh: int) -> None:
+        fc, n = self.fc, self.N
+        if self.splits > 1:
+            L.check(lib.tspm_linear_fwd_splitk(n, self.fin, self.hid, self.Xn.data_ptr(), self.fin, fc.weight.data_ptr(),
+                                               fc.bias.data_ptr(), 0, None, 1.0, self.emb.data_ptr(), self.hid,
+                                               self.splits, self.ws.data_ptr(), self.ws.numel() * 4, sh), "encoder fc")
+        else:
+            L.check(lib.tspm_linear_fwd(n, self.fin, self.hid, self.Xn.data_ptr(), self.fin, fc.weight.data_ptr(),
+                                        fc.bias.data_ptr(), 0, None, 1.0, self.emb.data_ptr(), self.hid, sh),
+                    "encoder fc")
+
+    def _head(self, lib, sh: int, train: bool) -> None:
+        n, hid, K = self.N, self.hid, self.K
+        cls = self.model.classifier
+        if self.fused_head:
+            d = L.MonoHeadBceDesc()
+            d.n, d.hid, d.classes, d.ld_emb, d.ld_demb = n, hid, K, hid, hid
+            d.loss_weight, d.threshold = self.weight, self.THRESHOLD
+            d.emb, d.w, d.b = self.emb.data_ptr(), cls.weight.data_ptr(), cls.bias.data_ptr()
+            d.targets, d.logits, d.loss = self.labels.data_ptr(), self.logits.data_ptr(), self.loss.data_ptr()
+            d.preds, d.stats = self._preds.data_ptr(), self.stats.data_ptr()
+            d.workspace, d.workspace_bytes = self.head_ws.data_ptr(), self.head_ws_bytes
+            if train:
+                d.dw, d.db, d.demb = cls.weight.grad.data_ptr(), cls.bias.grad.data_ptr(), self.demb.data_ptr()
+            L.check(lib.tspm_mono_head_bce_step(ctypes.byref(d), sh), "mono_head_bce_step")
+            return
+        L.check(lib.tspm_linear_fwd(n, hid, K, self.emb.data_ptr(), hid, cls.weight.data_ptr(), cls.bias.data_ptr(), 0,
+                                    None, 1.0, self.logits.data_ptr(), K, sh), "classifier fwd")
+        L.check(lib.tspm_bce_logits(n, K, self.logits.data_ptr(), self.labels.data_ptr(), self.loss.data_ptr(),
+                                    self.dlogits.data_ptr() if train else None, self.weight, self.THRESHOLD,
+                                    self.stats.data_ptr(), sh), "bce_with_logits")
+        if train:
+            linear_bwd(n, hid, K, self.emb.data_ptr(), hid, self.dlogits.data_ptr(), K, cls.weight.data_ptr(),
+                       cls.weight.grad.data_ptr(), cls.bias.grad.data_ptr(), self.demb.data_ptr(), hid, sh)
+
+    def _replay_or_enqueue(self) -> None:
+        if not self.use_graph or self.calls == 0:
+            self._enqueue()
+        else:
+            if self.graph is None:
+                torch.cuda.synchronize(self.device)
+                g = torch.cuda.CUDAGraph()
+                with L.graph_capture(g):
+                    self._enqueue()
+                self.graph = g
+            self.graph.replay()
+        self.calls += 1
+
+    def load_batch(self, x: torch.Tensor, labels: torch.Tensor) -> None:
+        if x.data_ptr() != self.X.data_ptr():
+            self.X.copy_(x.reshape(self.X.shape), non_blocking=True)
+        if labels.data_ptr() != self.labels.data_ptr():
+            self.labels.copy_(labels.reshape(self.labels.shape), non_blocking=True)
+
+    def matches_shape(self, x: torch.Tensor) -> bool:
+        return tuple(x.shape) == (self.N, self.fin)
+
+    def step(self, x: torch.Tensor, labels: torch.Tensor) -> Dict[str, torch.Tensor]:
+        self.load_batch(x, labels)
+        self.run()
+        return {"loss": self.loss, "logits": self.logits, "preds": self.preds}
+
+
+class FusedMMIMDbMonoStep(_MMIMDbMonoBuffers):
+    """MonomodalEncoder.train_step around an MMIMDbModalityEncoder (BatchNorm1d(in) → Linear(in, out)) under the
+    multi-label classifier as one HIP graph:
+
+        tspm_bn1d_fwd → tspm_linear_fwd → head (tspm_mono_head_bce_step: classifier, BCEWithLogits, predictions,
+        F1 counts, classifier backward) → encoder Linear backward → tspm_bn1d_bwd (no dx) → FusedAdam →
+        num_batches_tracked
+
+    ``x_shape`` is (batch, in).  ``fused_head=False`` runs the head as ``tspm_linear_fwd``, ``tspm_bce_logits`` and
+    ``tspm_linear_bwd`` (also taken for shapes outside the head kernel's limits).  Gradients go straight into
+    FusedAdam's flat views (overwritten).  First call eager, second captures, later calls replay."""
+
+    def __init__(self, model, optimizer: FusedAdam, loss_functions, x_shape, use_graph: bool = True, log=None,
+                 fused_head: Optional[bool] = None):
+        if not isinstance(optimizer, FusedAdam):
+            raise L.TspmError("FusedMMIMDbMonoStep needs tspm_amd.FusedAdam (the flat gradient buffer the kernels "
+                              "write)")
+        self._init_mmimdb(model, loss_functions, x_shape, fused_head, "FusedMMIMDbMonoStep")
+        if self.N < 2:
+            raise L.TspmError("BatchNorm1d in training mode needs more than one sample per batch")
+        model.train()
+        for p in model.parameters():
+            if p.requires_grad and p.grad is None:
+                raise L.TspmError("FusedMMIMDbMonoStep: parameter without a FusedAdam gradient view")
+        self.opt = optimizer
+        self.use_graph = use_graph and not os.environ.get("TSPM_NO_GRAPH")
+        f32 = dict(device=self.device, dtype=torch.float32)
+        self.mean, self.inv = torch.zeros(self.fin, **f32), torch.zeros(self.fin, **f32)
+        self.demb = torch.empty(self.N, self.hid, **f32)
+        self.dXn = torch.empty(self.N, self.fin, **f32)
+        self.dlogits = torch.empty(self.N, self.K, **f32)
+        self.nbt = shared_batches_tracked(model, self.device, (nn.BatchNorm1d,))
+        self._sig = (id(optimizer), id(loss_functions), self.fused_head)
+
+    def matches(self, x: torch.Tensor, optimizer, loss_functions, fused_head: Optional[bool] = None) -> bool:
+        fh = bce_head_choice(self.model.fused_head if fused_head is None else fused_head, self.N, self.hid, self.K)
+        return self._sig == (id(optimizer), id(loss_functions), fh) and self.matches_shape(x)
+
+    def _enqueue(self) -> None:
+        from .mmimdb import _bn
+        lib = L.lib()
+        sh = torch.cuda.current_stream().cuda_stream
+        n, fin, hid = self.N, self.fin, self.hid
+        bn, fc = self.bn, self.fc
+        g, b, rm, rv, eps, mom = _bn(bn)
+        L.check(lib.tspm_bn1d_fwd(n, fin, self.X.data_ptr(), g.data_ptr(), b.data_ptr(), rm.data_ptr(), rv.data_ptr(),
+                                  mom, eps, self.mean.data_ptr(), self.inv.data_ptr(), self.Xn.data_ptr(), sh),
+                "bn1d_fwd")
+        self._encoder_fc(lib, sh)
+        self._head(lib, sh, True)
+        # encoder Linear: weight and bias gradients, and the data gradient the BatchNorm1d backward needs
+        linear_bwd(n, fin, hid, self.Xn.data_ptr(), fin, self.demb.data_ptr(), hid, fc.weight.data_ptr(),
+                   fc.weight.grad.data_ptr(), fc.bias.grad.data_ptr(), self.dXn.data_ptr(), fin, sh)
+        L.check(lib.tspm_bn1d_bwd(n, fin, self.dXn.data_ptr(), self.X.data_ptr(), self.mean.data_ptr(),
+                                  self.inv.data_ptr(), bn.weight.data_ptr(), bn.weight.grad.data_ptr(),
+                                  bn.bias.grad.data_ptr(), None, sh), "bn1d_bwd")
+        self.opt.launch(sh)
+        L.counters_add(self.nbt)
+
+    def run(self) -> None:
+        """One training step on the batch in the static input buffers."""
+        self.model.train()
+        self.opt.sync_hyper()
+        self._replay_or_enqueue()
+        self.opt.note_steps(1)
+
+
+class FusedMMIMDbMonoEvalStep(_MMIMDbMonoBuffers):
+    """MonomodalEncoder.validation_step around an MMIMDbModalityEncoder as one HIP graph: ``tspm_bn_apply_eval``
+    (running statistics), the Linear, and the head in forward-only mode (logits, weighted BCE, predictions, F1
+    counts)."""
+
+    def __init__(self, model, loss_functions, x_shape, log=None, use_graph: bool = True,
+                 fused_head: Optional[bool] = None):
+        self._init_mmimdb(model, loss_functions, x_shape, fused_head, "FusedMMIMDbMonoEvalStep")
+        self.use_graph = use_graph and not os.environ.get("TSPM_NO_GRAPH")
+
+    def _enqueue(self) -> None:
+        from .mmimdb import _bn
+        lib = L.lib()
+        sh = torch.cuda.current_stream().cuda_stream
+        g, b, rm, rv, eps, _ = _bn(self.bn)
+        L.check(lib.tspm_bn_apply_eval(self.N, self.fin, self.X.data_ptr(), rm.data_ptr(), rv.data_ptr(), eps,
+                                       g.data_ptr(), b.data_ptr(), 0, None, None, None, None, None, 0,
+                                       self.Xn.data_ptr(), sh), "bn_apply_eval")
+        self._encoder_fc(lib, sh)
+        self._head(lib, sh, False)
+
+    def run(self) -> None:
+        self.model.eval()
+        self._replay_or_enqueue()
+
+
 class _MosiMonoFn(torch.autograd.Function):
     """MonomodalEncoder.forward around a MOSI encoder as one autograd node (encoder + classifier on the HIP
     schedule, forward and backward), for the reference's own train_step sequence with a torch optimizer."""
@@ -495,7 +738,7 @@ class _MosiMonoFn(torch.autograd.Function):
 class MonomodalEncoder(nn.Module):
     """train_monomodal.py:64-95 drop-in: ``encoder`` + ``classifier``, executed on libtspm."""
 
-    def __init__(self, encoder: nn.Module, output_dim: int, num_classes: int, fused_head: bool = FUSED_HEAD_DEFAULT):
+    def __init__(self, encoder: nn.Module, output_dim: int, num_classes: int, fused_head: Optional[bool] = None):
         super().__init__()
         self.encoder = encoder
         self.classifier = nn.Linear(output_dim, num_classes)
@@ -503,7 +746,12 @@ class MonomodalEncoder(nn.Module):
         self._eval_steps: Dict[Tuple, FusedMonoEvalStep] = {}
         # MOSI / MOSEI encoders (mosi.LSTMEncoder / mosi.TextCNN): the head in one launch (tspm_mono_head_step)
         # or, fused_head=False, the separate classifier / CE / classify / classifier-backward launches
-        self.fused_head = bool(fused_head)
+        # MMIMDb encoders (mmimdb.MMIMDbModalityEncoder): tspm_mono_head_bce_step or, fused_head=False, tspm_linear_fwd /
+        # tspm_bce_logits / tspm_linear_bwd.  None = the measured default: FUSED_HEAD_DEFAULT for the MOSI encoders,
+        # per batch size for the MMIMDb ones (bce_head_choice)
+        if fused_head is None and not self._mmimdb_encoder():
+            fused_head = FUSED_HEAD_DEFAULT
+        self.fused_head = None if fused_head is None else bool(fused_head)
         self._rng_seed = int(torch.initial_seed()) & ((1 << 63) - 1)  # the TextCNN dropout masks' seed
         self._mosi_engines: Dict[Tuple, Any] = {}
         self._by_buffer: Dict[int, Any] = {}  # input buffer address -> the MOSI step that owns it
@@ -556,9 +804,37 @@ class MonomodalEncoder(nn.Module):
         from .mosi import LSTMEncoder, TextCNN
         return isinstance(self.encoder, (LSTMEncoder, TextCNN))
 
+    def _mmimdb_encoder(self) -> bool:
+        from .mmimdb import MMIMDbModalityEncoder
+        return isinstance(self.encoder, MMIMDbModalityEncoder)
+
+    def _check_mmimdb_step(self, x: torch.Tensor, labels: torch.Tensor, optimizer, loss_functions, train: bool) -> None:
+        """An MMIMDbModalityEncoder trains and validates on the fused HIP steps only: anything they cannot take is
+        refused here (no autograd node is built for this encoder)."""
+        who = "MonomodalEncoder around an MMIMDbModalityEncoder"
+        try:
+            _bce_weight_of(loss_functions, who)
+        except L.TspmError as e:
+            raise L.TspmError(f"{who}: unsupported loss group ({e}); this encoder has no autograd path") from None
+        if train and not isinstance(optimizer, FusedAdam):
+            raise L.TspmError(f"{who} trains with tspm_amd.FusedAdam only (got {type(optimizer).__name__}): this "
+                              "encoder has no autograd path")
+        if not x.is_cuda:
+            raise L.TspmError("MonomodalEncoder (tspm_amd) runs on the MI355X only (there is no CPU fallback)")
+        if x.dim() != 2 or labels.dim() != 2 or not labels.is_floating_point():
+            raise L.TspmError(f"{who}: expected [n, in] features and float multi-hot [n, classes] labels, got "
+                              f"{tuple(x.shape)} and {labels.dtype} {tuple(labels.shape)}")
+
     def train_step_fused(self, x: torch.Tensor, labels: torch.Tensor, optimizer, loss_functions,
                          log: Optional[ClassificationLog] = None) -> FusedMonoStep:
         """Run one fused step on device tensors and return the step (its loss / logits / preds buffers)."""
+        if self._mmimdb_encoder():
+            self._check_mmimdb_step(x, labels, optimizer, loss_functions, True)
+            if not isinstance(self._fused, FusedMMIMDbMonoStep) or \
+                    not self._fused.matches(x, optimizer, loss_functions):
+                self._fused = FusedMMIMDbMonoStep(self, optimizer, loss_functions, tuple(x.shape))
+            self._fused.step(x, labels)
+            return self._fused
         if self._fused is None or not self._fused.matches(x, optimizer, loss_functions):
             own = self._by_buffer.get(x.data_ptr())
             if self._mosi_encoder():
@@ -573,6 +849,11 @@ class MonomodalEncoder(nn.Module):
     def eval_step_for(self, loss_functions, x_shape, log=None) -> FusedMonoEvalStep:
         key = tuple(x_shape)
         st = self._eval_steps.get(key)
+        if self._mmimdb_encoder():
+            if st is None or st.weight != _bce_weight_of(loss_functions, "MonomodalEncoder") or \
+                    st.fused_head != bce_head_choice(self.fused_head, st.N, st.hid, st.K):
+                st = self._eval_steps[key] = FusedMMIMDbMonoEvalStep(self, loss_functions, key)
+            return st
         if st is None or st.ce_weight != _ce_weight(loss_functions) or \
                 getattr(st, "fused_head", self.fused_head) != self.fused_head:
             cls = FusedMosiMonoEvalStep if self._mosi_encoder() else FusedMonoEvalStep
@@ -594,6 +875,9 @@ class MonomodalEncoder(nn.Module):
         group; otherwise the reference's autograd sequence on the HIP encoder / classifier."""
         key, x, labels = self._inputs(batch, config, device)
         dlog = _device_log(metric_recorder)
+        if self._mmimdb_encoder():
+            st = self.train_step_fused(x, labels, optimizer, loss_functions)
+            return self._finish(metric_recorder, dlog, key, st.preds, labels, st.loss)
         fused = (not os.environ.get("TSPM_DISABLE_FUSED_STEP") and isinstance(optimizer, FusedAdam)
                  and _ce_weight(loss_functions) is not None and x.is_cuda and labels.dim() == 1
                  and ((self._hip_encoder() and x.dim() in (3, 4)) or (self._mosi_encoder() and x.dim() == 3)))
@@ -615,6 +899,11 @@ class MonomodalEncoder(nn.Module):
         with torch.no_grad():
             key, x, labels = self._inputs(batch, config, device)
             dlog = _device_log(metric_recorder)
+            if self._mmimdb_encoder():
+                self._check_mmimdb_step(x, labels, None, loss_functions, False)
+                st = self.eval_step_for(loss_functions, tuple(x.shape))
+                st.step(x, labels)
+                return self._finish(metric_recorder, dlog, key, st.preds, labels, st.loss)
             if (not self.training and _ce_weight(loss_functions) is not None and x.is_cuda and labels.dim() == 1
                     and ((self._hip_encoder() and x.dim() in (3, 4)) or (self._mosi_encoder() and x.dim() == 3))):
                 st = self._eval_step_of(x, loss_functions, dlog)
@@ -671,6 +960,7 @@ class MonoEpochRunner:
         self.recorder: Optional[DeviceMetricRecorder] = None
         self.train_steps: Dict[Tuple, FusedMonoStep] = {}
         self._mosi = model._mosi_encoder()
+        self._mmimdb = model._mmimdb_encoder()
 
     # MOSI encoders: ``mosi_data.MOSI.loader(...)``'s ``step_for`` hooks — the loader gathers each batch time-major
     # straight into the step's input buffer (set on every loader that has the attribute, as harness.MosiHarness does)
@@ -718,8 +1008,53 @@ class MonoEpochRunner:
         if not started:
             raise ValueError("empty loader")
 
+    def _multilabel_epoch(self, loader, train: bool) -> Tuple[Dict[str, Any], float]:
+        """An epoch around an MMIMDbModalityEncoder: per batch one graph replay; the head's F1 accumulators and the
+        per-batch losses stay on the device and are read once.  Epoch dict = ``loss`` (np.mean over the batches, as
+        the reference) + mmimdb.f1_metrics of the epoch's counts, keys ``f"{metric}_{MODALITY}"``.  A one-row
+        training batch is skipped (BatchNorm1d in training mode rejects it, in the reference too)."""
+        from .mmimdb import f1_metrics
+        t0 = time.time()
+        self.model.train(train)
+        used: List[Any] = []
+        losses: List[torch.Tensor] = []
+        key = None
+        for b in loader:
+            key, x, lab = self.model._inputs(b, self.experiment_name, self.device)
+            if not used:
+                self.model._check_mmimdb_step(x, lab, self.optimizer, self.loss_functions, train)
+            shape = tuple(x.shape)
+            if train:
+                if shape[0] < 2:
+                    continue
+                st = self.train_steps.get(shape)
+                if st is None or not st.matches(x, self.optimizer, self.loss_functions):
+                    st = self.train_steps[shape] = FusedMMIMDbMonoStep(self.model, self.optimizer,
+                                                                       self.loss_functions, shape)
+            else:
+                st = self.model.eval_step_for(self.loss_functions, shape)
+            if not any(st is u for u in used):
+                st.stats.zero_()
+                used.append(st)
+            st.load_batch(x, lab)
+            st.run()
+            losses.append(st.loss.clone())
+        if not used:
+            raise ValueError("empty loader")
+        classes = self.model.classifier.out_features
+        host = torch.cat([torch.stack([u.stats for u in used]).sum(0), torch.cat(losses)]).cpu()  # the epoch's one read
+        stats, per_batch = host[:3 + 3 * classes], host[3 + 3 * classes:]
+        out: Dict[str, Any] = {"loss": float(np.mean(per_batch.numpy()))}
+        tag = str(key).replace("z", "").upper()
+        for name, v in f1_metrics(stats, classes).items():
+            if name != "loss":
+                out[f"{name}_{tag}"] = v
+        return out, time.time() - t0
+
     def train_epoch(self, loader: Iterable[Dict[str, Any]]):
         """→ (epoch metrics dict, seconds)."""
+        if self._mmimdb:
+            return self._multilabel_epoch(loader, True)
         t0 = time.time()
         accs: List[torch.Tensor] = []
         self.model.train()
@@ -739,6 +1074,8 @@ class MonoEpochRunner:
 
     @torch.no_grad()
     def validate_epoch(self, loader: Iterable[Dict[str, Any]]):
+        if self._mmimdb:
+            return self._multilabel_epoch(loader, False)
         t0 = time.time()
         accs: List[torch.Tensor] = []
         self.model.eval()
@@ -762,6 +1099,9 @@ def fit_monomodal(model: MonomodalEncoder, optimizer, loss_functions, loaders: D
     every epoch (the reference re-creates its scheduler each epoch, train_monomodal.py:810-815, so a
     ReduceLROnPlateau never accumulates patience — reproduced, not fixed) → test on the best model."""
     from .harness import CheckpointManager
+    if model._mmimdb_encoder() and save_metric != "loss":
+        raise ValueError(f"save_metric {save_metric!r}: a multi-label (MMIMDb) pre-training run has no accuracy; "
+                         "only save_metric='loss' is supported")
     runner = MonoEpochRunner(model, optimizer, loss_functions, experiment_name, metric_config)
     out_dir = Path(model_output_path) if model_output_path is not None else None
     ckpt = CheckpointManager(out_dir, save_metric, "minimize" if save_metric == "loss" else "maximize") \
