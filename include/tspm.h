@@ -50,7 +50,8 @@ enum {
  * 23 = tspm_mono_head_step, the monomodal pre-training head (classifier, cross-entropy, predictions, backward) in
  * one launch.  Added under 23 with no existing signature or struct changed (callers built against 23 keep working):
  * tspm_mono_head_bce_step / tspm_mono_head_bce_workspace, the multi-label (BCEWithLogits, F1 counts) form of that
- * head for the MMIMDb encoder pre-training step. */
+ * head for the MMIMDb encoder pre-training step; tspm_regress_head_step, the scalar-output head of the MOSI / MOSEI
+ * sentiment regression (L1 / MSE, backward, epoch accumulators, loss log) in one launch. */
 #define TSPM_ABI_VERSION 23
 int tspm_abi_version(void);  /* returns TSPM_ABI_VERSION */
 /* Static string for a status code. */
@@ -872,6 +873,59 @@ typedef struct tspm_mono_head_bce_desc {
 } tspm_mono_head_bce_desc;
 size_t tspm_mono_head_bce_workspace(int32_t n, int32_t hid, int32_t classes);
 int tspm_mono_head_bce_step(const tspm_mono_head_bce_desc* desc, tspm_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Regression head (added under ABI 23) — the scalar-output head Linear(hid, 1) of the CMU-MOSI / CMU-MOSEI sentiment
+ * regression (continuous score in [-3, 3]): FcClassifier.fc_out of the fusion model (hid 32 / 48) or the
+ * MonomodalEncoder's classifier (hid 64), with a float32 label per row, in ONE launch of ONE workgroup:
+ *   pred[r] = emb[r] . w + b;  e_r = pred[r] - labels[r];  loss[0] = loss_weight * mean_r l(e_r)
+ *   kind TSPM_REGRESS_L1:  l = |e|,  dpred = loss_weight * sign(e) / n   (sign(0) = 0, as torch)
+ *   kind TSPM_REGRESS_MSE: l = e^2,  dpred = loss_weight * 2 e / n
+ *   dw = sum_r dpred_r emb[r],  db = sum_r dpred_r,  demb[r] = dpred_r w   (all overwritten; padding columns of demb
+ *   untouched).  Forward-only mode (dw, db and demb all NULL) gives bitwise the training mode's pred and loss.
+ * stats (nullable): one tspm_regress_stats record per pattern group, g = groups ? groups[r] : 0; the call ADDS to
+ * every field over its rows.  e for the sums is (double)pred - (double)label.  conf7 is indexed
+ * [rintf(clip(y,-3,3)) + 3][rintf(clip(p,-3,3)) + 3] (half-to-even, numpy's round); sign3 by the sign of y and of p
+ * (0 negative, 1 zero, 2 positive; compared in fp32).  Acc-7 / Acc-5 / Acc-3 follow from conf7 (clipping to +-2 or
+ * +-1 after rounding equals rounding after that clip), both binary tasks from sign3, MAE and Pearson's r from the
+ * sums.  A row whose label or prediction is NaN, or whose group is outside [0, n_groups), is left out of every
+ * field (it still makes the loss NaN), as tspm_classify_update leaves out an out-of-range label.
+ * counters (nullable), once per call: loss_log[counters[0]] = loss[0] (if loss_log and counters[0] < log_capacity),
+ * counters[0] += 1, counters[1] += n — tspm_classify_update's log.
+ * The rows are walked in chunks of 64 staged in LDS; the loss and the seven sums run in double in a fixed order: no
+ * atomics, no workspace, two runs on the same input are bitwise equal and k calls add the same bits to the
+ * accumulators in every run.
+ * Limits: 1 <= n <= 1024; hid <= 128 and a multiple of 4; ld_emb, ld_demb >= hid and multiples of 4 with emb / demb
+ * 16-byte aligned; dw, db, demb all given or all NULL; kind 0 or 1; with stats 1 <= n_groups <= 16; loss_log needs
+ * counters; otherwise TSPM_ERR_INVALID before any launch. */
+#define TSPM_REGRESS_L1 0
+#define TSPM_REGRESS_MSE 1
+typedef struct tspm_regress_stats { /* 66 8-byte words */
+  int64_t n;                                                     /* rows counted */
+  double sum_abs, sum_sq, sum_p, sum_y, sum_pp, sum_yy, sum_py;  /* sum |e|, e^2, p, y, p^2, y^2, p y */
+  int64_t conf7[7][7];                                           /* [rounded clipped label + 3][... prediction + 3] */
+  int64_t sign3[3][3];                                           /* [sign of label][sign of prediction] */
+} tspm_regress_stats;
+typedef struct tspm_regress_head_desc {
+  int32_t n, hid, ld_emb, ld_demb, kind, n_groups;
+  float loss_weight;         /* the loss term's weight */
+  int32_t reserved_;
+  const float* emb;          /* [n, ld_emb] */
+  const float* w;            /* [1, hid] */
+  const float* b;            /* [1] */
+  const float* labels;       /* [n] */
+  const int32_t* groups;     /* nullable: [n] */
+  float* pred;               /* [n] (= logits [n, 1]) */
+  float* loss;               /* loss[0] */
+  float* dw;                 /* [1, hid] */
+  float* db;                 /* [1] */
+  float* demb;               /* [n, ld_demb] */
+  tspm_regress_stats* stats; /* nullable: [n_groups] */
+  float* loss_log;           /* nullable: [log_capacity] */
+  int64_t* counters;         /* nullable: {batches, samples} */
+  int64_t log_capacity;
+} tspm_regress_head_desc;
+int tspm_regress_head_step(const tspm_regress_head_desc* desc, tspm_stream_t stream);
 
 #ifdef __cplusplus
 }

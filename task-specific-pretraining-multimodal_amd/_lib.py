@@ -138,6 +138,24 @@ class MonoHeadBceDesc(Structure):
                                  "workspace")] + [("workspace_bytes", c_size_t)]
 
 
+REGRESS_L1, REGRESS_MSE = 0, 1
+REGRESS_STATS_WORDS = 66  # sizeof(tspm_regress_stats) / 8
+
+
+class RegressHeadDesc(Structure):
+    """tspm_regress_head_desc (added under ABI 23): the scalar-output regression head (Linear(hid, 1), L1 / MSE,
+    backward, per-group epoch accumulators, loss log) in one launch."""
+    _fields_ = [(n, c_int32) for n in ("n", "hid", "ld_emb", "ld_demb", "kind", "n_groups")] + \
+        [("loss_weight", c_float), ("reserved_", c_int32)] + \
+        [(n, c_void_p) for n in ("emb", "w", "b", "labels", "groups", "pred", "loss", "dw", "db", "demb", "stats",
+                                 "loss_log", "counters")] + [("log_capacity", c_int64)]
+
+
+def regress_head_supported(n: int, hid: int) -> bool:
+    """The limits of tspm_regress_head_step: 1 <= n <= 1024 rows, hid <= 128 and a multiple of 4."""
+    return 1 <= int(n) <= 1024 and 4 <= int(hid) <= 128 and int(hid) % 4 == 0
+
+
 _SIGS = {
     "tspm_abi_version": (c_int32, []),
     "tspm_status_string": (ctypes.c_char_p, [c_int32]),
@@ -260,6 +278,8 @@ _SIGS = {
     # added under ABI 23 (no existing signature changed): the multi-label (BCEWithLogits) form of that head, for the MMIMDb encoders
     "tspm_mono_head_bce_workspace": (c_size_t, [c_int32, c_int32, c_int32]),
     "tspm_mono_head_bce_step": (c_int32, [POINTER(MonoHeadBceDesc), _P]),
+    # added under ABI 23: the scalar-output regression head (MOSI / MOSEI sentiment score) in one launch
+    "tspm_regress_head_step": (c_int32, [POINTER(RegressHeadDesc), _P]),
 }
 
 EXPORTED = tuple(_SIGS)

@@ -1305,3 +1305,238 @@ extern "C" int tspm_mono_head_step(const tspm_mono_head_desc* desc, tspm_stream_
   TSPM_LAUNCH_CHECK();
   return TSPM_OK;
 }
+
+// ------------------------------------------------------------------------------------------------
+// Regression head step (added under ABI 23): the scalar-output head Linear(hid, 1), the weighted L1 / MSE loss, the
+// Linear's whole backward, the epoch's sentiment-regression accumulators (tspm_regress_stats per pattern group) and
+// the loss log in ONE launch of ONE workgroup, as k_mono_head: the rows are walked in chunks of RH_ROWS staged in
+// LDS, every thread keeps its dw element in a register across the chunks, the loss and the accumulator sums run in
+// double in a fixed order (no atomics, no workspace) — two runs are bitwise equal.
+// ------------------------------------------------------------------------------------------------
+namespace {
+constexpr int RH_THREADS = 256, RH_ROWS = 64, RH_MAXH = 128, RH_MAXN = 1024, RH_MAXG = 16;
+constexpr int RH_WAVES = RH_THREADS / 64;
+constexpr int RH_PRE = RH_ROWS * (RH_MAXH / 4) / RH_THREADS;  // float4 loads per thread and chunk (8)
+constexpr int RH_LDE = RH_MAXH + 4;    // LDS row stride of the chunk's embeddings (16-byte rows, bank offset 4)
+constexpr int RH_CELLS = 49 + 9;       // conf7 then sign3: words 8 .. 65 of a tspm_regress_stats record
+constexpr int RH_WORDS = 8 + RH_CELLS; // 8-byte words per record
+static_assert(sizeof(tspm_regress_stats) == RH_WORDS * 8, "tspm_regress_stats is 66 packed 8-byte words");
+
+__global__ __launch_bounds__(RH_THREADS) void k_regress_head(tspm_regress_head_desc d) {
+  __shared__ __attribute__((aligned(16))) float emb_s[RH_ROWS * RH_LDE];
+  __shared__ __attribute__((aligned(16))) float w_s[RH_MAXH];
+  __shared__ __attribute__((aligned(16))) unsigned int key_s[RH_MAXN];  // conf7 cell | sign3 cell << 16, + 58 * group
+  __shared__ float p_s[RH_MAXN], y_s[RH_MAXN];
+  __shared__ signed char g_s[RH_MAXN];  // the row's group, -1 = left out of the accumulators
+  __shared__ float dz_s[RH_ROWS];
+  __shared__ float dwp_s[2 * RH_MAXH];
+  __shared__ double lred_s[RH_ROWS];
+  __shared__ float dbred_s[RH_ROWS];
+  __shared__ unsigned short hist_s[RH_WAVES * RH_MAXG * RH_CELLS];  // every wave's own cell counts (<= 1024 each)
+  const int t = threadIdx.x, N = d.n, H = d.hid, H4 = H >> 2;
+  const bool train = d.dw != nullptr;
+  const bool acc = d.stats != nullptr;
+  const int G = d.n_groups;
+  for (int j = t; j < H; j += RH_THREADS) w_s[j] = d.w[j];
+  if (acc) {
+    for (int i = t; i < RH_MAXN; i += RH_THREADS) {
+      key_s[i] = 0xFFFFFFFFu;
+      g_s[i] = -1;
+    }
+    for (int i = t; i < RH_WAVES * RH_MAXG * RH_CELLS; i += RH_THREADS) hist_s[i] = 0;
+  }
+  const float bias = d.b[0];
+  const float gscale = d.loss_weight / (float)N;  // dpred = sign(e) * gscale (L1) or 2 e * gscale (MSE)
+  const int r = t >> 2, q = t & 3;                // the forward: 4 lanes per row of the chunk
+  const int dj = t & (RH_MAXH - 1), dh = t >> 7;  // the weight gradient: column dj, rows [32 dh, 32 dh + 32) of the chunk
+  float dwacc = 0.f, dbacc = 0.f;                 // dbacc, lsum: lane q == 0 of row slot r
+  double lsum = 0.0;
+  // A chunk's global reads (its embeddings, label and group) are issued one chunk ahead, into registers, so that
+  // only the first chunk waits for memory.
+  f32x4 pre[RH_PRE];
+  float y_pre = 0.f;
+  int g_pre = 0;
+  auto fetch = [&](int c0) {
+    const int crows = min(RH_ROWS, N - c0);
+#pragma unroll
+    for (int k = 0; k < RH_PRE; ++k) {
+      const int i = t + k * RH_THREADS;
+      if (i < crows * H4) pre[k] = ld4(d.emb + (long long)(c0 + i / H4) * d.ld_emb + (i % H4) * 4);
+    }
+    if (q == 0 && r < crows) {
+      y_pre = d.labels[c0 + r];
+      g_pre = (acc && d.groups) ? d.groups[c0 + r] : 0;
+    }
+  };
+  fetch(0);
+  for (int r0 = 0; r0 < N; r0 += RH_ROWS) {
+    const int rows = min(RH_ROWS, N - r0);
+    __syncthreads();  // the previous chunk's readers are done (and w_s / key_s / g_s / hist_s are written)
+#pragma unroll
+    for (int k = 0; k < RH_PRE; ++k) {
+      const int i = t + k * RH_THREADS;
+      if (i < rows * H4) st4(emb_s + (i / H4) * RH_LDE + (i % H4) * 4, pre[k]);
+    }
+    const float y = y_pre;
+    const int g = g_pre;
+    if (r0 + RH_ROWS < N) fetch(r0 + RH_ROWS);
+    __syncthreads();
+    float s = 0.f;
+    if (r < rows)
+      for (int j4 = q; j4 < H4; j4 += 4) {
+        const f32x4 a = ld4(emb_s + r * RH_LDE + j4 * 4), b = ld4(w_s + j4 * 4);
+        s += a[0] * b[0];
+        s += a[1] * b[1];
+        s += a[2] * b[2];
+        s += a[3] * b[3];
+      }
+    s += __shfl_xor(s, 1, 64);
+    s += __shfl_xor(s, 2, 64);
+    if (r < rows && q == 0) {
+      const int row = r0 + r;
+      const float p = s + bias;
+      const float e = p - y;
+      d.pred[row] = p;
+      const double ed = (double)p - (double)y;  // exact; NaN when the label or the prediction is
+      lsum += d.kind == 0 ? fabs(ed) : ed * ed;
+      if (train) {
+        float dz;
+        if (d.kind == 0) dz = e != e ? e : ((e > 0.f) ? gscale : (e < 0.f) ? -gscale : 0.f * gscale);
+        else dz = 2.f * e * gscale;
+        dz_s[r] = dz;
+        dbacc += dz;
+      }
+      if (acc) {
+        if (p == p && y == y && g >= 0 && g < G) {
+          const int c7 = ((int)rintf(fminf(fmaxf(y, -3.f), 3.f)) + 3) * 7 + (int)rintf(fminf(fmaxf(p, -3.f), 3.f)) + 3;
+          const int s3 = ((y > 0.f) ? 2 : (y < 0.f) ? 0 : 1) * 3 + ((p > 0.f) ? 2 : (p < 0.f) ? 0 : 1);
+          p_s[row] = p;
+          y_s[row] = y;
+          g_s[row] = (signed char)g;
+          key_s[row] = (unsigned)(g * RH_CELLS + c7) | ((unsigned)(g * RH_CELLS + 49 + s3) << 16);
+        }
+      }
+    }
+    if (!train) continue;  // uniform: forward only
+    __syncthreads();
+    // demb = dpred w for the chunk's rows
+    for (int i = t; i < rows * H4; i += RH_THREADS) {
+      const int rr = i / H4, j = (i % H4) * 4;
+      st4(d.demb + (long long)(r0 + rr) * d.ld_demb + j, dz_s[rr] * ld4(w_s + j));
+    }
+    // dw[j] += sum_r dpred[r] emb[r][j]: two halves of the chunk's rows per column, rows in order
+    if (dj < H) {
+      const int lo = dh * (RH_ROWS / 2), hi = min(rows, lo + RH_ROWS / 2);
+      float sacc = dwacc;
+      for (int rr = lo; rr < hi; ++rr) sacc += dz_s[rr] * emb_s[rr * RH_LDE + dj];
+      dwacc = sacc;
+    }
+  }
+  // the loss (double) and db (float): row slot 0, 1, ... 63 in order
+  if (q == 0) {
+    lred_s[r] = lsum;
+    dbred_s[r] = dbacc;
+  }
+  if (train) dwp_s[dh * RH_MAXH + dj] = dwacc;
+  __syncthreads();
+  if (train && t < H) d.dw[t] = dwp_s[t] + dwp_s[RH_MAXH + t];
+  if (t == 0) {
+    double ls = 0.0;
+    float dbs = 0.f;
+    for (int i = 0; i < RH_ROWS; ++i) {
+      ls += lred_s[i];
+      dbs += dbred_s[i];
+    }
+    const float loss = (float)((double)d.loss_weight * (ls / (double)N));
+    d.loss[0] = loss;
+    if (train) d.db[0] = dbs;
+    if (d.counters) {  // tspm_classify_update's log
+      const long long b = d.counters[0];
+      if (d.loss_log && b < d.log_capacity) d.loss_log[b] = loss;
+      d.counters[0] = b + 1;
+      d.counters[1] += N;
+    }
+  }
+  if (!acc) return;  // uniform
+  // The eight sums of every group.  Wave v sums the fields 2v and 2v + 1 (the field is wave-uniform: no divergence);
+  // its 64 lanes are (group, part): P lanes per group walk the rows i = part, part + P, ... and their partials are
+  // added by a butterfly — a fixed order for a given (n, n_groups).
+  const int wv = t >> 6, ln = t & 63;
+  {
+    int gp = 1;
+    while (gp < G) gp <<= 1;
+    const int P = 64 / gp;  // 4 .. 64 lanes per group, a power of two
+    const int g = ln / P, part = ln % P;
+    for (int f = 2 * wv; f < 2 * wv + 2; ++f) {
+      double sum = 0.0;
+      if (g < G)
+        for (int i = part; i < N; i += P) {
+          if (g_s[i] != g) continue;
+          const double pd = (double)p_s[i], yd = (double)y_s[i], ed = pd - yd;
+          switch (f) {  // uniform
+            case 0: sum += 1.0; break;
+            case 1: sum += fabs(ed); break;
+            case 2: sum += ed * ed; break;
+            case 3: sum += pd; break;
+            case 4: sum += yd; break;
+            case 5: sum += pd * pd; break;
+            case 6: sum += yd * yd; break;
+            default: sum += pd * yd; break;
+          }
+        }
+      for (int o = P >> 1; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
+      if (g < G && part == 0) {
+        if (f == 0) d.stats[g].n += (long long)sum;  // a count: exact in double
+        else reinterpret_cast<double*>(d.stats + g)[f] += sum;  // words 1 .. 7
+      }
+    }
+  }
+  // The 58 counts of every group.  Wave v takes the rows [64 (4c + v), 64 (4c + v) + 64): every lane counts the lanes
+  // of its wave that hold its key, the lowest such lane adds the count to the wave's own histogram (distinct keys:
+  // no two lanes write one cell), and the four histograms are added per cell at the end — integer counts, no atomics.
+  // Assumption (hardware, not the C++ memory model): a cell one lane updates in one (base, half) pass may be updated
+  // by ANOTHER lane of the same wave in a later pass with no barrier in between; that is ordered because a wave's
+  // lanes execute in lock step and the LDS serves one wave's operations in program order (gfx950).  Waves never
+  // share a histogram before the __syncthreads() below.
+  unsigned short* hist = hist_s + wv * (RH_MAXG * RH_CELLS);
+  for (int base = wv * 64; base < N; base += RH_THREADS) {
+    const unsigned kk = base + ln < N ? key_s[base + ln] : 0xFFFFFFFFu;
+    for (int half = 0; half < 2; ++half) {
+      const int key = (int)(half ? kk >> 16 : kk & 0xFFFFu);
+      int cnt = 0, lower = 0;
+      for (int l = 0; l < 64; ++l) {
+        const int eq = __builtin_amdgcn_readlane(key, l) == key;
+        cnt += eq;
+        lower += eq & (l < ln);
+      }
+      if (key != 0xFFFF && lower == 0) hist[key] = (unsigned short)(hist[key] + cnt);
+    }
+  }
+  __syncthreads();
+  for (int k = t; k < G * RH_CELLS; k += RH_THREADS) {
+    int cnt = 0;
+    for (int v = 0; v < RH_WAVES; ++v) cnt += hist_s[v * (RH_MAXG * RH_CELLS) + k];
+    if (cnt) reinterpret_cast<long long*>(d.stats + k / RH_CELLS)[8 + k % RH_CELLS] += cnt;
+  }
+}
+}  // namespace
+
+extern "C" int tspm_regress_head_step(const tspm_regress_head_desc* desc, tspm_stream_t stream) {
+  if (!desc) return TSPM_ERR_INVALID;
+  const tspm_regress_head_desc& d = *desc;
+  if (d.n < 1 || d.n > RH_MAXN || d.hid < 4 || d.hid > RH_MAXH || d.hid % 4) return TSPM_ERR_INVALID;
+  if (d.kind != TSPM_REGRESS_L1 && d.kind != TSPM_REGRESS_MSE) return TSPM_ERR_INVALID;
+  if (!d.emb || !d.w || !d.b || !d.labels || !d.pred || !d.loss) return TSPM_ERR_INVALID;
+  if (d.ld_emb < d.hid || d.ld_emb % 4 || !aligned16(d.emb)) return TSPM_ERR_INVALID;
+  const bool train = d.dw || d.db || d.demb;
+  if (train) {  // the whole backward or none of it
+    if (!d.dw || !d.db || !d.demb) return TSPM_ERR_INVALID;
+    if (d.ld_demb < d.hid || d.ld_demb % 4 || !aligned16(d.demb)) return TSPM_ERR_INVALID;
+  }
+  if (d.stats && (d.n_groups < 1 || d.n_groups > RH_MAXG || ((uintptr_t)d.stats & 7))) return TSPM_ERR_INVALID;
+  if (d.loss_log && !d.counters) return TSPM_ERR_INVALID;
+  if (d.log_capacity < 0) return TSPM_ERR_INVALID;
+  hipLaunchKernelGGL(k_regress_head, dim3(1), dim3(RH_THREADS), 0, static_cast<hipStream_t>(stream), d);
+  TSPM_LAUNCH_CHECK();
+  return TSPM_OK;
+}

@@ -30,7 +30,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from .metrics import ClassificationLog, DeviceMetricRecorder
+from .metrics import ClassificationLog, DeviceMetricRecorder, RegressionLog, RegressionMetricRecorder
 from .modules import modality_key
 from .step import FusedEvalStep, FusedTrainStep
 
@@ -188,11 +188,19 @@ class MosiEpochRunner:
     confusion-matrix functions (keys ``MSA_Has0_Accuracy_ATV`` ...; metric_recorder.py:147-209)."""
 
     def __init__(self, model, optimizer, loss_functions, metric_config=None, device=None, log_capacity: int = 1 << 16):
+        from .mosi import _regress_mode
         from .mosi_data import PATTERNS
         self.model, self.optimizer, self.loss_functions = model, optimizer, loss_functions
         self.device = device or next(model.parameters()).device
-        self.log = ClassificationLog(self.device, groups=PATTERNS, classes=3, capacity=log_capacity)
-        self.recorder = DeviceMetricRecorder(metric_config or MOSI_METRICS, self.log)
+        # regression mode (one-output fc_out, a single mean L1 / MSE term): the regression head's accumulators and
+        # the MSA_<key>_<PATTERN> scores of msa_metrics.msa_regression under the group "regression"
+        self.regression = _regress_mode(model, loss_functions) is not None
+        if self.regression:
+            self.log = RegressionLog(self.device, groups=PATTERNS, capacity=log_capacity)
+            self.recorder = RegressionMetricRecorder(self.log)
+        else:
+            self.log = ClassificationLog(self.device, groups=PATTERNS, classes=3, capacity=log_capacity)
+            self.recorder = DeviceMetricRecorder(metric_config or MOSI_METRICS, self.log)
         self.eval_steps: Dict[Tuple[int, int], Any] = {}
 
     def train_step_for(self, b: int, t: int):
@@ -237,7 +245,10 @@ class MosiEpochRunner:
     def _finish(self, t0: float):
         conf, losses, _ = self.log.fetch()  # the epoch's only host synchronisation
         mean = ClassificationLog.mean_loss(losses)
-        metrics = self.recorder.calculate_metrics_for_group("classification", loss=mean, conf=conf)
+        if self.regression:
+            metrics = self.recorder.calculate_metrics_for_group("regression", loss=mean, records=conf)
+        else:
+            metrics = self.recorder.calculate_metrics_for_group("classification", loss=mean, conf=conf)
         return mean, time.time() - t0, metrics, len(losses)
 
     def train_epoch(self, loader: Iterable[Dict[str, Any]]):
@@ -300,6 +311,9 @@ def fit(model, optimizer, loss_functions, loaders: Dict[str, Any], epochs: int, 
     (checked at the epoch's one host synchronisation; SURVEY §5 — the reference only turns three numpy
     RuntimeWarnings into errors, train_multimodal.py:46-60, and would keep training on NaN weights)."""
     runner = runner_for(model, optimizer, loss_functions, metric_config)
+    if getattr(runner, "regression", False) and save_metric != "loss":
+        raise ValueError(f"save_metric {save_metric!r}: a regression run selects its best epoch by the loss; only "
+                         "save_metric='loss' is supported")
     ckpt = CheckpointManager(checkpoint_dir, save_metric, mode) if checkpoint_dir is not None else None
     history: Dict[str, Any] = {"train": [], "validation": [], "epoch_metrics": []}
     best, wait = None, 0

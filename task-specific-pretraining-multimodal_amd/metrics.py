@@ -182,3 +182,93 @@ class DeviceMetricRecorder:
 
     def get_group_result(self, group_name: str, metric_name: str, default: Any = None) -> Any:
         return self.current_results.get(group_name, {}).get(metric_name, default)
+
+
+# ------------------------------------------------------------------------------------------------
+# Sentiment regression (MOSI / MOSEI regression_labels): the accumulators of tspm_regress_head_step
+# ------------------------------------------------------------------------------------------------
+_REGRESS_SUMS = ("sum_abs", "sum_sq", "sum_p", "sum_y", "sum_pp", "sum_yy", "sum_py")
+
+
+def regress_records(raw: np.ndarray) -> List[Dict[str, Any]]:
+    """int64 [groups, 66] words of ``tspm_regress_stats`` records → one dict per group (``n``, the seven double
+    sums, ``conf7`` [7, 7], ``sign3`` [3, 3]): the form ``msa_metrics.msa_regression`` takes."""
+    raw = np.ascontiguousarray(raw, dtype=np.int64).reshape(-1, L.REGRESS_STATS_WORDS)
+    out = []
+    for row in raw:
+        rec: Dict[str, Any] = {"n": int(row[0])}
+        rec.update(zip(_REGRESS_SUMS, row[1:8].view(np.float64).tolist()))
+        rec["conf7"], rec["sign3"] = row[8:57].reshape(7, 7).copy(), row[57:66].reshape(3, 3).copy()
+        out.append(rec)
+    return out
+
+
+class RegressionLog:
+    """Device buffers fed by ``tspm_regress_head_step``: one ``tspm_regress_stats`` record per group (int64 words
+    [groups, 66]), the per-batch loss log (fp32) and counters {batches, samples} — :class:`ClassificationLog`'s
+    interface (``reset`` / ``group_ids`` / ``fetch``) for the regression head."""
+
+    def __init__(self, device: torch.device, groups: Sequence[str] = ("all",), capacity: int = 1 << 16):
+        if device.type != "cuda":
+            raise L.TspmError("RegressionLog lives on the ROCm device")
+        if not 1 <= len(groups) <= 16:
+            raise L.TspmError("RegressionLog: 1 to 16 groups (tspm_regress_head_step)")
+        self.device, self.groups, self.capacity = device, list(groups), capacity
+        self.gid = {g: i for i, g in enumerate(self.groups)}
+        self.records = torch.zeros(len(self.groups), L.REGRESS_STATS_WORDS, dtype=torch.int64, device=device)
+        self.loss_log = torch.zeros(capacity, dtype=torch.float32, device=device)
+        self.counters = torch.zeros(2, dtype=torch.int64, device=device)
+
+    def reset(self) -> None:
+        self.records.zero_()
+        self.counters.zero_()
+
+    group_ids = ClassificationLog.group_ids
+
+    def fetch(self):
+        """(records: one dict per group, per-batch losses [batches] float32, samples) — one sync."""
+        cnt = self.counters.cpu()
+        b = int(cnt[0])
+        if b > self.capacity:
+            raise L.TspmError(f"loss log overflow: {b} batches > capacity {self.capacity}")
+        return regress_records(self.records.cpu().numpy()), self.loss_log[:b].cpu().numpy(), int(cnt[1])
+
+    mean_loss = staticmethod(ClassificationLog.mean_loss)
+
+
+class RegressionMetricRecorder:
+    """Epoch results of a :class:`RegressionLog` under :class:`DeviceMetricRecorder`'s interface: the one group
+    ``"regression"`` with keys ``MSA_<key>_<PATTERN>`` (``MSA_MAE_ATV`` ...; ``msa_metrics.msa_regression``'s keys,
+    patterns in DeviceMetricRecorder's order, a pattern without rows skipped)."""
+
+    def __init__(self, log: RegressionLog, name: str = "MSA"):
+        self.log, self.name = log, name
+        self.groups = {"regression": [name]}
+        self.current_results: Dict[str, Dict[str, Any]] = {}
+
+    def reset(self) -> None:
+        self.log.reset()
+        self.current_results.clear()
+
+    def calculate_metrics_for_group(self, group_name: str = "regression", epoch: Optional[int] = None,
+                                    loss: Optional[float] = None, records=None) -> Dict[str, Any]:
+        from .msa_metrics import msa_regression
+        if group_name not in self.groups:
+            raise ValueError(f"Unknown metric group: {group_name}")
+        if records is None:
+            records = self.log.fetch()[0]
+        results: Dict[str, Any] = {"loss": loss} if loss is not None else {}
+        for gi, pattern in sorted(enumerate(self.log.groups), key=lambda x: x[1]):
+            if records[gi]["n"] == 0:
+                continue
+            tag = pattern.replace("z", "").upper()
+            for k, v in msa_regression(records[gi]).items():
+                results[f"{self.name}_{k}_{tag}"] = v
+        self.current_results[group_name] = results
+        return results
+
+    def calculate_all_groups(self, epoch: Optional[int] = None, loss: Optional[float] = None) -> Dict[str, Dict]:
+        return {"regression": self.calculate_metrics_for_group("regression", epoch, loss)}
+
+    def get_group_result(self, group_name: str, metric_name: str, default: Any = None) -> Any:
+        return self.current_results.get(group_name, {}).get(metric_name, default)

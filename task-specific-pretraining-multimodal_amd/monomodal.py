@@ -19,7 +19,8 @@ pretrained late-fusion config loads (train_monomodal.py:789-802, train_multimoda
   pre-training): encoder forward (``mosi.MosiEncoderEngine``) → ``tspm_mono_head_step`` (classifier, CE,
   predictions and the classifier's backward in one launch; ``fused_head=False`` keeps the four separate
   launches) → encoder backward → FusedAdam.  Learning rate, weight decay and batch size are the caller's
-  optimizer and loader arguments.
+  optimizer and loader arguments.  Under a one-output classifier with a single mean L1 / MSE term (float32
+  sentiment scores) the head is ``tspm_regress_head_step`` and the epoch log a ``metrics.RegressionLog``.
 * :class:`FusedMMIMDbMonoStep` / :class:`FusedMMIMDbMonoEvalStep` — the same two steps around an MMIMDb encoder
   (``mmimdb.MMIMDbModalityEncoder``: BatchNorm1d → Linear) under the multi-label classifier: ``tspm_bn1d_fwd`` →
   ``tspm_linear_fwd`` → the head (``tspm_mono_head_bce_step``, or ``fused_head=False``: ``tspm_linear_fwd``,
@@ -44,7 +45,7 @@ import torch.nn as nn
 from . import _lib as L
 from ._lib import linear_bwd
 from .engine import EncoderEngine, prepare_encoder_layout
-from .metrics import ClassificationLog, DeviceMetricRecorder
+from .metrics import ClassificationLog, DeviceMetricRecorder, RegressionLog, RegressionMetricRecorder
 from .optim import FusedAdam
 from .step import _ce_weight, shared_batches_tracked
 
@@ -127,7 +128,21 @@ def _labels_of(batch: Dict[Any, Any]) -> torch.Tensor:
 
 
 def _device_log(metric_recorder) -> Optional[ClassificationLog]:
-    return metric_recorder.log if isinstance(metric_recorder, DeviceMetricRecorder) else None
+    return metric_recorder.log if isinstance(metric_recorder, (DeviceMetricRecorder, RegressionMetricRecorder)) else None
+
+
+def _mono_regress(model, loss_functions):
+    """(kind, weight) of the loss group's single mean L1 / MSE term (``mosi._regress_term``) when ``model`` wraps a
+    MOSI / MOSEI encoder under a one-output classifier — the sentiment-regression pre-training — else None."""
+    if not model._mosi_encoder() or model.classifier.out_features != 1:
+        return None
+    from .mosi import _regress_term
+    return _regress_term(loss_functions)
+
+
+def _loss_sig(model, loss_functions):
+    """What a MOSI monomodal step bakes in from the loss group: (cross-entropy weight, regression term)."""
+    return _ce_weight(loss_functions), _mono_regress(model, loss_functions)
 
 
 class _LinearFn(torch.autograd.Function):
@@ -328,8 +343,14 @@ class _MosiMonoBuffers(_MonoBuffers):
             raise L.TspmError(f"input features {f} != encoder input_size {model.encoder.input_size}")
         self._init_buffers(model, (t, b, f), log, batch=b)
         self.T = t
+        self.labels_f = torch.zeros(self.N, dtype=torch.float32, device=self.device)  # the regression head's labels
+        if self.regress is not None and not L.regress_head_supported(self.N, self.hid):
+            raise L.TspmError("the regression head takes at most 1024 rows and an encoder of at most 128 units, a "
+                              "multiple of 4")
         self.fused_head = bool(model.fused_head if fused_head is None else fused_head)
         self.eng = MosiEncoderEngine(model.encoder, b, t, self.device, seed=model._rng_seed, x=self.X, emb=self.emb)
+        if self.regress is not None:
+            self.preds = self.logits.view(-1)  # the float predictions
         self.demb = self.eng.demb
         model._by_buffer[self.X.data_ptr()] = self
 
@@ -346,12 +367,34 @@ class _MosiMonoBuffers(_MonoBuffers):
         input buffer (mosi_data.MOSI.device_loader(step_for=...) gathered into it: no copy)."""
         if x.data_ptr() != self.X.data_ptr():
             self.eng.load(x)
-        if labels.data_ptr() != self.labels.data_ptr():
-            self.labels.copy_(labels.reshape(-1), non_blocking=True)
+        dst = self.labels_f if self.regress is not None else self.labels  # by the step's mode, cast to its type
+        if labels.data_ptr() != dst.data_ptr():
+            dst.copy_(labels.reshape(-1), non_blocking=True)
+
+    def _head_regress(self, lib, sh: int, train: bool) -> None:
+        """``tspm_regress_head_step``: classifier Linear(hid, 1), the weighted L1 / MSE loss against ``labels_f``, the
+        epoch accumulators and loss log of ``log`` (a RegressionLog of one group) and, with ``train``, the
+        classifier's backward — the only head of this mode (``fused_head`` is ignored)."""
+        cls, log = self.model.classifier, self.log
+        if log is not None and not isinstance(log, RegressionLog):
+            raise L.TspmError("the regression head records into a metrics.RegressionLog")
+        d = L.RegressHeadDesc(n=self.N, hid=self.hid, ld_emb=self.hid, ld_demb=self.hid, kind=self.regress[0],
+                              n_groups=1, loss_weight=self.regress[1])
+        d.emb, d.w, d.b = self.emb.data_ptr(), cls.weight.data_ptr(), cls.bias.data_ptr()
+        d.labels, d.pred, d.loss = self.labels_f.data_ptr(), self.logits.data_ptr(), self.loss.data_ptr()
+        if train:
+            d.dw, d.db, d.demb = cls.weight.grad.data_ptr(), cls.bias.grad.data_ptr(), self.demb.data_ptr()
+        if log is not None:
+            d.n_groups, d.stats = len(log.groups), log.records.data_ptr()
+            d.loss_log, d.counters, d.log_capacity = log.loss_log.data_ptr(), log.counters.data_ptr(), log.capacity
+        L.check(lib.tspm_regress_head_step(ctypes.byref(d), sh), "regress_head_step")
 
     def _head(self, lib, sh: int, train: bool) -> None:
         n, hid, K = self.N, self.hid, self.K
         cls = self.model.classifier
+        if self.regress is not None:
+            self._head_regress(lib, sh, train)
+            return
         if self.fused_head:
             d = L.MonoHeadDesc()
             d.n, d.hid, d.classes, d.ld_emb, d.ld_demb, d.loss_weight = n, hid, K, hid, hid, self.ce_weight
@@ -387,13 +430,18 @@ class FusedMosiMonoStep(_MosiMonoBuffers):
     ``x_shape`` is the batch-first (B, T, F).  Gradients go straight into FusedAdam's flat views (overwritten);
     no gradient clip (MonomodalEncoder.train_step has none).  The TextCNN's dropout masks are drawn by
     ``tspm_dropout_mask`` on the optimizer's step counter (``keep_override = {"text": mask}`` injects one).  First
-    call eager, second captures, later calls replay."""
+    call eager, second captures, later calls replay.
+
+    Regression mode — ``classifier.out_features == 1`` with a single mean L1 / MSE term (float32 sentiment scores):
+    the head is ``tspm_regress_head_step`` only.  There is no separate-launch variant to choose from, so
+    ``fused_head`` is ignored in this mode; ``preds`` is then the float prediction [B] (a view of ``logits``)."""
 
     def __init__(self, model, optimizer: FusedAdam, loss_functions, x_shape, use_graph: bool = True, log=None,
                  fused_head: Optional[bool] = None):
-        self.ce_weight = _ce_weight(loss_functions)
-        if self.ce_weight is None:
-            raise L.TspmError("FusedMosiMonoStep: the loss group must be a single cross-entropy term")
+        self.ce_weight, self.regress = _loss_sig(model, loss_functions)
+        if self.ce_weight is None and self.regress is None:
+            raise L.TspmError("FusedMosiMonoStep: the loss group must be a single cross-entropy term (or, under a "
+                              "one-output classifier, a single mean L1 / MSE term)")
         if not isinstance(optimizer, FusedAdam):
             raise L.TspmError("FusedMosiMonoStep needs tspm_amd.FusedAdam")
         model.train()
@@ -441,9 +489,10 @@ class FusedMosiMonoEvalStep(_MosiMonoBuffers):
 
     def __init__(self, model, loss_functions, x_shape, log=None, use_graph: bool = True,
                  fused_head: Optional[bool] = None):
-        self.ce_weight = _ce_weight(loss_functions)
-        if self.ce_weight is None:
-            raise L.TspmError("FusedMosiMonoEvalStep: the loss group must be a single cross-entropy term")
+        self.ce_weight, self.regress = _loss_sig(model, loss_functions)
+        if self.ce_weight is None and self.regress is None:
+            raise L.TspmError("FusedMosiMonoEvalStep: the loss group must be a single cross-entropy term (or, under "
+                              "a one-output classifier, a single mean L1 / MSE term)")
         self._init_mosi(model, x_shape, log, fused_head)
         self.use_graph = use_graph and not os.environ.get("TSPM_NO_GRAPH")
 
@@ -854,7 +903,7 @@ class MonomodalEncoder(nn.Module):
                     st.fused_head != bce_head_choice(self.fused_head, st.N, st.hid, st.K):
                 st = self._eval_steps[key] = FusedMMIMDbMonoEvalStep(self, loss_functions, key)
             return st
-        if st is None or st.ce_weight != _ce_weight(loss_functions) or \
+        if st is None or (st.ce_weight, getattr(st, "regress", None)) != _loss_sig(self, loss_functions) or \
                 getattr(st, "fused_head", self.fused_head) != self.fused_head:
             cls = FusedMosiMonoEvalStep if self._mosi_encoder() else FusedMonoEvalStep
             st = cls(self, loss_functions, key, log)
@@ -865,7 +914,7 @@ class MonomodalEncoder(nn.Module):
     def _eval_step_of(self, x: torch.Tensor, loss_functions, log=None):
         """The eval step for batch x: the step whose input buffer x is (a loader gathered into it), else by shape."""
         own = self._by_buffer.get(x.data_ptr())
-        if isinstance(own, FusedMosiMonoEvalStep) and own.ce_weight == _ce_weight(loss_functions):
+        if isinstance(own, FusedMosiMonoEvalStep) and (own.ce_weight, own.regress) == _loss_sig(self, loss_functions):
             own.log = log
             return own
         return self.eval_step_for(loss_functions, tuple(x.shape), log)
@@ -878,8 +927,13 @@ class MonomodalEncoder(nn.Module):
         if self._mmimdb_encoder():
             st = self.train_step_fused(x, labels, optimizer, loss_functions)
             return self._finish(metric_recorder, dlog, key, st.preds, labels, st.loss)
+        reg = _mono_regress(self, loss_functions)
+        if reg is not None:  # sentiment regression: float32 scores [n]
+            labels = labels.float().reshape(-1)
+        head_ok = (_ce_weight(loss_functions) is not None if reg is None
+                   else L.regress_head_supported(x.shape[0], self.classifier.in_features))
         fused = (not os.environ.get("TSPM_DISABLE_FUSED_STEP") and isinstance(optimizer, FusedAdam)
-                 and _ce_weight(loss_functions) is not None and x.is_cuda and labels.dim() == 1
+                 and head_ok and x.is_cuda and labels.dim() == 1
                  and ((self._hip_encoder() and x.dim() in (3, 4)) or (self._mosi_encoder() and x.dim() == 3)))
         if fused:
             st = self.train_step_fused(x, labels, optimizer, loss_functions, dlog)
@@ -887,12 +941,15 @@ class MonomodalEncoder(nn.Module):
         else:
             optimizer.zero_grad()
             logits = self.forward(x)
+            if reg is not None:
+                logits = logits.reshape(-1)
             loss_t = loss_functions(logits, labels)["total_loss"]
             loss_t.backward()
             optimizer.step()
             with torch.no_grad():
-                preds = torch.argmax(logits, dim=1) if labels.dim() == 1 else torch.sigmoid(logits) > 0.5
-        return self._finish(metric_recorder, dlog, key, preds, labels, loss_t)
+                preds = logits.detach() if reg is not None else \
+                    torch.argmax(logits, dim=1) if labels.dim() == 1 else torch.sigmoid(logits) > 0.5
+        return self._finish(metric_recorder, dlog, key, preds, labels, loss_t, reg is not None)
 
     def validation_step(self, batch, loss_functions, device, metric_recorder, config=None, **kwargs):
         """train_monomodal.py:262-418 (the caller puts the model in eval mode, as train_monomodal does)."""
@@ -904,19 +961,27 @@ class MonomodalEncoder(nn.Module):
                 st = self.eval_step_for(loss_functions, tuple(x.shape))
                 st.step(x, labels)
                 return self._finish(metric_recorder, dlog, key, st.preds, labels, st.loss)
-            if (not self.training and _ce_weight(loss_functions) is not None and x.is_cuda and labels.dim() == 1
+            reg = _mono_regress(self, loss_functions)
+            if reg is not None:
+                labels = labels.float().reshape(-1)
+            head_ok = (_ce_weight(loss_functions) is not None if reg is None
+                       else L.regress_head_supported(x.shape[0], self.classifier.in_features))
+            if (not self.training and head_ok and x.is_cuda and labels.dim() == 1
                     and ((self._hip_encoder() and x.dim() in (3, 4)) or (self._mosi_encoder() and x.dim() == 3))):
                 st = self._eval_step_of(x, loss_functions, dlog)
                 st.step(x, labels)
                 loss_t, preds = st.loss, st.preds
             else:
                 logits = self.forward(x)
+                if reg is not None:
+                    logits = logits.reshape(-1)
                 loss_t = loss_functions(logits, labels)["total_loss"]
-                preds = torch.argmax(logits, dim=1) if labels.dim() == 1 else torch.sigmoid(logits) > 0.5
-            return self._finish(metric_recorder, dlog, key, preds, labels, loss_t)
+                preds = logits if reg is not None else \
+                    torch.argmax(logits, dim=1) if labels.dim() == 1 else torch.sigmoid(logits) > 0.5
+            return self._finish(metric_recorder, dlog, key, preds, labels, loss_t, reg is not None)
 
     @staticmethod
-    def _finish(metric_recorder, dlog, key, preds, labels, loss_t):
+    def _finish(metric_recorder, dlog, key, preds, labels, loss_t, regression: bool = False):
         with torch.no_grad():
             if metric_recorder is not None and dlog is None:
                 for group_name in metric_recorder.config.groups:
@@ -924,7 +989,7 @@ class MonomodalEncoder(nn.Module):
                                                  modality=str(key))
             loss = float(loss_t.item() if torch.is_tensor(loss_t) else loss_t)
             metrics = {"loss": loss}
-            if labels.dim() == 1:
+            if labels.dim() == 1 and not regression:
                 metrics["accuracy"] = (preds == labels).float().mean().item()
         return {"loss": loss, "metrics": metrics}
 
@@ -961,6 +1026,9 @@ class MonoEpochRunner:
         self.train_steps: Dict[Tuple, FusedMonoStep] = {}
         self._mosi = model._mosi_encoder()
         self._mmimdb = model._mmimdb_encoder()
+        # sentiment regression (one-output classifier, a single mean L1 / MSE term): the regression head's
+        # accumulators, MSA_<key>_<MODALITY> scores under the group "regression", no accuracy
+        self.regression = _mono_regress(model, loss_functions) is not None
 
     # MOSI encoders: ``mosi_data.MOSI.loader(...)``'s ``step_for`` hooks — the loader gathers each batch time-major
     # straight into the step's input buffer (set on every loader that has the attribute, as harness.MosiHarness does)
@@ -981,7 +1049,10 @@ class MonoEpochRunner:
             loader.step_for = self.train_step_for if train else self.eval_step_for
 
     def _ensure_log(self, key) -> None:
-        if self.log is None:
+        if self.log is None and self.regression:
+            self.log = RegressionLog(self.device, groups=(str(key),), capacity=self.log_capacity)
+            self.recorder = RegressionMetricRecorder(self.log)
+        elif self.log is None:
             self.log = ClassificationLog(self.device, groups=(str(key),), capacity=self.log_capacity)
             self.recorder = DeviceMetricRecorder(self.metric_config, self.log)
 
@@ -993,7 +1064,8 @@ class MonoEpochRunner:
         if acc:
             out["accuracy"] = float(np.mean(acc))
         for g in self.recorder.groups:
-            out.update(self.recorder.calculate_metrics_for_group(g, loss=mean, conf=conf))
+            out.update(self.recorder.calculate_metrics_for_group(g, loss=mean, records=conf) if self.regression
+                       else self.recorder.calculate_metrics_for_group(g, loss=mean, conf=conf))
         return out, time.time() - t0
 
     def _batches(self, loader):
@@ -1069,7 +1141,8 @@ class MonoEpochRunner:
                     self.train_steps[shape] = st
             st.log = self.log
             st.step(x, lab)
-            accs.append(st.batch_accuracy())
+            if not self.regression:
+                accs.append(st.batch_accuracy())
         return self._finish(t0, accs)
 
     @torch.no_grad()
@@ -1083,7 +1156,8 @@ class MonoEpochRunner:
         for x, lab in self._batches(loader):
             st = self.model._eval_step_of(x, self.loss_functions, self.log)
             st.step(x, lab)
-            accs.append(st.batch_accuracy())
+            if not self.regression:
+                accs.append(st.batch_accuracy())
         return self._finish(t0, accs)
 
 
@@ -1102,6 +1176,9 @@ def fit_monomodal(model: MonomodalEncoder, optimizer, loss_functions, loaders: D
     if model._mmimdb_encoder() and save_metric != "loss":
         raise ValueError(f"save_metric {save_metric!r}: a multi-label (MMIMDb) pre-training run has no accuracy; "
                          "only save_metric='loss' is supported")
+    if _mono_regress(model, loss_functions) is not None and save_metric != "loss":
+        raise ValueError(f"save_metric {save_metric!r}: a regression pre-training run has no accuracy; only "
+                         "save_metric='loss' is supported")
     runner = MonoEpochRunner(model, optimizer, loss_functions, experiment_name, metric_config)
     out_dir = Path(model_output_path) if model_output_path is not None else None
     ckpt = CheckpointManager(out_dir, save_metric, "minimize" if save_metric == "loss" else "maximize") \

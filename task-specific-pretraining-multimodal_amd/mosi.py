@@ -26,6 +26,12 @@ layout), pooling + dropout in ``tspm_textcnn_pool_fwd``, the sparse TextCNN weig
 ``tspm_textcnn_bwd``, the classifier on the small-GEMM kernel, cross-entropy, the clip coefficient
 (``tspm_grad_clip_coef``) and Adam (``tspm_adam_step_clip``).  ``FusedMosiStep`` captures all of it as
 one HIP graph.
+
+Sentiment regression (this project's addition; the reference's YAMLs train the three-class variant only): a
+one-output ``netC.fc_out`` (``build_utt_fusion(name, output_dim=1)``) with a single mean ``nn.L1Loss`` / ``nn.MSELoss``
+term (``_regress_term``) on the float32 ``regression_labels`` runs the same steps with the head — ``fc_out``, the loss,
+the per-pattern epoch accumulators, the loss log and ``fc_out``'s backward — in the one launch of
+``MosiEngine.head_regress`` (``tspm_regress_head_step``).
 """
 from __future__ import annotations
 
@@ -58,15 +64,17 @@ YAML_CONFIGS = {
 }
 
 
-def build_utt_fusion(name: str = "mosi") -> "UttFusionModel":
+def build_utt_fusion(name: str = "mosi", output_dim: int = 3) -> "UttFusionModel":
     """UttFusionModel of the named YAML (netA, netV, netT, netC constructed in the YAML's order, so a
-    ``torch.manual_seed`` before the call gives the reference's initial weights)."""
+    ``torch.manual_seed`` before the call gives the reference's initial weights).  ``output_dim=1`` builds the
+    sentiment-regression model (``regression_labels``: a continuous score in [-3, 3]); only ``netC.fc_out``, the last
+    module constructed, differs from the default build of the same seed."""
     c = YAML_CONFIGS[name]
     netA = LSTMEncoder(input_size=c["audio_dim"], hidden_size=64, embd_method=c["embd_method"])
     netV = LSTMEncoder(input_size=c["video_dim"], hidden_size=64, embd_method=c["embd_method"])
     netT = TextCNN(input_size=c["text_dim"], embd_size=64, dropout=c["text_dropout"], in_channels=1, out_channels=128,
                    kernel_heights=[3, 4, 5])
-    netC = FcClassifier(input_dim=192, layers=list(c["cls_layers"]), output_dim=3, dropout=c["cls_dropout"],
+    netC = FcClassifier(input_dim=192, layers=list(c["cls_layers"]), output_dim=output_dim, dropout=c["cls_dropout"],
                         use_bn=c["use_bn"])
     return UttFusionModel(netA, netV, netT, netC, clip=c["clip"])
 
@@ -355,6 +363,7 @@ class MosiEngine:
         self.V = torch.zeros(T, B, self.fv, **f)
         self.X = torch.zeros(T, B, self.ft, **f)
         self.labels = torch.zeros(B, dtype=torch.int64, device=device)
+        self.labels_f = torch.zeros(B, **f)               # the regression head's float32 labels
         self.groups = torch.zeros(B, dtype=torch.int32, device=device)
         self.E = a.hidden_size + v.hidden_size + t.hidden_size
         if c.linears()[0].in_features != self.E:
@@ -402,14 +411,19 @@ class MosiEngine:
         self._offs = torch.arange(B, dtype=torch.int64, device=device) * T
 
     # -- inputs -------------------------------------------------------------------------------------
-    def load(self, A: torch.Tensor, V: torch.Tensor, T: torch.Tensor, labels: Optional[torch.Tensor] = None) -> None:
+    def load(self, A: torch.Tensor, V: torch.Tensor, T: torch.Tensor, labels: Optional[torch.Tensor] = None,
+             regress: bool = False) -> None:
         """Batch-first [B, T, F] reference tensors → the time-major buffers (tspm_seq_gather: one launch per
-        modality, the dense batch seen as B sequences of length T)."""
+        modality, the dense batch seen as B sequences of length T).  ``labels`` go to the int64 ``labels`` of the
+        classification head or, with ``regress`` (the caller's mode, not the tensor's dtype), to the float32
+        ``labels_f`` of the regression head, cast to the buffer's type either way."""
         sh = L.stream_handle()
         for src, dst, nm in ((A, self.A, "audio"), (V, self.V, "video"), (T, self.X, "text")):
             _seq_load(src, dst, self.B, self.T, self._index, self._offs, self._lens, nm, sh)
         if labels is not None:
-            self.labels.copy_(labels.reshape(-1).to(self.labels.dtype), non_blocking=True)
+            dst = self.labels_f if regress else self.labels
+            if labels.data_ptr() != dst.data_ptr():
+                dst.copy_(labels.reshape(-1).to(dst.dtype), non_blocking=True)
 
     # -- forward ------------------------------------------------------------------------------------
     def apply_keep_override(self) -> None:
@@ -457,9 +471,10 @@ class MosiEngine:
         self._ev[1].record(self.side)
         torch.cuda.current_stream(self.device).wait_event(self._ev[1])
 
-    def forward(self, sh: int, train: bool) -> None:
+    def forward(self, sh: int, train: bool, head: bool = True) -> None:
         """Dropout masks, then the LSTM half (side stream) concurrently with the TextCNN half (caller's
-        stream), joined before the classifier; everything graph-capturable."""
+        stream), joined before the classifier; everything graph-capturable.  ``head=False`` stops before
+        ``fc_out`` (``head_regress`` runs it)."""
         self._keep_masks(train, sh)
         if self.concurrent:
             side, sh_side = self._fork()
@@ -470,7 +485,7 @@ class MosiEngine:
         else:
             self._forward_lstm(sh)
             self._forward_text(sh, train)
-        self._forward_classifier(sh, train)
+        self._forward_classifier(sh, train, head)
 
     def _forward_lstm(self, sh: int) -> None:
         lib, m = L.lib(), self.m
@@ -487,7 +502,7 @@ class MosiEngine:
         col_t = m.netA.hidden_size + m.netV.hidden_size
         _text_forward(self, t, sh, keep_t, self.fused.data_ptr() + col_t * 4, self.E)
 
-    def _forward_classifier(self, sh: int, train: bool) -> None:
+    def _forward_classifier(self, sh: int, train: bool, head: bool = True) -> None:
         lib, m, B = L.lib(), self.m, self.B
         # FcClassifier: (Linear, ReLU, [BatchNorm1d,] Dropout) per layer, fc_out
         c = m.netC
@@ -522,6 +537,8 @@ class MosiEngine:
                                             lin.bias.data_ptr(), 1, keep, 1.0 / (1.0 - cp) if cp < 1 else 0.0,
                                             hbuf.data_ptr(), lin.out_features, sh), f"classifier {j}")
                 x, fin = hbuf, lin.out_features
+        if not head:
+            return
         fo = c.fc_out
         L.check(lib.tspm_linear_fwd(B, fin, fo.out_features, x.data_ptr(), fin, fo.weight.data_ptr(),
                                     fo.bias.data_ptr(), 0, None, 1.0, self.logits.data_ptr(), fo.out_features, sh),
@@ -532,17 +549,41 @@ class MosiEngine:
                                            self.loss.data_ptr(), self.dlogits.data_ptr() if with_grad else None, weight,
                                            self.stats.data_ptr() if stats else None, sh), "cross_entropy")
 
+    def head_regress(self, sh: int, train: bool, kind: int, weight: float, log=None) -> None:
+        """The regression head in ONE launch (``tspm_regress_head_step``) in place of ``fc_out``'s tspm_linear_fwd,
+        tspm_cross_entropy, tspm_classify_update and ``fc_out``'s tspm_linear_bwd: predictions into ``logits``
+        [B, 1], the weighted L1 / MSE loss against ``labels_f`` into ``loss``, with ``train`` the gradients of
+        ``fc_out`` and ``dh[-1]`` (``backward(sh, from_head=False)`` continues from it), with ``log`` (a
+        metrics.RegressionLog) the epoch's per-pattern accumulators and loss log."""
+        fo, w = self.m.netC.fc_out, self.widths[-1]
+        if fo.out_features != 1 or not L.regress_head_supported(self.B, w):
+            raise L.TspmError(f"regression head: fc_out must be Linear(hid, 1) with hid <= 128 and a multiple of 4 and "
+                              f"at most 1024 rows (got Linear({w}, {fo.out_features}), {self.B} rows)")
+        g = self.grad_of
+        d = L.RegressHeadDesc(n=self.B, hid=w, ld_emb=w, ld_demb=w, kind=int(kind), n_groups=1,
+                              loss_weight=float(weight))
+        d.emb, d.w, d.b = self.h[-1].data_ptr(), fo.weight.data_ptr(), fo.bias.data_ptr()
+        d.labels, d.pred, d.loss = self.labels_f.data_ptr(), self.logits.data_ptr(), self.loss.data_ptr()
+        if train:
+            d.dw, d.db, d.demb = g(fo.weight).data_ptr(), g(fo.bias).data_ptr(), self.dh[-1].data_ptr()
+        if log is not None:
+            d.groups, d.n_groups, d.stats = self.groups.data_ptr(), len(log.groups), log.records.data_ptr()
+            d.loss_log, d.counters, d.log_capacity = log.loss_log.data_ptr(), log.counters.data_ptr(), log.capacity
+        L.check(L.lib().tspm_regress_head_step(ctypes.byref(d), sh), "regress_head_step")
+
     # -- backward -----------------------------------------------------------------------------------
-    def backward(self, sh: int) -> None:
+    def backward(self, sh: int, from_head: bool = True) -> None:
+        """``from_head=False``: ``dh[-1]`` and ``fc_out``'s gradients are already written (``head_regress``)."""
         lib, m, g = L.lib(), self.m, self.grad_of
         B, T = self.B, self.T
         c = m.netC
         cscale = 1.0 / (1.0 - c.dropout_p) if c.dropout_p > 0 else 1.0
         lins = c.linears()
         fo = c.fc_out
-        linear_bwd(B, self.widths[-1], fo.out_features, self.h[-1].data_ptr(), self.widths[-1], self.dlogits.data_ptr(),
-                   fo.out_features, fo.weight.data_ptr(), g(fo.weight).data_ptr(), g(fo.bias).data_ptr(),
-                   self.dh[-1].data_ptr(), self.widths[-1], sh)
+        if from_head:
+            linear_bwd(B, self.widths[-1], fo.out_features, self.h[-1].data_ptr(), self.widths[-1],
+                       self.dlogits.data_ptr(), fo.out_features, fo.weight.data_ptr(), g(fo.weight).data_ptr(),
+                       g(fo.bias).data_ptr(), self.dh[-1].data_ptr(), self.widths[-1], sh)
         bns = c.bns()
         for j in range(len(lins) - 1, -1, -1):
             w = self.widths[j]
@@ -692,9 +733,41 @@ def _ce_weight(loss_functions) -> Optional[float]:
     return ce(loss_functions)
 
 
+def _regress_term(loss_functions):
+    """(kind, weight) of the single L1 / MSE term of a LossFunctionGroup — kind ``L.REGRESS_L1`` for ``nn.L1Loss``,
+    ``L.REGRESS_MSE`` for ``nn.MSELoss``, both with ``reduction="mean"`` — or None when the group is anything else
+    (no group, several terms, another loss or reduction)."""
+    try:
+        items = list(loss_functions.items())
+    except AttributeError:
+        return None
+    if len(items) != 1:
+        return None
+    term = items[0][1]
+    fn = getattr(term, "loss_fn", None)
+    kind = L.REGRESS_L1 if isinstance(fn, nn.L1Loss) else L.REGRESS_MSE if isinstance(fn, nn.MSELoss) else None
+    if kind is None or fn.reduction != "mean":
+        return None
+    return kind, float(getattr(term, "weight", 1.0))
+
+
+def _regress_mode(model: "UttFusionModel", loss_functions):
+    """``_regress_term`` when the model is the regression model (``netC.fc_out`` has one output), else None."""
+    return _regress_term(loss_functions) if model.netC.fc_out.out_features == 1 else None
+
+
+def _check_regress_log(log) -> None:
+    from .metrics import RegressionLog
+    if log is not None and not isinstance(log, RegressionLog):
+        raise L.TspmError("the regression head records into a metrics.RegressionLog")
+
+
 class FusedMosiStep:
     """One UTT-Fusion train step — forward, cross-entropy, backward, gradient clip, Adam — as one HIP
-    graph (captured on the second call; the backward overwrites every gradient, no zero_grad pass)."""
+    graph (captured on the second call; the backward overwrites every gradient, no zero_grad pass).  With a
+    one-output ``netC.fc_out`` and a single mean L1 / MSE term (sentiment regression on float32 labels) the head —
+    ``fc_out``, the loss, the per-pattern epoch accumulators, the loss log and ``fc_out``'s backward — is the one
+    launch of ``MosiEngine.head_regress``; everything else is the classification step's schedule."""
 
     def __init__(self, model: "UttFusionModel", optimizer: FusedAdam, loss_functions, batch: int, steps: int,
                  use_graph: bool = True, allreduce=None):
@@ -708,8 +781,13 @@ class FusedMosiStep:
             raise L.TspmError("FusedMosiStep: one FusedAdam parameter group (the clip norm spans all parameters)")
         self.model, self.opt, self.N, self.T = model, optimizer, batch, steps
         self.weight = _ce_weight(loss_functions)
-        if self.weight is None:
-            raise L.TspmError("FusedMosiStep: the loss group must be a single cross-entropy term")
+        self.regress = _regress_mode(model, loss_functions)  # (kind, weight): the one-launch regression head
+        if self.regress is None and self.weight is None:
+            raise L.TspmError("FusedMosiStep: the loss group must be a single cross-entropy term (or, with a "
+                              "one-output fc_out, a single mean L1 / MSE term)")
+        if self.regress is not None and not L.regress_head_supported(batch, model.netC.widths[-1]):
+            raise L.TspmError("FusedMosiStep: the regression head takes at most 1024 rows and a last classifier "
+                              "layer of at most 128 units, a multiple of 4")
         self.eng = MosiEngine(model, batch, steps, dev)
         self.eng.rng_ctr_ptr = fgs[0].hyper.data_ptr() + L.HYPER_STEP_OFFSET
         if model.clip is not None:
@@ -718,7 +796,7 @@ class FusedMosiStep:
         self.allreduce = allreduce
         self.graph: Optional[torch.cuda.CUDAGraph] = None
         self.calls = 0
-        self.log = None  # metrics.ClassificationLog (train predictions on the device)
+        self.log = None  # metrics.ClassificationLog (train predictions on the device); RegressionLog in regression mode
 
     @property
     def keep_override(self):
@@ -731,6 +809,12 @@ class FusedMosiStep:
     def _fwd_bwd(self) -> None:
         sh = L.stream_handle()
         e = self.eng
+        if self.regress is not None:
+            _check_regress_log(self.log)
+            e.forward(sh, True, head=False)
+            e.head_regress(sh, True, *self.regress, self.log)
+            e.backward(sh, from_head=False)
+            return
         e.forward(sh, True)
         e.loss_fn(sh, self.weight, True, True)
         if self.log is not None:
@@ -754,7 +838,7 @@ class FusedMosiStep:
             self._opt()
 
     def step(self, A, V, T, labels) -> Dict[str, torch.Tensor]:
-        self.eng.load(A, V, T, labels)
+        self.eng.load(A, V, T, labels, self.regress is not None)
         self.run()
         return {"loss": self.eng.loss, "logits": self.eng.logits}
 
@@ -785,15 +869,21 @@ class FusedMosiEvalStep:
     """``validation_step``'s device work (utt_fusion.py:202-244) for one (batch, steps) shape as one HIP graph:
     eval-mode forward (no dropout; running statistics in the MOSEI classifier BatchNorm1d), the loss group's
     cross-entropy, and ``tspm_classify_update`` (softmax argmax, per-pattern confusion counts, the batch loss
-    appended to the epoch's log) — no host synchronisation.  Inputs are the engine's time-major buffers
+    appended to the epoch's log) — no host synchronisation.  In regression mode (one-output ``fc_out`` and a single
+    mean L1 / MSE term) the head is ``MosiEngine.head_regress`` in forward-only mode and ``log`` a RegressionLog.  Inputs are the engine's time-major buffers
     (``mosi_data.MOSI.device_loader(step_for=...)`` gathers into them) or a batch-first batch via ``step``."""
 
     def __init__(self, model: "UttFusionModel", loss_functions, batch: int, steps: int, log, use_graph: bool = True):
         dev = next(model.parameters()).device
         self.model, self.N, self.T, self.log = model, batch, steps, log
         self.weight = _ce_weight(loss_functions)
-        if self.weight is None:
-            raise L.TspmError("FusedMosiEvalStep: the loss group must be a single cross-entropy term")
+        self.regress = _regress_mode(model, loss_functions)
+        if self.regress is None and self.weight is None:
+            raise L.TspmError("FusedMosiEvalStep: the loss group must be a single cross-entropy term (or, with a "
+                              "one-output fc_out, a single mean L1 / MSE term)")
+        if self.regress is not None and not L.regress_head_supported(batch, model.netC.widths[-1]):
+            raise L.TspmError("FusedMosiEvalStep: the regression head takes at most 1024 rows and a last classifier "
+                              "layer of at most 128 units, a multiple of 4")
         self.eng = model._engine(batch, steps, dev)
         self.use_graph = use_graph and not os.environ.get("TSPM_NO_GRAPH")
         self.graph: Optional[torch.cuda.CUDAGraph] = None
@@ -801,6 +891,11 @@ class FusedMosiEvalStep:
 
     def _all(self) -> None:
         sh, e, lg = L.stream_handle(), self.eng, self.log
+        if self.regress is not None:
+            _check_regress_log(lg)
+            e.forward(sh, False, head=False)
+            e.head_regress(sh, False, *self.regress, lg)
+            return
         e.forward(sh, False)
         e.loss_fn(sh, self.weight, False)
         L.check(L.lib().tspm_classify_update(self.N, e.logits.shape[1], e.logits.data_ptr(), e.labels.data_ptr(),
@@ -809,7 +904,7 @@ class FusedMosiEvalStep:
                                              lg.capacity, sh), "classify_update")
 
     def step(self, A, V, T, labels) -> None:
-        self.eng.load(A, V, T, labels)
+        self.eng.load(A, V, T, labels, self.regress is not None)
         self.run()
 
     def run(self) -> None:
@@ -960,13 +1055,21 @@ class UttFusionModel(nn.Module):
                    **kwargs: Any) -> Dict[str, Any]:
         """utt_fusion.py:151-200.  With FusedAdam and the single cross-entropy loss group: one FusedMosiStep
         graph (forward, loss, backward, clip_grad_norm_, Adam); otherwise the reference's own sequence
-        on the HIP forward/backward (one autograd node)."""
+        on the HIP forward/backward (one autograd node).  Regression mode — a one-output ``netC.fc_out`` with a
+        single mean L1 / MSE term: float32 labels, the fused step with the one-launch regression head (the autograd
+        sequence when the head is outside the kernel's limits), and the float predictions recorded under the
+        ``"regression"`` group (this package's name for it)."""
         A = _modality(batch, "audio").to(device).float()
         V = _modality(batch, "video").to(device).float()
         T = _modality(batch, "text").to(device).float()
         labels = batch["label"].to(device)
         miss = batch.get("pattern_name")
-        if isinstance(optimizer, FusedAdam) and _ce_weight(loss_functions) is not None and A.is_cuda:
+        reg = _regress_mode(self, loss_functions)
+        if reg is not None:
+            labels = labels.float()
+        head_ok = (_ce_weight(loss_functions) is not None if reg is None
+                   else L.regress_head_supported(A.shape[0], self.netC.widths[-1]))
+        if isinstance(optimizer, FusedAdam) and head_ok and A.is_cuda:
             out = self.fused_step(optimizer, loss_functions, A.shape[0], A.shape[1]).step(A, V, T, labels)
             logits, loss = out["logits"], out["loss"]
         else:
@@ -978,7 +1081,11 @@ class UttFusionModel(nn.Module):
             if self.clip is not None:
                 torch.nn.utils.clip_grad_norm_(self.parameters(), self.clip)
             optimizer.step()
-        if metric_recorder is not None:
+        if metric_recorder is not None and reg is not None:  # the float predictions under the "regression" group
+            metric_recorder.update_group_all("regression", predictions=logits.detach().reshape(-1).cpu().numpy(),
+                                             targets=labels.reshape(-1).detach().cpu().numpy(),
+                                             m_types=np.array(miss if miss is not None else []))
+        elif metric_recorder is not None:
             preds = torch.softmax(logits.detach(), dim=-1).argmax(dim=-1).squeeze()
             metric_recorder.update_group_all("classification", predictions=preds.cpu().numpy(),
                                              targets=labels.squeeze().detach().cpu().numpy(),
@@ -996,8 +1103,28 @@ class UttFusionModel(nn.Module):
         labels = batch["label"].to(device)
         miss = np.array(batch.get("pattern_name", []))
         eng = self._engine(A.shape[0], A.shape[1], A.device)
-        eng.load(A, V, T, labels)
+        reg = _regress_mode(self, loss_functions)
+        if reg is not None:
+            labels = labels.float()
+        eng.load(A, V, T, labels, reg is not None)
         sh = L.stream_handle()
+        if reg is not None:
+            if L.regress_head_supported(eng.B, eng.widths[-1]):
+                eng.forward(sh, False, head=False)
+                eng.head_regress(sh, False, *reg)
+                loss = eng.loss.clone()
+            else:
+                eng.forward(sh, False)
+                loss = loss_functions(eng.logits.squeeze(), labels.squeeze())["total_loss"]
+            preds = eng.logits.reshape(-1).clone()
+            if metric_recorder is not None:
+                metric_recorder.update_group_all("regression", predictions=preds.cpu().numpy(),
+                                                 targets=labels.reshape(-1).cpu().numpy(), m_types=miss)
+            self.train()
+            if return_test_info:
+                return {"loss": loss.item(), "predictions": [preds.cpu().numpy()], "labels": [labels.cpu().numpy()],
+                        "miss_types": [list(miss)]}
+            return {"loss": loss.item()}
         eng.forward(sh, False)
         w = _ce_weight(loss_functions)
         if w is not None:

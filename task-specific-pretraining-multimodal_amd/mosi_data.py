@@ -88,13 +88,16 @@ class MosiCorpus:
 
 
 def synthetic_mosi_corpus(n: int, seed: int = 1234, steps: int = 50, min_len: Optional[int] = None,
-                          feats=(5, 20, 768)) -> MosiCorpus:
+                          feats=(5, 20, 768), regression: bool = False) -> MosiCorpus:
     """MOSI-shaped synthetic split: audio 5-d, video 20-d, text 768-d, 3 classes.  ``min_len``: ragged
     lengths uniform in [min_len, steps] (shared by the three modalities, as in the aligned data); None:
-    dense ``steps``-long sequences (aligned_50)."""
+    dense ``steps``-long sequences (aligned_50).  ``regression``: float32 sentiment scores on the 0.2 grid of
+    [-3, 3] (zeros included) in place of the class labels."""
     g = np.random.default_rng(seed)
     lens = np.full(n, steps, np.int32) if min_len is None else g.integers(min_len, steps + 1, n).astype(np.int32)
     seqs = {m: [g.standard_normal((int(l), f), dtype=np.float32) for l in lens] for m, f in zip(MODALITIES, feats)}
+    if regression:
+        return MosiCorpus(seqs, (g.integers(-15, 16, n) / 5.0).astype(np.float32))
     return MosiCorpus(seqs, g.integers(0, 3, n).astype(np.int64))
 
 
@@ -109,9 +112,16 @@ class DeviceMosiCorpus:
         self.data = {m: torch.from_numpy(corpus.data[m]).to(device) for m in MODALITIES}
         self.offsets = {m: torch.from_numpy(corpus.offsets[m]).to(device) for m in MODALITIES}
         self.lengths = {m: torch.from_numpy(corpus.lengths[m]).to(device) for m in MODALITIES}
-        self.labels = torch.from_numpy(np.ascontiguousarray(corpus.labels)).to(device)
-        if self.labels.dtype != torch.int64:
-            raise L.TspmError("device gather carries int64 class labels (classification_labels)")
+        lab = np.ascontiguousarray(corpus.labels)
+        # float32 [n] / [n, 1]: the continuous sentiment score (regression_labels), gathered one float per row
+        self.float_labels = lab.dtype == np.float32 and (lab.ndim == 1 or (lab.ndim == 2 and lab.shape[1] == 1))
+        if self.float_labels:
+            lab = lab.reshape(-1, 1)
+        elif lab.dtype != np.int64:
+            raise L.TspmError("device gather carries int64 class labels (classification_labels) or float32 scores "
+                              "[n] / [n, 1] (regression_labels)")
+        self.labels = torch.from_numpy(lab).to(device)
+        self.label_dtype = torch.float32 if self.float_labels else torch.int64
 
     def steps_for(self, index_host: np.ndarray, pad_to: int = 0, modalities: Sequence[str] = MODALITIES) -> int:
         """pad_sequence's padded length, the longest sequence of the batch — per modality in the reference
@@ -128,10 +138,17 @@ class DeviceMosiCorpus:
     def gather(self, index: torch.Tensor, steps_pad: int, out: Dict[str, torch.Tensor], time_major: bool,
                masks: Optional[Dict[str, torch.Tensor]] = None, labels_out: Optional[torch.Tensor] = None) -> None:
         """Write the batch ``index`` (device int64) into ``out[m]``: [T, B, F] (time_major) or [B, T, F], for
-        the modalities ``out`` names (all three for the fusion step, one for encoder pre-training); the labels
-        ride on the first launch."""
+        the modalities ``out`` names (all three for the fusion step, one for encoder pre-training); int64 labels
+        ride on the first launch, float32 labels (``labels_out`` float32 [B]) take one ``tspm_avmnist_gather``
+        launch of one float per row (an out-of-range index gives a NaN label)."""
         lib, sh = L.lib(), L.stream_handle()
         b = int(index.numel())
+        if labels_out is not None and labels_out.dtype != self.label_dtype:
+            raise L.TspmError(f"labels_out is {labels_out.dtype}, the corpus carries {self.label_dtype} labels")
+        if self.float_labels and labels_out is not None:
+            L.check(lib.tspm_avmnist_gather(b, index.data_ptr(), self.n, self.labels.data_ptr(), 1, None, 0, None, None,
+                                            None, None, labels_out.data_ptr(), None, None, sh), "label gather")
+            labels_out = None
         for j, m in enumerate([m for m in MODALITIES if m in out]):
             f, dst = self.feat[m], out[m]
             shape = (steps_pad, b, f) if time_major else (b, steps_pad, f)
@@ -141,7 +158,8 @@ class DeviceMosiCorpus:
             mk = masks.get(m) if masks else None
             L.check(lib.tspm_seq_gather(b, index.data_ptr(), self.n, self.data[m].data_ptr(), self.offsets[m].data_ptr(),
                                         self.lengths[m].data_ptr(), f, steps_pad, dst.data_ptr(), st_t, st_b,
-                                        None if mk is None else mk.data_ptr(), self.labels.data_ptr() if j == 0 else None,
+                                        None if mk is None else mk.data_ptr(),
+                                        self.labels.data_ptr() if (j == 0 and not self.float_labels) else None,
                                         labels_out.data_ptr() if (j == 0 and labels_out is not None) else None, sh),
                     "seq_gather")
 
@@ -277,10 +295,11 @@ class MOSI(torch.utils.data.Dataset):
         if step is not None:
             if (step.N, step.T) != (b, tpad):
                 raise L.TspmError(f"step planned for (B={step.N}, T={step.T}), batch is (B={b}, T={tpad})")
-            dc.gather(index, tpad, {m: step.X}, True, masks, step.labels)
-            return {m: step.X, "label": step.labels, "pattern_name": names}
+            lab = step.labels_f if dc.float_labels else step.labels
+            dc.gather(index, tpad, {m: step.X}, True, masks, lab)
+            return {m: step.X, "label": lab, "pattern_name": names}
         out = torch.empty(b, tpad, dc.feat[m], device=self.device)
-        lab = torch.empty(b, dtype=torch.int64, device=self.device)
+        lab = torch.empty(b, dtype=dc.label_dtype, device=self.device)
         dc.gather(index, tpad, {m: out}, False, masks, lab)
         return {m: out, "label": lab, "pattern_name": names}
 
@@ -296,11 +315,12 @@ class MOSI(torch.utils.data.Dataset):
             e = step.eng
             if (e.B, e.T) != (b, tpad):
                 raise L.TspmError(f"step planned for (B={e.B}, T={e.T}), batch is (B={b}, T={tpad})")
-            dc.gather(index, tpad, {"audio": e.A, "video": e.V, "text": e.X}, True, masks, e.labels)
-            return {"audio": e.A, "video": e.V, "text": e.X, "label": e.labels, "pattern_name": names,
+            lab = e.labels_f if dc.float_labels else e.labels
+            dc.gather(index, tpad, {"audio": e.A, "video": e.V, "text": e.X}, True, masks, lab)
+            return {"audio": e.A, "video": e.V, "text": e.X, "label": lab, "pattern_name": names,
                     "steps": tpad, "time_major": True}
         out = {m: torch.empty(b, tpad, dc.feat[m], device=self.device) for m in MODALITIES}
-        lab = torch.empty(b, dtype=torch.int64, device=self.device)
+        lab = torch.empty(b, dtype=dc.label_dtype, device=self.device)
         dc.gather(index, tpad, out, False, masks, lab)
         return {"audio": out["audio"], "video": out["video"], "text": out["text"], "label": lab,
                 "pattern_name": names, "pattern_names": names, "steps": tpad}
