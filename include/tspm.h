@@ -51,7 +51,8 @@ enum {
  * one launch.  Added under 23 with no existing signature or struct changed (callers built against 23 keep working):
  * tspm_mono_head_bce_step / tspm_mono_head_bce_workspace, the multi-label (BCEWithLogits, F1 counts) form of that
  * head for the MMIMDb encoder pre-training step; tspm_regress_head_step, the scalar-output head of the MOSI / MOSEI
- * sentiment regression (L1 / MSE, backward, epoch accumulators, loss log) in one launch. */
+ * sentiment regression (L1 / MSE, backward, epoch accumulators, loss log) in one launch; tspm_lstm_fwd_w /
+ * tspm_lstm_bwd_w, the LSTM recurrences at any hidden width that is a multiple of 4 up to 128 (same descriptors). */
 #define TSPM_ABI_VERSION 23
 int tspm_abi_version(void);  /* returns TSPM_ABI_VERSION */
 /* Static string for a status code. */
@@ -768,6 +769,16 @@ typedef struct tspm_lstm_bwd_desc {
   const uint8_t* argmax; /* nullable; ABI 14 */
 } tspm_lstm_bwd_desc;
 int tspm_lstm_bwd(int32_t count, const tspm_lstm_bwd_desc* descs, tspm_stream_t stream);
+/* The same recurrences at any hidden width (added under ABI 23; tspm_lstm_fwd / _bwd above keep refusing every width
+ * but 64): hidden a multiple of 4 with 4 <= hidden <= 128 — one thread per gate column with its row (column quarter)
+ * of W_hh in registers, 512 threads at most — anything else is TSPM_ERR_INVALID.  Same descriptors, semantics and
+ * memory layouts, with the real hidden as the width of every tensor (no padding in memory).  count is 1 or 2 and each
+ * descriptor has its own hidden / batch / steps; widths are served by three kernel tiers (32 / 64 / 128 lanes per
+ * gate, lanes past hidden idle) and the compile-time 64-wide kernels, two descriptors of one kind share a launch and
+ * two of different kinds take one launch each; either way the results are bitwise those of two count-1 calls, and at
+ * hidden = 64 bitwise those of tspm_lstm_fwd / tspm_lstm_bwd.  Every descriptor is validated before the first launch. */
+int tspm_lstm_fwd_w(int32_t count, const tspm_lstm_fwd_desc* descs, tspm_stream_t stream);
+int tspm_lstm_bwd_w(int32_t count, const tspm_lstm_bwd_desc* descs, tspm_stream_t stream);
 /* TextCNN pooling (models/msa/networks/textcnn.py:56-67): for conv i (kernel height heights[i], output
  * conv_out[i] time-major [steps-heights[i]+1][batch][channels] without bias), bias[i] added, ReLU,
  * max over time (first maximum, F.max_pool1d), concatenated over convs: pooled[b][i*C+c] and the

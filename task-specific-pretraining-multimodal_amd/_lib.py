@@ -156,6 +156,23 @@ def regress_head_supported(n: int, hid: int) -> bool:
     return 1 <= int(n) <= 1024 and 4 <= int(hid) <= 128 and int(hid) % 4 == 0
 
 
+def lstm_width_supported(h: int) -> bool:
+    """The limits of tspm_lstm_fwd_w / tspm_lstm_bwd_w: 4 <= hidden <= 128 and a multiple of 4."""
+    return 4 <= int(h) <= 128 and int(h) % 4 == 0
+
+
+def lstm_fwd(count: int, descs, sh) -> int:
+    """tspm_lstm_fwd when every LSTM of the launch is 64 wide (the compile-time kernels), else tspm_lstm_fwd_w."""
+    fn = lib().tspm_lstm_fwd if all(descs[i].hidden == 64 for i in range(count)) else lib().tspm_lstm_fwd_w
+    return fn(count, descs, sh)
+
+
+def lstm_bwd(count: int, descs, sh) -> int:
+    """tspm_lstm_bwd when every LSTM of the launch is 64 wide, else tspm_lstm_bwd_w."""
+    fn = lib().tspm_lstm_bwd if all(descs[i].hidden == 64 for i in range(count)) else lib().tspm_lstm_bwd_w
+    return fn(count, descs, sh)
+
+
 _SIGS = {
     "tspm_abi_version": (c_int32, []),
     "tspm_status_string": (ctypes.c_char_p, [c_int32]),
@@ -265,6 +282,8 @@ _SIGS = {
     "tspm_adam_step_clip": (c_int32, [c_int64, _P, _P, _P, _P, _P, _P, _P]),
     "tspm_lstm_fwd": (c_int32, [c_int32, POINTER(LstmFwdDesc), _P]),
     "tspm_lstm_bwd": (c_int32, [c_int32, POINTER(LstmBwdDesc), _P]),
+    "tspm_lstm_fwd_w": (c_int32, [c_int32, POINTER(LstmFwdDesc), _P]),
+    "tspm_lstm_bwd_w": (c_int32, [c_int32, POINTER(LstmBwdDesc), _P]),
     "tspm_textcnn_pool_fwd": (c_int32, [c_int32, c_int32, c_int32, _P, c_int32, _P, _P, _P, c_float, _P, _P, _P,
                                         c_int32, _P]),
     "tspm_textcnn_bwd": (c_int32, [c_int32, c_int32, c_int32, c_int32, _P, c_int32, _P, _P, c_int32, _P, c_float, _P,

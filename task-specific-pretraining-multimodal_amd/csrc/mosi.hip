@@ -124,6 +124,121 @@ __global__ __launch_bounds__(4 * H) void k_lstm_fwd(LstmFwdDesc d0, LstmFwdDesc 
 }
 
 // ------------------------------------------------------------------------------------------------
+// LSTM forward, any hidden width H (a multiple of 4, 4 <= H <= 128) at run time: the recurrence above on a
+// tier of HP = 32 / 64 / 128 lanes per gate.  Thread (q, u) = (gate, unit) of 4 * HP owns gate column
+// q * H + u when u < H; a padded lane (u >= H) holds zero weights, reads and writes no global memory and
+// never writes h (its LDS slot stays the initial zero).  The unrolled k loop runs in chunks of kLstmChunk lanes,
+// each under one wave-uniform guard, so a chunk wholly past H costs nothing, a chunk that straddles H adds 0 x 0
+// products only, and at H = HP the fmaf sequence is k_lstm_fwd's.  Memory layouts carry the real H: xg / gates
+// [T][B][4H], cs [T][B][H], hs [T+1][B][H].
+// ------------------------------------------------------------------------------------------------
+// The reductions of the run-time-width kernels are guarded per chunk of this many lanes, not per float4 group: one
+// wave-uniform branch per chunk (at most 4; 32 per-group guards hoisted out of the time loop as scalar masks spilled
+// 55 / 113 SGPRs in the 128 tier) and the chunk's LDS reads in flight together.  Inside a chunk that straddles the
+// width the padded products are 0 x 0: a padded weight is zero and a padded h / gate-gradient slot of LDS is zero from
+// the start and never written, so no NaN of a real unit can meet a padded zero.
+constexpr int kLstmChunk = 32;
+
+template <int HP, int RB>
+TSPM_DEV void lstm_fwd_w_body(const LstmFwdDesc& d, const int H, int chunk) {
+  constexpr int GP = 4 * HP;
+  __shared__ __attribute__((aligned(16))) float hsh[RB][HP];
+  __shared__ float gsh[RB][GP];
+  const int tid = threadIdx.x;
+  const int q = tid / HP, u = tid - (tid / HP) * HP;
+  const bool live = u < H;
+  const int G = 4 * H;
+  const int j = q * H + u;  // the gate column in memory (live lanes)
+  const int b0 = chunk * RB;
+  const int B = d.B, T = d.T;
+  float w[HP];
+#pragma unroll
+  for (int k = 0; k < HP; k += 4) {
+    f32x4 v = {0.f, 0.f, 0.f, 0.f};
+    if (live && k < H) v = ld4(d.whh + (long long)j * H + k);
+    w[k] = v[0]; w[k + 1] = v[1]; w[k + 2] = v[2]; w[k + 3] = v[3];
+  }
+  const float bh = (live && d.bhh) ? d.bhh[j] : 0.f;
+  // cell threads: (row cr, unit cu) = (q, u) of the first RB gate blocks; the ghost row of an odd batch reads the
+  // last real row's inputs (clamped index) and writes nothing
+  const int cr = q, cu = u;
+  const bool upd = tid < RB * HP && live;
+  const bool cell = upd && b0 + cr < B;
+  float c = 0.f, h = 0.f;
+  float mx = -INFINITY;
+  int am = 0;
+  if (tid < RB * HP) hsh[cr][cu] = 0.f;
+  if (cell) d.hs[(long long)(b0 + cr) * H + cu] = 0.f;
+  const bool sig = q != 2;
+  int rowc[RB];
+#pragma unroll
+  for (int r = 0; r < RB; ++r) rowc[r] = min(b0 + r, B - 1);
+  float xn[RB];
+#pragma unroll
+  for (int r = 0; r < RB; ++r) xn[r] = live ? d.xg[(long long)rowc[r] * G + j] : 0.f;
+  __syncthreads();
+  for (int t = 0; t < T; ++t) {
+    float xc[RB];
+#pragma unroll
+    for (int r = 0; r < RB; ++r) xc[r] = xn[r];
+    if (t + 1 < T && live) {
+#pragma unroll
+      for (int r = 0; r < RB; ++r) xn[r] = d.xg[((long long)(t + 1) * B + rowc[r]) * G + j];
+    }
+#pragma unroll
+    for (int r = 0; r < RB; ++r) {
+      float a4[4] = {0.f, 0.f, 0.f, 0.f};  // four interleaved partial sums (k mod 4): an H/4-deep chain
+#pragma unroll
+      for (int k0 = 0; k0 < HP; k0 += kLstmChunk) {
+        if (k0 < H) {  // wave-uniform: a chunk wholly past the width is skipped
+#pragma unroll
+          for (int k = k0; k < k0 + kLstmChunk; k += 4) {
+            const f32x4 hv = *reinterpret_cast<const f32x4*>(&hsh[r][k]);
+#pragma unroll
+            for (int v = 0; v < 4; ++v) a4[v] = fmaf(hv[v], w[k + v], a4[v]);
+          }
+        }
+      }
+      const float acc = (a4[0] + a4[1]) + (a4[2] + a4[3]);
+      const float pre = (acc + bh) + xc[r];
+      const float a = sig ? sigmoidf_(pre) : tanhf(pre);
+      gsh[r][tid] = a;
+      if (live && b0 + r < B) d.gates[((long long)t * B + b0 + r) * G + j] = a;
+    }
+    __syncthreads();
+    if (upd) {
+      const float ig = gsh[cr][cu], fg = gsh[cr][HP + cu], gg = gsh[cr][2 * HP + cu], og = gsh[cr][3 * HP + cu];
+      c = fg * c + ig * gg;
+      h = og * tanhf(c);
+      hsh[cr][cu] = h;
+    }
+    if (cell) {
+      const long long o = ((long long)t * B + b0 + cr) * H + cu;
+      d.cs[o] = c;
+      d.hs[o + (long long)B * H] = h;
+      if (d.arg && (h > mx || h != h)) {
+        mx = h;
+        am = t;
+      }
+    }
+    __syncthreads();
+  }
+  if (cell) {
+    d.hout[(long long)(b0 + cr) * d.ldh + cu] = d.arg ? mx : h;
+    if (d.arg) d.arg[(long long)(b0 + cr) * H + cu] = (uint8_t)am;
+  }
+}
+
+template <int HP, int RB>
+__global__ __launch_bounds__(4 * HP) void k_lstm_fwd_w(LstmFwdDesc d0, int h0, LstmFwdDesc d1, int h1, int nb0) {
+  static_assert(RB <= 4, "cell threads are the first RB gate blocks");
+  if ((int)blockIdx.x < nb0)
+    lstm_fwd_w_body<HP, RB>(d0, h0, blockIdx.x);
+  else
+    lstm_fwd_w_body<HP, RB>(d1, h1, blockIdx.x - nb0);
+}
+
+// ------------------------------------------------------------------------------------------------
 // LSTM backward through time: thread (q, k) = (gate quarter, hidden unit) keeps column k of the
 // quarter-q rows of W_hh in registers for dh_{t-1} = dgates_t @ W_hh (4 partial sums combined in
 // fixed order through LDS); threads (r, u) carry dc and form the pre-activation gate gradients
@@ -210,6 +325,89 @@ __global__ __launch_bounds__(4 * H) void k_lstm_bwd(LstmBwdDesc d0, LstmBwdDesc 
     lstm_bwd_body<H, RB>(d0, blockIdx.x);
   else
     lstm_bwd_body<H, RB>(d1, blockIdx.x - nb0);
+}
+
+// LSTM backward through time at a run-time width H on a tier of HP lanes per gate quarter (see k_lstm_fwd_w):
+// thread (q, k) keeps column k of the quarter-q rows of W_hh (zeros in a padded lane), the unrolled jj loop runs in
+// guarded chunks of kLstmChunk as the forward's k loop, padded lanes read and write no global memory, and only units < H are ever read back from LDS.
+template <int HP, int RB>
+TSPM_DEV void lstm_bwd_w_body(const LstmBwdDesc& d, const int H, int chunk) {
+  constexpr int GP = 4 * HP;
+  __shared__ __attribute__((aligned(16))) float dgs[RB][GP];
+  __shared__ float part[4][RB][HP];
+  const int tid = threadIdx.x;
+  const int q = tid / HP, k = tid - (tid / HP) * HP;
+  const bool live = k < H;
+  const int G = 4 * H;
+  const int b0 = chunk * RB;
+  const int B = d.B, T = d.T;
+  float wc[HP];
+#pragma unroll
+  for (int jj = 0; jj < HP; ++jj) wc[jj] = (live && jj < H) ? d.whh[(long long)(q * H + jj) * H + k] : 0.f;
+  const int cr = q, cu = k;
+  const bool cell = tid < RB * HP && live && b0 + cr < B;  // ghost rows and padded lanes compute zeros, write nothing
+  float dc = 0.f, dh = 0.f, gin = 0.f;
+  int am = T - 1;
+  if (cell) {
+    gin = d.dh[(long long)(b0 + cr) * d.lddh + cu];
+    if (d.arg) am = d.arg[(long long)(b0 + cr) * H + cu];
+  }
+  if (tid < RB * HP && !cell) {
+    dgs[cr][cu] = 0.f; dgs[cr][HP + cu] = 0.f; dgs[cr][2 * HP + cu] = 0.f; dgs[cr][3 * HP + cu] = 0.f;
+  }
+  for (int t = T - 1; t >= 0; --t) {
+    if (cell) {
+      if (t < T - 1) {
+        dh = ((part[0][cr][cu] + part[1][cr][cu]) + part[2][cr][cu]) + part[3][cr][cu];
+        if (t == am) dh += gin;
+      } else {
+        dh = am == T - 1 ? gin : 0.f;
+      }
+      const long long go = ((long long)t * B + b0 + cr) * G + cu;
+      const float ig = d.gates[go], fg = d.gates[go + H], gg = d.gates[go + 2 * H], og = d.gates[go + 3 * H];
+      const long long co = ((long long)t * B + b0 + cr) * H + cu;
+      const float c = d.cs[co];
+      const float cp = t > 0 ? d.cs[co - (long long)B * H] : 0.f;
+      const float tc = tanhf(c);
+      const float dog = dh * tc;
+      const float dcc = dc + dh * og * (1.f - tc * tc);
+      const float dig = dcc * gg, dgg = dcc * ig, dfg = dcc * cp;
+      dc = dcc * fg;
+      const float ai = dig * ig * (1.f - ig), af = dfg * fg * (1.f - fg);
+      const float ag = dgg * (1.f - gg * gg), ao = dog * og * (1.f - og);
+      dgs[cr][cu] = ai; dgs[cr][HP + cu] = af; dgs[cr][2 * HP + cu] = ag; dgs[cr][3 * HP + cu] = ao;
+      d.dgates[go] = ai; d.dgates[go + H] = af; d.dgates[go + 2 * H] = ag; d.dgates[go + 3 * H] = ao;
+    }
+    __syncthreads();
+    if (t > 0) {
+#pragma unroll
+      for (int r = 0; r < RB; ++r) {
+        float a4[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int j0 = 0; j0 < HP; j0 += kLstmChunk) {
+          if (j0 < H) {  // wave-uniform: a chunk wholly past the width is skipped
+#pragma unroll
+            for (int jj = j0; jj < j0 + kLstmChunk; jj += 4) {
+              const f32x4 dv = *reinterpret_cast<const f32x4*>(&dgs[r][q * HP + jj]);
+#pragma unroll
+              for (int v = 0; v < 4; ++v) a4[v] = fmaf(dv[v], wc[jj + v], a4[v]);
+            }
+          }
+        }
+        part[q][r][k] = (a4[0] + a4[1]) + (a4[2] + a4[3]);
+      }
+    }
+    __syncthreads();
+  }
+}
+
+template <int HP, int RB>
+__global__ __launch_bounds__(4 * HP) void k_lstm_bwd_w(LstmBwdDesc d0, int h0, LstmBwdDesc d1, int h1, int nb0) {
+  static_assert(RB <= 4, "cell threads are the first RB gate quarters");
+  if ((int)blockIdx.x < nb0)
+    lstm_bwd_w_body<HP, RB>(d0, h0, blockIdx.x);
+  else
+    lstm_bwd_w_body<HP, RB>(d1, h1, blockIdx.x - nb0);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -478,6 +676,39 @@ bool lstm_ok(int B, int T, int H, const void* p0, const void* p1, const void* p2
   return B > 0 && T > 0 && H == 64 && p0 && p1 && p2 && p3;
 }
 
+// The run-time-width recurrences: 4 <= H <= 128, a multiple of 4 (float4 rows of W_hh; one gate column per thread, at
+// most 512 threads with W_hh's row in registers).  kind: 0 = the compile-time 64-wide kernels, else the tier.
+bool lstm_width_ok(int H) { return H >= 4 && H <= 128 && (H & 3) == 0; }
+int lstm_kind(int H) { return H == 64 ? 0 : H <= 32 ? 32 : H <= 64 ? 64 : 128; }
+
+int launch_lstm_fwd_any(const LstmFwdDesc& a, int ha, const LstmFwdDesc* b, int hb, hipStream_t st) {
+  const int na = (a.B + kLstmRB - 1) / kLstmRB, nbb = b ? (b->B + kLstmRB - 1) / kLstmRB : 0;
+  const dim3 grid(na + nbb);
+  const LstmFwdDesc& b_ = b ? *b : a;
+  switch (lstm_kind(ha)) {
+    case 0: return launch_lstm_fwd<64, kLstmRB>(a, b, st);
+    case 32: hipLaunchKernelGGL((k_lstm_fwd_w<32, kLstmRB>), grid, dim3(128), 0, st, a, ha, b_, hb, na); break;
+    case 64: hipLaunchKernelGGL((k_lstm_fwd_w<64, kLstmRB>), grid, dim3(256), 0, st, a, ha, b_, hb, na); break;
+    default: hipLaunchKernelGGL((k_lstm_fwd_w<128, kLstmRB>), grid, dim3(512), 0, st, a, ha, b_, hb, na); break;
+  }
+  TSPM_LAUNCH_CHECK();
+  return TSPM_OK;
+}
+
+int launch_lstm_bwd_any(const LstmBwdDesc& a, int ha, const LstmBwdDesc* b, int hb, hipStream_t st) {
+  const int na = (a.B + kLstmRB - 1) / kLstmRB, nbb = b ? (b->B + kLstmRB - 1) / kLstmRB : 0;
+  const dim3 grid(na + nbb);
+  const LstmBwdDesc& b_ = b ? *b : a;
+  switch (lstm_kind(ha)) {
+    case 0: return launch_lstm_bwd<64, kLstmRB>(a, b, st);
+    case 32: hipLaunchKernelGGL((k_lstm_bwd_w<32, kLstmRB>), grid, dim3(128), 0, st, a, ha, b_, hb, na); break;
+    case 64: hipLaunchKernelGGL((k_lstm_bwd_w<64, kLstmRB>), grid, dim3(256), 0, st, a, ha, b_, hb, na); break;
+    default: hipLaunchKernelGGL((k_lstm_bwd_w<128, kLstmRB>), grid, dim3(512), 0, st, a, ha, b_, hb, na); break;
+  }
+  TSPM_LAUNCH_CHECK();
+  return TSPM_OK;
+}
+
 }  // namespace
 
 extern "C" int tspm_lstm_fwd(int32_t count, const tspm_lstm_fwd_desc* descs, tspm_stream_t stream) {
@@ -505,6 +736,50 @@ extern "C" int tspm_lstm_bwd(int32_t count, const tspm_lstm_bwd_desc* descs, tsp
     d[i] = LstmBwdDesc{s.batch, s.steps, s.w_hh, s.gates, s.cs, s.dh, s.ld_dh, s.dgates, s.argmax};
   }
   return launch_lstm_bwd<64, kLstmRB>(d[0], count > 1 ? &d[1] : nullptr, static_cast<hipStream_t>(stream));
+}
+
+// Any hidden width (4 <= hidden <= 128, a multiple of 4), each descriptor its own: two LSTMs of one kernel kind share a
+// launch, two of different kinds take one launch each (a workgroup's arithmetic does not depend on its neighbours, so
+// either way the results are those of two count-1 calls).  Everything is validated before the first launch.
+extern "C" int tspm_lstm_fwd_w(int32_t count, const tspm_lstm_fwd_desc* descs, tspm_stream_t stream) {
+  if (count < 1 || count > 2 || !descs) return TSPM_ERR_INVALID;
+  LstmFwdDesc d[2];
+  int hw[2] = {0, 0};
+  for (int i = 0; i < count; ++i) {
+    const tspm_lstm_fwd_desc& s = descs[i];
+    if (s.batch <= 0 || s.steps <= 0 || !lstm_width_ok(s.hidden) || !s.xg || !s.w_hh || !s.gates || !s.cs || !s.hs ||
+        !s.h_out || s.ld_out < s.hidden)
+      return TSPM_ERR_INVALID;
+    if (reinterpret_cast<uintptr_t>(s.w_hh) & 15) return TSPM_ERR_INVALID;
+    if (s.steps > 256 && s.argmax) return TSPM_ERR_INVALID;  // uint8 time index
+    d[i] = LstmFwdDesc{s.batch, s.steps, s.xg, s.w_hh, s.b_hh, s.gates, s.cs, s.hs, s.h_out, s.ld_out, s.argmax};
+    hw[i] = s.hidden;
+  }
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (count == 1 || lstm_kind(hw[0]) == lstm_kind(hw[1]))
+    return launch_lstm_fwd_any(d[0], hw[0], count > 1 ? &d[1] : nullptr, hw[1], st);
+  const int rc = launch_lstm_fwd_any(d[0], hw[0], nullptr, 0, st);
+  return rc != TSPM_OK ? rc : launch_lstm_fwd_any(d[1], hw[1], nullptr, 0, st);
+}
+
+extern "C" int tspm_lstm_bwd_w(int32_t count, const tspm_lstm_bwd_desc* descs, tspm_stream_t stream) {
+  if (count < 1 || count > 2 || !descs) return TSPM_ERR_INVALID;
+  LstmBwdDesc d[2];
+  int hw[2] = {0, 0};
+  for (int i = 0; i < count; ++i) {
+    const tspm_lstm_bwd_desc& s = descs[i];
+    if (s.batch <= 0 || s.steps <= 0 || !lstm_width_ok(s.hidden) || !s.w_hh || !s.gates || !s.cs || !s.dh ||
+        !s.dgates || s.ld_dh < s.hidden)
+      return TSPM_ERR_INVALID;
+    if (s.steps > 256 && s.argmax) return TSPM_ERR_INVALID;
+    d[i] = LstmBwdDesc{s.batch, s.steps, s.w_hh, s.gates, s.cs, s.dh, s.ld_dh, s.dgates, s.argmax};
+    hw[i] = s.hidden;
+  }
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (count == 1 || lstm_kind(hw[0]) == lstm_kind(hw[1]))
+    return launch_lstm_bwd_any(d[0], hw[0], count > 1 ? &d[1] : nullptr, hw[1], st);
+  const int rc = launch_lstm_bwd_any(d[0], hw[0], nullptr, 0, st);
+  return rc != TSPM_OK ? rc : launch_lstm_bwd_any(d[1], hw[1], nullptr, 0, st);
 }
 
 extern "C" int tspm_textcnn_pool_fwd(int32_t batch, int32_t steps, int32_t nconv, const int32_t* heights,

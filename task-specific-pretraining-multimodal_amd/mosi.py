@@ -19,7 +19,8 @@ ReLU → BatchNorm1d → Dropout 0.66), clip 0.5, Adam lr 2e-4 / wd 1e-5, batch 
 
 ``MosiEngine`` is the step's kernel schedule for a fixed (batch, steps): inputs time-major on the device
 ([T][B][F], rows (t, b)); LSTM input projections and weight gradients on the MFMA GEMM
-(``tspm_linear_*``), the recurrences in ``tspm_lstm_fwd/bwd`` (both encoders in one launch each), the
+(``tspm_linear_*``), the recurrences in ``tspm_lstm_fwd/bwd`` (both encoders in one launch each; with an LSTM
+``hidden_size`` other than 64 — any multiple of 4 up to 128, each encoder its own — ``tspm_lstm_fwd_w/bwd_w``), the
 TextCNN convolutions on the LDS-staged implicit-GEMM conv kernel (a (h, 768) kernel over [B,1,T,768]
 is a 1-D convolution with 768 input channels; the reference's [C,1,h,768] weight is already its OHWI
 layout), pooling + dropout in ``tspm_textcnn_pool_fwd``, the sparse TextCNN weight gradient in
@@ -64,17 +65,21 @@ YAML_CONFIGS = {
 }
 
 
-def build_utt_fusion(name: str = "mosi", output_dim: int = 3) -> "UttFusionModel":
+def build_utt_fusion(name: str = "mosi", output_dim: int = 3,
+                     embd_sizes: Sequence[int] = (64, 64, 64)) -> "UttFusionModel":
     """UttFusionModel of the named YAML (netA, netV, netT, netC constructed in the YAML's order, so a
     ``torch.manual_seed`` before the call gives the reference's initial weights).  ``output_dim=1`` builds the
     sentiment-regression model (``regression_labels``: a continuous score in [-3, 3]); only ``netC.fc_out``, the last
-    module constructed, differs from the default build of the same seed."""
+    module constructed, differs from the default build of the same seed.  ``embd_sizes`` = the (audio, video, text)
+    embedding widths (the YAMLs' ``hidden_size`` / ``embd_size`` fields; the LSTM widths within
+    ``L.lstm_width_supported``); the classifier's input is their sum."""
     c = YAML_CONFIGS[name]
-    netA = LSTMEncoder(input_size=c["audio_dim"], hidden_size=64, embd_method=c["embd_method"])
-    netV = LSTMEncoder(input_size=c["video_dim"], hidden_size=64, embd_method=c["embd_method"])
-    netT = TextCNN(input_size=c["text_dim"], embd_size=64, dropout=c["text_dropout"], in_channels=1, out_channels=128,
+    ha, hv, ht = (int(w) for w in embd_sizes)
+    netA = LSTMEncoder(input_size=c["audio_dim"], hidden_size=ha, embd_method=c["embd_method"])
+    netV = LSTMEncoder(input_size=c["video_dim"], hidden_size=hv, embd_method=c["embd_method"])
+    netT = TextCNN(input_size=c["text_dim"], embd_size=ht, dropout=c["text_dropout"], in_channels=1, out_channels=128,
                    kernel_heights=[3, 4, 5])
-    netC = FcClassifier(input_dim=192, layers=list(c["cls_layers"]), output_dim=output_dim, dropout=c["cls_dropout"],
+    netC = FcClassifier(input_dim=ha + hv + ht, layers=list(c["cls_layers"]), output_dim=output_dim, dropout=c["cls_dropout"],
                         use_bn=c["use_bn"])
     return UttFusionModel(netA, netV, netT, netC, clip=c["clip"])
 
@@ -208,8 +213,9 @@ def _lstm_alloc(enc: "LSTMEncoder", B: int, T: int, device, backward: bool = Tru
     """One LSTM's saved activations for a fixed (batch, steps): xg / gates [T*B, 4H], cs [T*B, H], hs [(T+1)*B, H],
     the gate gradients dg [T*B, 4H] (``backward``) and, for the "maxpool" embedding, the time index of each unit's
     maximum (uint8 [B][H])."""
-    if enc.hidden_size != 64:
-        raise NotImplementedError("MOSI HIP path: LSTM hidden size 64 (tspm_lstm_fwd)")
+    if not L.lstm_width_supported(enc.hidden_size):
+        raise L.TspmError(f"MOSI HIP path: LSTM hidden size {enc.hidden_size} — the recurrence kernels take a multiple "
+                          f"of 4 with 4 <= hidden_size <= 128 (tspm_lstm_fwd_w)")
     f, H = dict(device=device, dtype=torch.float32), enc.hidden_size
     bufs = dict(xg=torch.empty(T * B, 4 * H, **f), gates=torch.empty(T * B, 4 * H, **f),
                 cs=torch.empty(T * B, H, **f), hs=torch.empty((T + 1) * B, H, **f),
@@ -240,7 +246,7 @@ def _lstm_bwd_desc(d, enc: "LSTMEncoder", bufs, B: int, T: int, dh: int, ld_dh: 
     d.argmax = L.ptr(bufs["arg"])
 
 
-def _lstm_wgrad(enc: "LSTMEncoder", x: torch.Tensor, bufs, B: int, T: int, splits: Dict[int, int],
+def _lstm_wgrad(enc: "LSTMEncoder", x: torch.Tensor, bufs, B: int, T: int, split: int,
                 wg_ws: torch.Tensor, g, sh: int) -> None:
     """The LSTM weight gradients as GEMMs over the T*B rows of dgates (after tspm_lstm_bwd)."""
     lib, rnn, H, fin = L.lib(), enc.rnn, enc.hidden_size, enc.input_size
@@ -248,24 +254,25 @@ def _lstm_wgrad(enc: "LSTMEncoder", x: torch.Tensor, bufs, B: int, T: int, split
     # dW_hh = dgates^T h_{t-1} (rows (t, b) of hs[0:T]); db_hh = column sums of dgates
     L.check(lib.tspm_linear_bwd_weight_splitk(T * B, H, 4 * H, bufs["hs"].data_ptr(), H, bufs["dg"].data_ptr(),
                                               4 * H, g(rnn.weight_hh_l0).data_ptr(),
-                                              g(rnn.bias_hh_l0).data_ptr(), splits[H], ws, wsb, sh),
+                                              g(rnn.bias_hh_l0).data_ptr(), split, ws, wsb, sh),
             "lstm dW_hh")
     # dW_ih = dgates^T x; db_ih = the same column sums (same split and order: bitwise db_hh)
     L.check(lib.tspm_linear_bwd_weight_splitk(T * B, fin, 4 * H, x.data_ptr(), fin, bufs["dg"].data_ptr(),
                                               4 * H, g(rnn.weight_ih_l0).data_ptr(),
-                                              g(rnn.bias_ih_l0).data_ptr(), splits[fin], ws, wsb, sh),
+                                              g(rnn.bias_ih_l0).data_ptr(), split, ws, wsb, sh),
             "lstm dW_ih")
 
 
-def _lstm_wgrad_plan(B: int, T: int, fins, device):
-    """LSTM weight gradients reduce over T*B rows into 256 x {in, 64} outputs (8-16 output tiles): split the
+def _lstm_wgrad_plan(B: int, T: int, encs, device):
+    """LSTM weight gradients reduce over T*B rows into 4H x {in, H} outputs (a few output tiles): split the
     reduction so the launch fills the chip (tspm_linear_bwd_weight_splitk) — one split for every product
-    (db_ih and db_hh come from two calls and must stay bitwise equal).  → (splits by fan-in, workspace)."""
-    lib, H = L.lib(), 64
+    (db_ih and db_hh come from two calls and must stay bitwise equal).  → (the split, a workspace that holds the
+    largest product of the encoders `encs`)."""
+    lib = L.lib()
     sp = max(1, min(32, (T * B) // 128))
-    splits = {fin: sp for fin in tuple(fins) + (H,)}
-    wsb = max(int(lib.tspm_linear_bwd_weight_splitk_workspace(T * B, fin, 4 * H, sp)) for fin in splits)
-    return splits, torch.empty(max(wsb // 4, 1), device=device, dtype=torch.float32)
+    wsb = max(int(lib.tspm_linear_bwd_weight_splitk_workspace(T * B, fin, 4 * enc.hidden_size, sp))
+              for enc in encs for fin in (enc.input_size, enc.hidden_size))
+    return sp, torch.empty(max(wsb // 4, 1), device=device, dtype=torch.float32)
 
 
 def _text_alloc(o, t: "TextCNN", B: int, T: int, device) -> None:
@@ -357,7 +364,7 @@ class MosiEngine:
         self.m, self.B, self.T, self.device = model, batch, steps, device
         a, v, t, c = model.netA, model.netV, model.netT, model.netC
         f = dict(device=device, dtype=torch.float32)
-        B, T, H = batch, steps, 64
+        B, T = batch, steps
         self.fa, self.fv, self.ft = a.input_size, v.input_size, t.input_size
         self.A = torch.zeros(T, B, self.fa, **f)          # time-major inputs
         self.V = torch.zeros(T, B, self.fv, **f)
@@ -399,7 +406,7 @@ class MosiEngine:
         self.keep_override: Optional[Dict[str, torch.Tensor]] = None
         self.rng_ctr_ptr: Optional[int] = None
         self._host_ctr: Optional[torch.Tensor] = None
-        self.wg_splits, self.wg_ws = _lstm_wgrad_plan(B, T, (self.fa, self.fv), device)
+        self.wg_split, self.wg_ws = _lstm_wgrad_plan(B, T, (a, v), device)
         self.concurrent = os.environ.get("TSPM_MOSI_SERIAL", "0") != "1"
         self.side: Optional[torch.cuda.Stream] = None
         self.clip_coef = torch.ones(1, **f)
@@ -494,7 +501,7 @@ class MosiEngine:
         descs = (L.LstmFwdDesc * 2)()
         for i, (name, enc, x, col) in enumerate((("a", m.netA, self.A, 0), ("v", m.netV, self.V, m.netA.hidden_size))):
             _lstm_fwd_prepare(descs[i], enc, x, self.lstm[name], B, T, self.fused.data_ptr() + col * 4, self.E, sh)
-        L.check(lib.tspm_lstm_fwd(2, descs, sh), "lstm_fwd")
+        L.check(L.lstm_fwd(2, descs, sh), "lstm_fwd")
 
     def _forward_text(self, sh: int, train: bool) -> None:
         m, t = self.m, self.m.netT
@@ -627,9 +634,9 @@ class MosiEngine:
         descs = (L.LstmBwdDesc * 2)()
         for i, (name, enc, col) in enumerate((("a", m.netA, 0), ("v", m.netV, m.netA.hidden_size))):
             _lstm_bwd_desc(descs[i], enc, self.lstm[name], B, T, self.dfused.data_ptr() + col * 4, self.E)
-        L.check(lib.tspm_lstm_bwd(2, descs, sh), "lstm_bwd")
+        L.check(L.lstm_bwd(2, descs, sh), "lstm_bwd")
         for name, enc, x in (("a", m.netA, self.A), ("v", m.netV, self.V)):
-            _lstm_wgrad(enc, x, self.lstm[name], B, T, self.wg_splits, self.wg_ws, g, sh)
+            _lstm_wgrad(enc, x, self.lstm[name], B, T, self.wg_split, self.wg_ws, g, sh)
 
     def clip(self, sh: int, flat_grad: torch.Tensor, grad_scale: float) -> None:
         """clip_grad_norm_(model.parameters(), clip) coefficient into ``clip_coef`` (utt_fusion.py:188-189)."""
@@ -673,7 +680,7 @@ class MosiEncoderEngine:
             self.keep = torch.ones(B, self.nc, dtype=torch.uint8, device=device)
         else:
             self.bufs = _lstm_alloc(enc, B, T, device)
-            self.wg_splits, self.wg_ws = _lstm_wgrad_plan(B, T, (enc.input_size,), device)
+            self.wg_split, self.wg_ws = _lstm_wgrad_plan(B, T, (enc,), device)
         self.grad_of = lambda p: p.grad  # noqa: E731  (FusedAdam's flat gradient views)
         self._index = torch.arange(B, dtype=torch.int64, device=device)
         self._lens = torch.full((B,), T, dtype=torch.int32, device=device)
@@ -712,7 +719,7 @@ class MosiEncoderEngine:
             return
         d = (L.LstmFwdDesc * 1)()
         _lstm_fwd_prepare(d[0], self.enc, self.X, self.bufs, B, T, self.emb.data_ptr(), self.hidden, sh)
-        L.check(L.lib().tspm_lstm_fwd(1, d, sh), "lstm_fwd")
+        L.check(L.lstm_fwd(1, d, sh), "lstm_fwd")
 
     def backward(self, sh: int) -> None:
         """From ``demb`` (modified in place by the TextCNN's ReLU mask) to every parameter gradient."""
@@ -724,8 +731,8 @@ class MosiEncoderEngine:
             return
         d = (L.LstmBwdDesc * 1)()
         _lstm_bwd_desc(d[0], self.enc, self.bufs, B, T, self.demb.data_ptr(), self.hidden)
-        L.check(L.lib().tspm_lstm_bwd(1, d, sh), "lstm_bwd")
-        _lstm_wgrad(self.enc, self.X, self.bufs, B, T, self.wg_splits, self.wg_ws, self.grad_of, sh)
+        L.check(L.lstm_bwd(1, d, sh), "lstm_bwd")
+        _lstm_wgrad(self.enc, self.X, self.bufs, B, T, self.wg_split, self.wg_ws, self.grad_of, sh)
 
 
 def _ce_weight(loss_functions) -> Optional[float]:
@@ -1175,5 +1182,5 @@ def _encode_lstm(enc: LSTMEncoder, x: torch.Tensor) -> torch.Tensor:
     d = (L.LstmFwdDesc * 1)()
     _lstm_fwd_prepare(d[0], enc, xt, _lstm_alloc(enc, B, T, x.device, backward=False), B, T, out.data_ptr(),
                       enc.hidden_size, sh)
-    L.check(L.lib().tspm_lstm_fwd(1, d, sh), "lstm_fwd")
+    L.check(L.lstm_fwd(1, d, sh), "lstm_fwd")
     return out
