@@ -52,7 +52,8 @@ enum {
  * tspm_mono_head_bce_step / tspm_mono_head_bce_workspace, the multi-label (BCEWithLogits, F1 counts) form of that
  * head for the MMIMDb encoder pre-training step; tspm_regress_head_step, the scalar-output head of the MOSI / MOSEI
  * sentiment regression (L1 / MSE, backward, epoch accumulators, loss log) in one launch; tspm_lstm_fwd_w /
- * tspm_lstm_bwd_w, the LSTM recurrences at any hidden width that is a multiple of 4 up to 128 (same descriptors). */
+ * tspm_lstm_bwd_w, the LSTM recurrences at any hidden width that is a multiple of 4 up to 128 (same descriptors);
+ * tspm_lstm_fwd_t16 / tspm_lstm_bwd_t16, those recurrences with a 16-bit "maxpool" time index (up to 65535 steps). */
 #define TSPM_ABI_VERSION 23
 int tspm_abi_version(void);  /* returns TSPM_ABI_VERSION */
 /* Static string for a status code. */
@@ -779,6 +780,16 @@ int tspm_lstm_bwd(int32_t count, const tspm_lstm_bwd_desc* descs, tspm_stream_t 
  * hidden = 64 bitwise those of tspm_lstm_fwd / tspm_lstm_bwd.  Every descriptor is validated before the first launch. */
 int tspm_lstm_fwd_w(int32_t count, const tspm_lstm_fwd_desc* descs, tspm_stream_t stream);
 int tspm_lstm_bwd_w(int32_t count, const tspm_lstm_bwd_desc* descs, tspm_stream_t stream);
+/* tspm_lstm_fwd_w / tspm_lstm_bwd_w with a 16-bit time index (added under ABI 23, no existing signature changed): the
+ * "maxpool" embedding past 256 steps (the unaligned CMU-MOSI / CMU-MOSEI audio and video sequences).  Same descriptors,
+ * widths, tiers, launch sharing and semantics (first maximum, NaN wins; h_out is the kernel's own h at its own index; a
+ * ghost row writes nothing), with ONE difference: a non-NULL `argmax` field is read as `uint16_t*` — the caller casts
+ * its `uint16_t [batch][hidden]` buffer (2-byte aligned) to the field's declared `uint8_t*`, and must pass the same
+ * buffer to the backward.  With an index 1 <= steps <= 65535; with argmax NULL steps is unlimited, as in _w; anything
+ * else is TSPM_ERR_INVALID.  With argmax NULL the results are bitwise those of _w; with an index and steps <= 256 every
+ * float output is bitwise _w's and the index values are equal as integers. */
+int tspm_lstm_fwd_t16(int32_t count, const tspm_lstm_fwd_desc* descs, tspm_stream_t stream);
+int tspm_lstm_bwd_t16(int32_t count, const tspm_lstm_bwd_desc* descs, tspm_stream_t stream);
 /* TextCNN pooling (models/msa/networks/textcnn.py:56-67): for conv i (kernel height heights[i], output
  * conv_out[i] time-major [steps-heights[i]+1][batch][channels] without bias), bias[i] added, ReLU,
  * max over time (first maximum, F.max_pool1d), concatenated over convs: pooled[b][i*C+c] and the

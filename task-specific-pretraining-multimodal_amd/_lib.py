@@ -161,16 +161,45 @@ def lstm_width_supported(h: int) -> bool:
     return 4 <= int(h) <= 128 and int(h) % 4 == 0
 
 
-def lstm_fwd(count: int, descs, sh) -> int:
-    """tspm_lstm_fwd when every LSTM of the launch is 64 wide (the compile-time kernels), else tspm_lstm_fwd_w."""
+LSTM_STEPS_U8 = 256      # the most steps an 8-bit "maxpool" time index covers (tspm_lstm_fwd / _w)
+LSTM_STEPS_U16 = 65535   # ... and a 16-bit one (tspm_lstm_fwd_t16 / _bwd_t16)
+
+
+def lstm_steps_supported(steps: int, indexed: bool) -> bool:
+    """The step counts the LSTM recurrences take: any positive count without a time index (embd "last"), 1..65535 with
+    one (embd "maxpool": 1..256 on the 8-bit entry points, beyond that tspm_lstm_fwd_t16 / tspm_lstm_bwd_t16)."""
+    return int(steps) >= 1 and (not indexed or int(steps) <= LSTM_STEPS_U16)
+
+
+def lstm_wide_index(encs_steps) -> bool:
+    """Whether one LSTM launch takes the 16-bit index entry points: exactly when some (embd_method, steps) of the launch
+    is a "maxpool" embedding over more than 256 steps.  Every index buffer of that launch is then 16-bit."""
+    return any(m == "maxpool" and int(t) > LSTM_STEPS_U8 for m, t in encs_steps)
+
+
+def lstm_fwd(count: int, descs, sh, wide: bool = False) -> int:
+    """tspm_lstm_fwd when every LSTM of the launch is 64 wide (the compile-time kernels), else tspm_lstm_fwd_w; with
+    ``wide`` (16-bit index buffers, ``lstm_wide_index``) tspm_lstm_fwd_t16."""
+    if wide:
+        return lib().tspm_lstm_fwd_t16(count, descs, sh)
     fn = lib().tspm_lstm_fwd if all(descs[i].hidden == 64 for i in range(count)) else lib().tspm_lstm_fwd_w
     return fn(count, descs, sh)
 
 
-def lstm_bwd(count: int, descs, sh) -> int:
-    """tspm_lstm_bwd when every LSTM of the launch is 64 wide, else tspm_lstm_bwd_w."""
+def lstm_bwd(count: int, descs, sh, wide: bool = False) -> int:
+    """tspm_lstm_bwd when every LSTM of the launch is 64 wide, else tspm_lstm_bwd_w; with ``wide`` tspm_lstm_bwd_t16."""
+    if wide:
+        return lib().tspm_lstm_bwd_t16(count, descs, sh)
     fn = lib().tspm_lstm_bwd if all(descs[i].hidden == 64 for i in range(count)) else lib().tspm_lstm_bwd_w
     return fn(count, descs, sh)
+
+
+def index_to_int64(arg: torch.Tensor) -> torch.Tensor:
+    """A "maxpool" time-index buffer as int64 values: uint8 as it is; the 16-bit buffer is int16 storage holding the
+    unsigned pattern (torch's device support for uint16 is thin), widened without sign extension."""
+    if arg.dtype == torch.int16:
+        return arg.to(torch.int64) & 0xFFFF
+    return arg.to(torch.int64)
 
 
 _SIGS = {
@@ -284,6 +313,9 @@ _SIGS = {
     "tspm_lstm_bwd": (c_int32, [c_int32, POINTER(LstmBwdDesc), _P]),
     "tspm_lstm_fwd_w": (c_int32, [c_int32, POINTER(LstmFwdDesc), _P]),
     "tspm_lstm_bwd_w": (c_int32, [c_int32, POINTER(LstmBwdDesc), _P]),
+    # added under ABI 23: the same recurrences with a 16-bit "maxpool" time index (argmax points to uint16)
+    "tspm_lstm_fwd_t16": (c_int32, [c_int32, POINTER(LstmFwdDesc), _P]),
+    "tspm_lstm_bwd_t16": (c_int32, [c_int32, POINTER(LstmBwdDesc), _P]),
     "tspm_textcnn_pool_fwd": (c_int32, [c_int32, c_int32, c_int32, _P, c_int32, _P, _P, _P, c_float, _P, _P, _P,
                                         c_int32, _P]),
     "tspm_textcnn_bwd": (c_int32, [c_int32, c_int32, c_int32, c_int32, _P, c_int32, _P, _P, c_int32, _P, c_float, _P,

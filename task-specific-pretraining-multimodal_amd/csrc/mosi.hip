@@ -22,7 +22,11 @@ TSPM_DEV float sigmoidf_(float x) { return 1.f / (1.f + expf(-x)); }
 // gates = (h W_hh^T + b_hh) + (x W_ih^T + b_ih); i,f,o = sigmoid, g = tanh; c = f*c + i*g;
 // h = o * tanh(c).  Saved for the backward: activated gates, c_t, h_t.
 // ------------------------------------------------------------------------------------------------
-struct LstmFwdDesc {
+// Ix is the type of the "maxpool" time index: uint8_t (steps <= 256, tspm_lstm_fwd / _w) or uint16_t (steps <= 65535,
+// tspm_lstm_fwd_t16 / _bwd_t16).  It is a template parameter of the descriptors, the bodies and the kernels, so the two index
+// widths are one source and the uint8_t instantiations are the code they were before the parameter existed.
+template <typename Ix>
+struct LstmFwdDescT {
   int B, T;
   const float* xg;   // [T][B][4H]: x W_ih^T + b_ih
   const float* whh;  // [4H][H]
@@ -32,11 +36,12 @@ struct LstmFwdDesc {
   float* hs;         // [T+1][B][H], hs[0] = 0
   float* hout;       // h_T rows (embd "last") or max_t h_t (embd "maxpool"), stride ldh
   int ldh;
-  uint8_t* arg;      // embd "maxpool": [B][H] time index of the maximum (F.max_pool1d), else null
+  Ix* arg;           // embd "maxpool": [B][H] time index of the maximum (F.max_pool1d), else null
 };
+using LstmFwdDesc = LstmFwdDescT<uint8_t>;
 
-template <int H, int RB>
-TSPM_DEV void lstm_fwd_body(const LstmFwdDesc& d, int chunk) {
+template <int H, int RB, typename Ix>
+TSPM_DEV void lstm_fwd_body(const LstmFwdDescT<Ix>& d, int chunk) {
   constexpr int G = 4 * H;
   __shared__ __attribute__((aligned(16))) float hsh[RB][H];
   __shared__ float gsh[RB][G];
@@ -111,16 +116,16 @@ TSPM_DEV void lstm_fwd_body(const LstmFwdDesc& d, int chunk) {
   }
   if (cell) {
     d.hout[(long long)(b0 + cr) * d.ldh + cu] = d.arg ? mx : h;
-    if (d.arg) d.arg[(long long)(b0 + cr) * H + cu] = (uint8_t)am;
+    if (d.arg) d.arg[(long long)(b0 + cr) * H + cu] = (Ix)am;
   }
 }
 
-template <int H, int RB>
-__global__ __launch_bounds__(4 * H) void k_lstm_fwd(LstmFwdDesc d0, LstmFwdDesc d1, int nb0) {
+template <int H, int RB, typename Ix>
+__global__ __launch_bounds__(4 * H) void k_lstm_fwd(LstmFwdDescT<Ix> d0, LstmFwdDescT<Ix> d1, int nb0) {
   if ((int)blockIdx.x < nb0)
-    lstm_fwd_body<H, RB>(d0, blockIdx.x);
+    lstm_fwd_body<H, RB, Ix>(d0, blockIdx.x);
   else
-    lstm_fwd_body<H, RB>(d1, blockIdx.x - nb0);
+    lstm_fwd_body<H, RB, Ix>(d1, blockIdx.x - nb0);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -139,8 +144,8 @@ __global__ __launch_bounds__(4 * H) void k_lstm_fwd(LstmFwdDesc d0, LstmFwdDesc 
 // the start and never written, so no NaN of a real unit can meet a padded zero.
 constexpr int kLstmChunk = 32;
 
-template <int HP, int RB>
-TSPM_DEV void lstm_fwd_w_body(const LstmFwdDesc& d, const int H, int chunk) {
+template <int HP, int RB, typename Ix>
+TSPM_DEV void lstm_fwd_w_body(const LstmFwdDescT<Ix>& d, const int H, int chunk) {
   constexpr int GP = 4 * HP;
   __shared__ __attribute__((aligned(16))) float hsh[RB][HP];
   __shared__ float gsh[RB][GP];
@@ -225,17 +230,18 @@ TSPM_DEV void lstm_fwd_w_body(const LstmFwdDesc& d, const int H, int chunk) {
   }
   if (cell) {
     d.hout[(long long)(b0 + cr) * d.ldh + cu] = d.arg ? mx : h;
-    if (d.arg) d.arg[(long long)(b0 + cr) * H + cu] = (uint8_t)am;
+    if (d.arg) d.arg[(long long)(b0 + cr) * H + cu] = (Ix)am;
   }
 }
 
-template <int HP, int RB>
-__global__ __launch_bounds__(4 * HP) void k_lstm_fwd_w(LstmFwdDesc d0, int h0, LstmFwdDesc d1, int h1, int nb0) {
+template <int HP, int RB, typename Ix>
+__global__ __launch_bounds__(4 * HP) void k_lstm_fwd_w(LstmFwdDescT<Ix> d0, int h0, LstmFwdDescT<Ix> d1, int h1,
+                                                       int nb0) {
   static_assert(RB <= 4, "cell threads are the first RB gate blocks");
   if ((int)blockIdx.x < nb0)
-    lstm_fwd_w_body<HP, RB>(d0, h0, blockIdx.x);
+    lstm_fwd_w_body<HP, RB, Ix>(d0, h0, blockIdx.x);
   else
-    lstm_fwd_w_body<HP, RB>(d1, h1, blockIdx.x - nb0);
+    lstm_fwd_w_body<HP, RB, Ix>(d1, h1, blockIdx.x - nb0);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -244,7 +250,8 @@ __global__ __launch_bounds__(4 * HP) void k_lstm_fwd_w(LstmFwdDesc d0, int h0, L
 // fixed order through LDS); threads (r, u) carry dc and form the pre-activation gate gradients
 // (written time-major for the weight-gradient GEMMs that follow).
 // ------------------------------------------------------------------------------------------------
-struct LstmBwdDesc {
+template <typename Ix>
+struct LstmBwdDescT {
   int B, T;
   const float* whh;    // [4H][H]
   const float* gates;  // [T][B][4H]
@@ -252,11 +259,12 @@ struct LstmBwdDesc {
   const float* dh;     // gradient of the embedding rows (h_T, or max_t h_t at arg), stride lddh
   int lddh;
   float* dgates;       // [T][B][4H] out
-  const uint8_t* arg;  // embd "maxpool": [B][H] time index that received the embedding (null: T-1)
+  const Ix* arg;       // embd "maxpool": [B][H] time index that received the embedding (null: T-1)
 };
+using LstmBwdDesc = LstmBwdDescT<uint8_t>;
 
-template <int H, int RB>
-TSPM_DEV void lstm_bwd_body(const LstmBwdDesc& d, int chunk) {
+template <int H, int RB, typename Ix>
+TSPM_DEV void lstm_bwd_body(const LstmBwdDescT<Ix>& d, int chunk) {
   constexpr int G = 4 * H;
   __shared__ __attribute__((aligned(16))) float dgs[RB][G];
   __shared__ float part[4][RB][H];
@@ -319,19 +327,19 @@ TSPM_DEV void lstm_bwd_body(const LstmBwdDesc& d, int chunk) {
   }
 }
 
-template <int H, int RB>
-__global__ __launch_bounds__(4 * H) void k_lstm_bwd(LstmBwdDesc d0, LstmBwdDesc d1, int nb0) {
+template <int H, int RB, typename Ix>
+__global__ __launch_bounds__(4 * H) void k_lstm_bwd(LstmBwdDescT<Ix> d0, LstmBwdDescT<Ix> d1, int nb0) {
   if ((int)blockIdx.x < nb0)
-    lstm_bwd_body<H, RB>(d0, blockIdx.x);
+    lstm_bwd_body<H, RB, Ix>(d0, blockIdx.x);
   else
-    lstm_bwd_body<H, RB>(d1, blockIdx.x - nb0);
+    lstm_bwd_body<H, RB, Ix>(d1, blockIdx.x - nb0);
 }
 
 // LSTM backward through time at a run-time width H on a tier of HP lanes per gate quarter (see k_lstm_fwd_w):
 // thread (q, k) keeps column k of the quarter-q rows of W_hh (zeros in a padded lane), the unrolled jj loop runs in
 // guarded chunks of kLstmChunk as the forward's k loop, padded lanes read and write no global memory, and only units < H are ever read back from LDS.
-template <int HP, int RB>
-TSPM_DEV void lstm_bwd_w_body(const LstmBwdDesc& d, const int H, int chunk) {
+template <int HP, int RB, typename Ix>
+TSPM_DEV void lstm_bwd_w_body(const LstmBwdDescT<Ix>& d, const int H, int chunk) {
   constexpr int GP = 4 * HP;
   __shared__ __attribute__((aligned(16))) float dgs[RB][GP];
   __shared__ float part[4][RB][HP];
@@ -401,13 +409,14 @@ TSPM_DEV void lstm_bwd_w_body(const LstmBwdDesc& d, const int H, int chunk) {
   }
 }
 
-template <int HP, int RB>
-__global__ __launch_bounds__(4 * HP) void k_lstm_bwd_w(LstmBwdDesc d0, int h0, LstmBwdDesc d1, int h1, int nb0) {
+template <int HP, int RB, typename Ix>
+__global__ __launch_bounds__(4 * HP) void k_lstm_bwd_w(LstmBwdDescT<Ix> d0, int h0, LstmBwdDescT<Ix> d1, int h1,
+                                                       int nb0) {
   static_assert(RB <= 4, "cell threads are the first RB gate quarters");
   if ((int)blockIdx.x < nb0)
-    lstm_bwd_w_body<HP, RB>(d0, h0, blockIdx.x);
+    lstm_bwd_w_body<HP, RB, Ix>(d0, h0, blockIdx.x);
   else
-    lstm_bwd_w_body<HP, RB>(d1, h1, blockIdx.x - nb0);
+    lstm_bwd_w_body<HP, RB, Ix>(d1, h1, blockIdx.x - nb0);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -654,18 +663,18 @@ int grid_for(long long work) {
   return (int)(b < 1 ? 1 : b);
 }
 
-template <int H, int RB>
-int launch_lstm_fwd(const LstmFwdDesc& a, const LstmFwdDesc* b, hipStream_t st) {
+template <int H, int RB, typename Ix>
+int launch_lstm_fwd(const LstmFwdDescT<Ix>& a, const LstmFwdDescT<Ix>* b, hipStream_t st) {
   const int na = (a.B + RB - 1) / RB, nbb = b ? (b->B + RB - 1) / RB : 0;
-  hipLaunchKernelGGL((k_lstm_fwd<H, RB>), dim3(na + nbb), dim3(4 * H), 0, st, a, b ? *b : a, na);
+  hipLaunchKernelGGL((k_lstm_fwd<H, RB, Ix>), dim3(na + nbb), dim3(4 * H), 0, st, a, b ? *b : a, na);
   TSPM_LAUNCH_CHECK();
   return TSPM_OK;
 }
 
-template <int H, int RB>
-int launch_lstm_bwd(const LstmBwdDesc& a, const LstmBwdDesc* b, hipStream_t st) {
+template <int H, int RB, typename Ix>
+int launch_lstm_bwd(const LstmBwdDescT<Ix>& a, const LstmBwdDescT<Ix>* b, hipStream_t st) {
   const int na = (a.B + RB - 1) / RB, nbb = b ? (b->B + RB - 1) / RB : 0;
-  hipLaunchKernelGGL((k_lstm_bwd<H, RB>), dim3(na + nbb), dim3(4 * H), 0, st, a, b ? *b : a, na);
+  hipLaunchKernelGGL((k_lstm_bwd<H, RB, Ix>), dim3(na + nbb), dim3(4 * H), 0, st, a, b ? *b : a, na);
   TSPM_LAUNCH_CHECK();
   return TSPM_OK;
 }
@@ -681,32 +690,89 @@ bool lstm_ok(int B, int T, int H, const void* p0, const void* p1, const void* p2
 bool lstm_width_ok(int H) { return H >= 4 && H <= 128 && (H & 3) == 0; }
 int lstm_kind(int H) { return H == 64 ? 0 : H <= 32 ? 32 : H <= 64 ? 64 : 128; }
 
-int launch_lstm_fwd_any(const LstmFwdDesc& a, int ha, const LstmFwdDesc* b, int hb, hipStream_t st) {
+// The largest step count whose time index fits the index type: 256 steps (indices 0..255) in uint8_t, 65535 steps in
+// uint16_t (tspm.h states 1..65535; index 65535 is never produced).
+template <typename Ix> constexpr int kLstmIndexedSteps = sizeof(Ix) == 1 ? 256 : 65535;
+
+template <typename Ix>
+int launch_lstm_fwd_any(const LstmFwdDescT<Ix>& a, int ha, const LstmFwdDescT<Ix>* b, int hb, hipStream_t st) {
   const int na = (a.B + kLstmRB - 1) / kLstmRB, nbb = b ? (b->B + kLstmRB - 1) / kLstmRB : 0;
   const dim3 grid(na + nbb);
-  const LstmFwdDesc& b_ = b ? *b : a;
+  const LstmFwdDescT<Ix>& b_ = b ? *b : a;
   switch (lstm_kind(ha)) {
-    case 0: return launch_lstm_fwd<64, kLstmRB>(a, b, st);
-    case 32: hipLaunchKernelGGL((k_lstm_fwd_w<32, kLstmRB>), grid, dim3(128), 0, st, a, ha, b_, hb, na); break;
-    case 64: hipLaunchKernelGGL((k_lstm_fwd_w<64, kLstmRB>), grid, dim3(256), 0, st, a, ha, b_, hb, na); break;
-    default: hipLaunchKernelGGL((k_lstm_fwd_w<128, kLstmRB>), grid, dim3(512), 0, st, a, ha, b_, hb, na); break;
+    case 0: return launch_lstm_fwd<64, kLstmRB, Ix>(a, b, st);
+    case 32: hipLaunchKernelGGL((k_lstm_fwd_w<32, kLstmRB, Ix>), grid, dim3(128), 0, st, a, ha, b_, hb, na); break;
+    case 64: hipLaunchKernelGGL((k_lstm_fwd_w<64, kLstmRB, Ix>), grid, dim3(256), 0, st, a, ha, b_, hb, na); break;
+    default: hipLaunchKernelGGL((k_lstm_fwd_w<128, kLstmRB, Ix>), grid, dim3(512), 0, st, a, ha, b_, hb, na); break;
   }
   TSPM_LAUNCH_CHECK();
   return TSPM_OK;
 }
 
-int launch_lstm_bwd_any(const LstmBwdDesc& a, int ha, const LstmBwdDesc* b, int hb, hipStream_t st) {
+template <typename Ix>
+int launch_lstm_bwd_any(const LstmBwdDescT<Ix>& a, int ha, const LstmBwdDescT<Ix>* b, int hb, hipStream_t st) {
   const int na = (a.B + kLstmRB - 1) / kLstmRB, nbb = b ? (b->B + kLstmRB - 1) / kLstmRB : 0;
   const dim3 grid(na + nbb);
-  const LstmBwdDesc& b_ = b ? *b : a;
+  const LstmBwdDescT<Ix>& b_ = b ? *b : a;
   switch (lstm_kind(ha)) {
-    case 0: return launch_lstm_bwd<64, kLstmRB>(a, b, st);
-    case 32: hipLaunchKernelGGL((k_lstm_bwd_w<32, kLstmRB>), grid, dim3(128), 0, st, a, ha, b_, hb, na); break;
-    case 64: hipLaunchKernelGGL((k_lstm_bwd_w<64, kLstmRB>), grid, dim3(256), 0, st, a, ha, b_, hb, na); break;
-    default: hipLaunchKernelGGL((k_lstm_bwd_w<128, kLstmRB>), grid, dim3(512), 0, st, a, ha, b_, hb, na); break;
+    case 0: return launch_lstm_bwd<64, kLstmRB, Ix>(a, b, st);
+    case 32: hipLaunchKernelGGL((k_lstm_bwd_w<32, kLstmRB, Ix>), grid, dim3(128), 0, st, a, ha, b_, hb, na); break;
+    case 64: hipLaunchKernelGGL((k_lstm_bwd_w<64, kLstmRB, Ix>), grid, dim3(256), 0, st, a, ha, b_, hb, na); break;
+    default: hipLaunchKernelGGL((k_lstm_bwd_w<128, kLstmRB, Ix>), grid, dim3(512), 0, st, a, ha, b_, hb, na); break;
   }
   TSPM_LAUNCH_CHECK();
   return TSPM_OK;
+}
+
+// Any hidden width (4 <= hidden <= 128, a multiple of 4), each descriptor its own: two LSTMs of one kernel kind share a
+// launch, two of different kinds take one launch each (a workgroup's arithmetic does not depend on its neighbours, so
+// either way the results are those of two count-1 calls).  Everything is validated before the first launch.  Ix is the
+// type the descriptors' argmax field points to (tspm.h declares it uint8_t*; the _t16 entry points document the cast).
+template <typename Ix>
+int lstm_fwd_any_width(int32_t count, const tspm_lstm_fwd_desc* descs, tspm_stream_t stream) {
+  if (count < 1 || count > 2 || !descs) return TSPM_ERR_INVALID;
+  LstmFwdDescT<Ix> d[2];
+  int hw[2] = {0, 0};
+  for (int i = 0; i < count; ++i) {
+    const tspm_lstm_fwd_desc& s = descs[i];
+    if (s.batch <= 0 || s.steps <= 0 || !lstm_width_ok(s.hidden) || !s.xg || !s.w_hh || !s.gates || !s.cs || !s.hs ||
+        !s.h_out || s.ld_out < s.hidden)
+      return TSPM_ERR_INVALID;
+    if (reinterpret_cast<uintptr_t>(s.w_hh) & 15) return TSPM_ERR_INVALID;
+    if (s.steps > kLstmIndexedSteps<Ix> && s.argmax) return TSPM_ERR_INVALID;  // the time index must fit Ix
+    if (reinterpret_cast<uintptr_t>(s.argmax) & (sizeof(Ix) - 1)) return TSPM_ERR_INVALID;
+    d[i] = LstmFwdDescT<Ix>{s.batch, s.steps, s.xg, s.w_hh, s.b_hh, s.gates, s.cs, s.hs, s.h_out, s.ld_out,
+                            reinterpret_cast<Ix*>(s.argmax)};
+    hw[i] = s.hidden;
+  }
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (count == 1 || lstm_kind(hw[0]) == lstm_kind(hw[1]))
+    return launch_lstm_fwd_any<Ix>(d[0], hw[0], count > 1 ? &d[1] : nullptr, hw[1], st);
+  const int rc = launch_lstm_fwd_any<Ix>(d[0], hw[0], nullptr, 0, st);
+  return rc != TSPM_OK ? rc : launch_lstm_fwd_any<Ix>(d[1], hw[1], nullptr, 0, st);
+}
+
+template <typename Ix>
+int lstm_bwd_any_width(int32_t count, const tspm_lstm_bwd_desc* descs, tspm_stream_t stream) {
+  if (count < 1 || count > 2 || !descs) return TSPM_ERR_INVALID;
+  LstmBwdDescT<Ix> d[2];
+  int hw[2] = {0, 0};
+  for (int i = 0; i < count; ++i) {
+    const tspm_lstm_bwd_desc& s = descs[i];
+    if (s.batch <= 0 || s.steps <= 0 || !lstm_width_ok(s.hidden) || !s.w_hh || !s.gates || !s.cs || !s.dh ||
+        !s.dgates || s.ld_dh < s.hidden)
+      return TSPM_ERR_INVALID;
+    if (s.steps > kLstmIndexedSteps<Ix> && s.argmax) return TSPM_ERR_INVALID;
+    if (reinterpret_cast<uintptr_t>(s.argmax) & (sizeof(Ix) - 1)) return TSPM_ERR_INVALID;
+    d[i] = LstmBwdDescT<Ix>{s.batch, s.steps, s.w_hh, s.gates, s.cs, s.dh, s.ld_dh, s.dgates,
+                            reinterpret_cast<const Ix*>(s.argmax)};
+    hw[i] = s.hidden;
+  }
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (count == 1 || lstm_kind(hw[0]) == lstm_kind(hw[1]))
+    return launch_lstm_bwd_any<Ix>(d[0], hw[0], count > 1 ? &d[1] : nullptr, hw[1], st);
+  const int rc = launch_lstm_bwd_any<Ix>(d[0], hw[0], nullptr, 0, st);
+  return rc != TSPM_OK ? rc : launch_lstm_bwd_any<Ix>(d[1], hw[1], nullptr, 0, st);
 }
 
 }  // namespace
@@ -722,7 +788,7 @@ extern "C" int tspm_lstm_fwd(int32_t count, const tspm_lstm_fwd_desc* descs, tsp
     if (s.steps > 256 && s.argmax) return TSPM_ERR_INVALID;  // uint8 time index
     d[i] = LstmFwdDesc{s.batch, s.steps, s.xg, s.w_hh, s.b_hh, s.gates, s.cs, s.hs, s.h_out, s.ld_out, s.argmax};
   }
-  return launch_lstm_fwd<64, kLstmRB>(d[0], count > 1 ? &d[1] : nullptr, static_cast<hipStream_t>(stream));
+  return launch_lstm_fwd<64, kLstmRB, uint8_t>(d[0], count > 1 ? &d[1] : nullptr, static_cast<hipStream_t>(stream));
 }
 
 extern "C" int tspm_lstm_bwd(int32_t count, const tspm_lstm_bwd_desc* descs, tspm_stream_t stream) {
@@ -735,51 +801,24 @@ extern "C" int tspm_lstm_bwd(int32_t count, const tspm_lstm_bwd_desc* descs, tsp
     if (s.steps > 256 && s.argmax) return TSPM_ERR_INVALID;
     d[i] = LstmBwdDesc{s.batch, s.steps, s.w_hh, s.gates, s.cs, s.dh, s.ld_dh, s.dgates, s.argmax};
   }
-  return launch_lstm_bwd<64, kLstmRB>(d[0], count > 1 ? &d[1] : nullptr, static_cast<hipStream_t>(stream));
+  return launch_lstm_bwd<64, kLstmRB, uint8_t>(d[0], count > 1 ? &d[1] : nullptr, static_cast<hipStream_t>(stream));
 }
 
-// Any hidden width (4 <= hidden <= 128, a multiple of 4), each descriptor its own: two LSTMs of one kernel kind share a
-// launch, two of different kinds take one launch each (a workgroup's arithmetic does not depend on its neighbours, so
-// either way the results are those of two count-1 calls).  Everything is validated before the first launch.
 extern "C" int tspm_lstm_fwd_w(int32_t count, const tspm_lstm_fwd_desc* descs, tspm_stream_t stream) {
-  if (count < 1 || count > 2 || !descs) return TSPM_ERR_INVALID;
-  LstmFwdDesc d[2];
-  int hw[2] = {0, 0};
-  for (int i = 0; i < count; ++i) {
-    const tspm_lstm_fwd_desc& s = descs[i];
-    if (s.batch <= 0 || s.steps <= 0 || !lstm_width_ok(s.hidden) || !s.xg || !s.w_hh || !s.gates || !s.cs || !s.hs ||
-        !s.h_out || s.ld_out < s.hidden)
-      return TSPM_ERR_INVALID;
-    if (reinterpret_cast<uintptr_t>(s.w_hh) & 15) return TSPM_ERR_INVALID;
-    if (s.steps > 256 && s.argmax) return TSPM_ERR_INVALID;  // uint8 time index
-    d[i] = LstmFwdDesc{s.batch, s.steps, s.xg, s.w_hh, s.b_hh, s.gates, s.cs, s.hs, s.h_out, s.ld_out, s.argmax};
-    hw[i] = s.hidden;
-  }
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  if (count == 1 || lstm_kind(hw[0]) == lstm_kind(hw[1]))
-    return launch_lstm_fwd_any(d[0], hw[0], count > 1 ? &d[1] : nullptr, hw[1], st);
-  const int rc = launch_lstm_fwd_any(d[0], hw[0], nullptr, 0, st);
-  return rc != TSPM_OK ? rc : launch_lstm_fwd_any(d[1], hw[1], nullptr, 0, st);
+  return lstm_fwd_any_width<uint8_t>(count, descs, stream);
 }
 
 extern "C" int tspm_lstm_bwd_w(int32_t count, const tspm_lstm_bwd_desc* descs, tspm_stream_t stream) {
-  if (count < 1 || count > 2 || !descs) return TSPM_ERR_INVALID;
-  LstmBwdDesc d[2];
-  int hw[2] = {0, 0};
-  for (int i = 0; i < count; ++i) {
-    const tspm_lstm_bwd_desc& s = descs[i];
-    if (s.batch <= 0 || s.steps <= 0 || !lstm_width_ok(s.hidden) || !s.w_hh || !s.gates || !s.cs || !s.dh ||
-        !s.dgates || s.ld_dh < s.hidden)
-      return TSPM_ERR_INVALID;
-    if (s.steps > 256 && s.argmax) return TSPM_ERR_INVALID;
-    d[i] = LstmBwdDesc{s.batch, s.steps, s.w_hh, s.gates, s.cs, s.dh, s.ld_dh, s.dgates, s.argmax};
-    hw[i] = s.hidden;
-  }
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  if (count == 1 || lstm_kind(hw[0]) == lstm_kind(hw[1]))
-    return launch_lstm_bwd_any(d[0], hw[0], count > 1 ? &d[1] : nullptr, hw[1], st);
-  const int rc = launch_lstm_bwd_any(d[0], hw[0], nullptr, 0, st);
-  return rc != TSPM_OK ? rc : launch_lstm_bwd_any(d[1], hw[1], nullptr, 0, st);
+  return lstm_bwd_any_width<uint8_t>(count, descs, stream);
+}
+
+// The same launches with a 16-bit time index: argmax points to uint16_t [batch][hidden], 1 <= steps <= 65535 with it.
+extern "C" int tspm_lstm_fwd_t16(int32_t count, const tspm_lstm_fwd_desc* descs, tspm_stream_t stream) {
+  return lstm_fwd_any_width<uint16_t>(count, descs, stream);
+}
+
+extern "C" int tspm_lstm_bwd_t16(int32_t count, const tspm_lstm_bwd_desc* descs, tspm_stream_t stream) {
+  return lstm_bwd_any_width<uint16_t>(count, descs, stream);
 }
 
 extern "C" int tspm_textcnn_pool_fwd(int32_t batch, int32_t steps, int32_t nconv, const int32_t* heights,

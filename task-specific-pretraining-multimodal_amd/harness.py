@@ -203,16 +203,19 @@ class MosiEpochRunner:
             self.recorder = DeviceMetricRecorder(metric_config or MOSI_METRICS, self.log)
         self.eval_steps: Dict[Tuple[int, int], Any] = {}
 
-    def train_step_for(self, b: int, t: int):
+    def train_step_for(self, b: int, t):
+        """The model's cached FusedMosiStep for (b, t); ``t`` an ``int`` or a triple (Ta, Tv, Tt) (``mosi.norm_steps``)."""
         st = self.model.fused_step(self.optimizer, self.loss_functions, b, t)
         if st.log is not self.log:
             st.log, st.graph = self.log, None  # the captured graph must record into this log
         return st
 
-    def eval_step_for(self, b: int, t: int):
+    def eval_step_for(self, b: int, t):
         """The cached FusedMosiEvalStep for (b, t) — rebuilt when the model's engine for that shape is no longer
-        the one it captured (``UttFusionModel._apply`` drops the engines on .to() / re-materialisation)."""
-        from .mosi import FusedMosiEvalStep
+        the one it captured (``UttFusionModel._apply`` drops the engines on .to() / re-materialisation).  ``t``: an
+        ``int`` or a triple (Ta, Tv, Tt), keyed by its normalised value."""
+        from .mosi import FusedMosiEvalStep, norm_steps
+        t = norm_steps(t)
         st = self.eval_steps.get((b, t))
         if st is None or st.eng is not self.model._engine(b, t, self.device):
             st = FusedMosiEvalStep(self.model, self.loss_functions, b, t, self.log)
@@ -233,8 +236,12 @@ class MosiEpochRunner:
             st.step(b["audio"], b["video"], b["text"], b["label"])
 
     @staticmethod
-    def _shape(b: Dict[str, Any]) -> Tuple[int, int]:
-        return int(b["label"].numel()), int(b.get("steps") or b["audio"].shape[1])
+    def _shape(b: Dict[str, Any]) -> Tuple[int, Any]:
+        """(rows, steps): the batch's own ``"steps"`` (an ``int``, or the (Ta, Tv, Tt) triple of an unaligned batch) or,
+        for a batch-first batch without it, each modality's length read from its own tensor."""
+        from .mosi import norm_steps
+        steps = b.get("steps") or tuple(int(b[m].shape[1]) for m in ("audio", "video", "text"))
+        return int(b["label"].numel()), norm_steps(steps)
 
     @staticmethod
     def _groups(b: Dict[str, Any]):

@@ -28,6 +28,13 @@ layout), pooling + dropout in ``tspm_textcnn_pool_fwd``, the sparse TextCNN weig
 (``tspm_grad_clip_coef``) and Adam (``tspm_adam_step_clip``).  ``FusedMosiStep`` captures all of it as
 one HIP graph.
 
+``steps`` is an ``int`` or a triple ``(Ta, Tv, Tt)`` (``norm_steps``) everywhere: on the unaligned CMU-MOSI / CMU-MOSEI files
+audio, video and text keep their own frame rates and the reference's ``pad_sequence`` collate pads each modality to its own
+batch maximum, so the engine plans every modality's buffers, gather helpers and weight-gradient split at its own length; a
+triple of equal numbers is the ``int`` (same cached engine, step and graph, same launches as before).  A launch with a
+"maxpool" encoder of more than 256 steps takes ``tspm_lstm_fwd_t16/bwd_t16`` and 16-bit index buffers
+(``_lib.lstm_wide_index``); the text length stays within the TextCNN kernels' 255 steps.
+
 Sentiment regression (this project's addition; the reference's YAMLs train the three-class variant only): a
 one-output ``netC.fc_out`` (``build_utt_fusion(name, output_dim=1)``) with a single mean ``nn.L1Loss`` / ``nn.MSELoss``
 term (``_regress_term``) on the float32 ``regression_labels`` runs the same steps with the head — ``fc_out``, the loss,
@@ -209,19 +216,71 @@ def _conv_algo(n: int) -> L.ConvAlgo:
     return L.ConvAlgo()
 
 
-def _lstm_alloc(enc: "LSTMEncoder", B: int, T: int, device, backward: bool = True) -> Dict[str, Optional[torch.Tensor]]:
+TEXT_MAX_STEPS = 255  # the TextCNN kernels keep an 8-bit time index (tspm_textcnn_pool_fwd / tspm_textcnn_bwd)
+_MODALITY_ORDER = ("audio", "video", "text")  # the order of a steps triple (Ta, Tv, Tt)
+
+
+def _text_steps_error(tt: int) -> "L.TspmError":
+    return L.TspmError(f"MOSI HIP path: 1 <= kernel heights <= min(5, steps) and steps <= {TEXT_MAX_STEPS} for the text "
+                       f"modality (the TextCNN's 8-bit time index); the text length is {tt}")
+
+
+def norm_steps(steps):
+    """The padded length of a step: an ``int`` (every modality runs that many steps — aligned data) or a triple
+    ``(Ta, Tv, Tt)`` of the audio, video and text lengths (unaligned CMU-MOSI / CMU-MOSEI: each modality at its own
+    frame rate).  → the ``int`` when the three agree, else the tuple of ints; this value is what every cache is keyed by,
+    so ``50`` and ``(50, 50, 50)`` name the same engine, step and graph.  Raises on a non-positive length and on a text
+    length past the TextCNN's limit."""
+    if isinstance(steps, (tuple, list)) or (isinstance(steps, np.ndarray) and steps.ndim == 1):
+        if len(steps) != 3:
+            raise L.TspmError(f"steps: an int or a triple (Ta, Tv, Tt), got {tuple(steps)!r}")
+        tr = tuple(int(t) for t in steps)
+    else:
+        tr = (int(steps),) * 3
+    if min(tr) < 1:
+        raise L.TspmError(f"steps: every length must be >= 1, got {tr} (audio, video, text)")
+    if tr[2] > TEXT_MAX_STEPS:
+        raise _text_steps_error(tr[2])
+    return tr[0] if tr[0] == tr[1] == tr[2] else tr
+
+
+def steps_triple(steps):
+    """(Ta, Tv, Tt) of an ``int`` or triple (normalised first)."""
+    n = norm_steps(steps)
+    return (n, n, n) if isinstance(n, int) else n
+
+
+def _lstm_alloc(enc: "LSTMEncoder", B: int, T: int, device, backward: bool = True,
+                wide: bool = False) -> Dict[str, Optional[torch.Tensor]]:
     """One LSTM's saved activations for a fixed (batch, steps): xg / gates [T*B, 4H], cs [T*B, H], hs [(T+1)*B, H],
     the gate gradients dg [T*B, 4H] (``backward``) and, for the "maxpool" embedding, the time index of each unit's
-    maximum (uint8 [B][H])."""
+    maximum [B][H]: uint8, or with ``wide`` (the launch takes tspm_lstm_fwd_t16 / _bwd_t16, ``L.lstm_wide_index``) 16 bits
+    as int16 storage holding the unsigned pattern (``L.index_to_int64`` reads it)."""
     if not L.lstm_width_supported(enc.hidden_size):
         raise L.TspmError(f"MOSI HIP path: LSTM hidden size {enc.hidden_size} — the recurrence kernels take a multiple "
                           f"of 4 with 4 <= hidden_size <= 128 (tspm_lstm_fwd_w)")
+    indexed = enc.embd_method == "maxpool"
+    if not L.lstm_steps_supported(T, indexed) or (indexed and T > L.LSTM_STEPS_U8 and not wide):
+        raise L.TspmError(f"MOSI HIP path: {T} LSTM steps with the {enc.embd_method!r} embedding — the time index covers "
+                          f"1..{L.LSTM_STEPS_U16} steps (16-bit past {L.LSTM_STEPS_U8})")
+    _check_rows(T, B)
     f, H = dict(device=device, dtype=torch.float32), enc.hidden_size
     bufs = dict(xg=torch.empty(T * B, 4 * H, **f), gates=torch.empty(T * B, 4 * H, **f),
                 cs=torch.empty(T * B, H, **f), hs=torch.empty((T + 1) * B, H, **f),
                 dg=torch.empty(T * B, 4 * H, **f) if backward else None)
-    bufs["arg"] = torch.zeros(B, H, dtype=torch.uint8, device=device) if enc.embd_method == "maxpool" else None
+    bufs["arg"] = (torch.zeros(B, H, dtype=torch.int16 if wide else torch.uint8, device=device) if indexed else None)
     return bufs
+
+
+MAX_GEMM_ROWS = (1 << 31) - 1  # the dense kernels take the T*B row count as an int32
+
+
+def _check_rows(T: int, B: int) -> None:
+    """The dense kernels of the LSTM half (tspm_linear_fwd over T*B rows, tspm_linear_bwd_weight_splitk reducing over
+    them) and the recurrences form every address in 64 bits and their grids from cdiv(rows, 32) x cdiv(4H, 32) tiles, so
+    the one limit on rows is the int32 argument itself (the unaligned shapes reach 500 * 256 = 128000): refuse beyond."""
+    if T * B > MAX_GEMM_ROWS:
+        raise L.TspmError(f"MOSI HIP path: {T} steps x {B} rows = {T * B} LSTM rows exceed {MAX_GEMM_ROWS}")
 
 
 def _lstm_fwd_prepare(d, enc: "LSTMEncoder", x: torch.Tensor, bufs, B: int, T: int, h_out: int, ld_out: int,
@@ -263,26 +322,26 @@ def _lstm_wgrad(enc: "LSTMEncoder", x: torch.Tensor, bufs, B: int, T: int, split
             "lstm dW_ih")
 
 
-def _lstm_wgrad_plan(B: int, T: int, encs, device):
+def _lstm_wgrad_plan(B: int, plans, device):
     """LSTM weight gradients reduce over T*B rows into 4H x {in, H} outputs (a few output tiles): split the
-    reduction so the launch fills the chip (tspm_linear_bwd_weight_splitk) — one split for every product
-    (db_ih and db_hh come from two calls and must stay bitwise equal).  → (the split, a workspace that holds the
-    largest product of the encoders `encs`)."""
+    reduction so the launch fills the chip (tspm_linear_bwd_weight_splitk) — one split for both products of an
+    encoder (db_ih and db_hh come from two calls and must stay bitwise equal), chosen from that encoder's own T*B.
+    ``plans``: (encoder, steps) pairs.  → (the splits in that order, one workspace that holds the largest product)."""
     lib = L.lib()
-    sp = max(1, min(32, (T * B) // 128))
+    sps = [max(1, min(32, (T * B) // 128)) for _, T in plans]
     wsb = max(int(lib.tspm_linear_bwd_weight_splitk_workspace(T * B, fin, 4 * enc.hidden_size, sp))
-              for enc in encs for fin in (enc.input_size, enc.hidden_size))
-    return sp, torch.empty(max(wsb // 4, 1), device=device, dtype=torch.float32)
+              for (enc, T), sp in zip(plans, sps) for fin in (enc.input_size, enc.hidden_size))
+    return sps, torch.empty(max(wsb // 4, 1), device=device, dtype=torch.float32)
 
 
 def _text_alloc(o, t: "TextCNN", B: int, T: int, device) -> None:
     """The TextCNN half's plan for a fixed (batch, steps), set as attributes of its owner `o` (MosiEngine or
     MosiEncoderEngine): conv shapes / tiles / outputs / workspace, pooled values and their argmax, the embedding
     Linear's input and the backward's work buffers."""
-    if T > 255 or min(t.heights) > T or max(t.heights) > 5:
-        raise L.TspmError("MOSI HIP path: 1 <= kernel heights <= min(5, steps) and steps <= 255")
+    if T > TEXT_MAX_STEPS or min(t.heights) > T or max(t.heights) > 5:
+        raise _text_steps_error(T)
     f = dict(device=device, dtype=torch.float32)
-    o.ft = t.input_size
+    o.ft, o.Tt = t.input_size, T
     C, nc = t.out_channels, 3 * t.out_channels
     o.C, o.nc = C, nc
     o.conv_shapes = [L.ConvShape(B, T, 1, o.ft, C, k, 1, 1, 0, T - k + 1, 1) for k in t.heights]
@@ -308,7 +367,7 @@ def _text_alloc(o, t: "TextCNN", B: int, T: int, device) -> None:
 def _text_forward(o, t: "TextCNN", sh: int, keep: Optional[int], out: int, ld_out: int) -> None:
     """TextCNN forward on owner `o`'s plan: three convolutions (implicit GEMM), pooling + dropout (keep: the
     uint8 mask's pointer or None), embedding Linear + ReLU written to `out` (row stride ld_out)."""
-    lib, B, T = L.lib(), o.B, o.T
+    lib, B, T = L.lib(), o.B, o.Tt
     for conv, s, al, y in zip(t.convs(), o.conv_shapes, o.conv_algos, o.conv_out):
         L.check(lib.tspm_conv_fwd(ctypes.byref(s), ctypes.byref(al), o.X.data_ptr(), None,
                                   conv.weight.data_ptr(), y.data_ptr(), None, o.conv_ws.data_ptr(),
@@ -330,7 +389,7 @@ def _text_backward(o, t: "TextCNN", sh: int, keep: Optional[int], dout: int, ld_
                    g) -> None:
     """TextCNN backward from `dout` (the embedding's gradient, masked in place through the ReLU of `out`):
     embedding Linear, then pooling / dropout and the sparse conv weight gradients."""
-    lib, B, T = L.lib(), o.B, o.T
+    lib, B, T = L.lib(), o.B, o.Tt
     emb = t.embd[0]
     L.check(lib.tspm_act_bwd(B, emb.out_features, dout, ld_d, out, ld_out, 1.0, sh), "textcnn embd relu")
     linear_bwd(B, o.nc, emb.out_features, o.fc_in.data_ptr(), o.nc, dout, ld_d, emb.weight.data_ptr(),
@@ -349,7 +408,8 @@ def _seq_load(src: torch.Tensor, dst: torch.Tensor, B: int, T: int, index, offs,
     as B sequences of length T)."""
     L.require_cuda_f32(src, nm)
     if tuple(src.shape) != (B, T, dst.shape[2]):
-        raise L.TspmError(f"{nm} batch shape {tuple(src.shape)} != planned {(B, T, dst.shape[2])}")
+        raise L.TspmError(f"{nm} batch shape {tuple(src.shape)} != planned {(B, T, dst.shape[2])} (batch, {nm} "
+                          f"steps, features)")
     src = src.contiguous()
     L.check(L.lib().tspm_seq_gather(B, index.data_ptr(), B, src.data_ptr(), offs.data_ptr(), lens.data_ptr(),
                                     dst.shape[2], T, dst.data_ptr(), B * dst.shape[2], dst.shape[2], None, None, None,
@@ -358,17 +418,20 @@ def _seq_load(src: torch.Tensor, dst: torch.Tensor, B: int, T: int, index, offs,
 
 class MosiEngine:
     """Execution plan of UttFusionModel for a fixed (batch, steps): pre-allocated time-major buffers, one
-    fixed sequence of libtspm launches on the caller's stream (graph-capturable)."""
+    fixed sequence of libtspm launches on the caller's stream (graph-capturable).  ``steps`` is an ``int`` or a triple
+    (Ta, Tv, Tt) (``norm_steps``): each modality's input, saved activations, gather helpers and weight-gradient split
+    are planned at its own length (``Ts``); ``T`` is the normalised value (the ``int`` on aligned data)."""
 
-    def __init__(self, model: "UttFusionModel", batch: int, steps: int, device: torch.device):
-        self.m, self.B, self.T, self.device = model, batch, steps, device
+    def __init__(self, model: "UttFusionModel", batch: int, steps, device: torch.device):
+        self.m, self.B, self.T, self.device = model, batch, norm_steps(steps), device
         a, v, t, c = model.netA, model.netV, model.netT, model.netC
         f = dict(device=device, dtype=torch.float32)
-        B, T = batch, steps
+        B = batch
+        Ta, Tv, Tt = self.Ts = steps_triple(self.T)
         self.fa, self.fv, self.ft = a.input_size, v.input_size, t.input_size
-        self.A = torch.zeros(T, B, self.fa, **f)          # time-major inputs
-        self.V = torch.zeros(T, B, self.fv, **f)
-        self.X = torch.zeros(T, B, self.ft, **f)
+        self.A = torch.zeros(Ta, B, self.fa, **f)          # time-major inputs, each at its own length
+        self.V = torch.zeros(Tv, B, self.fv, **f)
+        self.X = torch.zeros(Tt, B, self.ft, **f)
         self.labels = torch.zeros(B, dtype=torch.int64, device=device)
         self.labels_f = torch.zeros(B, **f)               # the regression head's float32 labels
         self.groups = torch.zeros(B, dtype=torch.int32, device=device)
@@ -376,8 +439,11 @@ class MosiEngine:
         if c.linears()[0].in_features != self.E:
             raise L.TspmError("FcClassifier input_dim must equal the sum of the three embedding sizes")
         self.fused = torch.zeros(B, self.E, **f)
-        self.lstm = {name: _lstm_alloc(enc, B, T, device) for name, enc in (("a", a), ("v", v))}
-        _text_alloc(self, t, B, T, device)
+        # one launch runs both recurrences: 16-bit index buffers for both when either is "maxpool" past 256 steps
+        self.wide = L.lstm_wide_index(((a.embd_method, Ta), (v.embd_method, Tv)))
+        self.lstm = {name: _lstm_alloc(enc, B, T_m, device, wide=self.wide)
+                     for name, enc, T_m in (("a", a, Ta), ("v", v, Tv))}
+        _text_alloc(self, t, B, Tt, device)
         nc = self.nc
         lib = L.lib()
         self.widths = c.widths
@@ -406,7 +472,8 @@ class MosiEngine:
         self.keep_override: Optional[Dict[str, torch.Tensor]] = None
         self.rng_ctr_ptr: Optional[int] = None
         self._host_ctr: Optional[torch.Tensor] = None
-        self.wg_split, self.wg_ws = _lstm_wgrad_plan(B, T, (a, v), device)
+        (sa, sv), self.wg_ws = _lstm_wgrad_plan(B, ((a, Ta), (v, Tv)), device)
+        self.wg_splits = {"a": sa, "v": sv}
         self.concurrent = os.environ.get("TSPM_MOSI_SERIAL", "0") != "1"
         self.side: Optional[torch.cuda.Stream] = None
         self.clip_coef = torch.ones(1, **f)
@@ -414,8 +481,11 @@ class MosiEngine:
         self.clip_ws = torch.zeros(int(lib.tspm_grad_clip_workspace()) // 4 + 1, **f)
         self.grad_of = lambda p: p.grad  # noqa: E731  (FusedAdam's flat gradient views)
         self._index = torch.arange(B, dtype=torch.int64, device=device)
-        self._lens = torch.full((B,), T, dtype=torch.int32, device=device)
-        self._offs = torch.arange(B, dtype=torch.int64, device=device) * T
+        # the dense batch seen as B sequences of length T_m: per modality (equal lengths share one pair)
+        self._lens, self._offs = {}, {}
+        for T_m in dict.fromkeys(self.Ts):
+            self._lens[T_m] = torch.full((B,), T_m, dtype=torch.int32, device=device)
+            self._offs[T_m] = torch.arange(B, dtype=torch.int64, device=device) * T_m
 
     # -- inputs -------------------------------------------------------------------------------------
     def load(self, A: torch.Tensor, V: torch.Tensor, T: torch.Tensor, labels: Optional[torch.Tensor] = None,
@@ -425,8 +495,8 @@ class MosiEngine:
         classification head or, with ``regress`` (the caller's mode, not the tensor's dtype), to the float32
         ``labels_f`` of the regression head, cast to the buffer's type either way."""
         sh = L.stream_handle()
-        for src, dst, nm in ((A, self.A, "audio"), (V, self.V, "video"), (T, self.X, "text")):
-            _seq_load(src, dst, self.B, self.T, self._index, self._offs, self._lens, nm, sh)
+        for src, dst, nm, T_m in zip((A, V, T), (self.A, self.V, self.X), _MODALITY_ORDER, self.Ts):
+            _seq_load(src, dst, self.B, T_m, self._index, self._offs[T_m], self._lens[T_m], nm, sh)
         if labels is not None:
             dst = self.labels_f if regress else self.labels
             if labels.data_ptr() != dst.data_ptr():
@@ -496,12 +566,13 @@ class MosiEngine:
 
     def _forward_lstm(self, sh: int) -> None:
         lib, m = L.lib(), self.m
-        B, T = self.B, self.T
-        # LSTM input projections over all T*B rows, then both recurrences in one launch
+        B, (Ta, Tv, _) = self.B, self.Ts
+        # LSTM input projections over each encoder's T_m*B rows, then both recurrences in one launch
         descs = (L.LstmFwdDesc * 2)()
-        for i, (name, enc, x, col) in enumerate((("a", m.netA, self.A, 0), ("v", m.netV, self.V, m.netA.hidden_size))):
-            _lstm_fwd_prepare(descs[i], enc, x, self.lstm[name], B, T, self.fused.data_ptr() + col * 4, self.E, sh)
-        L.check(L.lstm_fwd(2, descs, sh), "lstm_fwd")
+        for i, (name, enc, x, col, T_m) in enumerate((("a", m.netA, self.A, 0, Ta),
+                                                      ("v", m.netV, self.V, m.netA.hidden_size, Tv))):
+            _lstm_fwd_prepare(descs[i], enc, x, self.lstm[name], B, T_m, self.fused.data_ptr() + col * 4, self.E, sh)
+        L.check(L.lstm_fwd(2, descs, sh, self.wide), "lstm_fwd")
 
     def _forward_text(self, sh: int, train: bool) -> None:
         m, t = self.m, self.m.netT
@@ -582,7 +653,7 @@ class MosiEngine:
     def backward(self, sh: int, from_head: bool = True) -> None:
         """``from_head=False``: ``dh[-1]`` and ``fc_out``'s gradients are already written (``head_regress``)."""
         lib, m, g = L.lib(), self.m, self.grad_of
-        B, T = self.B, self.T
+        B = self.B
         c = m.netC
         cscale = 1.0 / (1.0 - c.dropout_p) if c.dropout_p > 0 else 1.0
         lins = c.linears()
@@ -629,14 +700,14 @@ class MosiEngine:
 
     def _backward_lstm(self, sh: int) -> None:
         lib, m, g = L.lib(), self.m, self.grad_of
-        B, T = self.B, self.T
-        # LSTMs: backward through time (one launch for both), then the weight gradients as GEMMs over T*B rows
+        B, (Ta, Tv, _) = self.B, self.Ts
+        # LSTMs: backward through time (one launch for both), then the weight gradients as GEMMs over T_m*B rows
         descs = (L.LstmBwdDesc * 2)()
-        for i, (name, enc, col) in enumerate((("a", m.netA, 0), ("v", m.netV, m.netA.hidden_size))):
-            _lstm_bwd_desc(descs[i], enc, self.lstm[name], B, T, self.dfused.data_ptr() + col * 4, self.E)
-        L.check(L.lstm_bwd(2, descs, sh), "lstm_bwd")
-        for name, enc, x in (("a", m.netA, self.A), ("v", m.netV, self.V)):
-            _lstm_wgrad(enc, x, self.lstm[name], B, T, self.wg_split, self.wg_ws, g, sh)
+        for i, (name, enc, col, T_m) in enumerate((("a", m.netA, 0, Ta), ("v", m.netV, m.netA.hidden_size, Tv))):
+            _lstm_bwd_desc(descs[i], enc, self.lstm[name], B, T_m, self.dfused.data_ptr() + col * 4, self.E)
+        L.check(L.lstm_bwd(2, descs, sh, self.wide), "lstm_bwd")
+        for name, enc, x, T_m in (("a", m.netA, self.A, Ta), ("v", m.netV, self.V, Tv)):
+            _lstm_wgrad(enc, x, self.lstm[name], B, T_m, self.wg_splits[name], self.wg_ws, g, sh)
 
     def clip(self, sh: int, flat_grad: torch.Tensor, grad_scale: float) -> None:
         """clip_grad_norm_(model.parameters(), clip) coefficient into ``clip_coef`` (utt_fusion.py:188-189)."""
@@ -675,12 +746,14 @@ class MosiEncoderEngine:
         self.rng_ctr_ptr: Optional[int] = None
         self._host_ctr: Optional[torch.Tensor] = None
         self.seed = int(seed)
+        self.wide = False
         if self.is_text:
             _text_alloc(self, enc, B, T, device)
             self.keep = torch.ones(B, self.nc, dtype=torch.uint8, device=device)
         else:
-            self.bufs = _lstm_alloc(enc, B, T, device)
-            self.wg_split, self.wg_ws = _lstm_wgrad_plan(B, T, (enc,), device)
+            self.wide = L.lstm_wide_index(((enc.embd_method, T),))  # "maxpool" past 256 steps: the 16-bit index
+            self.bufs = _lstm_alloc(enc, B, T, device, wide=self.wide)
+            (self.wg_split,), self.wg_ws = _lstm_wgrad_plan(B, ((enc, T),), device)
         self.grad_of = lambda p: p.grad  # noqa: E731  (FusedAdam's flat gradient views)
         self._index = torch.arange(B, dtype=torch.int64, device=device)
         self._lens = torch.full((B,), T, dtype=torch.int32, device=device)
@@ -719,7 +792,7 @@ class MosiEncoderEngine:
             return
         d = (L.LstmFwdDesc * 1)()
         _lstm_fwd_prepare(d[0], self.enc, self.X, self.bufs, B, T, self.emb.data_ptr(), self.hidden, sh)
-        L.check(L.lstm_fwd(1, d, sh), "lstm_fwd")
+        L.check(L.lstm_fwd(1, d, sh, self.wide), "lstm_fwd")
 
     def backward(self, sh: int) -> None:
         """From ``demb`` (modified in place by the TextCNN's ReLU mask) to every parameter gradient."""
@@ -731,7 +804,7 @@ class MosiEncoderEngine:
             return
         d = (L.LstmBwdDesc * 1)()
         _lstm_bwd_desc(d[0], self.enc, self.bufs, B, T, self.demb.data_ptr(), self.hidden)
-        L.check(L.lstm_bwd(1, d, sh), "lstm_bwd")
+        L.check(L.lstm_bwd(1, d, sh, self.wide), "lstm_bwd")
         _lstm_wgrad(self.enc, self.X, self.bufs, B, T, self.wg_split, self.wg_ws, self.grad_of, sh)
 
 
@@ -776,7 +849,7 @@ class FusedMosiStep:
     ``fc_out``, the loss, the per-pattern epoch accumulators, the loss log and ``fc_out``'s backward — is the one
     launch of ``MosiEngine.head_regress``; everything else is the classification step's schedule."""
 
-    def __init__(self, model: "UttFusionModel", optimizer: FusedAdam, loss_functions, batch: int, steps: int,
+    def __init__(self, model: "UttFusionModel", optimizer: FusedAdam, loss_functions, batch: int, steps,
                  use_graph: bool = True, allreduce=None):
         if not isinstance(optimizer, FusedAdam):
             raise L.TspmError("FusedMosiStep needs FusedAdam (the flat gradient buffer the kernels write)")
@@ -786,7 +859,7 @@ class FusedMosiStep:
         fgs = optimizer.flat_groups()
         if len(fgs) != 1:
             raise L.TspmError("FusedMosiStep: one FusedAdam parameter group (the clip norm spans all parameters)")
-        self.model, self.opt, self.N, self.T = model, optimizer, batch, steps
+        self.model, self.opt, self.N, self.T = model, optimizer, batch, norm_steps(steps)
         self.weight = _ce_weight(loss_functions)
         self.regress = _regress_mode(model, loss_functions)  # (kind, weight): the one-launch regression head
         if self.regress is None and self.weight is None:
@@ -880,9 +953,9 @@ class FusedMosiEvalStep:
     mean L1 / MSE term) the head is ``MosiEngine.head_regress`` in forward-only mode and ``log`` a RegressionLog.  Inputs are the engine's time-major buffers
     (``mosi_data.MOSI.device_loader(step_for=...)`` gathers into them) or a batch-first batch via ``step``."""
 
-    def __init__(self, model: "UttFusionModel", loss_functions, batch: int, steps: int, log, use_graph: bool = True):
+    def __init__(self, model: "UttFusionModel", loss_functions, batch: int, steps, log, use_graph: bool = True):
         dev = next(model.parameters()).device
-        self.model, self.N, self.T, self.log = model, batch, steps, log
+        self.model, self.N, self.T, self.log = model, batch, norm_steps(steps), log
         self.weight = _ce_weight(loss_functions)
         self.regress = _regress_mode(model, loss_functions)
         if self.regress is None and self.weight is None:
@@ -940,13 +1013,21 @@ def _modality(batch: Dict[Any, Any], name: str):
     raise KeyError(f"batch has no {name!r} modality key (keys: {list(batch.keys())})")
 
 
+def _batch_steps(A: torch.Tensor, V: torch.Tensor, T: torch.Tensor):
+    """(Ta, Tv, Tt) of three batch-first [B, T_m, F] tensors, each modality's length read from its own tensor."""
+    for nm, x in zip(_MODALITY_ORDER, (A, V, T)):
+        if x.dim() != 3:
+            raise L.TspmError(f"{nm}: a batch-first [B, T, F] tensor, got shape {tuple(x.shape)}")
+    return (int(A.shape[1]), int(V.shape[1]), int(T.shape[1]))
+
+
 class _UttFn(torch.autograd.Function):
     """The whole UTT-Fusion forward as one autograd node (HIP schedule forward and backward), for the
     reference's own train_step sequence with a non-fused optimizer."""
 
     @staticmethod
     def forward(ctx, A, V, T, model: "UttFusionModel", *params):
-        eng = model._engine(A.shape[0], A.shape[1], A.device)
+        eng = model._engine(A.shape[0], _batch_steps(A, V, T), A.device)
         eng.load(A, V, T)
         eng.apply_keep_override()
         eng.forward(L.stream_handle(), True)
@@ -1000,9 +1081,11 @@ class UttFusionModel(nn.Module):
         self._engines, self._steps = {}, {}
         return out
 
-    def _engine(self, b: int, t: int, device) -> MosiEngine:
+    def _engine(self, b: int, t, device) -> MosiEngine:
+        """The cached MosiEngine for (batch, steps): ``t`` an ``int`` or a triple (Ta, Tv, Tt), keyed by ``norm_steps``."""
         if torch.device(device).type != "cuda":
             raise L.TspmError("UttFusionModel (tspm_amd) runs on the MI355X only (no CPU fallback)")
+        t = norm_steps(t)
         key = (b, t, device)
         eng = self._engines.get(key)
         if eng is None:
@@ -1010,13 +1093,16 @@ class UttFusionModel(nn.Module):
             self._engines[key] = eng
         return eng
 
-    def fused_step(self, optimizer: FusedAdam, loss_functions, batch: int, steps: int) -> FusedMosiStep:
+    def fused_step(self, optimizer: FusedAdam, loss_functions, batch: int, steps) -> FusedMosiStep:
         """The cached FusedMosiStep for (optimizer, loss group, batch, padded steps) — one captured graph per
-        padded length (mosi_data.MOSI.device_loader(step_for=...) gathers straight into its inputs)."""
-        key = (id(optimizer), id(loss_functions), int(batch), int(steps))
+        padded length (mosi_data.MOSI.device_loader(step_for=...) gathers straight into its inputs).  ``steps``: an
+        ``int`` or a triple (Ta, Tv, Tt); the key is ``norm_steps(steps)``, so ``50`` and ``(50, 50, 50)`` give the
+        same object."""
+        steps = norm_steps(steps)
+        key = (id(optimizer), id(loss_functions), int(batch), steps)
         st = self._steps.get(key)
         if st is None:
-            st = FusedMosiStep(self, optimizer, loss_functions, int(batch), int(steps))
+            st = FusedMosiStep(self, optimizer, loss_functions, int(batch), steps)
             self._steps[key] = st
         return st
 
@@ -1053,7 +1139,7 @@ class UttFusionModel(nn.Module):
         if self.training and torch.is_grad_enabled():
             params = list(self.parameters())
             return _UttFn.apply(A, V, T, self, *params)
-        eng = self._engine(A.shape[0], A.shape[1], A.device)
+        eng = self._engine(A.shape[0], _batch_steps(A, V, T), A.device)
         eng.load(A, V, T)
         eng.forward(L.stream_handle(), self.training)
         return eng.logits.clone()
@@ -1077,7 +1163,7 @@ class UttFusionModel(nn.Module):
         head_ok = (_ce_weight(loss_functions) is not None if reg is None
                    else L.regress_head_supported(A.shape[0], self.netC.widths[-1]))
         if isinstance(optimizer, FusedAdam) and head_ok and A.is_cuda:
-            out = self.fused_step(optimizer, loss_functions, A.shape[0], A.shape[1]).step(A, V, T, labels)
+            out = self.fused_step(optimizer, loss_functions, A.shape[0], _batch_steps(A, V, T)).step(A, V, T, labels)
             logits, loss = out["logits"], out["loss"]
         else:
             self.train()
@@ -1109,7 +1195,7 @@ class UttFusionModel(nn.Module):
         T = _modality(batch, "text").to(device).float()
         labels = batch["label"].to(device)
         miss = np.array(batch.get("pattern_name", []))
-        eng = self._engine(A.shape[0], A.shape[1], A.device)
+        eng = self._engine(A.shape[0], _batch_steps(A, V, T), A.device)
         reg = _regress_mode(self, loss_functions)
         if reg is not None:
             labels = labels.float()
@@ -1158,7 +1244,7 @@ class UttFusionModel(nn.Module):
             A = _modality(batch, "audio").to(device).float()
             V = _modality(batch, "video").to(device).float()
             T = _modality(batch, "text").to(device).float()
-            eng = self._engine(A.shape[0], A.shape[1], A.device)
+            eng = self._engine(A.shape[0], _batch_steps(A, V, T), A.device)
             eng.load(A, V, T)
             eng.forward(L.stream_handle(), False)
             ha, hv = self.netA.hidden_size, self.netV.hidden_size
@@ -1180,7 +1266,8 @@ def _encode_lstm(enc: LSTMEncoder, x: torch.Tensor) -> torch.Tensor:
     out = torch.empty(B, enc.hidden_size, device=x.device, dtype=torch.float32)
     sh = L.stream_handle()
     d = (L.LstmFwdDesc * 1)()
-    _lstm_fwd_prepare(d[0], enc, xt, _lstm_alloc(enc, B, T, x.device, backward=False), B, T, out.data_ptr(),
+    wide = L.lstm_wide_index(((enc.embd_method, T),))
+    _lstm_fwd_prepare(d[0], enc, xt, _lstm_alloc(enc, B, T, x.device, backward=False, wide=wide), B, T, out.data_ptr(),
                       enc.hidden_size, sh)
-    L.check(L.lstm_fwd(1, d, sh), "lstm_fwd")
+    L.check(L.lstm_fwd(1, d, sh, wide), "lstm_fwd")
     return out

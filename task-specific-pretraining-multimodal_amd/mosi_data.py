@@ -43,6 +43,23 @@ _PICKLE_KEYS = {"audio": "audio", "video": "vision", "text": "text"}  # data/mos
 PATTERNS = ["atv", "at", "av", "tv", "a", "t", "v"]  # data/mosi.py:61-69 order
 
 
+def pad_of(pad_to, modality: str) -> int:
+    """The minimum padded length of one modality: ``pad_to`` is an ``int`` (every modality), a dict by modality name
+    (a missing name: no minimum) or a triple in ``MODALITIES`` order (audio, video, text)."""
+    if isinstance(pad_to, dict):
+        return int(pad_to.get(modality, 0))
+    if isinstance(pad_to, (tuple, list)):
+        if len(pad_to) != len(MODALITIES):
+            raise L.TspmError(f"pad_to: an int, a dict by modality or a triple (audio, video, text), got {pad_to!r}")
+        return int(pad_to[MODALITIES.index(modality)])
+    return int(pad_to)
+
+
+def steps_of(steps, modality: str) -> int:
+    """One modality's length of a batch's ``steps``: the ``int`` common length or the (audio, video, text) triple."""
+    return int(steps) if not isinstance(steps, (tuple, list)) else int(steps[MODALITIES.index(modality)])
+
+
 def pattern_keep(pattern: str) -> Dict[str, float]:
     """1.0 for every modality whose first letter is in ``pattern`` (configs/mosi/*: missing_rate 0.0)."""
     return {m: 1.0 if m[0] in pattern else 0.0 for m in MODALITIES}
@@ -135,12 +152,32 @@ class DeviceMosiCorpus:
                               "(pad_sequence pads each to its own length); pass pad_to >= all of them")
         return max(max(mx), pad_to)
 
-    def gather(self, index: torch.Tensor, steps_pad: int, out: Dict[str, torch.Tensor], time_major: bool,
+    def steps_per_modality(self, index_host: np.ndarray, pad_to=0, modalities: Sequence[str] = MODALITIES):
+        """pad_sequence's padded length of each modality on its own (data/mosi.py:225-230): the batch's longest
+        sequence of that modality, at least that modality's ``pad_to`` (``pad_of``: an int, a dict or a triple) — a
+        tuple in the order of ``modalities``, (Ta, Tv, Tt) by default, the per-modality ``steps`` of the HIP step."""
+        if not len(index_host):
+            return tuple(pad_of(pad_to, m) for m in modalities)
+        return tuple(max(int(self.host_lengths[m][index_host].max()), pad_of(pad_to, m)) for m in modalities)
+
+    def batch_steps(self, index_host: np.ndarray, pad_to=0, modalities: Sequence[str] = MODALITIES):
+        """The ``steps`` of a batch: the common length (an ``int``) whenever ``steps_for`` accepts the batch — aligned
+        data, or an ``int`` ``pad_to`` that covers every modality — else the per-modality tuple of
+        ``steps_per_modality`` (an unaligned batch; an ``int`` again if its entries agree)."""
+        if isinstance(pad_to, (int, np.integer)):
+            mx = [int(self.host_lengths[m][index_host].max()) for m in modalities] if len(index_host) else [0]
+            if not (max(mx) > pad_to and len(set(mx)) > 1):
+                return self.steps_for(index_host, int(pad_to), modalities)
+        per = self.steps_per_modality(index_host, pad_to, modalities)
+        return per[0] if len(set(per)) == 1 else per
+
+    def gather(self, index: torch.Tensor, steps_pad, out: Dict[str, torch.Tensor], time_major: bool,
                masks: Optional[Dict[str, torch.Tensor]] = None, labels_out: Optional[torch.Tensor] = None) -> None:
         """Write the batch ``index`` (device int64) into ``out[m]``: [T, B, F] (time_major) or [B, T, F], for
         the modalities ``out`` names (all three for the fusion step, one for encoder pre-training); int64 labels
         ride on the first launch, float32 labels (``labels_out`` float32 [B]) take one ``tspm_avmnist_gather``
-        launch of one float per row (an out-of-range index gives a NaN label)."""
+        launch of one float per row (an out-of-range index gives a NaN label).  ``steps_pad``: the common padded
+        length, or the (audio, video, text) triple of an unaligned batch — each modality's launch pads to its own."""
         lib, sh = L.lib(), L.stream_handle()
         b = int(index.numel())
         if labels_out is not None and labels_out.dtype != self.label_dtype:
@@ -150,14 +187,14 @@ class DeviceMosiCorpus:
                                             None, None, labels_out.data_ptr(), None, None, sh), "label gather")
             labels_out = None
         for j, m in enumerate([m for m in MODALITIES if m in out]):
-            f, dst = self.feat[m], out[m]
-            shape = (steps_pad, b, f) if time_major else (b, steps_pad, f)
+            f, dst, tp = self.feat[m], out[m], steps_of(steps_pad, m)
+            shape = (tp, b, f) if time_major else (b, tp, f)
             if tuple(dst.shape) != shape or not dst.is_contiguous() or dst.dtype != torch.float32:
                 raise L.TspmError(f"{m}: output {tuple(dst.shape)} != {shape} (contiguous f32)")
-            st_t, st_b = (b * f, f) if time_major else (f, steps_pad * f)
+            st_t, st_b = (b * f, f) if time_major else (f, tp * f)
             mk = masks.get(m) if masks else None
             L.check(lib.tspm_seq_gather(b, index.data_ptr(), self.n, self.data[m].data_ptr(), self.offsets[m].data_ptr(),
-                                        self.lengths[m].data_ptr(), f, steps_pad, dst.data_ptr(), st_t, st_b,
+                                        self.lengths[m].data_ptr(), f, tp, dst.data_ptr(), st_t, st_b,
                                         None if mk is None else mk.data_ptr(),
                                         self.labels.data_ptr() if (j == 0 and not self.float_labels) else None,
                                         labels_out.data_ptr() if (j == 0 and labels_out is not None) else None, sh),
@@ -288,7 +325,7 @@ class MOSI(torch.utils.data.Dataset):
         non-bookkeeping key is the modality, monomodal.select_modality_key).  With ``step`` (a monomodal
         FusedMosiMonoStep / FusedMosiMonoEvalStep) the gather writes time-major straight into its input buffer."""
         dc, m = self.device_corpus, self.target_modality
-        b, tpad = len(rows), dc.steps_for(rows, pad_to, (m,))
+        b, tpad = len(rows), dc.steps_for(rows, pad_of(pad_to, m), (m,))
         index = torch.from_numpy(rows).to(self.device, non_blocking=True)
         masks = {k: v for k, v in self._masks(pid).items() if k == m}
         names = [self.selected_patterns[p] for p in pid]
@@ -307,7 +344,7 @@ class MOSI(torch.utils.data.Dataset):
         if self.target_modality != "multimodal":
             return self._collate_mono(rows, pid, step, pad_to)
         dc = self.device_corpus
-        b, tpad = len(rows), dc.steps_for(rows, pad_to)
+        b, tpad = len(rows), dc.batch_steps(rows, pad_to)  # an int, or (Ta, Tv, Tt) for an unaligned batch
         index = torch.from_numpy(rows).to(self.device, non_blocking=True)
         masks = self._masks(pid)
         names = [self.selected_patterns[p] for p in pid]
@@ -319,7 +356,7 @@ class MOSI(torch.utils.data.Dataset):
             dc.gather(index, tpad, {"audio": e.A, "video": e.V, "text": e.X}, True, masks, lab)
             return {"audio": e.A, "video": e.V, "text": e.X, "label": lab, "pattern_name": names,
                     "steps": tpad, "time_major": True}
-        out = {m: torch.empty(b, tpad, dc.feat[m], device=self.device) for m in MODALITIES}
+        out = {m: torch.empty(b, steps_of(tpad, m), dc.feat[m], device=self.device) for m in MODALITIES}
         lab = torch.empty(b, dtype=dc.label_dtype, device=self.device)
         dc.gather(index, tpad, out, False, masks, lab)
         return {"audio": out["audio"], "video": out["video"], "text": out["text"], "label": lab,
@@ -332,7 +369,11 @@ class MOSI(torch.utils.data.Dataset):
         ``FusedMosiEvalStep``): gather each batch time-major straight into that step's input buffers.
         ``pad_to``: pad every batch to at least this many steps (the aligned length, e.g. 50 for aligned_50:
         one captured step shape for the whole epoch; pad_sequence pads to the batch maximum, which equals it
-        on the reference's dense data).  ``group_patterns`` (default: valid / test splits, as collate_fn):
+        on the reference's dense data) — an ``int``, or per modality a dict / (audio, video, text) triple.  A batch
+        whose modalities differ in length (unaligned data) is padded per modality as pad_sequence pads it:
+        ``step_for`` then receives the triple (Ta, Tv, Tt), the batch's ``"steps"`` is that triple, and a per-modality
+        ``pad_to`` that covers the corpus gives one step shape, hence one graph, for the epoch.
+        ``group_patterns`` (default: valid / test splits, as collate_fn):
         each batch is ``{pattern: sub-batch}`` in first-seen order (data/mosi.py:236-251); with a single target
         modality the default is flat batches (``step_for`` then returns the monomodal train / eval step)."""
         n = len(self)
@@ -350,7 +391,9 @@ class MOSI(torch.utils.data.Dataset):
             for name, sel in parts:
                 r, q = rows[sel], pid[sel]
                 if step_for is not None:
-                    t = self.device_corpus.steps_for(r, pad_to, self._want())
+                    want = self._want()
+                    t = (self.device_corpus.batch_steps(r, pad_to) if len(want) > 1
+                         else self.device_corpus.steps_for(r, pad_of(pad_to, want[0]), want))
                     out[name] = self._collate(r, q, step_for(len(r), t), pad_to)
                     if grouped:
                         yield {name: out[name]}  # the step's buffers are reused: hand each group over at once
