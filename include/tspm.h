@@ -53,7 +53,9 @@ enum {
  * head for the MMIMDb encoder pre-training step; tspm_regress_head_step, the scalar-output head of the MOSI / MOSEI
  * sentiment regression (L1 / MSE, backward, epoch accumulators, loss log) in one launch; tspm_lstm_fwd_w /
  * tspm_lstm_bwd_w, the LSTM recurrences at any hidden width that is a multiple of 4 up to 128 (same descriptors);
- * tspm_lstm_fwd_t16 / tspm_lstm_bwd_t16, those recurrences with a 16-bit "maxpool" time index (up to 65535 steps). */
+ * tspm_lstm_fwd_t16 / tspm_lstm_bwd_t16, those recurrences with a 16-bit "maxpool" time index (up to 65535 steps);
+ * tspm_lstm_fwd_len / tspm_lstm_bwd_len, the recurrences with per-sample sequence lengths read on the device
+ * (pack_padded_sequence semantics; their own descriptors). */
 #define TSPM_ABI_VERSION 23
 int tspm_abi_version(void);  /* returns TSPM_ABI_VERSION */
 /* Static string for a status code. */
@@ -790,6 +792,57 @@ int tspm_lstm_bwd_w(int32_t count, const tspm_lstm_bwd_desc* descs, tspm_stream_
  * float output is bitwise _w's and the index values are equal as integers. */
 int tspm_lstm_fwd_t16(int32_t count, const tspm_lstm_fwd_desc* descs, tspm_stream_t stream);
 int tspm_lstm_bwd_t16(int32_t count, const tspm_lstm_bwd_desc* descs, tspm_stream_t stream);
+/* The recurrences with per-sample sequence lengths (added under ABI 23, no existing signature changed):
+ * pack_padded_sequence semantics over a padded batch.  The descriptors are tspm_lstm_fwd_desc / tspm_lstm_bwd_desc plus
+ *   lengths     int32 [batch] in DEVICE memory, required (NULL is TSPM_ERR_INVALID).  The host never reads the values; the
+ *               kernel runs row b for L_b = min(max(lengths[b], 1), steps) steps, so no value moves an access outside
+ *               the buffers, and a captured graph may be replayed after the buffer's contents change;
+ *   index_bits  the width of the `argmax` buffer: 8 (uint8 [batch][hidden], steps <= 256) or 16 (uint16 [batch][hidden],
+ *               2-byte aligned, steps <= 65535); with an index anything else is TSPM_ERR_INVALID, with argmax NULL the
+ *               field is ignored and steps is unlimited.  One pair of entry points covers what _w and _t16 cover.
+ * hidden: a multiple of 4 in 4..128, served by the tiers and kinds of tspm_lstm_fwd_w.  count is 1 or 2, each descriptor
+ * with its own batch / steps / hidden / lengths / index_bits; two descriptors of one kernel kind (and, where both carry
+ * an index, one index width) share a launch, otherwise one launch each, and the results are bitwise those of two
+ * count-1 calls.  Every descriptor is validated before the first launch.
+ * Forward, row b: for t < L_b the arithmetic of tspm_lstm_fwd_w unchanged (gates, cs, hs[t+1] saved as there).  argmax
+ * NULL ("last"): h_out[b] = h at step L_b - 1.  argmax non-NULL ("maxpool"): h_out[b] = max over t < L_b of h_t (first
+ * maximum, NaN wins) and the index written is < L_b.  hs[t+1][b] for L_b <= t < steps is written as +0.0 (what
+ * pad_packed_sequence returns; the dW_hh GEMM multiplies these rows by zero gate gradients, so they must be finite);
+ * gates and cs rows at t >= L_b are NOT written and nothing may read them.  With every length >= steps all outputs are
+ * bitwise those of tspm_lstm_fwd_w (index_bits 8) / tspm_lstm_fwd_t16 (16).
+ * Backward, row b: the embedding gradient dh enters at t = L_b - 1 ("last") or at the saved index ("maxpool"); for
+ * t < L_b the arithmetic of tspm_lstm_bwd_w unchanged; dgates[t][b] for L_b <= t < steps is written as +0.0, so the
+ * weight-gradient GEMMs over all steps * batch rows stay as they are.  Pass the forward's lengths.
+ * A 2-row workgroup runs max(L_b) over its rows (the ghost row of an odd batch takes the length of the row it clamps
+ * to), so a launch lasts as long as the batch's longest sequence, not the padded length. */
+typedef struct tspm_lstm_fwd_len_desc {
+  int32_t batch, steps, hidden, ld_out;
+  const float* xg;
+  const float* w_hh;
+  const float* b_hh; /* nullable */
+  float* gates;
+  float* cs;
+  float* hs;
+  float* h_out;
+  void* argmax; /* nullable; uint8 or uint16 by index_bits */
+  const int32_t* lengths;
+  int32_t index_bits;
+  int32_t reserved_; /* 0 */
+} tspm_lstm_fwd_len_desc;
+typedef struct tspm_lstm_bwd_len_desc {
+  int32_t batch, steps, hidden, ld_dh;
+  const float* w_hh;
+  const float* gates;
+  const float* cs;
+  const float* dh;
+  float* dgates;
+  const void* argmax; /* nullable; the forward's buffer */
+  const int32_t* lengths;
+  int32_t index_bits;
+  int32_t reserved_; /* 0 */
+} tspm_lstm_bwd_len_desc;
+int tspm_lstm_fwd_len(int32_t count, const tspm_lstm_fwd_len_desc* descs, tspm_stream_t stream);
+int tspm_lstm_bwd_len(int32_t count, const tspm_lstm_bwd_len_desc* descs, tspm_stream_t stream);
 /* TextCNN pooling (models/msa/networks/textcnn.py:56-67): for conv i (kernel height heights[i], output
  * conv_out[i] time-major [steps-heights[i]+1][batch][channels] without bias), bias[i] added, ReLU,
  * max over time (first maximum, F.max_pool1d), concatenated over convs: pooled[b][i*C+c] and the

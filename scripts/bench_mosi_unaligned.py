@@ -20,8 +20,9 @@ Legs:
   against this tree's, in fresh child processes in alternating order, ``--ab-runs`` each (5 by default):
   "within_range" = the median of this tree's medians lies inside the other library's own min–max range.  Every child
   also prints a checksum of the parameters, loss and logits after ``--check-steps`` seeded steps; the two libraries
-  must agree bitwise.  A library from before the 16-bit entry points lacks them; the child drops them from the
-  signature table before loading it (the aligned step never calls them).
+  must agree bitwise.  A library from before the 16-bit or the per-sample-length entry points lacks them; the child
+  drops the exports its library file does not have from the signature table before loading it (the aligned step never
+  calls them).
 
 Nothing in the package depends on the result.  Needs the MI355X: there is no CPU leg.
 
@@ -45,6 +46,7 @@ if REPO not in sys.path:
 SHAPES = {"mosi_aligned": ("mosi", 128, 50), "mosi": ("mosi", 128, (375, 500, 50)),
           "mosei_aligned": ("mosei", 256, 50), "mosei": ("mosei", 256, (500, 375, 50))}
 T16 = ("tspm_lstm_fwd_t16", "tspm_lstm_bwd_t16")
+LATER = T16 + ("tspm_lstm_fwd_len", "tspm_lstm_bwd_len")  # exports an older build of the library may lack
 
 
 def summarise(us):
@@ -138,7 +140,7 @@ def child(a) -> None:
     """One fresh process under TSPM_LIB: the aligned MOSI step's time and checksum as one JSON line."""
     if a.legacy_lib:
         from tspm_amd import _lib as L
-        for n in T16:
+        for n in missing_exports(L.LIB_PATH):
             L._SIGS.pop(n, None)
     print("CHILD " + json.dumps({"step": time_shape("mosi_aligned", a)["step"], "checksum": checksum(a)}), flush=True)
 
@@ -157,9 +159,14 @@ def run_child(lib_path, legacy, a):
     return json.loads([ln for ln in out.splitlines() if ln.startswith("CHILD ")][-1][6:])
 
 
+def missing_exports(path):
+    with open(path, "rb") as f:  # the exports' names in the file (no second libtspm loaded into this process)
+        blob = f.read()
+    return [n for n in LATER if n.encode() + b"\0" not in blob]
+
+
 def lacks_t16(path) -> bool:
-    with open(path, "rb") as f:  # the export's name in the file (no second libtspm loaded into this process)
-        return T16[0].encode() not in f.read()
+    return T16[0] in missing_exports(path)
 
 
 def main() -> None:
@@ -180,7 +187,7 @@ def main() -> None:
         return
     result = {"timing": "one pair of device events per graph replay / per launch; median over the timed samples"}
     if a.ab_lib:  # children first: this process has not touched the GPU yet
-        legacy = lacks_t16(a.ab_lib)
+        legacy = bool(missing_exports(a.ab_lib))
         runs = {"other": [], "this": []}
         for which in ("other", "this") * a.ab_runs:
             runs[which].append(run_child(os.path.abspath(a.ab_lib) if which == "other" else None,

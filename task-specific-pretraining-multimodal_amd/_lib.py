@@ -123,6 +123,17 @@ class LstmBwdDesc(Structure):
         [(n, c_void_p) for n in ("w_hh", "gates", "cs", "dh", "dgates", "argmax")]
 
 
+class LstmFwdLenDesc(Structure):
+    """tspm_lstm_fwd_len_desc (added under ABI 23): tspm_lstm_fwd_desc plus the per-sample ``lengths`` (int32 [batch] on
+    the device) and ``index_bits``, the width of the ``argmax`` buffer (8 or 16)."""
+    _fields_ = LstmFwdDesc._fields_ + [("lengths", c_void_p), ("index_bits", c_int32), ("reserved_", c_int32)]
+
+
+class LstmBwdLenDesc(Structure):
+    """tspm_lstm_bwd_len_desc (added under ABI 23): tspm_lstm_bwd_desc plus ``lengths`` and ``index_bits``."""
+    _fields_ = LstmBwdDesc._fields_ + [("lengths", c_void_p), ("index_bits", c_int32), ("reserved_", c_int32)]
+
+
 class MonoHeadDesc(Structure):
     """tspm_mono_head_desc (ABI 23): the monomodal head (classifier, CE, predictions, backward) in one launch."""
     _fields_ = [(n, c_int32) for n in ("n", "hid", "classes", "ld_emb", "ld_demb")] + [("loss_weight", c_float)] + \
@@ -192,6 +203,16 @@ def lstm_bwd(count: int, descs, sh, wide: bool = False) -> int:
         return lib().tspm_lstm_bwd_t16(count, descs, sh)
     fn = lib().tspm_lstm_bwd if all(descs[i].hidden == 64 for i in range(count)) else lib().tspm_lstm_bwd_w
     return fn(count, descs, sh)
+
+
+def lstm_fwd_len(count: int, descs, sh) -> int:
+    """tspm_lstm_fwd_len: the recurrences with per-sample lengths (``LstmFwdLenDesc``; every width and index width)."""
+    return lib().tspm_lstm_fwd_len(count, descs, sh)
+
+
+def lstm_bwd_len(count: int, descs, sh) -> int:
+    """tspm_lstm_bwd_len (``LstmBwdLenDesc``)."""
+    return lib().tspm_lstm_bwd_len(count, descs, sh)
 
 
 def index_to_int64(arg: torch.Tensor) -> torch.Tensor:
@@ -316,6 +337,9 @@ _SIGS = {
     # added under ABI 23: the same recurrences with a 16-bit "maxpool" time index (argmax points to uint16)
     "tspm_lstm_fwd_t16": (c_int32, [c_int32, POINTER(LstmFwdDesc), _P]),
     "tspm_lstm_bwd_t16": (c_int32, [c_int32, POINTER(LstmBwdDesc), _P]),
+    # added under ABI 23: the recurrences with per-sample sequence lengths (device int32 [batch]; their own descriptors)
+    "tspm_lstm_fwd_len": (c_int32, [c_int32, POINTER(LstmFwdLenDesc), _P]),
+    "tspm_lstm_bwd_len": (c_int32, [c_int32, POINTER(LstmBwdLenDesc), _P]),
     "tspm_textcnn_pool_fwd": (c_int32, [c_int32, c_int32, c_int32, _P, c_int32, _P, _P, _P, c_float, _P, _P, _P,
                                         c_int32, _P]),
     "tspm_textcnn_bwd": (c_int32, [c_int32, c_int32, c_int32, c_int32, _P, c_int32, _P, _P, c_int32, _P, c_float, _P,

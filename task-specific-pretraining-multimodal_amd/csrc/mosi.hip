@@ -22,6 +22,50 @@ TSPM_DEV float sigmoidf_(float x) { return 1.f / (1.f + expf(-x)); }
 // gates = (h W_hh^T + b_hh) + (x W_ih^T + b_ih); i,f,o = sigmoid, g = tanh; c = f*c + i*g;
 // h = o * tanh(c).  Saved for the backward: activated gates, c_t, h_t.
 // ------------------------------------------------------------------------------------------------
+// Per-sample lengths (tspm_lstm_fwd_len / tspm_lstm_bwd_len): row b runs L_b = min(max(lens[b], 1), T) steps and its
+// state freezes there (pack_padded_sequence).  Every thread of a workgroup reads the lengths of ALL the workgroup's RB
+// rows (the ghost row of an odd batch through its clamped index) from the same addresses, so `bound`, the trip count
+// of the time loop that holds the barriers, is the same in every thread; a thread's own row (`mine`) only masks work
+// between barriers.  The general template (Len false) is empty and folds to the unmasked code.
+template <int RB, bool Len>
+struct LstmLens {
+  static constexpr int mine = 0;
+  TSPM_DEV LstmLens(const int32_t*, const int*, int, int) {}
+  TSPM_DEV LstmLens(const int32_t*, int, int, int, int) {}
+  TSPM_DEV int bound(int T) const { return T; }
+  TSPM_DEV bool row_runs(int, int) const { return true; }
+  TSPM_DEV bool mine_runs(int) const { return true; }
+};
+template <int RB>
+struct LstmLens<RB, true> {
+  int len[RB];  // the workgroup's rows' clamped lengths (uniform)
+  int mine;     // the length of this thread's cell row (0 for a thread that owns no cell)
+  TSPM_DEV LstmLens(const int32_t* lens, const int* rowc, int T, int cr) {
+    mine = 0;
+#pragma unroll
+    for (int r = 0; r < RB; ++r) {
+      len[r] = min(max(lens[rowc[r]], 1), T);
+      if (r == cr) mine = len[r];
+    }
+  }
+  TSPM_DEV LstmLens(const int32_t* lens, int b0, int B, int T, int cr) {  // the backward: rows clamped here
+    mine = 0;
+#pragma unroll
+    for (int r = 0; r < RB; ++r) {
+      len[r] = min(max(lens[min(b0 + r, B - 1)], 1), T);
+      if (r == cr) mine = len[r];
+    }
+  }
+  TSPM_DEV int bound(int) const {
+    int m = len[0];
+#pragma unroll
+    for (int r = 1; r < RB; ++r) m = max(m, len[r]);
+    return m;
+  }
+  TSPM_DEV bool row_runs(int r, int t) const { return t < len[r]; }
+  TSPM_DEV bool mine_runs(int t) const { return t < mine; }
+};
+
 // Ix is the type of the "maxpool" time index: uint8_t (steps <= 256, tspm_lstm_fwd / _w) or uint16_t (steps <= 65535,
 // tspm_lstm_fwd_t16 / _bwd_t16).  It is a template parameter of the descriptors, the bodies and the kernels, so the two index
 // widths are one source and the uint8_t instantiations are the code they were before the parameter existed.
@@ -40,8 +84,10 @@ struct LstmFwdDescT {
 };
 using LstmFwdDesc = LstmFwdDescT<uint8_t>;
 
-template <int H, int RB, typename Ix>
-TSPM_DEV void lstm_fwd_body(const LstmFwdDescT<Ix>& d, int chunk) {
+// Len (tspm_lstm_fwd_len): per-row lengths `lens` [B] — see "Per-sample lengths" above; with Len false the body is the
+// code it was before the parameter existed.
+template <int H, int RB, typename Ix, bool Len = false>
+TSPM_DEV void lstm_fwd_body(const LstmFwdDescT<Ix>& d, int chunk, const int32_t* lens = nullptr) {
   constexpr int G = 4 * H;
   __shared__ __attribute__((aligned(16))) float hsh[RB][H];
   __shared__ float gsh[RB][G];
@@ -71,17 +117,20 @@ TSPM_DEV void lstm_fwd_body(const LstmFwdDescT<Ix>& d, int chunk) {
   float xn[RB];
 #pragma unroll
   for (int r = 0; r < RB; ++r) xn[r] = d.xg[(long long)rowc[r] * G + j];
+  const LstmLens<RB, Len> ln(lens, rowc, T, cr);
+  const int TL = ln.bound(T);
   __syncthreads();
-  for (int t = 0; t < T; ++t) {
+  for (int t = 0; t < TL; ++t) {
     float xc[RB];
 #pragma unroll
     for (int r = 0; r < RB; ++r) xc[r] = xn[r];
-    if (t + 1 < T) {
+    if (t + 1 < TL) {
 #pragma unroll
       for (int r = 0; r < RB; ++r) xn[r] = d.xg[((long long)(t + 1) * B + rowc[r]) * G + j];
     }
 #pragma unroll
     for (int r = 0; r < RB; ++r) {
+      if (!ln.row_runs(r, t)) continue;  // workgroup-uniform: a finished row's gates are not formed
       // four interleaved partial sums (k mod 4): a 16-deep dependent FMA chain instead of 64
       float a4[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -97,13 +146,13 @@ TSPM_DEV void lstm_fwd_body(const LstmFwdDescT<Ix>& d, int chunk) {
       if (b0 + r < B) d.gates[((long long)t * B + b0 + r) * G + j] = a;
     }
     __syncthreads();
-    if (j < RB * H) {
+    if (j < RB * H && ln.mine_runs(t)) {
       const float ig = gsh[cr][cu], fg = gsh[cr][H + cu], gg = gsh[cr][2 * H + cu], og = gsh[cr][3 * H + cu];
       c = fg * c + ig * gg;
       h = og * tanhf(c);
       hsh[cr][cu] = h;
     }
-    if (cell) {
+    if (cell && ln.mine_runs(t)) {
       const long long o = ((long long)t * B + b0 + cr) * H + cu;
       d.cs[o] = c;
       d.hs[o + (long long)B * H] = h;
@@ -117,6 +166,9 @@ TSPM_DEV void lstm_fwd_body(const LstmFwdDescT<Ix>& d, int chunk) {
   if (cell) {
     d.hout[(long long)(b0 + cr) * d.ldh + cu] = d.arg ? mx : h;
     if (d.arg) d.arg[(long long)(b0 + cr) * H + cu] = (Ix)am;
+    if constexpr (Len) {  // hs past the row's length: zeros (pad_packed_sequence; dW_hh's GEMM reads these rows)
+      for (int t = ln.mine; t < T; ++t) d.hs[((long long)(t + 1) * B + b0 + cr) * H + cu] = 0.f;
+    }
   }
 }
 
@@ -144,8 +196,8 @@ __global__ __launch_bounds__(4 * H) void k_lstm_fwd(LstmFwdDescT<Ix> d0, LstmFwd
 // the start and never written, so no NaN of a real unit can meet a padded zero.
 constexpr int kLstmChunk = 32;
 
-template <int HP, int RB, typename Ix>
-TSPM_DEV void lstm_fwd_w_body(const LstmFwdDescT<Ix>& d, const int H, int chunk) {
+template <int HP, int RB, typename Ix, bool Len = false>
+TSPM_DEV void lstm_fwd_w_body(const LstmFwdDescT<Ix>& d, const int H, int chunk, const int32_t* lens = nullptr) {
   constexpr int GP = 4 * HP;
   __shared__ __attribute__((aligned(16))) float hsh[RB][HP];
   __shared__ float gsh[RB][GP];
@@ -181,17 +233,20 @@ TSPM_DEV void lstm_fwd_w_body(const LstmFwdDescT<Ix>& d, const int H, int chunk)
   float xn[RB];
 #pragma unroll
   for (int r = 0; r < RB; ++r) xn[r] = live ? d.xg[(long long)rowc[r] * G + j] : 0.f;
+  const LstmLens<RB, Len> ln(lens, rowc, T, cr);
+  const int TL = ln.bound(T);
   __syncthreads();
-  for (int t = 0; t < T; ++t) {
+  for (int t = 0; t < TL; ++t) {
     float xc[RB];
 #pragma unroll
     for (int r = 0; r < RB; ++r) xc[r] = xn[r];
-    if (t + 1 < T && live) {
+    if (t + 1 < TL && live) {
 #pragma unroll
       for (int r = 0; r < RB; ++r) xn[r] = d.xg[((long long)(t + 1) * B + rowc[r]) * G + j];
     }
 #pragma unroll
     for (int r = 0; r < RB; ++r) {
+      if (!ln.row_runs(r, t)) continue;  // workgroup-uniform
       float a4[4] = {0.f, 0.f, 0.f, 0.f};  // four interleaved partial sums (k mod 4): an H/4-deep chain
 #pragma unroll
       for (int k0 = 0; k0 < HP; k0 += kLstmChunk) {
@@ -211,13 +266,13 @@ TSPM_DEV void lstm_fwd_w_body(const LstmFwdDescT<Ix>& d, const int H, int chunk)
       if (live && b0 + r < B) d.gates[((long long)t * B + b0 + r) * G + j] = a;
     }
     __syncthreads();
-    if (upd) {
+    if (upd && ln.mine_runs(t)) {
       const float ig = gsh[cr][cu], fg = gsh[cr][HP + cu], gg = gsh[cr][2 * HP + cu], og = gsh[cr][3 * HP + cu];
       c = fg * c + ig * gg;
       h = og * tanhf(c);
       hsh[cr][cu] = h;
     }
-    if (cell) {
+    if (cell && ln.mine_runs(t)) {
       const long long o = ((long long)t * B + b0 + cr) * H + cu;
       d.cs[o] = c;
       d.hs[o + (long long)B * H] = h;
@@ -231,6 +286,9 @@ TSPM_DEV void lstm_fwd_w_body(const LstmFwdDescT<Ix>& d, const int H, int chunk)
   if (cell) {
     d.hout[(long long)(b0 + cr) * d.ldh + cu] = d.arg ? mx : h;
     if (d.arg) d.arg[(long long)(b0 + cr) * H + cu] = (Ix)am;
+    if constexpr (Len) {
+      for (int t = ln.mine; t < T; ++t) d.hs[((long long)(t + 1) * B + b0 + cr) * H + cu] = 0.f;
+    }
   }
 }
 
@@ -263,8 +321,8 @@ struct LstmBwdDescT {
 };
 using LstmBwdDesc = LstmBwdDescT<uint8_t>;
 
-template <int H, int RB, typename Ix>
-TSPM_DEV void lstm_bwd_body(const LstmBwdDescT<Ix>& d, int chunk) {
+template <int H, int RB, typename Ix, bool Len = false>
+TSPM_DEV void lstm_bwd_body(const LstmBwdDescT<Ix>& d, int chunk, const int32_t* lens = nullptr) {
   constexpr int G = 4 * H;
   __shared__ __attribute__((aligned(16))) float dgs[RB][G];
   __shared__ float part[4][RB][H];
@@ -278,7 +336,8 @@ TSPM_DEV void lstm_bwd_body(const LstmBwdDescT<Ix>& d, int chunk) {
   const int cr = tid / H, cu = tid - (tid / H) * H;
   const bool cell = tid < RB * H && b0 + cr < B;  // a ghost row (odd batch) computes zeros, writes nothing
   float dc = 0.f, dh = 0.f, gin = 0.f;
-  int am = T - 1;  // the step whose h received the embedding gradient
+  const LstmLens<RB, Len> ln(lens, b0, B, T, cr);
+  int am = (Len ? ln.mine : T) - 1;  // the step whose h received the embedding gradient: the row's last step
   if (cell) {
     gin = d.dh[(long long)(b0 + cr) * d.lddh + cu];
     if (d.arg) am = d.arg[(long long)(b0 + cr) * H + cu];
@@ -286,13 +345,13 @@ TSPM_DEV void lstm_bwd_body(const LstmBwdDescT<Ix>& d, int chunk) {
   if (tid < RB * H && !cell) {
     dgs[cr][cu] = 0.f; dgs[cr][H + cu] = 0.f; dgs[cr][2 * H + cu] = 0.f; dgs[cr][3 * H + cu] = 0.f;
   }
-  for (int t = T - 1; t >= 0; --t) {
-    if (cell) {
-      if (t < T - 1) {
+  for (int t = (Len ? ln.bound(T) : T) - 1; t >= 0; --t) {
+    if (cell && (!Len || t < ln.mine)) {
+      if (t < (Len ? ln.mine : T) - 1) {
         dh = ((part[0][cr][cu] + part[1][cr][cu]) + part[2][cr][cu]) + part[3][cr][cu];
         if (t == am) dh += gin;  // max-pooled embedding: its gradient joins the recurrent one at the argmax
       } else {
-        dh = am == T - 1 ? gin : 0.f;
+        dh = am == (Len ? ln.mine : T) - 1 ? gin : 0.f;
       }
       const long long go = ((long long)t * B + b0 + cr) * G + cu;
       const float ig = d.gates[go], fg = d.gates[go + H], gg = d.gates[go + 2 * H], og = d.gates[go + 3 * H];
@@ -313,6 +372,9 @@ TSPM_DEV void lstm_bwd_body(const LstmBwdDescT<Ix>& d, int chunk) {
     if (t > 0) {
 #pragma unroll
       for (int r = 0; r < RB; ++r) {
+        if constexpr (Len) {
+          if (!ln.row_runs(r, t)) continue;  // workgroup-uniform: the row has not started yet
+        }
         float a4[4] = {0.f, 0.f, 0.f, 0.f};  // interleaved partial sums, as in the forward
 #pragma unroll
         for (int jj = 0; jj < H; jj += 4) {
@@ -324,6 +386,14 @@ TSPM_DEV void lstm_bwd_body(const LstmBwdDescT<Ix>& d, int chunk) {
       }
     }
     __syncthreads();
+  }
+  if constexpr (Len) {  // gate gradients past the row's length: zeros, so the weight-gradient GEMMs keep all T*B rows
+    if (cell) {
+      for (int t = ln.mine; t < T; ++t) {
+        const long long go = ((long long)t * B + b0 + cr) * G + cu;
+        d.dgates[go] = 0.f; d.dgates[go + H] = 0.f; d.dgates[go + 2 * H] = 0.f; d.dgates[go + 3 * H] = 0.f;
+      }
+    }
   }
 }
 
@@ -338,8 +408,9 @@ __global__ __launch_bounds__(4 * H) void k_lstm_bwd(LstmBwdDescT<Ix> d0, LstmBwd
 // LSTM backward through time at a run-time width H on a tier of HP lanes per gate quarter (see k_lstm_fwd_w):
 // thread (q, k) keeps column k of the quarter-q rows of W_hh (zeros in a padded lane), the unrolled jj loop runs in
 // guarded chunks of kLstmChunk as the forward's k loop, padded lanes read and write no global memory, and only units < H are ever read back from LDS.
-template <int HP, int RB, typename Ix>
-TSPM_DEV void lstm_bwd_w_body(const LstmBwdDescT<Ix>& d, const int H, int chunk) {
+template <int HP, int RB, typename Ix, bool Len = false>
+TSPM_DEV void lstm_bwd_w_body(const LstmBwdDescT<Ix>& d, const int H, int chunk,
+                              const int32_t* lens = nullptr) {
   constexpr int GP = 4 * HP;
   __shared__ __attribute__((aligned(16))) float dgs[RB][GP];
   __shared__ float part[4][RB][HP];
@@ -355,7 +426,8 @@ TSPM_DEV void lstm_bwd_w_body(const LstmBwdDescT<Ix>& d, const int H, int chunk)
   const int cr = q, cu = k;
   const bool cell = tid < RB * HP && live && b0 + cr < B;  // ghost rows and padded lanes compute zeros, write nothing
   float dc = 0.f, dh = 0.f, gin = 0.f;
-  int am = T - 1;
+  const LstmLens<RB, Len> ln(lens, b0, B, T, cr);
+  int am = (Len ? ln.mine : T) - 1;
   if (cell) {
     gin = d.dh[(long long)(b0 + cr) * d.lddh + cu];
     if (d.arg) am = d.arg[(long long)(b0 + cr) * H + cu];
@@ -363,13 +435,13 @@ TSPM_DEV void lstm_bwd_w_body(const LstmBwdDescT<Ix>& d, const int H, int chunk)
   if (tid < RB * HP && !cell) {
     dgs[cr][cu] = 0.f; dgs[cr][HP + cu] = 0.f; dgs[cr][2 * HP + cu] = 0.f; dgs[cr][3 * HP + cu] = 0.f;
   }
-  for (int t = T - 1; t >= 0; --t) {
-    if (cell) {
-      if (t < T - 1) {
+  for (int t = (Len ? ln.bound(T) : T) - 1; t >= 0; --t) {
+    if (cell && (!Len || t < ln.mine)) {
+      if (t < (Len ? ln.mine : T) - 1) {
         dh = ((part[0][cr][cu] + part[1][cr][cu]) + part[2][cr][cu]) + part[3][cr][cu];
         if (t == am) dh += gin;
       } else {
-        dh = am == T - 1 ? gin : 0.f;
+        dh = am == (Len ? ln.mine : T) - 1 ? gin : 0.f;
       }
       const long long go = ((long long)t * B + b0 + cr) * G + cu;
       const float ig = d.gates[go], fg = d.gates[go + H], gg = d.gates[go + 2 * H], og = d.gates[go + 3 * H];
@@ -390,6 +462,9 @@ TSPM_DEV void lstm_bwd_w_body(const LstmBwdDescT<Ix>& d, const int H, int chunk)
     if (t > 0) {
 #pragma unroll
       for (int r = 0; r < RB; ++r) {
+        if constexpr (Len) {
+          if (!ln.row_runs(r, t)) continue;  // workgroup-uniform
+        }
         float a4[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int j0 = 0; j0 < HP; j0 += kLstmChunk) {
@@ -406,6 +481,14 @@ TSPM_DEV void lstm_bwd_w_body(const LstmBwdDescT<Ix>& d, const int H, int chunk)
       }
     }
     __syncthreads();
+  }
+  if constexpr (Len) {
+    if (cell) {
+      for (int t = ln.mine; t < T; ++t) {
+        const long long go = ((long long)t * B + b0 + cr) * G + cu;
+        d.dgates[go] = 0.f; d.dgates[go + H] = 0.f; d.dgates[go + 2 * H] = 0.f; d.dgates[go + 3 * H] = 0.f;
+      }
+    }
   }
 }
 
@@ -775,7 +858,188 @@ int lstm_bwd_any_width(int32_t count, const tspm_lstm_bwd_desc* descs, tspm_stre
   return rc != TSPM_OK ? rc : launch_lstm_bwd_any<Ix>(d[1], hw[1], nullptr, 0, st);
 }
 
+// ------------------------------------------------------------------------------------------------
+// Per-sample lengths: the same bodies instantiated with Len = true (beside the instantiations above, whose code does not
+// change), each descriptor with its own `lengths` [batch] in device memory.  The host never reads the lengths: a row's
+// length is clamped to 1..steps in the kernel, so no value moves an access outside the buffers.
+// ------------------------------------------------------------------------------------------------
+template <int H, int RB, typename Ix>
+__global__ __launch_bounds__(4 * H) void k_lstm_fwd_len(LstmFwdDescT<Ix> d0, const int32_t* l0, LstmFwdDescT<Ix> d1,
+                                                        const int32_t* l1, int nb0) {
+  if ((int)blockIdx.x < nb0)
+    lstm_fwd_body<H, RB, Ix, true>(d0, blockIdx.x, l0);
+  else
+    lstm_fwd_body<H, RB, Ix, true>(d1, blockIdx.x - nb0, l1);
+}
+
+template <int HP, int RB, typename Ix>
+__global__ __launch_bounds__(4 * HP) void k_lstm_fwd_w_len(LstmFwdDescT<Ix> d0, int h0, const int32_t* l0,
+                                                           LstmFwdDescT<Ix> d1, int h1, const int32_t* l1, int nb0) {
+  static_assert(RB <= 4, "cell threads are the first RB gate blocks");
+  if ((int)blockIdx.x < nb0)
+    lstm_fwd_w_body<HP, RB, Ix, true>(d0, h0, blockIdx.x, l0);
+  else
+    lstm_fwd_w_body<HP, RB, Ix, true>(d1, h1, blockIdx.x - nb0, l1);
+}
+
+template <int H, int RB, typename Ix>
+__global__ __launch_bounds__(4 * H) void k_lstm_bwd_len(LstmBwdDescT<Ix> d0, const int32_t* l0, LstmBwdDescT<Ix> d1,
+                                                        const int32_t* l1, int nb0) {
+  if ((int)blockIdx.x < nb0)
+    lstm_bwd_body<H, RB, Ix, true>(d0, blockIdx.x, l0);
+  else
+    lstm_bwd_body<H, RB, Ix, true>(d1, blockIdx.x - nb0, l1);
+}
+
+template <int HP, int RB, typename Ix>
+__global__ __launch_bounds__(4 * HP) void k_lstm_bwd_w_len(LstmBwdDescT<Ix> d0, int h0, const int32_t* l0,
+                                                           LstmBwdDescT<Ix> d1, int h1, const int32_t* l1, int nb0) {
+  static_assert(RB <= 4, "cell threads are the first RB gate quarters");
+  if ((int)blockIdx.x < nb0)
+    lstm_bwd_w_body<HP, RB, Ix, true>(d0, h0, blockIdx.x, l0);
+  else
+    lstm_bwd_w_body<HP, RB, Ix, true>(d1, h1, blockIdx.x - nb0, l1);
+}
+
+// One validated problem of a _len call: the index pointer untyped (index_bits picks its type at the launch).
+struct LenFwd {
+  LstmFwdDescT<uint8_t> d;
+  int H, bits;  // bits: 8 / 16, or 0 when there is no index (either instantiation serves)
+  const int32_t* lens;
+};
+struct LenBwd {
+  LstmBwdDescT<uint8_t> d;
+  int H, bits;
+  const int32_t* lens;
+};
+
+template <typename Ix>
+LstmFwdDescT<Ix> len_desc(const LenFwd& p) {
+  return LstmFwdDescT<Ix>{p.d.B, p.d.T, p.d.xg, p.d.whh, p.d.bhh, p.d.gates, p.d.cs, p.d.hs, p.d.hout, p.d.ldh,
+                          reinterpret_cast<Ix*>(p.d.arg)};
+}
+template <typename Ix>
+LstmBwdDescT<Ix> len_desc(const LenBwd& p) {
+  return LstmBwdDescT<Ix>{p.d.B, p.d.T, p.d.whh, p.d.gates, p.d.cs, p.d.dh, p.d.lddh, p.d.dgates,
+                          reinterpret_cast<const Ix*>(p.d.arg)};
+}
+
+template <typename Ix>
+int launch_lstm_fwd_len(const LenFwd& a, const LenFwd* b, hipStream_t st) {
+  const int na = (a.d.B + kLstmRB - 1) / kLstmRB, nbb = b ? (b->d.B + kLstmRB - 1) / kLstmRB : 0;
+  const dim3 grid(na + nbb);
+  const LenFwd& b_ = b ? *b : a;
+  const LstmFwdDescT<Ix> da = len_desc<Ix>(a), db = len_desc<Ix>(b_);
+  switch (lstm_kind(a.H)) {
+    case 0:
+      hipLaunchKernelGGL((k_lstm_fwd_len<64, kLstmRB, Ix>), grid, dim3(256), 0, st, da, a.lens, db, b_.lens, na);
+      break;
+    case 32:
+      hipLaunchKernelGGL((k_lstm_fwd_w_len<32, kLstmRB, Ix>), grid, dim3(128), 0, st, da, a.H, a.lens, db, b_.H,
+                         b_.lens, na);
+      break;
+    case 64:
+      hipLaunchKernelGGL((k_lstm_fwd_w_len<64, kLstmRB, Ix>), grid, dim3(256), 0, st, da, a.H, a.lens, db, b_.H,
+                         b_.lens, na);
+      break;
+    default:
+      hipLaunchKernelGGL((k_lstm_fwd_w_len<128, kLstmRB, Ix>), grid, dim3(512), 0, st, da, a.H, a.lens, db, b_.H,
+                         b_.lens, na);
+      break;
+  }
+  TSPM_LAUNCH_CHECK();
+  return TSPM_OK;
+}
+
+template <typename Ix>
+int launch_lstm_bwd_len(const LenBwd& a, const LenBwd* b, hipStream_t st) {
+  const int na = (a.d.B + kLstmRB - 1) / kLstmRB, nbb = b ? (b->d.B + kLstmRB - 1) / kLstmRB : 0;
+  const dim3 grid(na + nbb);
+  const LenBwd& b_ = b ? *b : a;
+  const LstmBwdDescT<Ix> da = len_desc<Ix>(a), db = len_desc<Ix>(b_);
+  switch (lstm_kind(a.H)) {
+    case 0:
+      hipLaunchKernelGGL((k_lstm_bwd_len<64, kLstmRB, Ix>), grid, dim3(256), 0, st, da, a.lens, db, b_.lens, na);
+      break;
+    case 32:
+      hipLaunchKernelGGL((k_lstm_bwd_w_len<32, kLstmRB, Ix>), grid, dim3(128), 0, st, da, a.H, a.lens, db, b_.H,
+                         b_.lens, na);
+      break;
+    case 64:
+      hipLaunchKernelGGL((k_lstm_bwd_w_len<64, kLstmRB, Ix>), grid, dim3(256), 0, st, da, a.H, a.lens, db, b_.H,
+                         b_.lens, na);
+      break;
+    default:
+      hipLaunchKernelGGL((k_lstm_bwd_w_len<128, kLstmRB, Ix>), grid, dim3(512), 0, st, da, a.H, a.lens, db, b_.H,
+                         b_.lens, na);
+      break;
+  }
+  TSPM_LAUNCH_CHECK();
+  return TSPM_OK;
+}
+
+// The index checks of one _len descriptor → bits (0 without an index), or -1 when the descriptor is invalid.
+int len_index_bits(const void* argmax, int index_bits, int steps) {
+  if (!argmax) return 0;
+  if (index_bits == 8) return steps <= kLstmIndexedSteps<uint8_t> ? 8 : -1;
+  if (index_bits == 16)
+    return steps <= kLstmIndexedSteps<uint16_t> && !(reinterpret_cast<uintptr_t>(argmax) & 1) ? 16 : -1;
+  return -1;
+}
+
+// Two problems share a launch when they are of one kernel kind and their index widths agree (a problem without an index
+// goes with either); otherwise one launch each.  Rows of one workgroup never meet another's, so the results are the same.
+template <typename P, typename F8, typename F16>
+int len_dispatch(int count, const P* p, hipStream_t st, F8 run8, F16 run16) {
+  auto run = [&](const P& a, const P* b) {
+    const int bits = a.bits ? a.bits : (b ? b->bits : 0);
+    return bits == 16 ? run16(a, b, st) : run8(a, b, st);
+  };
+  const bool together = count == 2 && lstm_kind(p[0].H) == lstm_kind(p[1].H) &&
+                        (p[0].bits == p[1].bits || !p[0].bits || !p[1].bits);
+  if (count == 1 || together) return run(p[0], count > 1 ? &p[1] : nullptr);
+  const int rc = run(p[0], nullptr);
+  return rc != TSPM_OK ? rc : run(p[1], nullptr);
+}
+
 }  // namespace
+
+extern "C" int tspm_lstm_fwd_len(int32_t count, const tspm_lstm_fwd_len_desc* descs, tspm_stream_t stream) {
+  if (count < 1 || count > 2 || !descs) return TSPM_ERR_INVALID;
+  LenFwd p[2];
+  for (int i = 0; i < count; ++i) {
+    const tspm_lstm_fwd_len_desc& s = descs[i];
+    if (s.batch <= 0 || s.steps <= 0 || !lstm_width_ok(s.hidden) || !s.xg || !s.w_hh || !s.gates || !s.cs || !s.hs ||
+        !s.h_out || s.ld_out < s.hidden || !s.lengths)
+      return TSPM_ERR_INVALID;
+    if (reinterpret_cast<uintptr_t>(s.w_hh) & 15) return TSPM_ERR_INVALID;
+    const int bits = len_index_bits(s.argmax, s.index_bits, s.steps);
+    if (bits < 0) return TSPM_ERR_INVALID;
+    p[i] = LenFwd{LstmFwdDesc{s.batch, s.steps, s.xg, s.w_hh, s.b_hh, s.gates, s.cs, s.hs, s.h_out, s.ld_out,
+                              static_cast<uint8_t*>(s.argmax)},
+                  s.hidden, bits, s.lengths};
+  }
+  return len_dispatch(count, p, static_cast<hipStream_t>(stream), launch_lstm_fwd_len<uint8_t>,
+                      launch_lstm_fwd_len<uint16_t>);
+}
+
+extern "C" int tspm_lstm_bwd_len(int32_t count, const tspm_lstm_bwd_len_desc* descs, tspm_stream_t stream) {
+  if (count < 1 || count > 2 || !descs) return TSPM_ERR_INVALID;
+  LenBwd p[2];
+  for (int i = 0; i < count; ++i) {
+    const tspm_lstm_bwd_len_desc& s = descs[i];
+    if (s.batch <= 0 || s.steps <= 0 || !lstm_width_ok(s.hidden) || !s.w_hh || !s.gates || !s.cs || !s.dh ||
+        !s.dgates || s.ld_dh < s.hidden || !s.lengths)
+      return TSPM_ERR_INVALID;
+    const int bits = len_index_bits(s.argmax, s.index_bits, s.steps);
+    if (bits < 0) return TSPM_ERR_INVALID;
+    p[i] = LenBwd{LstmBwdDesc{s.batch, s.steps, s.w_hh, s.gates, s.cs, s.dh, s.ld_dh, s.dgates,
+                              static_cast<const uint8_t*>(s.argmax)},
+                  s.hidden, bits, s.lengths};
+  }
+  return len_dispatch(count, p, static_cast<hipStream_t>(stream), launch_lstm_bwd_len<uint8_t>,
+                      launch_lstm_bwd_len<uint16_t>);
+}
 
 extern "C" int tspm_lstm_fwd(int32_t count, const tspm_lstm_fwd_desc* descs, tspm_stream_t stream) {
   if (count < 1 || count > 2 || !descs) return TSPM_ERR_INVALID;

@@ -202,28 +202,34 @@ class MosiEpochRunner:
             self.log = ClassificationLog(self.device, groups=PATTERNS, classes=3, capacity=log_capacity)
             self.recorder = DeviceMetricRecorder(metric_config or MOSI_METRICS, self.log)
         self.eval_steps: Dict[Tuple[int, int], Any] = {}
+        self.ragged = False  # the loader's dataset carries per-sample lengths (mosi_data.MOSI(use_lengths=True))
 
-    def train_step_for(self, b: int, t):
-        """The model's cached FusedMosiStep for (b, t); ``t`` an ``int`` or a triple (Ta, Tv, Tt) (``mosi.norm_steps``)."""
-        st = self.model.fused_step(self.optimizer, self.loss_functions, b, t)
+    def train_step_for(self, b: int, t, ragged: Optional[bool] = None):
+        """The model's cached FusedMosiStep for (b, t); ``t`` an ``int`` or a triple (Ta, Tv, Tt) (``mosi.norm_steps``).
+        ``ragged`` (default: what the current loader's dataset says): the step that reads per-sample lengths."""
+        ragged = self.ragged if ragged is None else bool(ragged)
+        st = self.model.fused_step(self.optimizer, self.loss_functions, b, t, ragged=ragged)
         if st.log is not self.log:
             st.log, st.graph = self.log, None  # the captured graph must record into this log
         return st
 
-    def eval_step_for(self, b: int, t):
+    def eval_step_for(self, b: int, t, ragged: Optional[bool] = None):
         """The cached FusedMosiEvalStep for (b, t) — rebuilt when the model's engine for that shape is no longer
         the one it captured (``UttFusionModel._apply`` drops the engines on .to() / re-materialisation).  ``t``: an
         ``int`` or a triple (Ta, Tv, Tt), keyed by its normalised value."""
         from .mosi import FusedMosiEvalStep, norm_steps
         t = norm_steps(t)
-        st = self.eval_steps.get((b, t))
-        if st is None or st.eng is not self.model._engine(b, t, self.device):
-            st = FusedMosiEvalStep(self.model, self.loss_functions, b, t, self.log)
-            self.eval_steps[(b, t)] = st
+        ragged = self.ragged if ragged is None else bool(ragged)
+        key = (b, t, "ragged") if ragged else (b, t)
+        st = self.eval_steps.get(key)
+        if st is None or st.eng is not self.model._engine(b, t, self.device, ragged):
+            st = FusedMosiEvalStep(self.model, self.loss_functions, b, t, self.log, ragged=ragged)
+            self.eval_steps[key] = st
         return st
 
     def loader_for(self, loader, train: bool):
         """Point a ``MosiDeviceLoader`` at this runner's steps (batches gathered straight into their inputs)."""
+        self.ragged = bool(getattr(getattr(loader, "ds", None), "use_lengths", False))
         if hasattr(loader, "step_for"):
             loader.step_for = self.train_step_for if train else self.eval_step_for
         return loader
@@ -231,7 +237,9 @@ class MosiEpochRunner:
     def _run(self, st, b: Dict[str, Any]) -> None:
         st.eng.groups.copy_(self.log.group_ids(b.get("pattern_name") or b["pattern_names"]), non_blocking=True)
         if b.get("time_major") and b["audio"] is st.eng.A:
-            st.run()
+            st.run()  # the gather wrote the inputs (and, for a ragged step, the length buffers) in place
+        elif st.ragged:
+            st.step(b["audio"], b["video"], b["text"], b["label"], b.get("lengths"))
         else:
             st.step(b["audio"], b["video"], b["text"], b["label"])
 
@@ -264,7 +272,7 @@ class MosiEpochRunner:
         t0 = time.time()
         for b in self.loader_for(loader, True):
             for g in self._groups(b):
-                self._run(self.train_step_for(*self._shape(g)), g)
+                self._run(self.train_step_for(*self._shape(g), ragged="lengths" in g), g)
         return self._finish(t0)
 
     @torch.no_grad()
@@ -275,7 +283,7 @@ class MosiEpochRunner:
         try:
             for b in self.loader_for(loader, False):
                 for g in self._groups(b):
-                    self._run(self.eval_step_for(*self._shape(g)), g)
+                    self._run(self.eval_step_for(*self._shape(g), ragged="lengths" in g), g)
         finally:
             self.model.train()
         return self._finish(t0)

@@ -53,7 +53,7 @@ ARGMAX_LOGITS = 1  # TSPM_ARGMAX_LOGITS (include/tspm.h)
 # keys train_monomodal.py:110-112 never treats as a modality (+ this package's device pattern index
 # and mosi_data's loader bookkeeping)
 _RESERVED = ("labels", "label", "genres", "imdb_ids", "pattern_name", "missing_masks", "sample_idx", "pattern_ids",
-             "steps", "time_major", "pattern_names")
+             "steps", "time_major", "pattern_names", "lengths")
 # MonomodalEncoder(fused_head=...) default for MOSI encoders: tspm_mono_head_step against the four separate launches,
 # graph-replayed at B=128, T=50 (scripts/bench_mosi_mono.py, profiles/mosi_mono_head_ab.json)
 FUSED_HEAD_DEFAULT = True
@@ -336,7 +336,7 @@ class _MosiMonoBuffers(_MonoBuffers):
     """What the MOSI-encoder train and eval steps share: the single-encoder engine on the step's time-major
     input buffer, and the head — ``tspm_mono_head_step`` or the separate launches."""
 
-    def _init_mosi(self, model, x_shape, log, fused_head: Optional[bool]) -> None:
+    def _init_mosi(self, model, x_shape, log, fused_head: Optional[bool], ragged: bool = False) -> None:
         from .mosi import MosiEncoderEngine
         b, t, f = (int(v) for v in x_shape)
         if f != model.encoder.input_size:
@@ -348,7 +348,9 @@ class _MosiMonoBuffers(_MonoBuffers):
             raise L.TspmError("the regression head takes at most 1024 rows and an encoder of at most 128 units, a "
                               "multiple of 4")
         self.fused_head = bool(model.fused_head if fused_head is None else fused_head)
-        self.eng = MosiEncoderEngine(model.encoder, b, t, self.device, seed=model._rng_seed, x=self.X, emb=self.emb)
+        self.ragged = bool(ragged)  # per-sample lengths: the LSTM recurrences read the engine's length buffer
+        self.eng = MosiEncoderEngine(model.encoder, b, t, self.device, seed=model._rng_seed, x=self.X, emb=self.emb,
+                                     ragged=self.ragged)
         if self.regress is not None:
             self.preds = self.logits.view(-1)  # the float predictions
         self.demb = self.eng.demb
@@ -362,11 +364,13 @@ class _MosiMonoBuffers(_MonoBuffers):
     def keep_override(self, v):
         self.eng.keep_override = v
 
-    def load_batch(self, x: torch.Tensor, labels: torch.Tensor) -> None:
+    def load_batch(self, x: torch.Tensor, labels: torch.Tensor, lengths: Optional[torch.Tensor] = None) -> None:
         """x: a batch-first [B, T, F] batch (one tspm_seq_gather into the time-major buffer), or the step's own
-        input buffer (mosi_data.MOSI.device_loader(step_for=...) gathered into it: no copy)."""
+        input buffer (mosi_data.MOSI.device_loader(step_for=...) gathered into it: no copy).  ``lengths`` (a ragged
+        step): int [B], copied on the device into the engine's length buffer (or that buffer itself: no copy)."""
         if x.data_ptr() != self.X.data_ptr():
             self.eng.load(x)
+        self.eng.set_lengths(lengths)
         dst = self.labels_f if self.regress is not None else self.labels  # by the step's mode, cast to its type
         if labels.data_ptr() != dst.data_ptr():
             dst.copy_(labels.reshape(-1), non_blocking=True)
@@ -437,7 +441,7 @@ class FusedMosiMonoStep(_MosiMonoBuffers):
     ``fused_head`` is ignored in this mode; ``preds`` is then the float prediction [B] (a view of ``logits``)."""
 
     def __init__(self, model, optimizer: FusedAdam, loss_functions, x_shape, use_graph: bool = True, log=None,
-                 fused_head: Optional[bool] = None):
+                 fused_head: Optional[bool] = None, ragged: bool = False):
         self.ce_weight, self.regress = _loss_sig(model, loss_functions)
         if self.ce_weight is None and self.regress is None:
             raise L.TspmError("FusedMosiMonoStep: the loss group must be a single cross-entropy term (or, under a "
@@ -448,18 +452,20 @@ class FusedMosiMonoStep(_MosiMonoBuffers):
         for p in model.parameters():
             if p.requires_grad and p.grad is None:
                 raise L.TspmError("FusedMosiMonoStep: parameter without a FusedAdam gradient view")
-        self._init_mosi(model, x_shape, log, fused_head)
+        self._init_mosi(model, x_shape, log, fused_head, ragged)
         self.opt = optimizer
         self.use_graph = use_graph and not os.environ.get("TSPM_NO_GRAPH")
         self.eng.rng_ctr_ptr = optimizer.flat_groups()[0].hyper.data_ptr() + L.HYPER_STEP_OFFSET
         f32 = dict(device=self.device, dtype=torch.float32)
         self.dlogits = torch.empty(self.N, self.K, **f32)
         self.stats = torch.zeros(4, **f32)
-        self._sig = (id(optimizer), id(loss_functions), self.fused_head)
+        self._sig = (id(optimizer), id(loss_functions), self.fused_head) + (("ragged",) if self.ragged else ())
 
-    def matches(self, x: torch.Tensor, optimizer, loss_functions, fused_head: Optional[bool] = None) -> bool:
+    def matches(self, x: torch.Tensor, optimizer, loss_functions, fused_head: Optional[bool] = None,
+                ragged: bool = False) -> bool:
         fh = bool(self.model.fused_head if fused_head is None else fused_head)
-        return self._sig == (id(optimizer), id(loss_functions), fh) and self.matches_shape(x)
+        sig = (id(optimizer), id(loss_functions), fh) + (("ragged",) if ragged else ())
+        return self._sig == sig and self.matches_shape(x)
 
     def _enqueue(self) -> None:
         lib = L.lib()
@@ -477,8 +483,9 @@ class FusedMosiMonoStep(_MosiMonoBuffers):
         self._replay_or_enqueue()
         self.opt.note_steps(1)
 
-    def step(self, x: torch.Tensor, labels: torch.Tensor) -> Dict[str, torch.Tensor]:
-        self.load_batch(x, labels)
+    def step(self, x: torch.Tensor, labels: torch.Tensor,
+             lengths: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+        self.load_batch(x, labels, lengths)
         self.run()
         return {"loss": self.loss, "logits": self.logits, "preds": self.preds}
 
@@ -488,12 +495,12 @@ class FusedMosiMonoEvalStep(_MosiMonoBuffers):
     dropout) and the head in forward-only mode (logits, weighted CE, argmax)."""
 
     def __init__(self, model, loss_functions, x_shape, log=None, use_graph: bool = True,
-                 fused_head: Optional[bool] = None):
+                 fused_head: Optional[bool] = None, ragged: bool = False):
         self.ce_weight, self.regress = _loss_sig(model, loss_functions)
         if self.ce_weight is None and self.regress is None:
             raise L.TspmError("FusedMosiMonoEvalStep: the loss group must be a single cross-entropy term (or, under "
                               "a one-output classifier, a single mean L1 / MSE term)")
-        self._init_mosi(model, x_shape, log, fused_head)
+        self._init_mosi(model, x_shape, log, fused_head, ragged)
         self.use_graph = use_graph and not os.environ.get("TSPM_NO_GRAPH")
 
     def _enqueue(self) -> None:
@@ -505,8 +512,9 @@ class FusedMosiMonoEvalStep(_MosiMonoBuffers):
         self.model.eval()
         self._replay_or_enqueue()
 
-    def step(self, x: torch.Tensor, labels: torch.Tensor) -> Dict[str, torch.Tensor]:
-        self.load_batch(x, labels)
+    def step(self, x: torch.Tensor, labels: torch.Tensor,
+             lengths: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+        self.load_batch(x, labels, lengths)
         self.run()
         return {"loss": self.loss, "logits": self.logits, "preds": self.preds}
 
@@ -750,9 +758,10 @@ class _MosiMonoFn(torch.autograd.Function):
     schedule, forward and backward), for the reference's own train_step sequence with a torch optimizer."""
 
     @staticmethod
-    def forward(ctx, x, model: "MonomodalEncoder", *params):
-        eng = model._mosi_engine(x.shape[0], x.shape[1], x.device)
+    def forward(ctx, x, model: "MonomodalEncoder", lengths, *params):
+        eng = model._mosi_engine(x.shape[0], x.shape[1], x.device, lengths is not None)
         eng.load(x)
+        eng.set_lengths(lengths)
         eng.apply_keep_override()
         sh = L.stream_handle()
         eng.forward(sh, True)
@@ -781,7 +790,7 @@ class _MosiMonoFn(torch.autograd.Function):
             eng.backward(sh)
         finally:
             eng.grad_of = lambda p: p.grad  # noqa: E731
-        return (None, None, *[grads[id(p)] for p in model.parameters()])
+        return (None, None, None, *[grads[id(p)] for p in model.parameters()])
 
 
 class MonomodalEncoder(nn.Module):
@@ -811,23 +820,36 @@ class MonomodalEncoder(nn.Module):
         self._mosi_engines = {}
         return out
 
-    def _mosi_engine(self, b: int, t: int, device):
+    def _mosi_engine(self, b: int, t: int, device, ragged: bool = False):
         from .mosi import MosiEncoderEngine
-        key = (int(b), int(t), device)
+        key = (int(b), int(t), device) + (("ragged",) if ragged else ())
         eng = self._mosi_engines.get(key)
         if eng is None:
-            eng = self._mosi_engines[key] = MosiEncoderEngine(self.encoder, b, t, device, seed=self._rng_seed)
+            eng = self._mosi_engines[key] = MosiEncoderEngine(self.encoder, b, t, device, seed=self._rng_seed,
+                                                              ragged=ragged)
         return eng
 
-    def forward(self, x):
+    def _lengths_of(self, batch, key) -> Optional[torch.Tensor]:
+        """The batch's per-sample lengths for an LSTM encoder (``"lengths"``: an int tensor [B], or a dict by modality
+        name as the fusion loader delivers); None for every other encoder and for a batch without them."""
+        from .mosi import LSTMEncoder
+        lengths = batch.get("lengths") if isinstance(self.encoder, LSTMEncoder) else None
+        if isinstance(lengths, dict):
+            lengths = lengths.get(str(getattr(key, "value", key)).lower().split(".")[-1])
+        return lengths
+
+    def forward(self, x, lengths: Optional[torch.Tensor] = None):
+        """``lengths`` (an LSTMEncoder only): int [B], each row's real length (``LSTMEncoder.forward``)."""
         if isinstance(x, list):
             x = torch.stack(x)
+        if lengths is not None and not self._mosi_encoder():
+            raise L.TspmError("MonomodalEncoder: lengths are taken by an LSTMEncoder only")
         if self._mosi_encoder() and self.training and torch.is_grad_enabled():
             x = x.float()
             if not x.is_cuda:
                 raise L.TspmError("MonomodalEncoder (tspm_amd) runs on the MI355X only (there is no CPU fallback)")
-            return _MosiMonoFn.apply(x, self, *self.parameters())
-        encoded = self.encoder(x)
+            return _MosiMonoFn.apply(x, self, lengths, *self.parameters())
+        encoded = self.encoder(x) if lengths is None else self.encoder(x, lengths)
         if encoded.dim() > 2:  # train_monomodal.py:83-86
             encoded = encoded.reshape(encoded.shape[0], -1)
         if not encoded.is_cuda:
@@ -875,8 +897,20 @@ class MonomodalEncoder(nn.Module):
                               f"{tuple(x.shape)} and {labels.dtype} {tuple(labels.shape)}")
 
     def train_step_fused(self, x: torch.Tensor, labels: torch.Tensor, optimizer, loss_functions,
-                         log: Optional[ClassificationLog] = None) -> FusedMonoStep:
-        """Run one fused step on device tensors and return the step (its loss / logits / preds buffers)."""
+                         log: Optional[ClassificationLog] = None,
+                         lengths: Optional[torch.Tensor] = None) -> FusedMonoStep:
+        """Run one fused step on device tensors and return the step (its loss / logits / preds buffers).  ``lengths``
+        (an LSTMEncoder): int [B] — the ragged step, one graph per padded shape whatever the lengths."""
+        if lengths is not None:
+            st = self._by_buffer.get(x.data_ptr())
+            if not (isinstance(st, FusedMosiMonoStep) and st.matches(x, optimizer, loss_functions, ragged=True)):
+                st = self._fused
+            if not (isinstance(st, FusedMosiMonoStep) and st.matches(x, optimizer, loss_functions, ragged=True)):
+                st = FusedMosiMonoStep(self, optimizer, loss_functions, tuple(x.shape), ragged=True)
+            self._fused = st
+            st.log = log
+            st.step(x, labels, lengths)
+            return st
         if self._mmimdb_encoder():
             self._check_mmimdb_step(x, labels, optimizer, loss_functions, True)
             if not isinstance(self._fused, FusedMMIMDbMonoStep) or \
@@ -895,8 +929,8 @@ class MonomodalEncoder(nn.Module):
         self._fused.step(x, labels)
         return self._fused
 
-    def eval_step_for(self, loss_functions, x_shape, log=None) -> FusedMonoEvalStep:
-        key = tuple(x_shape)
+    def eval_step_for(self, loss_functions, x_shape, log=None, ragged: bool = False) -> FusedMonoEvalStep:
+        key = tuple(x_shape) + (("ragged",) if ragged else ())
         st = self._eval_steps.get(key)
         if self._mmimdb_encoder():
             if st is None or st.weight != _bce_weight_of(loss_functions, "MonomodalEncoder") or \
@@ -905,19 +939,23 @@ class MonomodalEncoder(nn.Module):
             return st
         if st is None or (st.ce_weight, getattr(st, "regress", None)) != _loss_sig(self, loss_functions) or \
                 getattr(st, "fused_head", self.fused_head) != self.fused_head:
-            cls = FusedMosiMonoEvalStep if self._mosi_encoder() else FusedMonoEvalStep
-            st = cls(self, loss_functions, key, log)
+            if ragged:
+                st = FusedMosiMonoEvalStep(self, loss_functions, tuple(x_shape), log, ragged=True)
+            else:
+                cls = FusedMosiMonoEvalStep if self._mosi_encoder() else FusedMonoEvalStep
+                st = cls(self, loss_functions, key, log)
             self._eval_steps[key] = st
         st.log = log
         return st
 
-    def _eval_step_of(self, x: torch.Tensor, loss_functions, log=None):
+    def _eval_step_of(self, x: torch.Tensor, loss_functions, log=None, ragged: bool = False):
         """The eval step for batch x: the step whose input buffer x is (a loader gathered into it), else by shape."""
         own = self._by_buffer.get(x.data_ptr())
-        if isinstance(own, FusedMosiMonoEvalStep) and (own.ce_weight, own.regress) == _loss_sig(self, loss_functions):
+        if isinstance(own, FusedMosiMonoEvalStep) and (own.ce_weight, own.regress) == _loss_sig(self, loss_functions) \
+                and own.ragged == bool(ragged):
             own.log = log
             return own
-        return self.eval_step_for(loss_functions, tuple(x.shape), log)
+        return self.eval_step_for(loss_functions, tuple(x.shape), log, ragged)
 
     def train_step(self, batch, optimizer, loss_functions, device, metric_recorder, config=None, **kwargs):
         """train_monomodal.py:97-260.  Fused HIP graph with FusedAdam and the single cross-entropy loss
@@ -935,12 +973,13 @@ class MonomodalEncoder(nn.Module):
         fused = (not os.environ.get("TSPM_DISABLE_FUSED_STEP") and isinstance(optimizer, FusedAdam)
                  and head_ok and x.is_cuda and labels.dim() == 1
                  and ((self._hip_encoder() and x.dim() in (3, 4)) or (self._mosi_encoder() and x.dim() == 3)))
+        lengths = self._lengths_of(batch, key)
         if fused:
-            st = self.train_step_fused(x, labels, optimizer, loss_functions, dlog)
+            st = self.train_step_fused(x, labels, optimizer, loss_functions, dlog, lengths)
             loss_t, preds = st.loss, st.preds
         else:
             optimizer.zero_grad()
-            logits = self.forward(x)
+            logits = self.forward(x, lengths) if lengths is not None else self.forward(x)
             if reg is not None:
                 logits = logits.reshape(-1)
             loss_t = loss_functions(logits, labels)["total_loss"]
@@ -968,11 +1007,13 @@ class MonomodalEncoder(nn.Module):
                        else L.regress_head_supported(x.shape[0], self.classifier.in_features))
             if (not self.training and head_ok and x.is_cuda and labels.dim() == 1
                     and ((self._hip_encoder() and x.dim() in (3, 4)) or (self._mosi_encoder() and x.dim() == 3))):
-                st = self._eval_step_of(x, loss_functions, dlog)
-                st.step(x, labels)
+                lengths = self._lengths_of(batch, key)
+                st = self._eval_step_of(x, loss_functions, dlog, lengths is not None)
+                st.step(x, labels, lengths) if lengths is not None else st.step(x, labels)
                 loss_t, preds = st.loss, st.preds
             else:
-                logits = self.forward(x)
+                lengths = self._lengths_of(batch, key)
+                logits = self.forward(x, lengths) if lengths is not None else self.forward(x)
                 if reg is not None:
                     logits = logits.reshape(-1)
                 loss_t = loss_functions(logits, labels)["total_loss"]
@@ -1026,25 +1067,37 @@ class MonoEpochRunner:
         self.train_steps: Dict[Tuple, FusedMonoStep] = {}
         self._mosi = model._mosi_encoder()
         self._mmimdb = model._mmimdb_encoder()
+        self.ragged = False
         # sentiment regression (one-output classifier, a single mean L1 / MSE term): the regression head's
         # accumulators, MSA_<key>_<MODALITY> scores under the group "regression", no accuracy
         self.regression = _mono_regress(model, loss_functions) is not None
 
     # MOSI encoders: ``mosi_data.MOSI.loader(...)``'s ``step_for`` hooks — the loader gathers each batch time-major
     # straight into the step's input buffer (set on every loader that has the attribute, as harness.MosiHarness does)
-    def train_step_for(self, b: int, t: int):
+    def train_step_for(self, b: int, t: int, ragged: Optional[bool] = None):
         shape = (int(b), int(t), int(self.model.encoder.input_size))
-        st = self.train_steps.get(shape)
+        ragged = self.ragged if ragged is None else bool(ragged)
+        key = shape + (("ragged",) if ragged else ())
+        st = self.train_steps.get(key)
         if st is None or (self._mosi and st.fused_head != self.model.fused_head):
-            cls = FusedMosiMonoStep if self._mosi else FusedMonoStep
-            st = self.train_steps[shape] = cls(self.model, self.optimizer, self.loss_functions, shape)
+            if ragged:
+                st = FusedMosiMonoStep(self.model, self.optimizer, self.loss_functions, shape, ragged=True)
+            else:
+                cls = FusedMosiMonoStep if self._mosi else FusedMonoStep
+                st = cls(self.model, self.optimizer, self.loss_functions, shape)
+            self.train_steps[key] = st
         return st
 
-    def eval_step_for(self, b: int, t: int):
+    def eval_step_for(self, b: int, t: int, ragged: Optional[bool] = None):
+        ragged = self.ragged if ragged is None else bool(ragged)
         return self.model.eval_step_for(self.loss_functions, (int(b), int(t), int(self.model.encoder.input_size)),
-                                        self.log)
+                                        self.log, ragged)
 
     def _hook(self, loader, train: bool) -> None:
+        from .mosi import LSTMEncoder
+        # the loader's dataset carries per-sample lengths (mosi_data.MOSI(use_lengths=True)): the ragged steps
+        self.ragged = bool(getattr(getattr(loader, "ds", None), "use_lengths", False)) and \
+            isinstance(self.model.encoder, LSTMEncoder)
         if self._mosi and hasattr(loader, "step_for"):
             loader.step_for = self.train_step_for if train else self.eval_step_for
 
@@ -1076,7 +1129,7 @@ class MonoEpochRunner:
             if not started:
                 self.log.reset()
                 started = True
-            yield x, lab
+            yield x, lab, self.model._lengths_of(b, key)
         if not started:
             raise ValueError("empty loader")
 
@@ -1131,16 +1184,17 @@ class MonoEpochRunner:
         accs: List[torch.Tensor] = []
         self.model.train()
         self._hook(loader, True)
-        for x, lab in self._batches(loader):
+        for x, lab, lens in self._batches(loader):
             st = self.model._by_buffer.get(x.data_ptr()) if self._mosi else None
-            if not isinstance(st, FusedMosiMonoStep):
+            if not isinstance(st, FusedMosiMonoStep) or st.ragged != (lens is not None):
                 shape = tuple(x.shape)
-                st = self.train_step_for(*shape[:2]) if self._mosi else self.train_steps.get(shape)
+                st = (self.train_step_for(*shape[:2], ragged=lens is not None) if self._mosi
+                      else self.train_steps.get(shape))
                 if st is None:
                     st = FusedMonoStep(self.model, self.optimizer, self.loss_functions, shape)
                     self.train_steps[shape] = st
             st.log = self.log
-            st.step(x, lab)
+            st.step(x, lab, lens) if lens is not None else st.step(x, lab)
             if not self.regression:
                 accs.append(st.batch_accuracy())
         return self._finish(t0, accs)
@@ -1153,9 +1207,9 @@ class MonoEpochRunner:
         accs: List[torch.Tensor] = []
         self.model.eval()
         self._hook(loader, False)
-        for x, lab in self._batches(loader):
-            st = self.model._eval_step_of(x, self.loss_functions, self.log)
-            st.step(x, lab)
+        for x, lab, lens in self._batches(loader):
+            st = self.model._eval_step_of(x, self.loss_functions, self.log, lens is not None)
+            st.step(x, lab, lens) if lens is not None else st.step(x, lab)
             if not self.regression:
                 accs.append(st.batch_accuracy())
         return self._finish(t0, accs)

@@ -35,6 +35,13 @@ triple of equal numbers is the ``int`` (same cached engine, step and graph, same
 "maxpool" encoder of more than 256 steps takes ``tspm_lstm_fwd_t16/bwd_t16`` and 16-bit index buffers
 (``_lib.lstm_wide_index``); the text length stays within the TextCNN kernels' 255 steps.
 
+Per-sample sequence lengths (this project's addition; the reference runs the padded length): ``ragged`` engines and steps
+(``UttFusionModel.forward(..., lengths=...)``, ``fused_step(..., ragged=True)``, ``LSTMEncoder.forward(x, lengths)``) run
+the recurrences through ``tspm_lstm_fwd_len/bwd_len`` on persistent ``int32 [B]`` device length buffers, one per LSTM
+encoder: each row's state freezes at its own last step (``pack_padded_sequence`` semantics), the buffers are refreshed
+device-to-device before each replay, and one captured graph serves every batch of a padded ``steps``.  ``ragged`` is a
+trailing element of every cache key, so the keys without it are unchanged.  The text modality has no length input.
+
 Sentiment regression (this project's addition; the reference's YAMLs train the three-class variant only): a
 one-output ``netC.fc_out`` (``build_utt_fusion(name, output_dim=1)``) with a single mean ``nn.L1Loss`` / ``nn.MSELoss``
 term (``_regress_term``) on the float32 ``regression_labels`` runs the same steps with the head — ``fc_out``, the loss,
@@ -109,11 +116,13 @@ class LSTMEncoder(nn.Module):
                                       "UTT-Fusion configs)")
         self.embd_method = embd_method
 
-    def forward(self, x: torch.Tensor) -> torch.Tensor:
-        """Inference embedding h_T of x [B, T, input] (gradients flow through UttFusionModel only)."""
+    def forward(self, x: torch.Tensor, lengths: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Inference embedding h_T of x [B, T, input] (gradients flow through UttFusionModel only).  ``lengths`` (int
+        tensor [B], optional): each row's real length — the state freezes at the row's own last step
+        (``pack_padded_sequence`` semantics, ``tspm_lstm_fwd_len``); without it every row runs the padded length."""
         if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()) and x.requires_grad:
             raise L.TspmError("LSTMEncoder: train it inside UttFusionModel (the fused HIP step / its autograd node)")
-        return _encode_lstm(self, x)
+        return _encode_lstm(self, x, lengths)
 
 
 class TextCNN(nn.Module):
@@ -305,6 +314,44 @@ def _lstm_bwd_desc(d, enc: "LSTMEncoder", bufs, B: int, T: int, dh: int, ld_dh: 
     d.argmax = L.ptr(bufs["arg"])
 
 
+RAGGED_MODALITIES = ("audio", "video")  # the LSTM encoders; the text modality has no length input (TextCNN)
+
+
+def _ragged_key(key: tuple, ragged: bool) -> tuple:
+    """A cache key with the ragged mode in it: unchanged (the key as it always was) when ``ragged`` is off."""
+    return key + ("ragged",) if ragged else key
+
+
+def _length_buffer(B: int, T: int, device) -> torch.Tensor:
+    """A persistent int32 [B] length buffer of one LSTM encoder, at the padded length until a batch's lengths are copied
+    in (the captured graph reads it; the kernels clamp every value to 1..T)."""
+    return torch.full((B,), int(T), dtype=torch.int32, device=device)
+
+
+def _set_lengths(buf: torch.Tensor, lengths: Optional[torch.Tensor], T: int, nm: str) -> None:
+    """The batch's lengths into an encoder's length buffer: a device-to-device copy on the current stream, no host
+    synchronisation (``None``: the encoder runs at the full padded length)."""
+    if lengths is None:
+        buf.fill_(int(T))
+        return
+    if not torch.is_tensor(lengths) or lengths.is_floating_point() or lengths.numel() != buf.numel():
+        raise L.TspmError(f"lengths[{nm!r}]: an integer tensor of {buf.numel()} elements (one per batch row)")
+    if lengths.data_ptr() == buf.data_ptr():
+        return  # gathered straight into the buffer (mosi_data.DeviceMosiCorpus.gather(lengths_out=...))
+    buf.copy_(lengths.reshape(-1), non_blocking=True)
+
+
+def _check_lengths_arg(lengths) -> None:
+    if not isinstance(lengths, dict) or any(k not in RAGGED_MODALITIES for k in lengths):
+        raise L.TspmError(f"lengths: a dict with keys among {RAGGED_MODALITIES} (int tensors [B]); the text modality "
+                          f"has no length input")
+
+
+def _len_desc(d, lengths: torch.Tensor, wide: bool) -> None:
+    """The two extra fields of a tspm_lstm_*_len descriptor."""
+    d.lengths, d.index_bits = lengths.data_ptr(), 16 if wide else 8
+
+
 def _lstm_wgrad(enc: "LSTMEncoder", x: torch.Tensor, bufs, B: int, T: int, split: int,
                 wg_ws: torch.Tensor, g, sh: int) -> None:
     """The LSTM weight gradients as GEMMs over the T*B rows of dgates (after tspm_lstm_bwd)."""
@@ -422,8 +469,9 @@ class MosiEngine:
     (Ta, Tv, Tt) (``norm_steps``): each modality's input, saved activations, gather helpers and weight-gradient split
     are planned at its own length (``Ts``); ``T`` is the normalised value (the ``int`` on aligned data)."""
 
-    def __init__(self, model: "UttFusionModel", batch: int, steps, device: torch.device):
+    def __init__(self, model: "UttFusionModel", batch: int, steps, device: torch.device, ragged: bool = False):
         self.m, self.B, self.T, self.device = model, batch, norm_steps(steps), device
+        self.ragged = bool(ragged)
         a, v, t, c = model.netA, model.netV, model.netT, model.netC
         f = dict(device=device, dtype=torch.float32)
         B = batch
@@ -443,6 +491,8 @@ class MosiEngine:
         self.wide = L.lstm_wide_index(((a.embd_method, Ta), (v.embd_method, Tv)))
         self.lstm = {name: _lstm_alloc(enc, B, T_m, device, wide=self.wide)
                      for name, enc, T_m in (("a", a, Ta), ("v", v, Tv))}
+        # ragged mode: one persistent int32 [B] length buffer per LSTM encoder, read by tspm_lstm_fwd_len / _bwd_len
+        self.lens = {"a": _length_buffer(B, Ta, device), "v": _length_buffer(B, Tv, device)} if self.ragged else None
         _text_alloc(self, t, B, Tt, device)
         nc = self.nc
         lib = L.lib()
@@ -488,6 +538,18 @@ class MosiEngine:
             self._offs[T_m] = torch.arange(B, dtype=torch.int64, device=device) * T_m
 
     # -- inputs -------------------------------------------------------------------------------------
+    def set_lengths(self, lengths: Optional[Dict[str, torch.Tensor]]) -> None:
+        """Ragged mode: the batch's ``{"audio": int [B], "video": int [B]}`` into the length buffers (device-to-device,
+        outside any captured graph, which reads the buffers); an absent key runs that encoder at the full length."""
+        if not self.ragged:
+            if lengths is not None:
+                raise L.TspmError("MosiEngine: lengths given to an engine built without ragged=True")
+            return
+        lengths = lengths or {}
+        _check_lengths_arg(lengths)
+        for nm, key, T_m in (("audio", "a", self.Ts[0]), ("video", "v", self.Ts[1])):
+            _set_lengths(self.lens[key], lengths.get(nm), T_m, nm)
+
     def load(self, A: torch.Tensor, V: torch.Tensor, T: torch.Tensor, labels: Optional[torch.Tensor] = None,
              regress: bool = False) -> None:
         """Batch-first [B, T, F] reference tensors → the time-major buffers (tspm_seq_gather: one launch per
@@ -568,10 +630,15 @@ class MosiEngine:
         lib, m = L.lib(), self.m
         B, (Ta, Tv, _) = self.B, self.Ts
         # LSTM input projections over each encoder's T_m*B rows, then both recurrences in one launch
-        descs = (L.LstmFwdDesc * 2)()
+        descs = ((L.LstmFwdLenDesc if self.ragged else L.LstmFwdDesc) * 2)()
         for i, (name, enc, x, col, T_m) in enumerate((("a", m.netA, self.A, 0, Ta),
                                                       ("v", m.netV, self.V, m.netA.hidden_size, Tv))):
             _lstm_fwd_prepare(descs[i], enc, x, self.lstm[name], B, T_m, self.fused.data_ptr() + col * 4, self.E, sh)
+            if self.ragged:
+                _len_desc(descs[i], self.lens[name], self.wide)
+        if self.ragged:
+            L.check(L.lstm_fwd_len(2, descs, sh), "lstm_fwd_len")
+            return
         L.check(L.lstm_fwd(2, descs, sh, self.wide), "lstm_fwd")
 
     def _forward_text(self, sh: int, train: bool) -> None:
@@ -702,10 +769,15 @@ class MosiEngine:
         lib, m, g = L.lib(), self.m, self.grad_of
         B, (Ta, Tv, _) = self.B, self.Ts
         # LSTMs: backward through time (one launch for both), then the weight gradients as GEMMs over T_m*B rows
-        descs = (L.LstmBwdDesc * 2)()
+        descs = ((L.LstmBwdLenDesc if self.ragged else L.LstmBwdDesc) * 2)()
         for i, (name, enc, col, T_m) in enumerate((("a", m.netA, 0, Ta), ("v", m.netV, m.netA.hidden_size, Tv))):
             _lstm_bwd_desc(descs[i], enc, self.lstm[name], B, T_m, self.dfused.data_ptr() + col * 4, self.E)
-        L.check(L.lstm_bwd(2, descs, sh, self.wide), "lstm_bwd")
+            if self.ragged:
+                _len_desc(descs[i], self.lens[name], self.wide)
+        if self.ragged:  # dgates past each row's length are written as zeros: the GEMMs below keep all T_m*B rows
+            L.check(L.lstm_bwd_len(2, descs, sh), "lstm_bwd_len")
+        else:
+            L.check(L.lstm_bwd(2, descs, sh, self.wide), "lstm_bwd")
         for name, enc, x, T_m in (("a", m.netA, self.A, Ta), ("v", m.netV, self.V, Tv)):
             _lstm_wgrad(enc, x, self.lstm[name], B, T_m, self.wg_splits[name], self.wg_ws, g, sh)
 
@@ -726,10 +798,14 @@ class MosiEncoderEngine:
     gradients; TextCNN = three convs + pool/dropout + embedding Linear / act_bwd + linear_bwd + textcnn_bwd."""
 
     def __init__(self, enc: nn.Module, batch: int, steps: int, device, seed: int = 0,
-                 x: Optional[torch.Tensor] = None, emb: Optional[torch.Tensor] = None):
+                 x: Optional[torch.Tensor] = None, emb: Optional[torch.Tensor] = None, ragged: bool = False):
         if torch.device(device).type != "cuda":
             raise L.TspmError("MOSI encoders (tspm_amd) run on the MI355X only (no CPU fallback)")
         self.enc, self.B, self.T, self.device = enc, int(batch), int(steps), device
+        self.ragged = bool(ragged)
+        if self.ragged and isinstance(enc, TextCNN):
+            raise L.TspmError("MosiEncoderEngine: the TextCNN has no length input (ragged mode is the LSTM encoders')")
+        self.lens = _length_buffer(self.B, self.T, device) if self.ragged else None
         B, T = self.B, self.T
         f = dict(device=device, dtype=torch.float32)
         self.is_text = isinstance(enc, TextCNN)
@@ -758,6 +834,14 @@ class MosiEncoderEngine:
         self._index = torch.arange(B, dtype=torch.int64, device=device)
         self._lens = torch.full((B,), T, dtype=torch.int32, device=device)
         self._offs = torch.arange(B, dtype=torch.int64, device=device) * T
+
+    def set_lengths(self, lengths: Optional[torch.Tensor]) -> None:
+        """Ragged mode: the batch's int lengths [B] into the length buffer (``None``: the full padded length)."""
+        if not self.ragged:
+            if lengths is not None:
+                raise L.TspmError("MosiEncoderEngine: lengths given to an engine built without ragged=True")
+            return
+        _set_lengths(self.lens, lengths, self.T, "input")
 
     def load(self, x: torch.Tensor) -> None:
         """A batch-first [B, T, F] tensor → the time-major input buffer."""
@@ -790,8 +874,12 @@ class MosiEncoderEngine:
         if self.is_text:
             _text_forward(self, self.enc, sh, self._keep_mask(train, sh), self.emb.data_ptr(), self.hidden)
             return
-        d = (L.LstmFwdDesc * 1)()
+        d = ((L.LstmFwdLenDesc if self.ragged else L.LstmFwdDesc) * 1)()
         _lstm_fwd_prepare(d[0], self.enc, self.X, self.bufs, B, T, self.emb.data_ptr(), self.hidden, sh)
+        if self.ragged:
+            _len_desc(d[0], self.lens, self.wide)
+            L.check(L.lstm_fwd_len(1, d, sh), "lstm_fwd_len")
+            return
         L.check(L.lstm_fwd(1, d, sh, self.wide), "lstm_fwd")
 
     def backward(self, sh: int) -> None:
@@ -802,9 +890,13 @@ class MosiEncoderEngine:
             _text_backward(self, self.enc, sh, keep, self.demb.data_ptr(), self.hidden, self.emb.data_ptr(),
                            self.hidden, self.grad_of)
             return
-        d = (L.LstmBwdDesc * 1)()
+        d = ((L.LstmBwdLenDesc if self.ragged else L.LstmBwdDesc) * 1)()
         _lstm_bwd_desc(d[0], self.enc, self.bufs, B, T, self.demb.data_ptr(), self.hidden)
-        L.check(L.lstm_bwd(1, d, sh, self.wide), "lstm_bwd")
+        if self.ragged:
+            _len_desc(d[0], self.lens, self.wide)
+            L.check(L.lstm_bwd_len(1, d, sh), "lstm_bwd_len")
+        else:
+            L.check(L.lstm_bwd(1, d, sh, self.wide), "lstm_bwd")
         _lstm_wgrad(self.enc, self.X, self.bufs, B, T, self.wg_split, self.wg_ws, self.grad_of, sh)
 
 
@@ -850,7 +942,7 @@ class FusedMosiStep:
     launch of ``MosiEngine.head_regress``; everything else is the classification step's schedule."""
 
     def __init__(self, model: "UttFusionModel", optimizer: FusedAdam, loss_functions, batch: int, steps,
-                 use_graph: bool = True, allreduce=None):
+                 use_graph: bool = True, allreduce=None, ragged: bool = False):
         if not isinstance(optimizer, FusedAdam):
             raise L.TspmError("FusedMosiStep needs FusedAdam (the flat gradient buffer the kernels write)")
         dev = next(model.parameters()).device
@@ -868,7 +960,8 @@ class FusedMosiStep:
         if self.regress is not None and not L.regress_head_supported(batch, model.netC.widths[-1]):
             raise L.TspmError("FusedMosiStep: the regression head takes at most 1024 rows and a last classifier "
                               "layer of at most 128 units, a multiple of 4")
-        self.eng = MosiEngine(model, batch, steps, dev)
+        self.ragged = bool(ragged)
+        self.eng = MosiEngine(model, batch, steps, dev, ragged=self.ragged)
         self.eng.rng_ctr_ptr = fgs[0].hyper.data_ptr() + L.HYPER_STEP_OFFSET
         if model.clip is not None:
             optimizer.clip_coef = self.eng.clip_coef
@@ -917,8 +1010,11 @@ class FusedMosiStep:
         if self.allreduce is None:
             self._opt()
 
-    def step(self, A, V, T, labels) -> Dict[str, torch.Tensor]:
+    def step(self, A, V, T, labels, lengths: Optional[Dict[str, torch.Tensor]] = None) -> Dict[str, torch.Tensor]:
+        """``lengths`` (a ragged step only): ``{"audio": int [B], "video": int [B]}``, copied on the device into the
+        length buffers the captured graph reads — one graph serves every batch of this padded ``steps``."""
         self.eng.load(A, V, T, labels, self.regress is not None)
+        self.eng.set_lengths(lengths)
         self.run()
         return {"loss": self.eng.loss, "logits": self.eng.logits}
 
@@ -953,8 +1049,10 @@ class FusedMosiEvalStep:
     mean L1 / MSE term) the head is ``MosiEngine.head_regress`` in forward-only mode and ``log`` a RegressionLog.  Inputs are the engine's time-major buffers
     (``mosi_data.MOSI.device_loader(step_for=...)`` gathers into them) or a batch-first batch via ``step``."""
 
-    def __init__(self, model: "UttFusionModel", loss_functions, batch: int, steps, log, use_graph: bool = True):
+    def __init__(self, model: "UttFusionModel", loss_functions, batch: int, steps, log, use_graph: bool = True,
+                 ragged: bool = False):
         dev = next(model.parameters()).device
+        self.ragged = bool(ragged)
         self.model, self.N, self.T, self.log = model, batch, norm_steps(steps), log
         self.weight = _ce_weight(loss_functions)
         self.regress = _regress_mode(model, loss_functions)
@@ -964,7 +1062,7 @@ class FusedMosiEvalStep:
         if self.regress is not None and not L.regress_head_supported(batch, model.netC.widths[-1]):
             raise L.TspmError("FusedMosiEvalStep: the regression head takes at most 1024 rows and a last classifier "
                               "layer of at most 128 units, a multiple of 4")
-        self.eng = model._engine(batch, steps, dev)
+        self.eng = model._engine(batch, steps, dev, self.ragged)
         self.use_graph = use_graph and not os.environ.get("TSPM_NO_GRAPH")
         self.graph: Optional[torch.cuda.CUDAGraph] = None
         self.calls = 0
@@ -983,8 +1081,9 @@ class FusedMosiEvalStep:
                                              e.loss.data_ptr(), lg.loss_log.data_ptr(), lg.counters.data_ptr(),
                                              lg.capacity, sh), "classify_update")
 
-    def step(self, A, V, T, labels) -> None:
+    def step(self, A, V, T, labels, lengths: Optional[Dict[str, torch.Tensor]] = None) -> None:
         self.eng.load(A, V, T, labels, self.regress is not None)
+        self.eng.set_lengths(lengths)
         self.run()
 
     def run(self) -> None:
@@ -1026,9 +1125,10 @@ class _UttFn(torch.autograd.Function):
     reference's own train_step sequence with a non-fused optimizer."""
 
     @staticmethod
-    def forward(ctx, A, V, T, model: "UttFusionModel", *params):
-        eng = model._engine(A.shape[0], _batch_steps(A, V, T), A.device)
+    def forward(ctx, A, V, T, model: "UttFusionModel", lengths, *params):
+        eng = model._engine(A.shape[0], _batch_steps(A, V, T), A.device, lengths is not None)
         eng.load(A, V, T)
+        eng.set_lengths(lengths)
         eng.apply_keep_override()
         eng.forward(L.stream_handle(), True)
         model._fwd_generation += 1
@@ -1056,7 +1156,7 @@ class _UttFn(torch.autograd.Function):
             eng.backward(L.stream_handle())
         finally:
             eng.grad_of = lambda p: p.grad  # noqa: E731
-        return (None, None, None, None, *[grads.get(id(p)) for p in model.parameters()])
+        return (None, None, None, None, None, *[grads.get(id(p)) for p in model.parameters()])
 
 
 class UttFusionModel(nn.Module):
@@ -1081,28 +1181,31 @@ class UttFusionModel(nn.Module):
         self._engines, self._steps = {}, {}
         return out
 
-    def _engine(self, b: int, t, device) -> MosiEngine:
-        """The cached MosiEngine for (batch, steps): ``t`` an ``int`` or a triple (Ta, Tv, Tt), keyed by ``norm_steps``."""
+    def _engine(self, b: int, t, device, ragged: bool = False) -> MosiEngine:
+        """The cached MosiEngine for (batch, steps): ``t`` an ``int`` or a triple (Ta, Tv, Tt), keyed by ``norm_steps``;
+        a ``ragged`` engine (per-sample lengths) is a separate entry, the key without it is unchanged."""
         if torch.device(device).type != "cuda":
             raise L.TspmError("UttFusionModel (tspm_amd) runs on the MI355X only (no CPU fallback)")
         t = norm_steps(t)
-        key = (b, t, device)
+        key = _ragged_key((b, t, device), ragged)
         eng = self._engines.get(key)
         if eng is None:
-            eng = MosiEngine(self, b, t, device)
+            eng = MosiEngine(self, b, t, device, ragged=ragged)
             self._engines[key] = eng
         return eng
 
-    def fused_step(self, optimizer: FusedAdam, loss_functions, batch: int, steps) -> FusedMosiStep:
+    def fused_step(self, optimizer: FusedAdam, loss_functions, batch: int, steps,
+                   ragged: bool = False) -> FusedMosiStep:
         """The cached FusedMosiStep for (optimizer, loss group, batch, padded steps) — one captured graph per
         padded length (mosi_data.MOSI.device_loader(step_for=...) gathers straight into its inputs).  ``steps``: an
         ``int`` or a triple (Ta, Tv, Tt); the key is ``norm_steps(steps)``, so ``50`` and ``(50, 50, 50)`` give the
-        same object."""
+        same object.  ``ragged``: the step whose recurrences read per-sample lengths (``step(..., lengths=...)``) — one
+        captured graph for every batch of this padded length, whatever its real lengths; a separate cache entry."""
         steps = norm_steps(steps)
-        key = (id(optimizer), id(loss_functions), int(batch), steps)
+        key = _ragged_key((id(optimizer), id(loss_functions), int(batch), steps), ragged)
         st = self._steps.get(key)
         if st is None:
-            st = FusedMosiStep(self, optimizer, loss_functions, int(batch), steps)
+            st = FusedMosiStep(self, optimizer, loss_functions, int(batch), steps, ragged=ragged)
             self._steps[key] = st
         return st
 
@@ -1125,9 +1228,12 @@ class UttFusionModel(nn.Module):
 
     def forward(self, A: Optional[torch.Tensor] = None, V: Optional[torch.Tensor] = None,
                 T: Optional[torch.Tensor] = None, *, is_embd_A: bool = False, is_embd_V: bool = False,
-                is_embd_T: bool = False) -> torch.Tensor:
+                is_embd_T: bool = False, lengths: Optional[Dict[str, torch.Tensor]] = None) -> torch.Tensor:
         """utt_fusion.py:105-140 with all three modalities given as [B, T, F] sequences (a missing modality
-        is the zeroed tensor the dataset delivers, data/base_dataset.py:61-74)."""
+        is the zeroed tensor the dataset delivers, data/base_dataset.py:61-74).  ``lengths`` (this project's addition):
+        ``{"audio": int tensor [B], "video": int tensor [B]}``, either key optional — the LSTM encoders then freeze each
+        row's state at its own last step (``pack_padded_sequence`` semantics), so the embedding no longer depends on the
+        padding; the text modality has no length input."""
         assert not all((A is None, V is None, T is None)), "At least one of A, V, T must be provided"
         assert not all([is_embd_A, is_embd_V, is_embd_T]), "Cannot have all embeddings as True"
         if A is None or V is None or T is None or is_embd_A or is_embd_V or is_embd_T:
@@ -1138,9 +1244,10 @@ class UttFusionModel(nn.Module):
                               "ROCm device (there is no CPU fallback)")
         if self.training and torch.is_grad_enabled():
             params = list(self.parameters())
-            return _UttFn.apply(A, V, T, self, *params)
-        eng = self._engine(A.shape[0], _batch_steps(A, V, T), A.device)
+            return _UttFn.apply(A, V, T, self, lengths, *params)
+        eng = self._engine(A.shape[0], _batch_steps(A, V, T), A.device, lengths is not None)
         eng.load(A, V, T)
+        eng.set_lengths(lengths)
         eng.forward(L.stream_handle(), self.training)
         return eng.logits.clone()
 
@@ -1162,12 +1269,14 @@ class UttFusionModel(nn.Module):
             labels = labels.float()
         head_ok = (_ce_weight(loss_functions) is not None if reg is None
                    else L.regress_head_supported(A.shape[0], self.netC.widths[-1]))
+        lengths = batch.get("lengths")  # per-sample lengths (mosi_data.MOSI(use_lengths=True)): the ragged step
         if isinstance(optimizer, FusedAdam) and head_ok and A.is_cuda:
-            out = self.fused_step(optimizer, loss_functions, A.shape[0], _batch_steps(A, V, T)).step(A, V, T, labels)
+            out = self.fused_step(optimizer, loss_functions, A.shape[0], _batch_steps(A, V, T),
+                                  ragged=lengths is not None).step(A, V, T, labels, lengths)
             logits, loss = out["logits"], out["loss"]
         else:
             self.train()
-            logits = self.forward(A, V, T)
+            logits = self.forward(A, V, T, lengths=lengths)
             optimizer.zero_grad()
             loss = loss_functions(logits.squeeze(), labels.squeeze())["total_loss"]
             loss.backward()
@@ -1195,11 +1304,13 @@ class UttFusionModel(nn.Module):
         T = _modality(batch, "text").to(device).float()
         labels = batch["label"].to(device)
         miss = np.array(batch.get("pattern_name", []))
-        eng = self._engine(A.shape[0], _batch_steps(A, V, T), A.device)
+        lengths = batch.get("lengths")
+        eng = self._engine(A.shape[0], _batch_steps(A, V, T), A.device, lengths is not None)
         reg = _regress_mode(self, loss_functions)
         if reg is not None:
             labels = labels.float()
         eng.load(A, V, T, labels, reg is not None)
+        eng.set_lengths(lengths)
         sh = L.stream_handle()
         if reg is not None:
             if L.regress_head_supported(eng.B, eng.widths[-1]):
@@ -1244,8 +1355,10 @@ class UttFusionModel(nn.Module):
             A = _modality(batch, "audio").to(device).float()
             V = _modality(batch, "video").to(device).float()
             T = _modality(batch, "text").to(device).float()
-            eng = self._engine(A.shape[0], _batch_steps(A, V, T), A.device)
+            lengths = batch.get("lengths")
+            eng = self._engine(A.shape[0], _batch_steps(A, V, T), A.device, lengths is not None)
             eng.load(A, V, T)
+            eng.set_lengths(lengths)
             eng.forward(L.stream_handle(), False)
             ha, hv = self.netA.hidden_size, self.netV.hidden_size
             keys = [k for k in batch.keys() if str(getattr(k, "value", k)).lower().split(".")[-1] in
@@ -1258,16 +1371,23 @@ class UttFusionModel(nn.Module):
         return emb
 
 
-def _encode_lstm(enc: LSTMEncoder, x: torch.Tensor) -> torch.Tensor:
-    """Standalone LSTMEncoder embedding (inference): projection GEMM + one-problem tspm_lstm_fwd."""
+def _encode_lstm(enc: LSTMEncoder, x: torch.Tensor, lengths: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Standalone LSTMEncoder embedding (inference): projection GEMM + one-problem tspm_lstm_fwd (with ``lengths``,
+    tspm_lstm_fwd_len)."""
     L.require_cuda_f32(x, "LSTMEncoder input")
     B, T, F = x.shape
     xt = x.transpose(0, 1).contiguous() if T > 1 else x.reshape(1, B, F).contiguous()
     out = torch.empty(B, enc.hidden_size, device=x.device, dtype=torch.float32)
     sh = L.stream_handle()
-    d = (L.LstmFwdDesc * 1)()
+    d = ((L.LstmFwdDesc if lengths is None else L.LstmFwdLenDesc) * 1)()
     wide = L.lstm_wide_index(((enc.embd_method, T),))
     _lstm_fwd_prepare(d[0], enc, xt, _lstm_alloc(enc, B, T, x.device, backward=False, wide=wide), B, T, out.data_ptr(),
                       enc.hidden_size, sh)
+    if lengths is not None:
+        lens = _length_buffer(B, T, x.device)
+        _set_lengths(lens, lengths.to(x.device), T, "input")
+        _len_desc(d[0], lens, wide)
+        L.check(L.lstm_fwd_len(1, d, sh), "lstm_fwd_len")
+        return out
     L.check(L.lstm_fwd(1, d, sh, wide), "lstm_fwd")
     return out

@@ -41,6 +41,7 @@ from . import _lib as L
 MODALITIES = ("audio", "video", "text")
 _PICKLE_KEYS = {"audio": "audio", "video": "vision", "text": "text"}  # data/mosi.py:135-138
 PATTERNS = ["atv", "at", "av", "tv", "a", "t", "v"]  # data/mosi.py:61-69 order
+LENGTH_MODALITIES = ("audio", "video")  # the LSTM encoders take per-sample lengths; the TextCNN has no length input
 
 
 def pad_of(pad_to, modality: str) -> int:
@@ -172,14 +173,22 @@ class DeviceMosiCorpus:
         return per[0] if len(set(per)) == 1 else per
 
     def gather(self, index: torch.Tensor, steps_pad, out: Dict[str, torch.Tensor], time_major: bool,
-               masks: Optional[Dict[str, torch.Tensor]] = None, labels_out: Optional[torch.Tensor] = None) -> None:
+               masks: Optional[Dict[str, torch.Tensor]] = None, labels_out: Optional[torch.Tensor] = None,
+               lengths_out: Optional[Dict[str, torch.Tensor]] = None) -> None:
         """Write the batch ``index`` (device int64) into ``out[m]``: [T, B, F] (time_major) or [B, T, F], for
         the modalities ``out`` names (all three for the fusion step, one for encoder pre-training); int64 labels
         ride on the first launch, float32 labels (``labels_out`` float32 [B]) take one ``tspm_avmnist_gather``
         launch of one float per row (an out-of-range index gives a NaN label).  ``steps_pad``: the common padded
-        length, or the (audio, video, text) triple of an unaligned batch — each modality's launch pads to its own."""
+        length, or the (audio, video, text) triple of an unaligned batch — each modality's launch pads to its own.
+        ``lengths_out``: ``{modality: int32 [B]}`` device buffers filled with the batch's true lengths
+        (``self.lengths[m][index]``, on the device, no host sync) — a ragged step's length buffers, or a batch's
+        ``"lengths"``."""
         lib, sh = L.lib(), L.stream_handle()
         b = int(index.numel())
+        for m, buf in (lengths_out or {}).items():
+            if buf.dtype != torch.int32 or tuple(buf.shape) != (b,):
+                raise L.TspmError(f"lengths_out[{m!r}]: an int32 [{b}] device buffer")
+            torch.index_select(self.lengths[m], 0, index, out=buf)
         if labels_out is not None and labels_out.dtype != self.label_dtype:
             raise L.TspmError(f"labels_out is {labels_out.dtype}, the corpus carries {self.label_dtype} labels")
         if self.float_labels and labels_out is not None:
@@ -212,7 +221,7 @@ class MOSI(torch.utils.data.Dataset):
                  missing_patterns=None, selected_patterns: Optional[List[str]] = None,
                  labels_key: str = "classification_labels", aligned: bool = False, length: Optional[int] = None,
                  num_classes: Optional[int] = None, batch_size: int = 1, corpus: Optional[MosiCorpus] = None,
-                 device=None, seed: int = 0, allow_pickle: bool = False) -> None:
+                 device=None, seed: int = 0, allow_pickle: bool = False, use_lengths: bool = False) -> None:
         split = split.lower()
         if split not in self.VALID_SPLITS:
             raise AssertionError(f"Invalid split provided, must be one of {self.VALID_SPLITS}")
@@ -233,6 +242,10 @@ class MOSI(torch.utils.data.Dataset):
         self.missing_patterns = missing_patterns
         self._batch_size = batch_size
         self.allow_pickle = allow_pickle
+        # use_lengths: batches carry each sample's true audio / video length (``"lengths"``, or written into a ragged
+        # step's length buffers) and an unaligned file is trimmed to its audio_lengths / vision_lengths; the LSTM
+        # encoders then stop at each sample's own last frame.  The text modality has no length input.
+        self.use_lengths = bool(use_lengths)
         if corpus is None:
             corpus = self._load(data_fp)
         self.corpus = corpus
@@ -268,10 +281,14 @@ class MOSI(torch.utils.data.Dataset):
             raise KeyError(f"Labels key '{self.labels_key}' not found in data")
         # The reference keeps the dense [N, T, F] arrays even for unaligned files and never trims them to
         # audio_lengths / vision_lengths (data/mosi.py:134-152: lengths are metadata only); so here.
-        corpus = MosiCorpus.from_split(split, self.labels_key, None)
+        # With ``use_lengths`` the corpus is trimmed to them instead (this project's addition).
+        true_lengths = None
         if not self.aligned and "audio_lengths" in split:
-            corpus.true_lengths = {"audio": np.asarray(split["audio_lengths"]).astype(np.int64),
-                                   "video": np.asarray(split["vision_lengths"]).astype(np.int64)}
+            true_lengths = {"audio": np.asarray(split["audio_lengths"]).astype(np.int64),
+                            "video": np.asarray(split["vision_lengths"]).astype(np.int64)}
+        corpus = MosiCorpus.from_split(split, self.labels_key, true_lengths if self.use_lengths else None)
+        if true_lengths is not None:
+            corpus.true_lengths = true_lengths
         return corpus
 
     # -- reference Dataset API ----------------------------------------------------------------------
@@ -329,16 +346,23 @@ class MOSI(torch.utils.data.Dataset):
         index = torch.from_numpy(rows).to(self.device, non_blocking=True)
         masks = {k: v for k, v in self._masks(pid).items() if k == m}
         names = [self.selected_patterns[p] for p in pid]
+        ragged = self.use_lengths and m in LENGTH_MODALITIES
         if step is not None:
             if (step.N, step.T) != (b, tpad):
                 raise L.TspmError(f"step planned for (B={step.N}, T={step.T}), batch is (B={b}, T={tpad})")
             lab = step.labels_f if dc.float_labels else step.labels
-            dc.gather(index, tpad, {m: step.X}, True, masks, lab)
-            return {m: step.X, "label": lab, "pattern_name": names}
+            lens = None
+            if ragged:
+                lens = getattr(step.eng, "lens", None)
+                if lens is None:
+                    raise L.TspmError("use_lengths: the step was built without ragged=True (no length buffer)")
+            dc.gather(index, tpad, {m: step.X}, True, masks, lab, {m: lens} if ragged else None)
+            return {m: step.X, "label": lab, "pattern_name": names, **({"lengths": lens} if ragged else {})}
         out = torch.empty(b, tpad, dc.feat[m], device=self.device)
         lab = torch.empty(b, dtype=dc.label_dtype, device=self.device)
-        dc.gather(index, tpad, {m: out}, False, masks, lab)
-        return {m: out, "label": lab, "pattern_name": names}
+        lens = torch.empty(b, dtype=torch.int32, device=self.device) if ragged else None
+        dc.gather(index, tpad, {m: out}, False, masks, lab, {m: lens} if ragged else None)
+        return {m: out, "label": lab, "pattern_name": names, **({"lengths": lens} if ragged else {})}
 
     def _collate(self, rows: np.ndarray, pid: np.ndarray, step=None, pad_to: int = 0) -> Dict[str, Any]:
         if self.target_modality != "multimodal":
@@ -353,14 +377,22 @@ class MOSI(torch.utils.data.Dataset):
             if (e.B, e.T) != (b, tpad):
                 raise L.TspmError(f"step planned for (B={e.B}, T={e.T}), batch is (B={b}, T={tpad})")
             lab = e.labels_f if dc.float_labels else e.labels
-            dc.gather(index, tpad, {"audio": e.A, "video": e.V, "text": e.X}, True, masks, lab)
+            lens = None
+            if self.use_lengths:
+                if getattr(e, "lens", None) is None:
+                    raise L.TspmError("use_lengths: the step was built without ragged=True (no length buffers)")
+                lens = {"audio": e.lens["a"], "video": e.lens["v"]}
+            dc.gather(index, tpad, {"audio": e.A, "video": e.V, "text": e.X}, True, masks, lab, lens)
             return {"audio": e.A, "video": e.V, "text": e.X, "label": lab, "pattern_name": names,
-                    "steps": tpad, "time_major": True}
+                    "steps": tpad, "time_major": True, **({"lengths": lens} if lens is not None else {})}
         out = {m: torch.empty(b, steps_of(tpad, m), dc.feat[m], device=self.device) for m in MODALITIES}
         lab = torch.empty(b, dtype=dc.label_dtype, device=self.device)
-        dc.gather(index, tpad, out, False, masks, lab)
+        lens = ({m: torch.empty(b, dtype=torch.int32, device=self.device) for m in LENGTH_MODALITIES}
+                if self.use_lengths else None)
+        dc.gather(index, tpad, out, False, masks, lab, lens)
         return {"audio": out["audio"], "video": out["video"], "text": out["text"], "label": lab,
-                "pattern_name": names, "pattern_names": names, "steps": tpad}
+                "pattern_name": names, "pattern_names": names, "steps": tpad,
+                **({"lengths": lens} if lens is not None else {})}
 
     def device_loader(self, batch_size: int, shuffle: bool = False, drop_last: bool = False,
                       generator: Optional[torch.Generator] = None, step_for=None,
