@@ -10,6 +10,8 @@
 // Layout: sequences are TIME-MAJOR on the device — row (t, b) of a [T][B][F] tensor — so every
 // step's rows are contiguous, the LSTM weight gradients are plain GEMMs over the T*B rows, and the
 // text input is an HWNC tensor (H = T, W = 1, N = B, C = 768) for the LDS-staged conv kernel.
+#include <type_traits>
+
 #include "common.h"
 
 namespace {
@@ -66,11 +68,9 @@ struct LstmLens<RB, true> {
   TSPM_DEV bool mine_runs(int t) const { return t < mine; }
 };
 
-// Ix is the type of the "maxpool" time index: uint8_t (steps <= 256, tspm_lstm_fwd / _w) or uint16_t (steps <= 65535,
-// tspm_lstm_fwd_t16 / _bwd_t16).  It is a template parameter of the descriptors, the bodies and the kernels, so the two index
-// widths are one source and the uint8_t instantiations are the code they were before the parameter existed.
-template <typename Ix>
-struct LstmFwdDescT {
+// One problem of a launch.  The "maxpool" time index `arg` is untyped here: the kernels' template parameter Ix says
+// whether it is uint8_t (steps <= 256) or uint16_t (steps <= 65535), and the bodies cast it where they use it.
+struct LstmFwdDesc {
   int B, T;
   const float* xg;   // [T][B][4H]: x W_ih^T + b_ih
   const float* whh;  // [4H][H]
@@ -80,124 +80,40 @@ struct LstmFwdDescT {
   float* hs;         // [T+1][B][H], hs[0] = 0
   float* hout;       // h_T rows (embd "last") or max_t h_t (embd "maxpool"), stride ldh
   int ldh;
-  Ix* arg;           // embd "maxpool": [B][H] time index of the maximum (F.max_pool1d), else null
+  void* arg;         // embd "maxpool": Ix [B][H] time index of the maximum (F.max_pool1d), else null
 };
-using LstmFwdDesc = LstmFwdDescT<uint8_t>;
 
-// Len (tspm_lstm_fwd_len): per-row lengths `lens` [B] — see "Per-sample lengths" above; with Len false the body is the
-// code it was before the parameter existed.
-template <int H, int RB, typename Ix, bool Len = false>
-TSPM_DEV void lstm_fwd_body(const LstmFwdDescT<Ix>& d, int chunk, const int32_t* lens = nullptr) {
-  constexpr int G = 4 * H;
-  __shared__ __attribute__((aligned(16))) float hsh[RB][H];
-  __shared__ float gsh[RB][G];
-  const int j = threadIdx.x;
-  const int b0 = chunk * RB;
-  const int B = d.B, T = d.T;
-  float w[H];
-#pragma unroll
-  for (int k = 0; k < H; k += 4) {
-    const f32x4 v = ld4(d.whh + (long long)j * H + k);
-    w[k] = v[0]; w[k + 1] = v[1]; w[k + 2] = v[2]; w[k + 3] = v[3];
-  }
-  const float bh = d.bhh ? d.bhh[j] : 0.f;
-  // an odd batch leaves the last workgroup one row short: that ghost row reads the last real row's inputs
-  // (clamped index) and writes nothing
-  const int cr = j / H, cu = j - (j / H) * H;
-  const bool cell = j < RB * H && b0 + cr < B;
-  float c = 0.f, h = 0.f;
-  float mx = -INFINITY;  // embd "maxpool": running max over t of h_t and its first index (NaN wins, as
-  int am = 0;            // max_pool2d_with_indices: val > max || isnan(val))
-  if (j < RB * H) hsh[cr][cu] = 0.f;
-  if (cell) d.hs[(long long)(b0 + cr) * H + cu] = 0.f;
-  const bool sig = j < 2 * H || j >= 3 * H;
-  int rowc[RB];  // clamped row of each of the workgroup's rows
-#pragma unroll
-  for (int r = 0; r < RB; ++r) rowc[r] = min(b0 + r, B - 1);
-  float xn[RB];
-#pragma unroll
-  for (int r = 0; r < RB; ++r) xn[r] = d.xg[(long long)rowc[r] * G + j];
-  const LstmLens<RB, Len> ln(lens, rowc, T, cr);
-  const int TL = ln.bound(T);
-  __syncthreads();
-  for (int t = 0; t < TL; ++t) {
-    float xc[RB];
-#pragma unroll
-    for (int r = 0; r < RB; ++r) xc[r] = xn[r];
-    if (t + 1 < TL) {
-#pragma unroll
-      for (int r = 0; r < RB; ++r) xn[r] = d.xg[((long long)(t + 1) * B + rowc[r]) * G + j];
-    }
-#pragma unroll
-    for (int r = 0; r < RB; ++r) {
-      if (!ln.row_runs(r, t)) continue;  // workgroup-uniform: a finished row's gates are not formed
-      // four interleaved partial sums (k mod 4): a 16-deep dependent FMA chain instead of 64
-      float a4[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int k = 0; k < H; k += 4) {
-        const f32x4 hv = *reinterpret_cast<const f32x4*>(&hsh[r][k]);
-#pragma unroll
-        for (int u = 0; u < 4; ++u) a4[u] = fmaf(hv[u], w[k + u], a4[u]);
-      }
-      const float acc = (a4[0] + a4[1]) + (a4[2] + a4[3]);
-      const float pre = (acc + bh) + xc[r];
-      const float a = sig ? sigmoidf_(pre) : tanhf(pre);
-      gsh[r][j] = a;
-      if (b0 + r < B) d.gates[((long long)t * B + b0 + r) * G + j] = a;
-    }
-    __syncthreads();
-    if (j < RB * H && ln.mine_runs(t)) {
-      const float ig = gsh[cr][cu], fg = gsh[cr][H + cu], gg = gsh[cr][2 * H + cu], og = gsh[cr][3 * H + cu];
-      c = fg * c + ig * gg;
-      h = og * tanhf(c);
-      hsh[cr][cu] = h;
-    }
-    if (cell && ln.mine_runs(t)) {
-      const long long o = ((long long)t * B + b0 + cr) * H + cu;
-      d.cs[o] = c;
-      d.hs[o + (long long)B * H] = h;
-      if (d.arg && (h > mx || h != h)) {
-        mx = h;
-        am = t;
-      }
-    }
-    __syncthreads();
-  }
-  if (cell) {
-    d.hout[(long long)(b0 + cr) * d.ldh + cu] = d.arg ? mx : h;
-    if (d.arg) d.arg[(long long)(b0 + cr) * H + cu] = (Ix)am;
-    if constexpr (Len) {  // hs past the row's length: zeros (pad_packed_sequence; dW_hh's GEMM reads these rows)
-      for (int t = ln.mine; t < T; ++t) d.hs[((long long)(t + 1) * B + b0 + cr) * H + cu] = 0.f;
-    }
-  }
-}
+// What a kernel takes per problem after the descriptor, as a pack X of plain kernel arguments: `int` — the run-time
+// width, absent when the width is the compile-time HP (Fixed) — then `const int32_t*` — the lengths, present with Len.
+// A kernel so carries only what it reads, and its argument list is (d0, x0..., d1, x1..., nb0).
+struct LstmExtra {
+  int H;  // unused when Fixed
+  const int32_t* lens;
+};
+TSPM_DEV LstmExtra lstm_extra() { return {0, nullptr}; }
+TSPM_DEV LstmExtra lstm_extra(int H) { return {H, nullptr}; }
+TSPM_DEV LstmExtra lstm_extra(const int32_t* lens) { return {0, lens}; }
+TSPM_DEV LstmExtra lstm_extra(int H, const int32_t* lens) { return {H, lens}; }
+template <typename... X> constexpr bool kLstmFixed = !(std::is_same_v<X, int> || ...);
+template <typename... X> constexpr bool kLstmLen = (std::is_same_v<X, const int32_t*> || ...);
 
-template <int H, int RB, typename Ix>
-__global__ __launch_bounds__(4 * H) void k_lstm_fwd(LstmFwdDescT<Ix> d0, LstmFwdDescT<Ix> d1, int nb0) {
-  if ((int)blockIdx.x < nb0)
-    lstm_fwd_body<H, RB, Ix>(d0, blockIdx.x);
-  else
-    lstm_fwd_body<H, RB, Ix>(d1, blockIdx.x - nb0);
-}
-
-// ------------------------------------------------------------------------------------------------
-// LSTM forward, any hidden width H (a multiple of 4, 4 <= H <= 128) at run time: the recurrence above on a
-// tier of HP = 32 / 64 / 128 lanes per gate.  Thread (q, u) = (gate, unit) of 4 * HP owns gate column
-// q * H + u when u < H; a padded lane (u >= H) holds zero weights, reads and writes no global memory and
-// never writes h (its LDS slot stays the initial zero).  The unrolled k loop runs in chunks of kLstmChunk lanes,
-// each under one wave-uniform guard, so a chunk wholly past H costs nothing, a chunk that straddles H adds 0 x 0
-// products only, and at H = HP the fmaf sequence is k_lstm_fwd's.  Memory layouts carry the real H: xg / gates
-// [T][B][4H], cs [T][B][H], hs [T+1][B][H].
-// ------------------------------------------------------------------------------------------------
-// The reductions of the run-time-width kernels are guarded per chunk of this many lanes, not per float4 group: one
-// wave-uniform branch per chunk (at most 4; 32 per-group guards hoisted out of the time loop as scalar masks spilled
-// 55 / 113 SGPRs in the 128 tier) and the chunk's LDS reads in flight together.  Inside a chunk that straddles the
-// width the padded products are 0 x 0: a padded weight is zero and a padded h / gate-gradient slot of LDS is zero from
-// the start and never written, so no NaN of a real unit can meet a padded zero.
+// The reductions are guarded per chunk of this many lanes, not per float4 group: one wave-uniform branch per chunk (at
+// most 4; 32 per-group guards hoisted out of the time loop as scalar masks spilled 55 / 113 SGPRs in the 128 tier) and
+// the chunk's LDS reads in flight together.  Inside a chunk that straddles the width the padded products are 0 x 0: a
+// padded weight is zero and a padded h / gate-gradient slot of LDS is zero from the start and never written, so no NaN
+// of a real unit can meet a padded zero.
 constexpr int kLstmChunk = 32;
 
-template <int HP, int RB, typename Ix, bool Len = false>
-TSPM_DEV void lstm_fwd_w_body(const LstmFwdDescT<Ix>& d, const int H, int chunk, const int32_t* lens = nullptr) {
+// The forward recurrence on HP lanes per gate.  Thread (q, u) = (gate, unit) of 4 * HP owns gate column q * H + u when
+// u < H.  Width policy: Fixed — H is HP itself, every guard on H folds away and the k loop is one straight unrolled
+// chain; otherwise H (a multiple of 4, 4 <= H <= HP) comes with the problem: a padded lane (u >= H) holds zero weights,
+// reads and writes no global memory and never writes h (its LDS slot stays the initial zero), a chunk of the k loop
+// wholly past H is skipped, and at H = HP the fmaf sequence is the fixed one's.  Memory layouts carry the real H: xg /
+// gates [T][B][4H], cs [T][B][H], hs [T+1][B][H].  Len: per-row lengths, see "Per-sample lengths" above.
+template <int HP, int RB, typename Ix, bool Fixed, bool Len>
+TSPM_DEV void lstm_fwd_body(const LstmFwdDesc& d, const LstmExtra x, int chunk) {
+  const int H = Fixed ? HP : x.H;
+  const int32_t* lens = x.lens;
   constexpr int GP = 4 * HP;
   __shared__ __attribute__((aligned(16))) float hsh[RB][HP];
   __shared__ float gsh[RB][GP];
@@ -222,12 +138,14 @@ TSPM_DEV void lstm_fwd_w_body(const LstmFwdDescT<Ix>& d, const int H, int chunk,
   const bool upd = tid < RB * HP && live;
   const bool cell = upd && b0 + cr < B;
   float c = 0.f, h = 0.f;
-  float mx = -INFINITY;
-  int am = 0;
+  float mx = -INFINITY;  // embd "maxpool": running max over t of h_t and its first index (NaN wins, as
+  int am = 0;            // max_pool2d_with_indices: val > max || isnan(val))
   if (tid < RB * HP) hsh[cr][cu] = 0.f;
   if (cell) d.hs[(long long)(b0 + cr) * H + cu] = 0.f;
-  const bool sig = q != 2;
-  int rowc[RB];
+  // i, f, o = sigmoid, g = tanh.  The fixed spelling is kept as it is: `q != 2` gives the fixed-width kernels another
+  // register assignment.
+  const bool sig = Fixed ? (tid < 2 * HP || tid >= 3 * HP) : q != 2;
+  int rowc[RB];  // clamped row of each of the workgroup's rows
 #pragma unroll
   for (int r = 0; r < RB; ++r) rowc[r] = min(b0 + r, B - 1);
   float xn[RB];
@@ -246,8 +164,8 @@ TSPM_DEV void lstm_fwd_w_body(const LstmFwdDescT<Ix>& d, const int H, int chunk,
     }
 #pragma unroll
     for (int r = 0; r < RB; ++r) {
-      if (!ln.row_runs(r, t)) continue;  // workgroup-uniform
-      float a4[4] = {0.f, 0.f, 0.f, 0.f};  // four interleaved partial sums (k mod 4): an H/4-deep chain
+      if (!ln.row_runs(r, t)) continue;  // workgroup-uniform: a finished row's gates are not formed
+      float a4[4] = {0.f, 0.f, 0.f, 0.f};  // four interleaved partial sums (k mod 4): an H/4-deep chain, not H
 #pragma unroll
       for (int k0 = 0; k0 < HP; k0 += kLstmChunk) {
         if (k0 < H) {  // wave-uniform: a chunk wholly past the width is skipped
@@ -285,21 +203,22 @@ TSPM_DEV void lstm_fwd_w_body(const LstmFwdDescT<Ix>& d, const int H, int chunk,
   }
   if (cell) {
     d.hout[(long long)(b0 + cr) * d.ldh + cu] = d.arg ? mx : h;
-    if (d.arg) d.arg[(long long)(b0 + cr) * H + cu] = (Ix)am;
-    if constexpr (Len) {
+    if (d.arg) static_cast<Ix*>(d.arg)[(long long)(b0 + cr) * H + cu] = (Ix)am;
+    if constexpr (Len) {  // hs past the row's length: zeros (pad_packed_sequence; dW_hh's GEMM reads these rows)
       for (int t = ln.mine; t < T; ++t) d.hs[((long long)(t + 1) * B + b0 + cr) * H + cu] = 0.f;
     }
   }
 }
 
-template <int HP, int RB, typename Ix>
-__global__ __launch_bounds__(4 * HP) void k_lstm_fwd_w(LstmFwdDescT<Ix> d0, int h0, LstmFwdDescT<Ix> d1, int h1,
-                                                       int nb0) {
+// Both problems of a launch: workgroups [0, nb0) run problem 0, the rest problem 1 (a count-1 launch passes its
+// problem twice and nb0 = the grid).
+template <int HP, int RB, typename Ix, typename... X>
+__global__ __launch_bounds__(4 * HP) void k_lstm_fwd(LstmFwdDesc d0, X... x0, LstmFwdDesc d1, X... x1, int nb0) {
   static_assert(RB <= 4, "cell threads are the first RB gate blocks");
   if ((int)blockIdx.x < nb0)
-    lstm_fwd_w_body<HP, RB, Ix>(d0, h0, blockIdx.x);
+    lstm_fwd_body<HP, RB, Ix, kLstmFixed<X...>, kLstmLen<X...>>(d0, lstm_extra(x0...), blockIdx.x);
   else
-    lstm_fwd_w_body<HP, RB, Ix>(d1, h1, blockIdx.x - nb0);
+    lstm_fwd_body<HP, RB, Ix, kLstmFixed<X...>, kLstmLen<X...>>(d1, lstm_extra(x1...), blockIdx.x - nb0);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -308,8 +227,7 @@ __global__ __launch_bounds__(4 * HP) void k_lstm_fwd_w(LstmFwdDescT<Ix> d0, int 
 // fixed order through LDS); threads (r, u) carry dc and form the pre-activation gate gradients
 // (written time-major for the weight-gradient GEMMs that follow).
 // ------------------------------------------------------------------------------------------------
-template <typename Ix>
-struct LstmBwdDescT {
+struct LstmBwdDesc {
   int B, T;
   const float* whh;    // [4H][H]
   const float* gates;  // [T][B][4H]
@@ -317,100 +235,17 @@ struct LstmBwdDescT {
   const float* dh;     // gradient of the embedding rows (h_T, or max_t h_t at arg), stride lddh
   int lddh;
   float* dgates;       // [T][B][4H] out
-  const Ix* arg;       // embd "maxpool": [B][H] time index that received the embedding (null: T-1)
+  const void* arg;     // embd "maxpool": Ix [B][H] time index that received the embedding (null: T-1)
 };
-using LstmBwdDesc = LstmBwdDescT<uint8_t>;
 
-template <int H, int RB, typename Ix, bool Len = false>
-TSPM_DEV void lstm_bwd_body(const LstmBwdDescT<Ix>& d, int chunk, const int32_t* lens = nullptr) {
-  constexpr int G = 4 * H;
-  __shared__ __attribute__((aligned(16))) float dgs[RB][G];
-  __shared__ float part[4][RB][H];
-  const int tid = threadIdx.x;
-  const int q = tid / H, k = tid - (tid / H) * H;
-  const int b0 = chunk * RB;
-  const int B = d.B, T = d.T;
-  float wc[H];
-#pragma unroll
-  for (int jj = 0; jj < H; ++jj) wc[jj] = d.whh[(long long)(q * H + jj) * H + k];
-  const int cr = tid / H, cu = tid - (tid / H) * H;
-  const bool cell = tid < RB * H && b0 + cr < B;  // a ghost row (odd batch) computes zeros, writes nothing
-  float dc = 0.f, dh = 0.f, gin = 0.f;
-  const LstmLens<RB, Len> ln(lens, b0, B, T, cr);
-  int am = (Len ? ln.mine : T) - 1;  // the step whose h received the embedding gradient: the row's last step
-  if (cell) {
-    gin = d.dh[(long long)(b0 + cr) * d.lddh + cu];
-    if (d.arg) am = d.arg[(long long)(b0 + cr) * H + cu];
-  }
-  if (tid < RB * H && !cell) {
-    dgs[cr][cu] = 0.f; dgs[cr][H + cu] = 0.f; dgs[cr][2 * H + cu] = 0.f; dgs[cr][3 * H + cu] = 0.f;
-  }
-  for (int t = (Len ? ln.bound(T) : T) - 1; t >= 0; --t) {
-    if (cell && (!Len || t < ln.mine)) {
-      if (t < (Len ? ln.mine : T) - 1) {
-        dh = ((part[0][cr][cu] + part[1][cr][cu]) + part[2][cr][cu]) + part[3][cr][cu];
-        if (t == am) dh += gin;  // max-pooled embedding: its gradient joins the recurrent one at the argmax
-      } else {
-        dh = am == (Len ? ln.mine : T) - 1 ? gin : 0.f;
-      }
-      const long long go = ((long long)t * B + b0 + cr) * G + cu;
-      const float ig = d.gates[go], fg = d.gates[go + H], gg = d.gates[go + 2 * H], og = d.gates[go + 3 * H];
-      const long long co = ((long long)t * B + b0 + cr) * H + cu;
-      const float c = d.cs[co];
-      const float cp = t > 0 ? d.cs[co - (long long)B * H] : 0.f;
-      const float tc = tanhf(c);
-      const float dog = dh * tc;
-      const float dcc = dc + dh * og * (1.f - tc * tc);
-      const float dig = dcc * gg, dgg = dcc * ig, dfg = dcc * cp;
-      dc = dcc * fg;
-      const float ai = dig * ig * (1.f - ig), af = dfg * fg * (1.f - fg);
-      const float ag = dgg * (1.f - gg * gg), ao = dog * og * (1.f - og);
-      dgs[cr][cu] = ai; dgs[cr][H + cu] = af; dgs[cr][2 * H + cu] = ag; dgs[cr][3 * H + cu] = ao;
-      d.dgates[go] = ai; d.dgates[go + H] = af; d.dgates[go + 2 * H] = ag; d.dgates[go + 3 * H] = ao;
-    }
-    __syncthreads();
-    if (t > 0) {
-#pragma unroll
-      for (int r = 0; r < RB; ++r) {
-        if constexpr (Len) {
-          if (!ln.row_runs(r, t)) continue;  // workgroup-uniform: the row has not started yet
-        }
-        float a4[4] = {0.f, 0.f, 0.f, 0.f};  // interleaved partial sums, as in the forward
-#pragma unroll
-        for (int jj = 0; jj < H; jj += 4) {
-          const f32x4 dv = *reinterpret_cast<const f32x4*>(&dgs[r][q * H + jj]);
-#pragma unroll
-          for (int u = 0; u < 4; ++u) a4[u] = fmaf(dv[u], wc[jj + u], a4[u]);
-        }
-        part[q][r][k] = (a4[0] + a4[1]) + (a4[2] + a4[3]);
-      }
-    }
-    __syncthreads();
-  }
-  if constexpr (Len) {  // gate gradients past the row's length: zeros, so the weight-gradient GEMMs keep all T*B rows
-    if (cell) {
-      for (int t = ln.mine; t < T; ++t) {
-        const long long go = ((long long)t * B + b0 + cr) * G + cu;
-        d.dgates[go] = 0.f; d.dgates[go + H] = 0.f; d.dgates[go + 2 * H] = 0.f; d.dgates[go + 3 * H] = 0.f;
-      }
-    }
-  }
-}
-
-template <int H, int RB, typename Ix>
-__global__ __launch_bounds__(4 * H) void k_lstm_bwd(LstmBwdDescT<Ix> d0, LstmBwdDescT<Ix> d1, int nb0) {
-  if ((int)blockIdx.x < nb0)
-    lstm_bwd_body<H, RB, Ix>(d0, blockIdx.x);
-  else
-    lstm_bwd_body<H, RB, Ix>(d1, blockIdx.x - nb0);
-}
-
-// LSTM backward through time at a run-time width H on a tier of HP lanes per gate quarter (see k_lstm_fwd_w):
-// thread (q, k) keeps column k of the quarter-q rows of W_hh (zeros in a padded lane), the unrolled jj loop runs in
-// guarded chunks of kLstmChunk as the forward's k loop, padded lanes read and write no global memory, and only units < H are ever read back from LDS.
-template <int HP, int RB, typename Ix, bool Len = false>
-TSPM_DEV void lstm_bwd_w_body(const LstmBwdDescT<Ix>& d, const int H, int chunk,
-                              const int32_t* lens = nullptr) {
+// On HP lanes per gate quarter, with the forward's width policy: a padded lane (k >= H) keeps zeros for its column of
+// W_hh, the unrolled jj loop runs in guarded chunks of kLstmChunk as the forward's k loop, padded lanes read and write
+// no global memory, and only units < H are ever read back from LDS.  The step bounds are spelled with compile-time
+// ternaries on Len (not through LstmLens), which the front end folds before any pass sees them.
+template <int HP, int RB, typename Ix, bool Fixed, bool Len>
+TSPM_DEV void lstm_bwd_body(const LstmBwdDesc& d, const LstmExtra x, int chunk) {
+  const int H = Fixed ? HP : x.H;
+  const int32_t* lens = x.lens;
   constexpr int GP = 4 * HP;
   __shared__ __attribute__((aligned(16))) float dgs[RB][GP];
   __shared__ float part[4][RB][HP];
@@ -427,10 +262,10 @@ TSPM_DEV void lstm_bwd_w_body(const LstmBwdDescT<Ix>& d, const int H, int chunk,
   const bool cell = tid < RB * HP && live && b0 + cr < B;  // ghost rows and padded lanes compute zeros, write nothing
   float dc = 0.f, dh = 0.f, gin = 0.f;
   const LstmLens<RB, Len> ln(lens, b0, B, T, cr);
-  int am = (Len ? ln.mine : T) - 1;
+  int am = (Len ? ln.mine : T) - 1;  // the step whose h received the embedding gradient: the row's last step
   if (cell) {
     gin = d.dh[(long long)(b0 + cr) * d.lddh + cu];
-    if (d.arg) am = d.arg[(long long)(b0 + cr) * H + cu];
+    if (d.arg) am = static_cast<const Ix*>(d.arg)[(long long)(b0 + cr) * H + cu];
   }
   if (tid < RB * HP && !cell) {
     dgs[cr][cu] = 0.f; dgs[cr][HP + cu] = 0.f; dgs[cr][2 * HP + cu] = 0.f; dgs[cr][3 * HP + cu] = 0.f;
@@ -439,7 +274,7 @@ TSPM_DEV void lstm_bwd_w_body(const LstmBwdDescT<Ix>& d, const int H, int chunk,
     if (cell && (!Len || t < ln.mine)) {
       if (t < (Len ? ln.mine : T) - 1) {
         dh = ((part[0][cr][cu] + part[1][cr][cu]) + part[2][cr][cu]) + part[3][cr][cu];
-        if (t == am) dh += gin;
+        if (t == am) dh += gin;  // max-pooled embedding: its gradient joins the recurrent one at the argmax
       } else {
         dh = am == (Len ? ln.mine : T) - 1 ? gin : 0.f;
       }
@@ -463,9 +298,9 @@ TSPM_DEV void lstm_bwd_w_body(const LstmBwdDescT<Ix>& d, const int H, int chunk,
 #pragma unroll
       for (int r = 0; r < RB; ++r) {
         if constexpr (Len) {
-          if (!ln.row_runs(r, t)) continue;  // workgroup-uniform
+          if (!ln.row_runs(r, t)) continue;  // workgroup-uniform: the row has not started yet
         }
-        float a4[4] = {0.f, 0.f, 0.f, 0.f};
+        float a4[4] = {0.f, 0.f, 0.f, 0.f};  // interleaved partial sums, as in the forward
 #pragma unroll
         for (int j0 = 0; j0 < HP; j0 += kLstmChunk) {
           if (j0 < H) {  // wave-uniform: a chunk wholly past the width is skipped
@@ -482,7 +317,7 @@ TSPM_DEV void lstm_bwd_w_body(const LstmBwdDescT<Ix>& d, const int H, int chunk,
     }
     __syncthreads();
   }
-  if constexpr (Len) {
+  if constexpr (Len) {  // gate gradients past the row's length: zeros, so the weight-gradient GEMMs keep all T*B rows
     if (cell) {
       for (int t = ln.mine; t < T; ++t) {
         const long long go = ((long long)t * B + b0 + cr) * G + cu;
@@ -492,14 +327,13 @@ TSPM_DEV void lstm_bwd_w_body(const LstmBwdDescT<Ix>& d, const int H, int chunk,
   }
 }
 
-template <int HP, int RB, typename Ix>
-__global__ __launch_bounds__(4 * HP) void k_lstm_bwd_w(LstmBwdDescT<Ix> d0, int h0, LstmBwdDescT<Ix> d1, int h1,
-                                                       int nb0) {
+template <int HP, int RB, typename Ix, typename... X>
+__global__ __launch_bounds__(4 * HP) void k_lstm_bwd(LstmBwdDesc d0, X... x0, LstmBwdDesc d1, X... x1, int nb0) {
   static_assert(RB <= 4, "cell threads are the first RB gate quarters");
   if ((int)blockIdx.x < nb0)
-    lstm_bwd_w_body<HP, RB, Ix>(d0, h0, blockIdx.x);
+    lstm_bwd_body<HP, RB, Ix, kLstmFixed<X...>, kLstmLen<X...>>(d0, lstm_extra(x0...), blockIdx.x);
   else
-    lstm_bwd_w_body<HP, RB, Ix>(d1, h1, blockIdx.x - nb0);
+    lstm_bwd_body<HP, RB, Ix, kLstmFixed<X...>, kLstmLen<X...>>(d1, lstm_extra(x1...), blockIdx.x - nb0);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -746,254 +580,112 @@ int grid_for(long long work) {
   return (int)(b < 1 ? 1 : b);
 }
 
-template <int H, int RB, typename Ix>
-int launch_lstm_fwd(const LstmFwdDescT<Ix>& a, const LstmFwdDescT<Ix>* b, hipStream_t st) {
-  const int na = (a.B + RB - 1) / RB, nbb = b ? (b->B + RB - 1) / RB : 0;
-  hipLaunchKernelGGL((k_lstm_fwd<H, RB, Ix>), dim3(na + nbb), dim3(4 * H), 0, st, a, b ? *b : a, na);
-  TSPM_LAUNCH_CHECK();
-  return TSPM_OK;
-}
-
-template <int H, int RB, typename Ix>
-int launch_lstm_bwd(const LstmBwdDescT<Ix>& a, const LstmBwdDescT<Ix>* b, hipStream_t st) {
-  const int na = (a.B + RB - 1) / RB, nbb = b ? (b->B + RB - 1) / RB : 0;
-  hipLaunchKernelGGL((k_lstm_bwd<H, RB, Ix>), dim3(na + nbb), dim3(4 * H), 0, st, a, b ? *b : a, na);
-  TSPM_LAUNCH_CHECK();
-  return TSPM_OK;
-}
-
+// ------------------------------------------------------------------------------------------------
+// LSTM host path: each of the eight entry points fills one LstmProb per descriptor, validates it against the entry
+// point's rules and hands the problems to lstm_dispatch.
+// ------------------------------------------------------------------------------------------------
 constexpr int kLstmRB = 2;  // batch rows per workgroup (B = 128: 64 workgroups per LSTM)
 
-bool lstm_ok(int B, int T, int H, const void* p0, const void* p1, const void* p2, const void* p3) {
-  return B > 0 && T > 0 && H == 64 && p0 && p1 && p2 && p3;
-}
-
-// The run-time-width recurrences: 4 <= H <= 128, a multiple of 4 (float4 rows of W_hh; one gate column per thread, at
+// The widths of the recurrences: 4 <= H <= 128, a multiple of 4 (float4 rows of W_hh; one gate column per thread, at
 // most 512 threads with W_hh's row in registers).  kind: 0 = the compile-time 64-wide kernels, else the tier.
 bool lstm_width_ok(int H) { return H >= 4 && H <= 128 && (H & 3) == 0; }
 int lstm_kind(int H) { return H == 64 ? 0 : H <= 32 ? 32 : H <= 64 ? 64 : 128; }
 
-// The largest step count whose time index fits the index type: 256 steps (indices 0..255) in uint8_t, 65535 steps in
-// uint16_t (tspm.h states 1..65535; index 65535 is never produced).
-template <typename Ix> constexpr int kLstmIndexedSteps = sizeof(Ix) == 1 ? 256 : 65535;
-
-template <typename Ix>
-int launch_lstm_fwd_any(const LstmFwdDescT<Ix>& a, int ha, const LstmFwdDescT<Ix>* b, int hb, hipStream_t st) {
-  const int na = (a.B + kLstmRB - 1) / kLstmRB, nbb = b ? (b->B + kLstmRB - 1) / kLstmRB : 0;
-  const dim3 grid(na + nbb);
-  const LstmFwdDescT<Ix>& b_ = b ? *b : a;
-  switch (lstm_kind(ha)) {
-    case 0: return launch_lstm_fwd<64, kLstmRB, Ix>(a, b, st);
-    case 32: hipLaunchKernelGGL((k_lstm_fwd_w<32, kLstmRB, Ix>), grid, dim3(128), 0, st, a, ha, b_, hb, na); break;
-    case 64: hipLaunchKernelGGL((k_lstm_fwd_w<64, kLstmRB, Ix>), grid, dim3(256), 0, st, a, ha, b_, hb, na); break;
-    default: hipLaunchKernelGGL((k_lstm_fwd_w<128, kLstmRB, Ix>), grid, dim3(512), 0, st, a, ha, b_, hb, na); break;
-  }
-  TSPM_LAUNCH_CHECK();
-  return TSPM_OK;
-}
-
-template <typename Ix>
-int launch_lstm_bwd_any(const LstmBwdDescT<Ix>& a, int ha, const LstmBwdDescT<Ix>* b, int hb, hipStream_t st) {
-  const int na = (a.B + kLstmRB - 1) / kLstmRB, nbb = b ? (b->B + kLstmRB - 1) / kLstmRB : 0;
-  const dim3 grid(na + nbb);
-  const LstmBwdDescT<Ix>& b_ = b ? *b : a;
-  switch (lstm_kind(ha)) {
-    case 0: return launch_lstm_bwd<64, kLstmRB, Ix>(a, b, st);
-    case 32: hipLaunchKernelGGL((k_lstm_bwd_w<32, kLstmRB, Ix>), grid, dim3(128), 0, st, a, ha, b_, hb, na); break;
-    case 64: hipLaunchKernelGGL((k_lstm_bwd_w<64, kLstmRB, Ix>), grid, dim3(256), 0, st, a, ha, b_, hb, na); break;
-    default: hipLaunchKernelGGL((k_lstm_bwd_w<128, kLstmRB, Ix>), grid, dim3(512), 0, st, a, ha, b_, hb, na); break;
-  }
-  TSPM_LAUNCH_CHECK();
-  return TSPM_OK;
-}
-
-// Any hidden width (4 <= hidden <= 128, a multiple of 4), each descriptor its own: two LSTMs of one kernel kind share a
-// launch, two of different kinds take one launch each (a workgroup's arithmetic does not depend on its neighbours, so
-// either way the results are those of two count-1 calls).  Everything is validated before the first launch.  Ix is the
-// type the descriptors' argmax field points to (tspm.h declares it uint8_t*; the _t16 entry points document the cast).
-template <typename Ix>
-int lstm_fwd_any_width(int32_t count, const tspm_lstm_fwd_desc* descs, tspm_stream_t stream) {
-  if (count < 1 || count > 2 || !descs) return TSPM_ERR_INVALID;
-  LstmFwdDescT<Ix> d[2];
-  int hw[2] = {0, 0};
-  for (int i = 0; i < count; ++i) {
-    const tspm_lstm_fwd_desc& s = descs[i];
-    if (s.batch <= 0 || s.steps <= 0 || !lstm_width_ok(s.hidden) || !s.xg || !s.w_hh || !s.gates || !s.cs || !s.hs ||
-        !s.h_out || s.ld_out < s.hidden)
-      return TSPM_ERR_INVALID;
-    if (reinterpret_cast<uintptr_t>(s.w_hh) & 15) return TSPM_ERR_INVALID;
-    if (s.steps > kLstmIndexedSteps<Ix> && s.argmax) return TSPM_ERR_INVALID;  // the time index must fit Ix
-    if (reinterpret_cast<uintptr_t>(s.argmax) & (sizeof(Ix) - 1)) return TSPM_ERR_INVALID;
-    d[i] = LstmFwdDescT<Ix>{s.batch, s.steps, s.xg, s.w_hh, s.b_hh, s.gates, s.cs, s.hs, s.h_out, s.ld_out,
-                            reinterpret_cast<Ix*>(s.argmax)};
-    hw[i] = s.hidden;
-  }
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  if (count == 1 || lstm_kind(hw[0]) == lstm_kind(hw[1]))
-    return launch_lstm_fwd_any<Ix>(d[0], hw[0], count > 1 ? &d[1] : nullptr, hw[1], st);
-  const int rc = launch_lstm_fwd_any<Ix>(d[0], hw[0], nullptr, 0, st);
-  return rc != TSPM_OK ? rc : launch_lstm_fwd_any<Ix>(d[1], hw[1], nullptr, 0, st);
-}
-
-template <typename Ix>
-int lstm_bwd_any_width(int32_t count, const tspm_lstm_bwd_desc* descs, tspm_stream_t stream) {
-  if (count < 1 || count > 2 || !descs) return TSPM_ERR_INVALID;
-  LstmBwdDescT<Ix> d[2];
-  int hw[2] = {0, 0};
-  for (int i = 0; i < count; ++i) {
-    const tspm_lstm_bwd_desc& s = descs[i];
-    if (s.batch <= 0 || s.steps <= 0 || !lstm_width_ok(s.hidden) || !s.w_hh || !s.gates || !s.cs || !s.dh ||
-        !s.dgates || s.ld_dh < s.hidden)
-      return TSPM_ERR_INVALID;
-    if (s.steps > kLstmIndexedSteps<Ix> && s.argmax) return TSPM_ERR_INVALID;
-    if (reinterpret_cast<uintptr_t>(s.argmax) & (sizeof(Ix) - 1)) return TSPM_ERR_INVALID;
-    d[i] = LstmBwdDescT<Ix>{s.batch, s.steps, s.w_hh, s.gates, s.cs, s.dh, s.ld_dh, s.dgates,
-                            reinterpret_cast<const Ix*>(s.argmax)};
-    hw[i] = s.hidden;
-  }
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  if (count == 1 || lstm_kind(hw[0]) == lstm_kind(hw[1]))
-    return launch_lstm_bwd_any<Ix>(d[0], hw[0], count > 1 ? &d[1] : nullptr, hw[1], st);
-  const int rc = launch_lstm_bwd_any<Ix>(d[0], hw[0], nullptr, 0, st);
-  return rc != TSPM_OK ? rc : launch_lstm_bwd_any<Ix>(d[1], hw[1], nullptr, 0, st);
-}
-
-// ------------------------------------------------------------------------------------------------
-// Per-sample lengths: the same bodies instantiated with Len = true (beside the instantiations above, whose code does not
-// change), each descriptor with its own `lengths` [batch] in device memory.  The host never reads the lengths: a row's
-// length is clamped to 1..steps in the kernel, so no value moves an access outside the buffers.
-// ------------------------------------------------------------------------------------------------
-template <int H, int RB, typename Ix>
-__global__ __launch_bounds__(4 * H) void k_lstm_fwd_len(LstmFwdDescT<Ix> d0, const int32_t* l0, LstmFwdDescT<Ix> d1,
-                                                        const int32_t* l1, int nb0) {
-  if ((int)blockIdx.x < nb0)
-    lstm_fwd_body<H, RB, Ix, true>(d0, blockIdx.x, l0);
-  else
-    lstm_fwd_body<H, RB, Ix, true>(d1, blockIdx.x - nb0, l1);
-}
-
-template <int HP, int RB, typename Ix>
-__global__ __launch_bounds__(4 * HP) void k_lstm_fwd_w_len(LstmFwdDescT<Ix> d0, int h0, const int32_t* l0,
-                                                           LstmFwdDescT<Ix> d1, int h1, const int32_t* l1, int nb0) {
-  static_assert(RB <= 4, "cell threads are the first RB gate blocks");
-  if ((int)blockIdx.x < nb0)
-    lstm_fwd_w_body<HP, RB, Ix, true>(d0, h0, blockIdx.x, l0);
-  else
-    lstm_fwd_w_body<HP, RB, Ix, true>(d1, h1, blockIdx.x - nb0, l1);
-}
-
-template <int H, int RB, typename Ix>
-__global__ __launch_bounds__(4 * H) void k_lstm_bwd_len(LstmBwdDescT<Ix> d0, const int32_t* l0, LstmBwdDescT<Ix> d1,
-                                                        const int32_t* l1, int nb0) {
-  if ((int)blockIdx.x < nb0)
-    lstm_bwd_body<H, RB, Ix, true>(d0, blockIdx.x, l0);
-  else
-    lstm_bwd_body<H, RB, Ix, true>(d1, blockIdx.x - nb0, l1);
-}
-
-template <int HP, int RB, typename Ix>
-__global__ __launch_bounds__(4 * HP) void k_lstm_bwd_w_len(LstmBwdDescT<Ix> d0, int h0, const int32_t* l0,
-                                                           LstmBwdDescT<Ix> d1, int h1, const int32_t* l1, int nb0) {
-  static_assert(RB <= 4, "cell threads are the first RB gate quarters");
-  if ((int)blockIdx.x < nb0)
-    lstm_bwd_w_body<HP, RB, Ix, true>(d0, h0, blockIdx.x, l0);
-  else
-    lstm_bwd_w_body<HP, RB, Ix, true>(d1, h1, blockIdx.x - nb0, l1);
-}
-
-// One validated problem of a _len call: the index pointer untyped (index_bits picks its type at the launch).
-struct LenFwd {
-  LstmFwdDescT<uint8_t> d;
-  int H, bits;  // bits: 8 / 16, or 0 when there is no index (either instantiation serves)
-  const int32_t* lens;
-};
-struct LenBwd {
-  LstmBwdDescT<uint8_t> d;
+// One problem of a call: the descriptor (index pointer untyped), the hidden width, the lengths or null (which picks
+// the Len kernels), and the width of the time index — 8 or 16 as the entry point (or a _len descriptor's index_bits)
+// says, 0 for a _len problem without an index, which either instantiation serves.
+template <typename Desc>
+struct LstmProb {
+  Desc d;
   int H, bits;
   const int32_t* lens;
 };
+using LstmFwdProb = LstmProb<LstmFwdDesc>;
+using LstmBwdProb = LstmProb<LstmBwdDesc>;
 
-template <typename Ix>
-LstmFwdDescT<Ix> len_desc(const LenFwd& p) {
-  return LstmFwdDescT<Ix>{p.d.B, p.d.T, p.d.xg, p.d.whh, p.d.bhh, p.d.gates, p.d.cs, p.d.hs, p.d.hout, p.d.ldh,
-                          reinterpret_cast<Ix*>(p.d.arg)};
+// tspm_lstm_fwd_desc / _fwd_len_desc and the two backward descriptors agree on these fields.
+template <typename S>
+LstmFwdProb lstm_fwd_prob(const S& s, int bits, const int32_t* lens) {
+  return {{s.batch, s.steps, s.xg, s.w_hh, s.b_hh, s.gates, s.cs, s.hs, s.h_out, s.ld_out, s.argmax}, s.hidden, bits, lens};
 }
-template <typename Ix>
-LstmBwdDescT<Ix> len_desc(const LenBwd& p) {
-  return LstmBwdDescT<Ix>{p.d.B, p.d.T, p.d.whh, p.d.gates, p.d.cs, p.d.dh, p.d.lddh, p.d.dgates,
-                          reinterpret_cast<const Ix*>(p.d.arg)};
+template <typename S>
+LstmBwdProb lstm_bwd_prob(const S& s, int bits, const int32_t* lens) {
+  return {{s.batch, s.steps, s.w_hh, s.gates, s.cs, s.dh, s.ld_dh, s.dgates, s.argmax}, s.hidden, bits, lens};
 }
 
-template <typename Ix>
-int launch_lstm_fwd_len(const LenFwd& a, const LenFwd* b, hipStream_t st) {
-  const int na = (a.d.B + kLstmRB - 1) / kLstmRB, nbb = b ? (b->d.B + kLstmRB - 1) / kLstmRB : 0;
+// What differs between the entry points: tspm_lstm_fwd / _bwd take width 64 only, the _len pair needs lengths.  The
+// index width is in the problem (8: at most 256 steps with an index; 16: at most 65535, indices 0..65534, and a
+// 2-byte aligned buffer); without an index steps is unlimited and bits is not looked at.
+struct LstmRules {
+  bool any_width, lens;
+};
+
+bool lstm_shape_ok(int B, int T, int H, int ld, const void* arg, int bits, const int32_t* lens, LstmRules r) {
+  if (B <= 0 || T <= 0 || ld < H || (r.any_width ? !lstm_width_ok(H) : H != 64) || (r.lens && !lens)) return false;
+  if (!arg) return true;
+  if (bits == 8) return T <= 256;
+  return bits == 16 && T <= 65535 && !(reinterpret_cast<uintptr_t>(arg) & 1);
+}
+bool lstm_valid(const LstmFwdProb& p, LstmRules r) {  // the forward reads W_hh's rows as float4
+  const LstmFwdDesc& d = p.d;
+  return lstm_shape_ok(d.B, d.T, p.H, d.ldh, d.arg, p.bits, p.lens, r) && d.xg && d.whh && d.gates && d.cs && d.hs &&
+         d.hout && !(reinterpret_cast<uintptr_t>(d.whh) & 15);
+}
+bool lstm_valid(const LstmBwdProb& p, LstmRules r) {
+  const LstmBwdDesc& d = p.d;
+  return lstm_shape_ok(d.B, d.T, p.H, d.lddh, d.arg, p.bits, p.lens, r) && d.whh && d.gates && d.cs && d.dh && d.dgates;
+}
+
+// The one place that names the kernels: X is the kernel's pack of per-problem extras, A the arguments after d0.
+template <int HP, typename Ix, typename... X, typename... A>
+void lstm_kernel(dim3 grid, hipStream_t st, const LstmFwdDesc& d0, A... rest) {
+  hipLaunchKernelGGL((k_lstm_fwd<HP, kLstmRB, Ix, X...>), grid, dim3(4 * HP), 0, st, d0, rest...);
+}
+template <int HP, typename Ix, typename... X, typename... A>
+void lstm_kernel(dim3 grid, hipStream_t st, const LstmBwdDesc& d0, A... rest) {
+  hipLaunchKernelGGL((k_lstm_bwd<HP, kLstmRB, Ix, X...>), grid, dim3(4 * HP), 0, st, d0, rest...);
+}
+
+template <int HP, bool Fixed, typename Ix, bool Len, typename Desc>
+int lstm_launch(const LstmProb<Desc>& a, const LstmProb<Desc>* b, hipStream_t st) {
+  const int na = cdiv(a.d.B, kLstmRB), nbb = b ? cdiv(b->d.B, kLstmRB) : 0;
   const dim3 grid(na + nbb);
-  const LenFwd& b_ = b ? *b : a;
-  const LstmFwdDescT<Ix> da = len_desc<Ix>(a), db = len_desc<Ix>(b_);
-  switch (lstm_kind(a.H)) {
-    case 0:
-      hipLaunchKernelGGL((k_lstm_fwd_len<64, kLstmRB, Ix>), grid, dim3(256), 0, st, da, a.lens, db, b_.lens, na);
-      break;
-    case 32:
-      hipLaunchKernelGGL((k_lstm_fwd_w_len<32, kLstmRB, Ix>), grid, dim3(128), 0, st, da, a.H, a.lens, db, b_.H,
-                         b_.lens, na);
-      break;
-    case 64:
-      hipLaunchKernelGGL((k_lstm_fwd_w_len<64, kLstmRB, Ix>), grid, dim3(256), 0, st, da, a.H, a.lens, db, b_.H,
-                         b_.lens, na);
-      break;
-    default:
-      hipLaunchKernelGGL((k_lstm_fwd_w_len<128, kLstmRB, Ix>), grid, dim3(512), 0, st, da, a.H, a.lens, db, b_.H,
-                         b_.lens, na);
-      break;
-  }
+  const LstmProb<Desc>& b_ = b ? *b : a;
+  if constexpr (Fixed && !Len)
+    lstm_kernel<HP, Ix>(grid, st, a.d, b_.d, na);
+  else if constexpr (Fixed)
+    lstm_kernel<HP, Ix, const int32_t*>(grid, st, a.d, a.lens, b_.d, b_.lens, na);
+  else if constexpr (!Len)
+    lstm_kernel<HP, Ix, int>(grid, st, a.d, a.H, b_.d, b_.H, na);
+  else
+    lstm_kernel<HP, Ix, int, const int32_t*>(grid, st, a.d, a.H, a.lens, b_.d, b_.H, b_.lens, na);
   TSPM_LAUNCH_CHECK();
   return TSPM_OK;
 }
 
-template <typename Ix>
-int launch_lstm_bwd_len(const LenBwd& a, const LenBwd* b, hipStream_t st) {
-  const int na = (a.d.B + kLstmRB - 1) / kLstmRB, nbb = b ? (b->d.B + kLstmRB - 1) / kLstmRB : 0;
-  const dim3 grid(na + nbb);
-  const LenBwd& b_ = b ? *b : a;
-  const LstmBwdDescT<Ix> da = len_desc<Ix>(a), db = len_desc<Ix>(b_);
+// One launch of one kernel kind (a's; b, if any, is of the same kind): width 64 on the compile-time kernels, every
+// other width on its tier.
+template <typename Ix, bool Len, typename Desc>
+int lstm_launch_kind(const LstmProb<Desc>& a, const LstmProb<Desc>* b, hipStream_t st) {
   switch (lstm_kind(a.H)) {
-    case 0:
-      hipLaunchKernelGGL((k_lstm_bwd_len<64, kLstmRB, Ix>), grid, dim3(256), 0, st, da, a.lens, db, b_.lens, na);
-      break;
-    case 32:
-      hipLaunchKernelGGL((k_lstm_bwd_w_len<32, kLstmRB, Ix>), grid, dim3(128), 0, st, da, a.H, a.lens, db, b_.H,
-                         b_.lens, na);
-      break;
-    case 64:
-      hipLaunchKernelGGL((k_lstm_bwd_w_len<64, kLstmRB, Ix>), grid, dim3(256), 0, st, da, a.H, a.lens, db, b_.H,
-                         b_.lens, na);
-      break;
-    default:
-      hipLaunchKernelGGL((k_lstm_bwd_w_len<128, kLstmRB, Ix>), grid, dim3(512), 0, st, da, a.H, a.lens, db, b_.H,
-                         b_.lens, na);
-      break;
+    case 0: return lstm_launch<64, true, Ix, Len>(a, b, st);
+    case 32: return lstm_launch<32, false, Ix, Len>(a, b, st);
+    case 64: return lstm_launch<64, false, Ix, Len>(a, b, st);
+    default: return lstm_launch<128, false, Ix, Len>(a, b, st);
   }
-  TSPM_LAUNCH_CHECK();
-  return TSPM_OK;
 }
 
-// The index checks of one _len descriptor → bits (0 without an index), or -1 when the descriptor is invalid.
-int len_index_bits(const void* argmax, int index_bits, int steps) {
-  if (!argmax) return 0;
-  if (index_bits == 8) return steps <= kLstmIndexedSteps<uint8_t> ? 8 : -1;
-  if (index_bits == 16)
-    return steps <= kLstmIndexedSteps<uint16_t> && !(reinterpret_cast<uintptr_t>(argmax) & 1) ? 16 : -1;
-  return -1;
-}
-
-// Two problems share a launch when they are of one kernel kind and their index widths agree (a problem without an index
-// goes with either); otherwise one launch each.  Rows of one workgroup never meet another's, so the results are the same.
-template <typename P, typename F8, typename F16>
-int len_dispatch(int count, const P* p, hipStream_t st, F8 run8, F16 run16) {
-  auto run = [&](const P& a, const P* b) {
-    const int bits = a.bits ? a.bits : (b ? b->bits : 0);
-    return bits == 16 ? run16(a, b, st) : run8(a, b, st);
+// Validated problems to launches.  Two problems share a launch when they are of one kernel kind and their index widths
+// agree (a problem without an index width goes with either, and alone takes the 8-bit kernels); otherwise one launch
+// each.  A workgroup's arithmetic does not depend on its neighbours, so either way the results are those of two
+// count-1 calls.  All problems of a call have lengths or none has.
+template <typename Desc>
+int lstm_dispatch(int count, const LstmProb<Desc>* p, tspm_stream_t stream) {
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  auto run = [&](const LstmProb<Desc>& a, const LstmProb<Desc>* b) {
+    const bool wide = (a.bits ? a.bits : (b ? b->bits : 0)) == 16;
+    if (a.lens) return wide ? lstm_launch_kind<uint16_t, true>(a, b, st) : lstm_launch_kind<uint8_t, true>(a, b, st);
+    return wide ? lstm_launch_kind<uint16_t, false>(a, b, st) : lstm_launch_kind<uint8_t, false>(a, b, st);
   };
   const bool together = count == 2 && lstm_kind(p[0].H) == lstm_kind(p[1].H) &&
                         (p[0].bits == p[1].bits || !p[0].bits || !p[1].bits);
@@ -1002,87 +694,65 @@ int len_dispatch(int count, const P* p, hipStream_t st, F8 run8, F16 run16) {
   return rc != TSPM_OK ? rc : run(p[1], nullptr);
 }
 
+// An entry point: every descriptor filled and validated before the first launch.
+template <typename Desc, typename S, typename Fill>
+int lstm_entry(int32_t count, const S* descs, tspm_stream_t stream, LstmRules rules, Fill fill) {
+  if (count < 1 || count > 2 || !descs) return TSPM_ERR_INVALID;
+  LstmProb<Desc> p[2];
+  for (int i = 0; i < count; ++i) {
+    p[i] = fill(descs[i]);
+    if (!lstm_valid(p[i], rules)) return TSPM_ERR_INVALID;
+  }
+  return lstm_dispatch(count, p, stream);
+}
+
+constexpr LstmRules kRules64{false, false}, kRulesAnyWidth{true, false}, kRulesLen{true, true};
+
 }  // namespace
 
-extern "C" int tspm_lstm_fwd_len(int32_t count, const tspm_lstm_fwd_len_desc* descs, tspm_stream_t stream) {
-  if (count < 1 || count > 2 || !descs) return TSPM_ERR_INVALID;
-  LenFwd p[2];
-  for (int i = 0; i < count; ++i) {
-    const tspm_lstm_fwd_len_desc& s = descs[i];
-    if (s.batch <= 0 || s.steps <= 0 || !lstm_width_ok(s.hidden) || !s.xg || !s.w_hh || !s.gates || !s.cs || !s.hs ||
-        !s.h_out || s.ld_out < s.hidden || !s.lengths)
-      return TSPM_ERR_INVALID;
-    if (reinterpret_cast<uintptr_t>(s.w_hh) & 15) return TSPM_ERR_INVALID;
-    const int bits = len_index_bits(s.argmax, s.index_bits, s.steps);
-    if (bits < 0) return TSPM_ERR_INVALID;
-    p[i] = LenFwd{LstmFwdDesc{s.batch, s.steps, s.xg, s.w_hh, s.b_hh, s.gates, s.cs, s.hs, s.h_out, s.ld_out,
-                              static_cast<uint8_t*>(s.argmax)},
-                  s.hidden, bits, s.lengths};
-  }
-  return len_dispatch(count, p, static_cast<hipStream_t>(stream), launch_lstm_fwd_len<uint8_t>,
-                      launch_lstm_fwd_len<uint16_t>);
-}
-
-extern "C" int tspm_lstm_bwd_len(int32_t count, const tspm_lstm_bwd_len_desc* descs, tspm_stream_t stream) {
-  if (count < 1 || count > 2 || !descs) return TSPM_ERR_INVALID;
-  LenBwd p[2];
-  for (int i = 0; i < count; ++i) {
-    const tspm_lstm_bwd_len_desc& s = descs[i];
-    if (s.batch <= 0 || s.steps <= 0 || !lstm_width_ok(s.hidden) || !s.w_hh || !s.gates || !s.cs || !s.dh ||
-        !s.dgates || s.ld_dh < s.hidden || !s.lengths)
-      return TSPM_ERR_INVALID;
-    const int bits = len_index_bits(s.argmax, s.index_bits, s.steps);
-    if (bits < 0) return TSPM_ERR_INVALID;
-    p[i] = LenBwd{LstmBwdDesc{s.batch, s.steps, s.w_hh, s.gates, s.cs, s.dh, s.ld_dh, s.dgates,
-                              static_cast<const uint8_t*>(s.argmax)},
-                  s.hidden, bits, s.lengths};
-  }
-  return len_dispatch(count, p, static_cast<hipStream_t>(stream), launch_lstm_bwd_len<uint8_t>,
-                      launch_lstm_bwd_len<uint16_t>);
-}
-
 extern "C" int tspm_lstm_fwd(int32_t count, const tspm_lstm_fwd_desc* descs, tspm_stream_t stream) {
-  if (count < 1 || count > 2 || !descs) return TSPM_ERR_INVALID;
-  LstmFwdDesc d[2];
-  for (int i = 0; i < count; ++i) {
-    const tspm_lstm_fwd_desc& s = descs[i];
-    if (!lstm_ok(s.batch, s.steps, s.hidden, s.xg, s.w_hh, s.gates, s.cs) || !s.hs || !s.h_out || s.ld_out < s.hidden)
-      return TSPM_ERR_INVALID;
-    if (reinterpret_cast<uintptr_t>(s.w_hh) & 15) return TSPM_ERR_INVALID;
-    if (s.steps > 256 && s.argmax) return TSPM_ERR_INVALID;  // uint8 time index
-    d[i] = LstmFwdDesc{s.batch, s.steps, s.xg, s.w_hh, s.b_hh, s.gates, s.cs, s.hs, s.h_out, s.ld_out, s.argmax};
-  }
-  return launch_lstm_fwd<64, kLstmRB, uint8_t>(d[0], count > 1 ? &d[1] : nullptr, static_cast<hipStream_t>(stream));
+  return lstm_entry<LstmFwdDesc>(count, descs, stream, kRules64,
+                                 [](const tspm_lstm_fwd_desc& s) { return lstm_fwd_prob(s, 8, nullptr); });
 }
 
 extern "C" int tspm_lstm_bwd(int32_t count, const tspm_lstm_bwd_desc* descs, tspm_stream_t stream) {
-  if (count < 1 || count > 2 || !descs) return TSPM_ERR_INVALID;
-  LstmBwdDesc d[2];
-  for (int i = 0; i < count; ++i) {
-    const tspm_lstm_bwd_desc& s = descs[i];
-    if (!lstm_ok(s.batch, s.steps, s.hidden, s.w_hh, s.gates, s.cs, s.dh) || !s.dgates || s.ld_dh < s.hidden)
-      return TSPM_ERR_INVALID;
-    if (s.steps > 256 && s.argmax) return TSPM_ERR_INVALID;
-    d[i] = LstmBwdDesc{s.batch, s.steps, s.w_hh, s.gates, s.cs, s.dh, s.ld_dh, s.dgates, s.argmax};
-  }
-  return launch_lstm_bwd<64, kLstmRB, uint8_t>(d[0], count > 1 ? &d[1] : nullptr, static_cast<hipStream_t>(stream));
+  return lstm_entry<LstmBwdDesc>(count, descs, stream, kRules64,
+                                 [](const tspm_lstm_bwd_desc& s) { return lstm_bwd_prob(s, 8, nullptr); });
 }
 
 extern "C" int tspm_lstm_fwd_w(int32_t count, const tspm_lstm_fwd_desc* descs, tspm_stream_t stream) {
-  return lstm_fwd_any_width<uint8_t>(count, descs, stream);
+  return lstm_entry<LstmFwdDesc>(count, descs, stream, kRulesAnyWidth,
+                                 [](const tspm_lstm_fwd_desc& s) { return lstm_fwd_prob(s, 8, nullptr); });
 }
 
 extern "C" int tspm_lstm_bwd_w(int32_t count, const tspm_lstm_bwd_desc* descs, tspm_stream_t stream) {
-  return lstm_bwd_any_width<uint8_t>(count, descs, stream);
+  return lstm_entry<LstmBwdDesc>(count, descs, stream, kRulesAnyWidth,
+                                 [](const tspm_lstm_bwd_desc& s) { return lstm_bwd_prob(s, 8, nullptr); });
 }
 
 // The same launches with a 16-bit time index: argmax points to uint16_t [batch][hidden], 1 <= steps <= 65535 with it.
 extern "C" int tspm_lstm_fwd_t16(int32_t count, const tspm_lstm_fwd_desc* descs, tspm_stream_t stream) {
-  return lstm_fwd_any_width<uint16_t>(count, descs, stream);
+  return lstm_entry<LstmFwdDesc>(count, descs, stream, kRulesAnyWidth,
+                                 [](const tspm_lstm_fwd_desc& s) { return lstm_fwd_prob(s, 16, nullptr); });
 }
 
 extern "C" int tspm_lstm_bwd_t16(int32_t count, const tspm_lstm_bwd_desc* descs, tspm_stream_t stream) {
-  return lstm_bwd_any_width<uint16_t>(count, descs, stream);
+  return lstm_entry<LstmBwdDesc>(count, descs, stream, kRulesAnyWidth,
+                                 [](const tspm_lstm_bwd_desc& s) { return lstm_bwd_prob(s, 16, nullptr); });
+}
+
+// Per-sample lengths: each descriptor with its own `lengths` [batch] in device memory.  The host never reads them: a
+// row's length is clamped to 1..steps in the kernel, so no value moves an access outside the buffers.
+extern "C" int tspm_lstm_fwd_len(int32_t count, const tspm_lstm_fwd_len_desc* descs, tspm_stream_t stream) {
+  return lstm_entry<LstmFwdDesc>(count, descs, stream, kRulesLen, [](const tspm_lstm_fwd_len_desc& s) {
+    return lstm_fwd_prob(s, s.argmax ? s.index_bits : 0, s.lengths);
+  });
+}
+
+extern "C" int tspm_lstm_bwd_len(int32_t count, const tspm_lstm_bwd_len_desc* descs, tspm_stream_t stream) {
+  return lstm_entry<LstmBwdDesc>(count, descs, stream, kRulesLen, [](const tspm_lstm_bwd_len_desc& s) {
+    return lstm_bwd_prob(s, s.argmax ? s.index_bits : 0, s.lengths);
+  });
 }
 
 extern "C" int tspm_textcnn_pool_fwd(int32_t batch, int32_t steps, int32_t nconv, const int32_t* heights,

@@ -352,6 +352,32 @@ def _len_desc(d, lengths: torch.Tensor, wide: bool) -> None:
     d.lengths, d.index_bits = lengths.data_ptr(), 16 if wide else 8
 
 
+def _lstm_fwd_launch(probs, B: int, sh: int, wide: bool) -> None:
+    """The input projections and ONE forward recurrence call: per LSTM (encoder, input, buffers, T, h_out pointer,
+    ld_out, length buffer or None); with length buffers (all or none) tspm_lstm_fwd_len, else ``L.lstm_fwd`` picks."""
+    ragged = probs[0][6] is not None
+    descs = ((L.LstmFwdLenDesc if ragged else L.LstmFwdDesc) * len(probs))()
+    for i, (enc, x, bufs, T, h_out, ld_out, lens) in enumerate(probs):
+        _lstm_fwd_prepare(descs[i], enc, x, bufs, B, T, h_out, ld_out, sh)
+        if ragged:
+            _len_desc(descs[i], lens, wide)
+    rc = L.lstm_fwd_len(len(probs), descs, sh) if ragged else L.lstm_fwd(len(probs), descs, sh, wide)
+    L.check(rc, "lstm_fwd_len" if ragged else "lstm_fwd")
+
+
+def _lstm_bwd_launch(probs, B: int, sh: int, wide: bool) -> None:
+    """ONE backward-through-time call: per LSTM (encoder, buffers, T, dh pointer, ld_dh, length buffer or None).  With
+    lengths, dgates past each row's length are written as zeros: the weight-gradient GEMMs keep all T*B rows."""
+    ragged = probs[0][5] is not None
+    descs = ((L.LstmBwdLenDesc if ragged else L.LstmBwdDesc) * len(probs))()
+    for i, (enc, bufs, T, dh, ld_dh, lens) in enumerate(probs):
+        _lstm_bwd_desc(descs[i], enc, bufs, B, T, dh, ld_dh)
+        if ragged:
+            _len_desc(descs[i], lens, wide)
+    rc = L.lstm_bwd_len(len(probs), descs, sh) if ragged else L.lstm_bwd(len(probs), descs, sh, wide)
+    L.check(rc, "lstm_bwd_len" if ragged else "lstm_bwd")
+
+
 def _lstm_wgrad(enc: "LSTMEncoder", x: torch.Tensor, bufs, B: int, T: int, split: int,
                 wg_ws: torch.Tensor, g, sh: int) -> None:
     """The LSTM weight gradients as GEMMs over the T*B rows of dgates (after tspm_lstm_bwd)."""
@@ -630,16 +656,11 @@ class MosiEngine:
         lib, m = L.lib(), self.m
         B, (Ta, Tv, _) = self.B, self.Ts
         # LSTM input projections over each encoder's T_m*B rows, then both recurrences in one launch
-        descs = ((L.LstmFwdLenDesc if self.ragged else L.LstmFwdDesc) * 2)()
-        for i, (name, enc, x, col, T_m) in enumerate((("a", m.netA, self.A, 0, Ta),
-                                                      ("v", m.netV, self.V, m.netA.hidden_size, Tv))):
-            _lstm_fwd_prepare(descs[i], enc, x, self.lstm[name], B, T_m, self.fused.data_ptr() + col * 4, self.E, sh)
-            if self.ragged:
-                _len_desc(descs[i], self.lens[name], self.wide)
-        if self.ragged:
-            L.check(L.lstm_fwd_len(2, descs, sh), "lstm_fwd_len")
-            return
-        L.check(L.lstm_fwd(2, descs, sh, self.wide), "lstm_fwd")
+        _lstm_fwd_launch([(enc, x, self.lstm[name], T_m, self.fused.data_ptr() + col * 4, self.E,
+                           self.lens[name] if self.ragged else None)
+                          for name, enc, x, col, T_m in (("a", m.netA, self.A, 0, Ta),
+                                                         ("v", m.netV, self.V, m.netA.hidden_size, Tv))],
+                         B, sh, self.wide)
 
     def _forward_text(self, sh: int, train: bool) -> None:
         m, t = self.m, self.m.netT
@@ -769,15 +790,10 @@ class MosiEngine:
         lib, m, g = L.lib(), self.m, self.grad_of
         B, (Ta, Tv, _) = self.B, self.Ts
         # LSTMs: backward through time (one launch for both), then the weight gradients as GEMMs over T_m*B rows
-        descs = ((L.LstmBwdLenDesc if self.ragged else L.LstmBwdDesc) * 2)()
-        for i, (name, enc, col, T_m) in enumerate((("a", m.netA, 0, Ta), ("v", m.netV, m.netA.hidden_size, Tv))):
-            _lstm_bwd_desc(descs[i], enc, self.lstm[name], B, T_m, self.dfused.data_ptr() + col * 4, self.E)
-            if self.ragged:
-                _len_desc(descs[i], self.lens[name], self.wide)
-        if self.ragged:  # dgates past each row's length are written as zeros: the GEMMs below keep all T_m*B rows
-            L.check(L.lstm_bwd_len(2, descs, sh), "lstm_bwd_len")
-        else:
-            L.check(L.lstm_bwd(2, descs, sh, self.wide), "lstm_bwd")
+        _lstm_bwd_launch([(enc, self.lstm[name], T_m, self.dfused.data_ptr() + col * 4, self.E,
+                           self.lens[name] if self.ragged else None)
+                          for name, enc, col, T_m in (("a", m.netA, 0, Ta), ("v", m.netV, m.netA.hidden_size, Tv))],
+                         B, sh, self.wide)
         for name, enc, x, T_m in (("a", m.netA, self.A, Ta), ("v", m.netV, self.V, Tv)):
             _lstm_wgrad(enc, x, self.lstm[name], B, T_m, self.wg_splits[name], self.wg_ws, g, sh)
 
@@ -874,13 +890,8 @@ class MosiEncoderEngine:
         if self.is_text:
             _text_forward(self, self.enc, sh, self._keep_mask(train, sh), self.emb.data_ptr(), self.hidden)
             return
-        d = ((L.LstmFwdLenDesc if self.ragged else L.LstmFwdDesc) * 1)()
-        _lstm_fwd_prepare(d[0], self.enc, self.X, self.bufs, B, T, self.emb.data_ptr(), self.hidden, sh)
-        if self.ragged:
-            _len_desc(d[0], self.lens, self.wide)
-            L.check(L.lstm_fwd_len(1, d, sh), "lstm_fwd_len")
-            return
-        L.check(L.lstm_fwd(1, d, sh, self.wide), "lstm_fwd")
+        _lstm_fwd_launch([(self.enc, self.X, self.bufs, T, self.emb.data_ptr(), self.hidden, self.lens)], B, sh,
+                         self.wide)
 
     def backward(self, sh: int) -> None:
         """From ``demb`` (modified in place by the TextCNN's ReLU mask) to every parameter gradient."""
@@ -890,13 +901,7 @@ class MosiEncoderEngine:
             _text_backward(self, self.enc, sh, keep, self.demb.data_ptr(), self.hidden, self.emb.data_ptr(),
                            self.hidden, self.grad_of)
             return
-        d = ((L.LstmBwdLenDesc if self.ragged else L.LstmBwdDesc) * 1)()
-        _lstm_bwd_desc(d[0], self.enc, self.bufs, B, T, self.demb.data_ptr(), self.hidden)
-        if self.ragged:
-            _len_desc(d[0], self.lens, self.wide)
-            L.check(L.lstm_bwd_len(1, d, sh), "lstm_bwd_len")
-        else:
-            L.check(L.lstm_bwd(1, d, sh, self.wide), "lstm_bwd")
+        _lstm_bwd_launch([(self.enc, self.bufs, T, self.demb.data_ptr(), self.hidden, self.lens)], B, sh, self.wide)
         _lstm_wgrad(self.enc, self.X, self.bufs, B, T, self.wg_split, self.wg_ws, self.grad_of, sh)
 
 
@@ -1379,15 +1384,10 @@ def _encode_lstm(enc: LSTMEncoder, x: torch.Tensor, lengths: Optional[torch.Tens
     xt = x.transpose(0, 1).contiguous() if T > 1 else x.reshape(1, B, F).contiguous()
     out = torch.empty(B, enc.hidden_size, device=x.device, dtype=torch.float32)
     sh = L.stream_handle()
-    d = ((L.LstmFwdDesc if lengths is None else L.LstmFwdLenDesc) * 1)()
     wide = L.lstm_wide_index(((enc.embd_method, T),))
-    _lstm_fwd_prepare(d[0], enc, xt, _lstm_alloc(enc, B, T, x.device, backward=False, wide=wide), B, T, out.data_ptr(),
-                      enc.hidden_size, sh)
-    if lengths is not None:
-        lens = _length_buffer(B, T, x.device)
+    lens = None if lengths is None else _length_buffer(B, T, x.device)
+    if lens is not None:
         _set_lengths(lens, lengths.to(x.device), T, "input")
-        _len_desc(d[0], lens, wide)
-        L.check(L.lstm_fwd_len(1, d, sh), "lstm_fwd_len")
-        return out
-    L.check(L.lstm_fwd(1, d, sh, wide), "lstm_fwd")
+    _lstm_fwd_launch([(enc, xt, _lstm_alloc(enc, B, T, x.device, backward=False, wide=wide), T, out.data_ptr(),
+                       enc.hidden_size, lens)], B, sh, wide)
     return out
