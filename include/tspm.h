@@ -55,7 +55,8 @@ enum {
  * tspm_lstm_bwd_w, the LSTM recurrences at any hidden width that is a multiple of 4 up to 128 (same descriptors);
  * tspm_lstm_fwd_t16 / tspm_lstm_bwd_t16, those recurrences with a 16-bit "maxpool" time index (up to 65535 steps);
  * tspm_lstm_fwd_len / tspm_lstm_bwd_len, the recurrences with per-sample sequence lengths read on the device
- * (pack_padded_sequence semantics; their own descriptors). */
+ * (pack_padded_sequence semantics; their own descriptors); tspm_textcnn_pool_fwd_len, the TextCNN pooling over each
+ * row's own windows (per-sample text lengths read on the device). */
 #define TSPM_ABI_VERSION 23
 int tspm_abi_version(void);  /* returns TSPM_ABI_VERSION */
 /* Static string for a status code. */
@@ -852,6 +853,21 @@ int tspm_textcnn_pool_fwd(int32_t batch, int32_t steps, int32_t nconv, const int
                           int32_t channels, const float* const* conv_out, const float* const* bias,
                           const uint8_t* keep, float keep_scale, float* pooled, uint8_t* argmax,
                           float* out, int32_t ld_out, tspm_stream_t stream);
+/* The same pooling with per-sample text lengths (added under ABI 23): the arguments of tspm_textcnn_pool_fwd in their
+ * order plus lengths, int32 [batch] in device memory (required: NULL is TSPM_ERR_INVALID).  The host never reads a
+ * length; the kernel clamps L_b = min(max(lengths[b], 1), steps), so no value moves an access outside the buffers and a
+ * captured graph may be replayed after the buffer's contents change.  Row b of conv i has
+ * n_i(b) = max(L_b - heights[i] + 1, 1) windows: bias, ReLU and the first maximum (NaN wins) run over t < n_i(b), and the
+ * index written is < n_i(b); pooled, argmax, the dropout and out are as in tspm_textcnn_pool_fwd.  That is the TextCNN
+ * applied to the row's own first L_b steps, zero-padded to max(L_b, heights[i]).  PRECONDITION: for a row shorter than a
+ * kernel height the single window reads the input's padding rows [L_b, heights[i]), which must be zero (what
+ * pad_sequence and tspm_seq_gather write) — the one place where the padding's content, not its extent, still matters.
+ * With every length >= steps the outputs are bitwise those of tspm_textcnn_pool_fwd.  tspm_textcnn_bwd takes the indices
+ * written here unchanged: it reads x only at argmax + dt, dt < heights[i], which stays below max(L_b, heights[i]). */
+int tspm_textcnn_pool_fwd_len(int32_t batch, int32_t steps, int32_t nconv, const int32_t* heights,
+                              int32_t channels, const float* const* conv_out, const float* const* bias,
+                              const uint8_t* keep, float keep_scale, float* pooled, uint8_t* argmax,
+                              float* out, int32_t ld_out, const int32_t* lengths, tspm_stream_t stream);
 /* TextCNN backward from dout (gradient of the embedding Linear's input, row stride ld_dout): through the
  * dropout and the ReLU at the argmax; conv weight gradients dw[i] ([C][heights[i]][feat], the
  * nn.Conv2d(1, C, (h, feat)) weight layout) and bias gradients db[i] (nullable) from the argmax rows

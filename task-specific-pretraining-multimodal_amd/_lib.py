@@ -342,6 +342,9 @@ _SIGS = {
     "tspm_lstm_bwd_len": (c_int32, [c_int32, POINTER(LstmBwdLenDesc), _P]),
     "tspm_textcnn_pool_fwd": (c_int32, [c_int32, c_int32, c_int32, _P, c_int32, _P, _P, _P, c_float, _P, _P, _P,
                                         c_int32, _P]),
+    # added under ABI 23: the pooling over each row's own windows (per-sample text lengths, device int32 [batch])
+    "tspm_textcnn_pool_fwd_len": (c_int32, [c_int32, c_int32, c_int32, _P, c_int32, _P, _P, _P, c_float, _P, _P, _P,
+                                            c_int32, _P, _P]),
     "tspm_textcnn_bwd": (c_int32, [c_int32, c_int32, c_int32, c_int32, _P, c_int32, _P, _P, c_int32, _P, c_float, _P,
                                    _P, _P, _P, _P, _P]),
     "tspm_grad_clip_workspace": (c_size_t, []),

@@ -372,6 +372,36 @@ __global__ __launch_bounds__(256) void k_textcnn_pool(int B, int T, int nconv, i
   }
 }
 
+// The same pooling over each row's own windows (tspm_textcnn_pool_fwd_len): row b has max(L_b - kh_i + 1, 1) of them, L_b =
+// lengths[b] clamped to 1..T here.  A kernel of its own, not a template parameter of k_textcnn_pool: sharing the loop
+// body through a device function changed the unmasked kernel's instructions, and that kernel stays as it was.
+__global__ __launch_bounds__(256) void k_textcnn_pool_len(int B, int T, int nconv, int C, PoolSet ps,
+                                                          const uint8_t* __restrict__ keep, float scale,
+                                                          float* __restrict__ pre, uint8_t* __restrict__ arg,
+                                                          float* __restrict__ out, int ldo,
+                                                          const int32_t* __restrict__ lengths) {
+  const int nc = nconv * C;
+  const long long total = (long long)B * nc;
+  for (long long e = blockIdx.x * 256LL + threadIdx.x; e < total; e += (long long)gridDim.x * 256) {
+    const int b = (int)(e / nc), ci = (int)(e - (long long)b * nc);
+    const int i = ci / C, c = ci - i * C;
+    const int lb = min(max(lengths[b], 1), T);
+    const int tout = max(lb - ps.kh[i] + 1, 1);  // <= T - kh + 1: no length moves a read outside conv_out
+    const float* y = ps.y[i];
+    const float bv = ps.bias[i] ? ps.bias[i][c] : 0.f;
+    float best = -1.f;
+    int bi = 0;
+    for (int t = 0; t < tout; ++t) {
+      float v = y[((long long)t * B + b) * C + c] + bv;
+      v = v > 0.f ? v : (v != v ? v : 0.f);  // ReLU (NaN propagates)
+      if (v > best || v != v) { best = v; bi = t; }
+    }
+    pre[e] = best;
+    arg[e] = (uint8_t)bi;
+    out[(long long)b * ldo + ci] = keep ? best * (keep[e] ? scale : 0.f) : best;
+  }
+}
+
 // grad of the pooled features: through the dropout (keep * scale) and the ReLU at the argmax.
 __global__ __launch_bounds__(256) void k_textcnn_pool_grad(long long total, int nc, const float* __restrict__ dout,
                                                            int ldd, const uint8_t* __restrict__ keep, float scale,
@@ -755,10 +785,12 @@ extern "C" int tspm_lstm_bwd_len(int32_t count, const tspm_lstm_bwd_len_desc* de
   });
 }
 
-extern "C" int tspm_textcnn_pool_fwd(int32_t batch, int32_t steps, int32_t nconv, const int32_t* heights,
-                                     int32_t channels, const float* const* conv_out, const float* const* bias,
-                                     const uint8_t* keep, float keep_scale, float* pooled, uint8_t* argmax,
-                                     float* out, int32_t ld_out, tspm_stream_t stream) {
+namespace {
+// One host path behind tspm_textcnn_pool_fwd and tspm_textcnn_pool_fwd_len (`lengths`: device memory, never read here).
+int textcnn_pool_launch(int32_t batch, int32_t steps, int32_t nconv, const int32_t* heights, int32_t channels,
+                        const float* const* conv_out, const float* const* bias, const uint8_t* keep, float keep_scale,
+                        float* pooled, uint8_t* argmax, float* out, int32_t ld_out, const int32_t* lengths,
+                        tspm_stream_t stream) {
   if (batch <= 0 || steps <= 0 || nconv < 1 || nconv > 4 || !heights || channels <= 0 || !conv_out || !pooled ||
       !argmax || !out || ld_out < nconv * channels || steps > 256)
     return TSPM_ERR_INVALID;
@@ -769,11 +801,36 @@ extern "C" int tspm_textcnn_pool_fwd(int32_t batch, int32_t steps, int32_t nconv
     ps.bias[i] = bias ? bias[i] : nullptr;
     ps.kh[i] = heights[i];
   }
-  hipLaunchKernelGGL(k_textcnn_pool, dim3(grid_for((long long)batch * nconv * channels)), dim3(256), 0,
-                     static_cast<hipStream_t>(stream), batch, steps, nconv, channels, ps, keep, keep_scale, pooled,
-                     argmax, out, ld_out);
+  const dim3 grid(grid_for((long long)batch * nconv * channels));
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (lengths)
+    hipLaunchKernelGGL(k_textcnn_pool_len, grid, dim3(256), 0, st, batch, steps, nconv, channels, ps, keep, keep_scale,
+                       pooled, argmax, out, ld_out, lengths);
+  else
+    hipLaunchKernelGGL(k_textcnn_pool, grid, dim3(256), 0, st, batch, steps, nconv, channels, ps, keep, keep_scale,
+                       pooled, argmax, out, ld_out);
   TSPM_LAUNCH_CHECK();
   return TSPM_OK;
+}
+}  // namespace
+
+extern "C" int tspm_textcnn_pool_fwd(int32_t batch, int32_t steps, int32_t nconv, const int32_t* heights,
+                                     int32_t channels, const float* const* conv_out, const float* const* bias,
+                                     const uint8_t* keep, float keep_scale, float* pooled, uint8_t* argmax,
+                                     float* out, int32_t ld_out, tspm_stream_t stream) {
+  return textcnn_pool_launch(batch, steps, nconv, heights, channels, conv_out, bias, keep, keep_scale, pooled, argmax,
+                             out, ld_out, nullptr, stream);
+}
+
+// Per-sample text lengths: row b pools over its own max(L_b - kh_i + 1, 1) windows, L_b = lengths[b] clamped to
+// 1..steps in the kernel.  The host checks `lengths` for non-NULL only: no value moves an access outside the buffers.
+extern "C" int tspm_textcnn_pool_fwd_len(int32_t batch, int32_t steps, int32_t nconv, const int32_t* heights,
+                                         int32_t channels, const float* const* conv_out, const float* const* bias,
+                                         const uint8_t* keep, float keep_scale, float* pooled, uint8_t* argmax,
+                                         float* out, int32_t ld_out, const int32_t* lengths, tspm_stream_t stream) {
+  if (!lengths) return TSPM_ERR_INVALID;
+  return textcnn_pool_launch(batch, steps, nconv, heights, channels, conv_out, bias, keep, keep_scale, pooled, argmax,
+                             out, ld_out, lengths, stream);
 }
 
 extern "C" int tspm_textcnn_bwd(int32_t batch, int32_t steps, int32_t feat, int32_t nconv, const int32_t* heights,

@@ -203,33 +203,38 @@ class MosiEpochRunner:
             self.recorder = DeviceMetricRecorder(metric_config or MOSI_METRICS, self.log)
         self.eval_steps: Dict[Tuple[int, int], Any] = {}
         self.ragged = False  # the loader's dataset carries per-sample lengths (mosi_data.MOSI(use_lengths=True))
+        self.text_lengths = False  # ... and the text lengths too (mosi_data.MOSI(text_lengths=True))
 
-    def train_step_for(self, b: int, t, ragged: Optional[bool] = None):
+    def train_step_for(self, b: int, t, ragged: Optional[bool] = None, text_lengths: Optional[bool] = None):
         """The model's cached FusedMosiStep for (b, t); ``t`` an ``int`` or a triple (Ta, Tv, Tt) (``mosi.norm_steps``).
-        ``ragged`` (default: what the current loader's dataset says): the step that reads per-sample lengths."""
+        ``ragged`` (default: what the current loader's dataset says): the step that reads per-sample lengths;
+        ``text_lengths`` (same default): the step whose TextCNN reads the text lengths."""
         ragged = self.ragged if ragged is None else bool(ragged)
-        st = self.model.fused_step(self.optimizer, self.loss_functions, b, t, ragged=ragged)
+        tl = self.text_lengths if text_lengths is None else bool(text_lengths)
+        st = self.model.fused_step(self.optimizer, self.loss_functions, b, t, ragged=ragged, text_lengths=tl)
         if st.log is not self.log:
             st.log, st.graph = self.log, None  # the captured graph must record into this log
         return st
 
-    def eval_step_for(self, b: int, t, ragged: Optional[bool] = None):
+    def eval_step_for(self, b: int, t, ragged: Optional[bool] = None, text_lengths: Optional[bool] = None):
         """The cached FusedMosiEvalStep for (b, t) — rebuilt when the model's engine for that shape is no longer
         the one it captured (``UttFusionModel._apply`` drops the engines on .to() / re-materialisation).  ``t``: an
         ``int`` or a triple (Ta, Tv, Tt), keyed by its normalised value."""
         from .mosi import FusedMosiEvalStep, norm_steps
         t = norm_steps(t)
         ragged = self.ragged if ragged is None else bool(ragged)
-        key = (b, t, "ragged") if ragged else (b, t)
+        tl = self.text_lengths if text_lengths is None else bool(text_lengths)
+        key = ((b, t, "ragged") if ragged else (b, t)) + (("text_lengths",) if tl else ())
         st = self.eval_steps.get(key)
-        if st is None or st.eng is not self.model._engine(b, t, self.device, ragged):
-            st = FusedMosiEvalStep(self.model, self.loss_functions, b, t, self.log, ragged=ragged)
+        if st is None or st.eng is not self.model._engine(b, t, self.device, ragged, tl):
+            st = FusedMosiEvalStep(self.model, self.loss_functions, b, t, self.log, ragged=ragged, text_lengths=tl)
             self.eval_steps[key] = st
         return st
 
     def loader_for(self, loader, train: bool):
         """Point a ``MosiDeviceLoader`` at this runner's steps (batches gathered straight into their inputs)."""
         self.ragged = bool(getattr(getattr(loader, "ds", None), "use_lengths", False))
+        self.text_lengths = bool(getattr(getattr(loader, "ds", None), "text_lengths", False))
         if hasattr(loader, "step_for"):
             loader.step_for = self.train_step_for if train else self.eval_step_for
         return loader
@@ -238,7 +243,7 @@ class MosiEpochRunner:
         st.eng.groups.copy_(self.log.group_ids(b.get("pattern_name") or b["pattern_names"]), non_blocking=True)
         if b.get("time_major") and b["audio"] is st.eng.A:
             st.run()  # the gather wrote the inputs (and, for a ragged step, the length buffers) in place
-        elif st.ragged:
+        elif st.ragged or st.text_lengths:
             st.step(b["audio"], b["video"], b["text"], b["label"], b.get("lengths"))
         else:
             st.step(b["audio"], b["video"], b["text"], b["label"])
@@ -250,6 +255,12 @@ class MosiEpochRunner:
         from .mosi import norm_steps
         steps = b.get("steps") or tuple(int(b[m].shape[1]) for m in ("audio", "video", "text"))
         return int(b["label"].numel()), norm_steps(steps)
+
+    @staticmethod
+    def _modes(b: Dict[str, Any]) -> Dict[str, bool]:
+        """The step modes a batch asks for: ``ragged`` when it carries lengths, ``text_lengths`` when the text's too."""
+        lengths = b.get("lengths")
+        return dict(ragged=lengths is not None, text_lengths=isinstance(lengths, dict) and "text" in lengths)
 
     @staticmethod
     def _groups(b: Dict[str, Any]):
@@ -272,7 +283,7 @@ class MosiEpochRunner:
         t0 = time.time()
         for b in self.loader_for(loader, True):
             for g in self._groups(b):
-                self._run(self.train_step_for(*self._shape(g), ragged="lengths" in g), g)
+                self._run(self.train_step_for(*self._shape(g), **self._modes(g)), g)
         return self._finish(t0)
 
     @torch.no_grad()
@@ -283,7 +294,7 @@ class MosiEpochRunner:
         try:
             for b in self.loader_for(loader, False):
                 for g in self._groups(b):
-                    self._run(self.eval_step_for(*self._shape(g), ragged="lengths" in g), g)
+                    self._run(self.eval_step_for(*self._shape(g), **self._modes(g)), g)
         finally:
             self.model.train()
         return self._finish(t0)

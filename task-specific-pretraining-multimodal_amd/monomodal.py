@@ -332,11 +332,18 @@ class FusedMonoEvalStep(_MonoBuffers):
         return {"loss": self.loss, "logits": self.logits, "preds": self.preds}
 
 
+def _len_tag(ragged: bool, text_lengths: bool = False) -> tuple:
+    """The trailing cache-key elements of the per-sample-length modes (``ragged``: an LSTMEncoder's, ``text_lengths``: a
+    TextCNN's); empty — the key as it always was — with both off."""
+    return (("ragged",) if ragged else ()) + (("text_lengths",) if text_lengths else ())
+
+
 class _MosiMonoBuffers(_MonoBuffers):
     """What the MOSI-encoder train and eval steps share: the single-encoder engine on the step's time-major
     input buffer, and the head — ``tspm_mono_head_step`` or the separate launches."""
 
-    def _init_mosi(self, model, x_shape, log, fused_head: Optional[bool], ragged: bool = False) -> None:
+    def _init_mosi(self, model, x_shape, log, fused_head: Optional[bool], ragged: bool = False,
+                   text_lengths: bool = False) -> None:
         from .mosi import MosiEncoderEngine
         b, t, f = (int(v) for v in x_shape)
         if f != model.encoder.input_size:
@@ -349,8 +356,9 @@ class _MosiMonoBuffers(_MonoBuffers):
                               "multiple of 4")
         self.fused_head = bool(model.fused_head if fused_head is None else fused_head)
         self.ragged = bool(ragged)  # per-sample lengths: the LSTM recurrences read the engine's length buffer
+        self.text_lengths = bool(text_lengths)  # ... a TextCNN's pooling reads the engine's text length buffer
         self.eng = MosiEncoderEngine(model.encoder, b, t, self.device, seed=model._rng_seed, x=self.X, emb=self.emb,
-                                     ragged=self.ragged)
+                                     ragged=self.ragged, text_lengths=self.text_lengths)
         if self.regress is not None:
             self.preds = self.logits.view(-1)  # the float predictions
         self.demb = self.eng.demb
@@ -367,7 +375,8 @@ class _MosiMonoBuffers(_MonoBuffers):
     def load_batch(self, x: torch.Tensor, labels: torch.Tensor, lengths: Optional[torch.Tensor] = None) -> None:
         """x: a batch-first [B, T, F] batch (one tspm_seq_gather into the time-major buffer), or the step's own
         input buffer (mosi_data.MOSI.device_loader(step_for=...) gathered into it: no copy).  ``lengths`` (a ragged
-        step): int [B], copied on the device into the engine's length buffer (or that buffer itself: no copy)."""
+        or text_lengths step): int [B], copied on the device into the engine's length buffer (or that buffer itself: no
+        copy)."""
         if x.data_ptr() != self.X.data_ptr():
             self.eng.load(x)
         self.eng.set_lengths(lengths)
@@ -441,7 +450,7 @@ class FusedMosiMonoStep(_MosiMonoBuffers):
     ``fused_head`` is ignored in this mode; ``preds`` is then the float prediction [B] (a view of ``logits``)."""
 
     def __init__(self, model, optimizer: FusedAdam, loss_functions, x_shape, use_graph: bool = True, log=None,
-                 fused_head: Optional[bool] = None, ragged: bool = False):
+                 fused_head: Optional[bool] = None, ragged: bool = False, text_lengths: bool = False):
         self.ce_weight, self.regress = _loss_sig(model, loss_functions)
         if self.ce_weight is None and self.regress is None:
             raise L.TspmError("FusedMosiMonoStep: the loss group must be a single cross-entropy term (or, under a "
@@ -452,19 +461,19 @@ class FusedMosiMonoStep(_MosiMonoBuffers):
         for p in model.parameters():
             if p.requires_grad and p.grad is None:
                 raise L.TspmError("FusedMosiMonoStep: parameter without a FusedAdam gradient view")
-        self._init_mosi(model, x_shape, log, fused_head, ragged)
+        self._init_mosi(model, x_shape, log, fused_head, ragged, text_lengths)
         self.opt = optimizer
         self.use_graph = use_graph and not os.environ.get("TSPM_NO_GRAPH")
         self.eng.rng_ctr_ptr = optimizer.flat_groups()[0].hyper.data_ptr() + L.HYPER_STEP_OFFSET
         f32 = dict(device=self.device, dtype=torch.float32)
         self.dlogits = torch.empty(self.N, self.K, **f32)
         self.stats = torch.zeros(4, **f32)
-        self._sig = (id(optimizer), id(loss_functions), self.fused_head) + (("ragged",) if self.ragged else ())
+        self._sig = (id(optimizer), id(loss_functions), self.fused_head) + _len_tag(self.ragged, self.text_lengths)
 
     def matches(self, x: torch.Tensor, optimizer, loss_functions, fused_head: Optional[bool] = None,
-                ragged: bool = False) -> bool:
+                ragged: bool = False, text_lengths: bool = False) -> bool:
         fh = bool(self.model.fused_head if fused_head is None else fused_head)
-        sig = (id(optimizer), id(loss_functions), fh) + (("ragged",) if ragged else ())
+        sig = (id(optimizer), id(loss_functions), fh) + _len_tag(ragged, text_lengths)
         return self._sig == sig and self.matches_shape(x)
 
     def _enqueue(self) -> None:
@@ -495,12 +504,12 @@ class FusedMosiMonoEvalStep(_MosiMonoBuffers):
     dropout) and the head in forward-only mode (logits, weighted CE, argmax)."""
 
     def __init__(self, model, loss_functions, x_shape, log=None, use_graph: bool = True,
-                 fused_head: Optional[bool] = None, ragged: bool = False):
+                 fused_head: Optional[bool] = None, ragged: bool = False, text_lengths: bool = False):
         self.ce_weight, self.regress = _loss_sig(model, loss_functions)
         if self.ce_weight is None and self.regress is None:
             raise L.TspmError("FusedMosiMonoEvalStep: the loss group must be a single cross-entropy term (or, under "
                               "a one-output classifier, a single mean L1 / MSE term)")
-        self._init_mosi(model, x_shape, log, fused_head, ragged)
+        self._init_mosi(model, x_shape, log, fused_head, ragged, text_lengths)
         self.use_graph = use_graph and not os.environ.get("TSPM_NO_GRAPH")
 
     def _enqueue(self) -> None:
@@ -759,7 +768,7 @@ class _MosiMonoFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, model: "MonomodalEncoder", lengths, *params):
-        eng = model._mosi_engine(x.shape[0], x.shape[1], x.device, lengths is not None)
+        eng = model._mosi_engine(x.shape[0], x.shape[1], x.device, **model._len_modes(lengths is not None))
         eng.load(x)
         eng.set_lengths(lengths)
         eng.apply_keep_override()
@@ -820,30 +829,38 @@ class MonomodalEncoder(nn.Module):
         self._mosi_engines = {}
         return out
 
-    def _mosi_engine(self, b: int, t: int, device, ragged: bool = False):
+    def _mosi_engine(self, b: int, t: int, device, ragged: bool = False, text_lengths: bool = False):
         from .mosi import MosiEncoderEngine
-        key = (int(b), int(t), device) + (("ragged",) if ragged else ())
+        key = (int(b), int(t), device) + _len_tag(ragged, text_lengths)
         eng = self._mosi_engines.get(key)
         if eng is None:
             eng = self._mosi_engines[key] = MosiEncoderEngine(self.encoder, b, t, device, seed=self._rng_seed,
-                                                              ragged=ragged)
+                                                              ragged=ragged, text_lengths=text_lengths)
         return eng
 
+    def _len_modes(self, on: bool) -> Dict[str, bool]:
+        """The step / engine keywords of a batch with (``on``) or without per-sample lengths: ``ragged`` around an
+        LSTMEncoder, ``text_lengths`` around a TextCNN."""
+        from .mosi import TextCNN
+        text = isinstance(self.encoder, TextCNN)
+        return dict(ragged=bool(on) and not text, text_lengths=bool(on) and text)
+
     def _lengths_of(self, batch, key) -> Optional[torch.Tensor]:
-        """The batch's per-sample lengths for an LSTM encoder (``"lengths"``: an int tensor [B], or a dict by modality
-        name as the fusion loader delivers); None for every other encoder and for a batch without them."""
-        from .mosi import LSTMEncoder
-        lengths = batch.get("lengths") if isinstance(self.encoder, LSTMEncoder) else None
+        """The batch's per-sample lengths for an LSTMEncoder or a TextCNN (``"lengths"``: an int tensor [B], or a dict
+        by modality name as the fusion loader delivers — the text modality's only from a ``text_lengths`` dataset);
+        None for every other encoder and for a batch without them."""
+        lengths = batch.get("lengths") if self._mosi_encoder() else None
         if isinstance(lengths, dict):
             lengths = lengths.get(str(getattr(key, "value", key)).lower().split(".")[-1])
         return lengths
 
     def forward(self, x, lengths: Optional[torch.Tensor] = None):
-        """``lengths`` (an LSTMEncoder only): int [B], each row's real length (``LSTMEncoder.forward``)."""
+        """``lengths`` (an LSTMEncoder or a TextCNN only): int [B], each row's real length (``LSTMEncoder.forward``,
+        ``TextCNN.forward``)."""
         if isinstance(x, list):
             x = torch.stack(x)
         if lengths is not None and not self._mosi_encoder():
-            raise L.TspmError("MonomodalEncoder: lengths are taken by an LSTMEncoder only")
+            raise L.TspmError("MonomodalEncoder: lengths are taken by an LSTMEncoder or a TextCNN only")
         if self._mosi_encoder() and self.training and torch.is_grad_enabled():
             x = x.float()
             if not x.is_cuda:
@@ -900,13 +917,15 @@ class MonomodalEncoder(nn.Module):
                          log: Optional[ClassificationLog] = None,
                          lengths: Optional[torch.Tensor] = None) -> FusedMonoStep:
         """Run one fused step on device tensors and return the step (its loss / logits / preds buffers).  ``lengths``
-        (an LSTMEncoder): int [B] — the ragged step, one graph per padded shape whatever the lengths."""
+        (an LSTMEncoder: the ragged step; a TextCNN: the text_lengths step): int [B] — one graph per padded shape whatever
+        the lengths."""
         if lengths is not None:
+            modes = self._len_modes(True)
             st = self._by_buffer.get(x.data_ptr())
-            if not (isinstance(st, FusedMosiMonoStep) and st.matches(x, optimizer, loss_functions, ragged=True)):
+            if not (isinstance(st, FusedMosiMonoStep) and st.matches(x, optimizer, loss_functions, **modes)):
                 st = self._fused
-            if not (isinstance(st, FusedMosiMonoStep) and st.matches(x, optimizer, loss_functions, ragged=True)):
-                st = FusedMosiMonoStep(self, optimizer, loss_functions, tuple(x.shape), ragged=True)
+            if not (isinstance(st, FusedMosiMonoStep) and st.matches(x, optimizer, loss_functions, **modes)):
+                st = FusedMosiMonoStep(self, optimizer, loss_functions, tuple(x.shape), **modes)
             self._fused = st
             st.log = log
             st.step(x, labels, lengths)
@@ -929,8 +948,9 @@ class MonomodalEncoder(nn.Module):
         self._fused.step(x, labels)
         return self._fused
 
-    def eval_step_for(self, loss_functions, x_shape, log=None, ragged: bool = False) -> FusedMonoEvalStep:
-        key = tuple(x_shape) + (("ragged",) if ragged else ())
+    def eval_step_for(self, loss_functions, x_shape, log=None, ragged: bool = False,
+                      text_lengths: bool = False) -> FusedMonoEvalStep:
+        key = tuple(x_shape) + _len_tag(ragged, text_lengths)
         st = self._eval_steps.get(key)
         if self._mmimdb_encoder():
             if st is None or st.weight != _bce_weight_of(loss_functions, "MonomodalEncoder") or \
@@ -939,8 +959,9 @@ class MonomodalEncoder(nn.Module):
             return st
         if st is None or (st.ce_weight, getattr(st, "regress", None)) != _loss_sig(self, loss_functions) or \
                 getattr(st, "fused_head", self.fused_head) != self.fused_head:
-            if ragged:
-                st = FusedMosiMonoEvalStep(self, loss_functions, tuple(x_shape), log, ragged=True)
+            if ragged or text_lengths:
+                st = FusedMosiMonoEvalStep(self, loss_functions, tuple(x_shape), log, ragged=ragged,
+                                           text_lengths=text_lengths)
             else:
                 cls = FusedMosiMonoEvalStep if self._mosi_encoder() else FusedMonoEvalStep
                 st = cls(self, loss_functions, key, log)
@@ -948,14 +969,15 @@ class MonomodalEncoder(nn.Module):
         st.log = log
         return st
 
-    def _eval_step_of(self, x: torch.Tensor, loss_functions, log=None, ragged: bool = False):
+    def _eval_step_of(self, x: torch.Tensor, loss_functions, log=None, ragged: bool = False,
+                      text_lengths: bool = False):
         """The eval step for batch x: the step whose input buffer x is (a loader gathered into it), else by shape."""
         own = self._by_buffer.get(x.data_ptr())
         if isinstance(own, FusedMosiMonoEvalStep) and (own.ce_weight, own.regress) == _loss_sig(self, loss_functions) \
-                and own.ragged == bool(ragged):
+                and (own.ragged, own.text_lengths) == (bool(ragged), bool(text_lengths)):
             own.log = log
             return own
-        return self.eval_step_for(loss_functions, tuple(x.shape), log, ragged)
+        return self.eval_step_for(loss_functions, tuple(x.shape), log, ragged, text_lengths)
 
     def train_step(self, batch, optimizer, loss_functions, device, metric_recorder, config=None, **kwargs):
         """train_monomodal.py:97-260.  Fused HIP graph with FusedAdam and the single cross-entropy loss
@@ -1008,7 +1030,7 @@ class MonomodalEncoder(nn.Module):
             if (not self.training and head_ok and x.is_cuda and labels.dim() == 1
                     and ((self._hip_encoder() and x.dim() in (3, 4)) or (self._mosi_encoder() and x.dim() == 3))):
                 lengths = self._lengths_of(batch, key)
-                st = self._eval_step_of(x, loss_functions, dlog, lengths is not None)
+                st = self._eval_step_of(x, loss_functions, dlog, **self._len_modes(lengths is not None))
                 st.step(x, labels, lengths) if lengths is not None else st.step(x, labels)
                 loss_t, preds = st.loss, st.preds
             else:
@@ -1068,36 +1090,43 @@ class MonoEpochRunner:
         self._mosi = model._mosi_encoder()
         self._mmimdb = model._mmimdb_encoder()
         self.ragged = False
+        self.text_lengths = False
         # sentiment regression (one-output classifier, a single mean L1 / MSE term): the regression head's
         # accumulators, MSA_<key>_<MODALITY> scores under the group "regression", no accuracy
         self.regression = _mono_regress(model, loss_functions) is not None
 
     # MOSI encoders: ``mosi_data.MOSI.loader(...)``'s ``step_for`` hooks — the loader gathers each batch time-major
     # straight into the step's input buffer (set on every loader that has the attribute, as harness.MosiHarness does)
-    def train_step_for(self, b: int, t: int, ragged: Optional[bool] = None):
+    def train_step_for(self, b: int, t: int, ragged: Optional[bool] = None, text_lengths: Optional[bool] = None):
         shape = (int(b), int(t), int(self.model.encoder.input_size))
         ragged = self.ragged if ragged is None else bool(ragged)
-        key = shape + (("ragged",) if ragged else ())
+        tl = self.text_lengths if text_lengths is None else bool(text_lengths)
+        key = shape + _len_tag(ragged, tl)
         st = self.train_steps.get(key)
         if st is None or (self._mosi and st.fused_head != self.model.fused_head):
-            if ragged:
-                st = FusedMosiMonoStep(self.model, self.optimizer, self.loss_functions, shape, ragged=True)
+            if ragged or tl:
+                st = FusedMosiMonoStep(self.model, self.optimizer, self.loss_functions, shape, ragged=ragged,
+                                       text_lengths=tl)
             else:
                 cls = FusedMosiMonoStep if self._mosi else FusedMonoStep
                 st = cls(self.model, self.optimizer, self.loss_functions, shape)
             self.train_steps[key] = st
         return st
 
-    def eval_step_for(self, b: int, t: int, ragged: Optional[bool] = None):
+    def eval_step_for(self, b: int, t: int, ragged: Optional[bool] = None, text_lengths: Optional[bool] = None):
         ragged = self.ragged if ragged is None else bool(ragged)
+        tl = self.text_lengths if text_lengths is None else bool(text_lengths)
         return self.model.eval_step_for(self.loss_functions, (int(b), int(t), int(self.model.encoder.input_size)),
-                                        self.log, ragged)
+                                        self.log, ragged, tl)
 
     def _hook(self, loader, train: bool) -> None:
-        from .mosi import LSTMEncoder
-        # the loader's dataset carries per-sample lengths (mosi_data.MOSI(use_lengths=True)): the ragged steps
+        from .mosi import LSTMEncoder, TextCNN
+        # the loader's dataset carries per-sample lengths (mosi_data.MOSI(use_lengths=True)): the ragged steps; the
+        # text lengths too (text_lengths=True): a TextCNN's text_lengths steps
         self.ragged = bool(getattr(getattr(loader, "ds", None), "use_lengths", False)) and \
             isinstance(self.model.encoder, LSTMEncoder)
+        self.text_lengths = bool(getattr(getattr(loader, "ds", None), "text_lengths", False)) and \
+            isinstance(self.model.encoder, TextCNN)
         if self._mosi and hasattr(loader, "step_for"):
             loader.step_for = self.train_step_for if train else self.eval_step_for
 
@@ -1186,9 +1215,10 @@ class MonoEpochRunner:
         self._hook(loader, True)
         for x, lab, lens in self._batches(loader):
             st = self.model._by_buffer.get(x.data_ptr()) if self._mosi else None
-            if not isinstance(st, FusedMosiMonoStep) or st.ragged != (lens is not None):
+            modes = self.model._len_modes(lens is not None)
+            if not isinstance(st, FusedMosiMonoStep) or (st.ragged, st.text_lengths) != tuple(modes.values()):
                 shape = tuple(x.shape)
-                st = (self.train_step_for(*shape[:2], ragged=lens is not None) if self._mosi
+                st = (self.train_step_for(*shape[:2], **modes) if self._mosi
                       else self.train_steps.get(shape))
                 if st is None:
                     st = FusedMonoStep(self.model, self.optimizer, self.loss_functions, shape)
@@ -1208,7 +1238,7 @@ class MonoEpochRunner:
         self.model.eval()
         self._hook(loader, False)
         for x, lab, lens in self._batches(loader):
-            st = self.model._eval_step_of(x, self.loss_functions, self.log, lens is not None)
+            st = self.model._eval_step_of(x, self.loss_functions, self.log, **self.model._len_modes(lens is not None))
             st.step(x, lab, lens) if lens is not None else st.step(x, lab)
             if not self.regression:
                 accs.append(st.batch_accuracy())

@@ -40,7 +40,11 @@ Per-sample sequence lengths (this project's addition; the reference runs the pad
 the recurrences through ``tspm_lstm_fwd_len/bwd_len`` on persistent ``int32 [B]`` device length buffers, one per LSTM
 encoder: each row's state freezes at its own last step (``pack_padded_sequence`` semantics), the buffers are refreshed
 device-to-device before each replay, and one captured graph serves every batch of a padded ``steps``.  ``ragged`` is a
-trailing element of every cache key, so the keys without it are unchanged.  The text modality has no length input.
+trailing element of every cache key, so the keys without it are unchanged.  The text modality's lengths are a separate
+opt-in, ``text_lengths`` (``fused_step(..., text_lengths=True)``, a ``"text"`` key in ``lengths``, ``TextCNN.forward(x,
+lengths)``): the pooling runs in ``tspm_textcnn_pool_fwd_len`` over each row's own windows on one more ``int32 [B]`` buffer
+— the TextCNN of the row's first ``L_b`` steps, whatever the padding — independent of ``ragged`` and a further trailing
+key element.  The loaders' zero padding is a precondition for rows shorter than a kernel height (include/tspm.h).
 
 Sentiment regression (this project's addition; the reference's YAMLs train the three-class variant only): a
 one-output ``netC.fc_out`` (``build_utt_fusion(name, output_dim=1)``) with a single mean ``nn.L1Loss`` / ``nn.MSELoss``
@@ -152,18 +156,23 @@ class TextCNN(nn.Module):
         self._engines = {}
         return out
 
-    def forward(self, x: torch.Tensor) -> torch.Tensor:
+    def forward(self, x: torch.Tensor, lengths: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Inference embedding of x [B, T, input] (no dropout; gradients flow through UttFusionModel or
-        MonomodalEncoder only)."""
+        MonomodalEncoder only).  ``lengths`` (int tensor [B], optional): each row's real length — the time-max runs over
+        the row's own windows (``tspm_textcnn_pool_fwd_len``; rows past a length must be zero padding); without it every
+        row pools over the padded length."""
         if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()) and x.requires_grad:
             raise L.TspmError("TextCNN: train it inside UttFusionModel or MonomodalEncoder (the fused HIP step / its "
                               "autograd node)")
         L.require_cuda_f32(x, "TextCNN input")
-        key = (x.shape[0], x.shape[1], x.device)
+        tl = lengths is not None
+        key = _text_lengths_key((x.shape[0], x.shape[1], x.device), tl)
         eng = self._engines.get(key)
         if eng is None:
-            eng = self._engines[key] = MosiEncoderEngine(self, x.shape[0], x.shape[1], x.device)
+            eng = self._engines[key] = MosiEncoderEngine(self, x.shape[0], x.shape[1], x.device, text_lengths=tl)
         eng.load(x)
+        if tl:
+            eng.set_lengths(lengths.to(x.device))
         eng.forward(L.stream_handle(), False)
         return eng.emb.clone()
 
@@ -314,7 +323,7 @@ def _lstm_bwd_desc(d, enc: "LSTMEncoder", bufs, B: int, T: int, dh: int, ld_dh: 
     d.argmax = L.ptr(bufs["arg"])
 
 
-RAGGED_MODALITIES = ("audio", "video")  # the LSTM encoders; the text modality has no length input (TextCNN)
+RAGGED_MODALITIES = ("audio", "video")  # the LSTM encoders (ragged); the TextCNN's "text" key is text_lengths' own
 
 
 def _ragged_key(key: tuple, ragged: bool) -> tuple:
@@ -322,8 +331,22 @@ def _ragged_key(key: tuple, ragged: bool) -> tuple:
     return key + ("ragged",) if ragged else key
 
 
+def _text_lengths_key(key: tuple, text_lengths: bool) -> tuple:
+    """A cache key with the text-length mode in it, after the ragged element if any: unchanged when it is off."""
+    return key + ("text_lengths",) if text_lengths else key
+
+
+def _split_lengths(lengths) -> tuple:
+    """(ragged, text_lengths) of a ``lengths`` argument: a ``"text"`` key asks for the TextCNN's length input; anything
+    else — an empty dict too, as before — for the ragged LSTM recurrences.  ``{"text": ...}`` alone is text-only."""
+    if lengths is None:
+        return False, False
+    tl = isinstance(lengths, dict) and "text" in lengths
+    return (not tl) or len(lengths) > 1, tl
+
+
 def _length_buffer(B: int, T: int, device) -> torch.Tensor:
-    """A persistent int32 [B] length buffer of one LSTM encoder, at the padded length until a batch's lengths are copied
+    """A persistent int32 [B] length buffer of one encoder, at the padded length until a batch's lengths are copied
     in (the captured graph reads it; the kernels clamp every value to 1..T)."""
     return torch.full((B,), int(T), dtype=torch.int32, device=device)
 
@@ -341,10 +364,12 @@ def _set_lengths(buf: torch.Tensor, lengths: Optional[torch.Tensor], T: int, nm:
     buf.copy_(lengths.reshape(-1), non_blocking=True)
 
 
-def _check_lengths_arg(lengths) -> None:
-    if not isinstance(lengths, dict) or any(k not in RAGGED_MODALITIES for k in lengths):
-        raise L.TspmError(f"lengths: a dict with keys among {RAGGED_MODALITIES} (int tensors [B]); the text modality "
-                          f"has no length input")
+def _check_lengths_arg(lengths, ragged: bool = True, text_lengths: bool = False) -> None:
+    allowed = (RAGGED_MODALITIES if ragged else ()) + (("text",) if text_lengths else ())
+    if not isinstance(lengths, dict) or any(k not in allowed for k in lengths):
+        raise L.TspmError(f"lengths: a dict with keys among {allowed} (int tensors [B]) for this engine; \"audio\" / "
+                          f"\"video\" need ragged=True, and the text modality has a length input only with "
+                          f"text_lengths=True")
 
 
 def _len_desc(d, lengths: torch.Tensor, wide: bool) -> None:
@@ -410,7 +435,8 @@ def _lstm_wgrad_plan(B: int, plans, device):
 def _text_alloc(o, t: "TextCNN", B: int, T: int, device) -> None:
     """The TextCNN half's plan for a fixed (batch, steps), set as attributes of its owner `o` (MosiEngine or
     MosiEncoderEngine): conv shapes / tiles / outputs / workspace, pooled values and their argmax, the embedding
-    Linear's input and the backward's work buffers."""
+    Linear's input and the backward's work buffers.  ``o.text_lens`` (set by the owner before this call): the int32 [B]
+    text length buffer of a ``text_lengths`` owner, else None."""
     if T > TEXT_MAX_STEPS or min(t.heights) > T or max(t.heights) > 5:
         raise _text_steps_error(T)
     f = dict(device=device, dtype=torch.float32)
@@ -439,7 +465,8 @@ def _text_alloc(o, t: "TextCNN", B: int, T: int, device) -> None:
 
 def _text_forward(o, t: "TextCNN", sh: int, keep: Optional[int], out: int, ld_out: int) -> None:
     """TextCNN forward on owner `o`'s plan: three convolutions (implicit GEMM), pooling + dropout (keep: the
-    uint8 mask's pointer or None), embedding Linear + ReLU written to `out` (row stride ld_out)."""
+    uint8 mask's pointer or None; with the owner's ``text_lens`` buffer over each row's own windows), embedding Linear +
+    ReLU written to `out` (row stride ld_out)."""
     lib, B, T = L.lib(), o.B, o.Tt
     for conv, s, al, y in zip(t.convs(), o.conv_shapes, o.conv_algos, o.conv_out):
         L.check(lib.tspm_conv_fwd(ctypes.byref(s), ctypes.byref(al), o.X.data_ptr(), None,
@@ -449,9 +476,14 @@ def _text_forward(o, t: "TextCNN", sh: int, keep: Optional[int], out: int, ld_ou
     outs = (ctypes.c_void_p * 3)(*[y.data_ptr() for y in o.conv_out])
     biases = (ctypes.c_void_p * 3)(*[cv.bias.data_ptr() for cv in t.convs()])
     tp = t.dropout.p
-    L.check(lib.tspm_textcnn_pool_fwd(B, T, 3, heights, o.C, outs, biases, keep,
-                                      1.0 / (1.0 - tp) if tp < 1 else 0.0, o.pooled.data_ptr(),
-                                      o.argmax.data_ptr(), o.fc_in.data_ptr(), o.nc, sh), "textcnn pool")
+    scale = 1.0 / (1.0 - tp) if tp < 1 else 0.0
+    if o.text_lens is not None:  # text_lengths: each row pools over its own windows
+        L.check(lib.tspm_textcnn_pool_fwd_len(B, T, 3, heights, o.C, outs, biases, keep, scale, o.pooled.data_ptr(),
+                                              o.argmax.data_ptr(), o.fc_in.data_ptr(), o.nc, o.text_lens.data_ptr(), sh),
+                "textcnn pool (lengths)")
+    else:
+        L.check(lib.tspm_textcnn_pool_fwd(B, T, 3, heights, o.C, outs, biases, keep, scale, o.pooled.data_ptr(),
+                                          o.argmax.data_ptr(), o.fc_in.data_ptr(), o.nc, sh), "textcnn pool")
     emb = t.embd[0]
     L.check(lib.tspm_linear_fwd(B, o.nc, emb.out_features, o.fc_in.data_ptr(), o.nc, emb.weight.data_ptr(),
                                 emb.bias.data_ptr(), 1, None, 1.0, out, ld_out, sh),
@@ -495,9 +527,10 @@ class MosiEngine:
     (Ta, Tv, Tt) (``norm_steps``): each modality's input, saved activations, gather helpers and weight-gradient split
     are planned at its own length (``Ts``); ``T`` is the normalised value (the ``int`` on aligned data)."""
 
-    def __init__(self, model: "UttFusionModel", batch: int, steps, device: torch.device, ragged: bool = False):
+    def __init__(self, model: "UttFusionModel", batch: int, steps, device: torch.device, ragged: bool = False,
+                 text_lengths: bool = False):
         self.m, self.B, self.T, self.device = model, batch, norm_steps(steps), device
-        self.ragged = bool(ragged)
+        self.ragged, self.text_lengths = bool(ragged), bool(text_lengths)
         a, v, t, c = model.netA, model.netV, model.netT, model.netC
         f = dict(device=device, dtype=torch.float32)
         B = batch
@@ -519,6 +552,8 @@ class MosiEngine:
                      for name, enc, T_m in (("a", a, Ta), ("v", v, Tv))}
         # ragged mode: one persistent int32 [B] length buffer per LSTM encoder, read by tspm_lstm_fwd_len / _bwd_len
         self.lens = {"a": _length_buffer(B, Ta, device), "v": _length_buffer(B, Tv, device)} if self.ragged else None
+        # text_lengths: the TextCNN's own persistent int32 [B] length buffer, read by tspm_textcnn_pool_fwd_len
+        self.text_lens = _length_buffer(B, Tt, device) if self.text_lengths else None
         _text_alloc(self, t, B, Tt, device)
         nc = self.nc
         lib = L.lib()
@@ -566,15 +601,19 @@ class MosiEngine:
     # -- inputs -------------------------------------------------------------------------------------
     def set_lengths(self, lengths: Optional[Dict[str, torch.Tensor]]) -> None:
         """Ragged mode: the batch's ``{"audio": int [B], "video": int [B]}`` into the length buffers (device-to-device,
-        outside any captured graph, which reads the buffers); an absent key runs that encoder at the full length."""
-        if not self.ragged:
+        outside any captured graph, which reads the buffers); an absent key runs that encoder at the full length.  A
+        ``text_lengths`` engine takes ``"text"`` the same way; any other engine refuses that key."""
+        if not self.ragged and not self.text_lengths:
             if lengths is not None:
                 raise L.TspmError("MosiEngine: lengths given to an engine built without ragged=True")
             return
         lengths = lengths or {}
-        _check_lengths_arg(lengths)
-        for nm, key, T_m in (("audio", "a", self.Ts[0]), ("video", "v", self.Ts[1])):
-            _set_lengths(self.lens[key], lengths.get(nm), T_m, nm)
+        _check_lengths_arg(lengths, self.ragged, self.text_lengths)
+        if self.ragged:
+            for nm, key, T_m in (("audio", "a", self.Ts[0]), ("video", "v", self.Ts[1])):
+                _set_lengths(self.lens[key], lengths.get(nm), T_m, nm)
+        if self.text_lengths:
+            _set_lengths(self.text_lens, lengths.get("text"), self.Ts[2], "text")
 
     def load(self, A: torch.Tensor, V: torch.Tensor, T: torch.Tensor, labels: Optional[torch.Tensor] = None,
              regress: bool = False) -> None:
@@ -814,14 +853,21 @@ class MosiEncoderEngine:
     gradients; TextCNN = three convs + pool/dropout + embedding Linear / act_bwd + linear_bwd + textcnn_bwd."""
 
     def __init__(self, enc: nn.Module, batch: int, steps: int, device, seed: int = 0,
-                 x: Optional[torch.Tensor] = None, emb: Optional[torch.Tensor] = None, ragged: bool = False):
+                 x: Optional[torch.Tensor] = None, emb: Optional[torch.Tensor] = None, ragged: bool = False,
+                 text_lengths: bool = False):
         if torch.device(device).type != "cuda":
             raise L.TspmError("MOSI encoders (tspm_amd) run on the MI355X only (no CPU fallback)")
         self.enc, self.B, self.T, self.device = enc, int(batch), int(steps), device
-        self.ragged = bool(ragged)
+        self.ragged, self.text_lengths = bool(ragged), bool(text_lengths)
         if self.ragged and isinstance(enc, TextCNN):
-            raise L.TspmError("MosiEncoderEngine: the TextCNN has no length input (ragged mode is the LSTM encoders')")
+            raise L.TspmError("MosiEncoderEngine: ragged mode is the LSTM encoders' (the TextCNN's length input is "
+                              "text_lengths=True)")
+        if self.text_lengths and not isinstance(enc, TextCNN):
+            raise L.TspmError("MosiEncoderEngine: text_lengths is the TextCNN's length input (an LSTMEncoder takes "
+                              "ragged=True)")
         self.lens = _length_buffer(self.B, self.T, device) if self.ragged else None
+        # text_lengths: the TextCNN's persistent int32 [B] length buffer, read by tspm_textcnn_pool_fwd_len
+        self.text_lens = _length_buffer(self.B, self.T, device) if self.text_lengths else None
         B, T = self.B, self.T
         f = dict(device=device, dtype=torch.float32)
         self.is_text = isinstance(enc, TextCNN)
@@ -852,12 +898,14 @@ class MosiEncoderEngine:
         self._offs = torch.arange(B, dtype=torch.int64, device=device) * T
 
     def set_lengths(self, lengths: Optional[torch.Tensor]) -> None:
-        """Ragged mode: the batch's int lengths [B] into the length buffer (``None``: the full padded length)."""
-        if not self.ragged:
+        """Ragged / text_lengths mode: the batch's int lengths [B] into the length buffer (``None``: the full padded
+        length)."""
+        if not self.ragged and not self.text_lengths:
             if lengths is not None:
-                raise L.TspmError("MosiEncoderEngine: lengths given to an engine built without ragged=True")
+                raise L.TspmError("MosiEncoderEngine: lengths given to an engine built without ragged=True (an "
+                                  "LSTMEncoder) or text_lengths=True (a TextCNN)")
             return
-        _set_lengths(self.lens, lengths, self.T, "input")
+        _set_lengths(self.lens if self.ragged else self.text_lens, lengths, self.T, "input")
 
     def load(self, x: torch.Tensor) -> None:
         """A batch-first [B, T, F] tensor → the time-major input buffer."""
@@ -947,7 +995,7 @@ class FusedMosiStep:
     launch of ``MosiEngine.head_regress``; everything else is the classification step's schedule."""
 
     def __init__(self, model: "UttFusionModel", optimizer: FusedAdam, loss_functions, batch: int, steps,
-                 use_graph: bool = True, allreduce=None, ragged: bool = False):
+                 use_graph: bool = True, allreduce=None, ragged: bool = False, text_lengths: bool = False):
         if not isinstance(optimizer, FusedAdam):
             raise L.TspmError("FusedMosiStep needs FusedAdam (the flat gradient buffer the kernels write)")
         dev = next(model.parameters()).device
@@ -965,8 +1013,8 @@ class FusedMosiStep:
         if self.regress is not None and not L.regress_head_supported(batch, model.netC.widths[-1]):
             raise L.TspmError("FusedMosiStep: the regression head takes at most 1024 rows and a last classifier "
                               "layer of at most 128 units, a multiple of 4")
-        self.ragged = bool(ragged)
-        self.eng = MosiEngine(model, batch, steps, dev, ragged=self.ragged)
+        self.ragged, self.text_lengths = bool(ragged), bool(text_lengths)
+        self.eng = MosiEngine(model, batch, steps, dev, ragged=self.ragged, text_lengths=self.text_lengths)
         self.eng.rng_ctr_ptr = fgs[0].hyper.data_ptr() + L.HYPER_STEP_OFFSET
         if model.clip is not None:
             optimizer.clip_coef = self.eng.clip_coef
@@ -1016,8 +1064,9 @@ class FusedMosiStep:
             self._opt()
 
     def step(self, A, V, T, labels, lengths: Optional[Dict[str, torch.Tensor]] = None) -> Dict[str, torch.Tensor]:
-        """``lengths`` (a ragged step only): ``{"audio": int [B], "video": int [B]}``, copied on the device into the
-        length buffers the captured graph reads — one graph serves every batch of this padded ``steps``."""
+        """``lengths`` (a ragged and / or text_lengths step only): ``{"audio": int [B], "video": int [B]}`` and, with
+        ``text_lengths``, ``"text"``, copied on the device into the length buffers the captured graph reads — one graph
+        serves every batch of this padded ``steps``."""
         self.eng.load(A, V, T, labels, self.regress is not None)
         self.eng.set_lengths(lengths)
         self.run()
@@ -1055,9 +1104,9 @@ class FusedMosiEvalStep:
     (``mosi_data.MOSI.device_loader(step_for=...)`` gathers into them) or a batch-first batch via ``step``."""
 
     def __init__(self, model: "UttFusionModel", loss_functions, batch: int, steps, log, use_graph: bool = True,
-                 ragged: bool = False):
+                 ragged: bool = False, text_lengths: bool = False):
         dev = next(model.parameters()).device
-        self.ragged = bool(ragged)
+        self.ragged, self.text_lengths = bool(ragged), bool(text_lengths)
         self.model, self.N, self.T, self.log = model, batch, norm_steps(steps), log
         self.weight = _ce_weight(loss_functions)
         self.regress = _regress_mode(model, loss_functions)
@@ -1067,7 +1116,7 @@ class FusedMosiEvalStep:
         if self.regress is not None and not L.regress_head_supported(batch, model.netC.widths[-1]):
             raise L.TspmError("FusedMosiEvalStep: the regression head takes at most 1024 rows and a last classifier "
                               "layer of at most 128 units, a multiple of 4")
-        self.eng = model._engine(batch, steps, dev, self.ragged)
+        self.eng = model._engine(batch, steps, dev, self.ragged, self.text_lengths)
         self.use_graph = use_graph and not os.environ.get("TSPM_NO_GRAPH")
         self.graph: Optional[torch.cuda.CUDAGraph] = None
         self.calls = 0
@@ -1131,7 +1180,7 @@ class _UttFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, A, V, T, model: "UttFusionModel", lengths, *params):
-        eng = model._engine(A.shape[0], _batch_steps(A, V, T), A.device, lengths is not None)
+        eng = model._engine(A.shape[0], _batch_steps(A, V, T), A.device, *_split_lengths(lengths))
         eng.load(A, V, T)
         eng.set_lengths(lengths)
         eng.apply_keep_override()
@@ -1186,31 +1235,35 @@ class UttFusionModel(nn.Module):
         self._engines, self._steps = {}, {}
         return out
 
-    def _engine(self, b: int, t, device, ragged: bool = False) -> MosiEngine:
+    def _engine(self, b: int, t, device, ragged: bool = False, text_lengths: bool = False) -> MosiEngine:
         """The cached MosiEngine for (batch, steps): ``t`` an ``int`` or a triple (Ta, Tv, Tt), keyed by ``norm_steps``;
-        a ``ragged`` engine (per-sample lengths) is a separate entry, the key without it is unchanged."""
+        a ``ragged`` engine (per-sample lengths) and a ``text_lengths`` engine (the TextCNN's lengths) are separate
+        entries, the key without them is unchanged."""
         if torch.device(device).type != "cuda":
             raise L.TspmError("UttFusionModel (tspm_amd) runs on the MI355X only (no CPU fallback)")
         t = norm_steps(t)
-        key = _ragged_key((b, t, device), ragged)
+        key = _text_lengths_key(_ragged_key((b, t, device), ragged), text_lengths)
         eng = self._engines.get(key)
         if eng is None:
-            eng = MosiEngine(self, b, t, device, ragged=ragged)
+            eng = MosiEngine(self, b, t, device, ragged=ragged, text_lengths=text_lengths)
             self._engines[key] = eng
         return eng
 
     def fused_step(self, optimizer: FusedAdam, loss_functions, batch: int, steps,
-                   ragged: bool = False) -> FusedMosiStep:
+                   ragged: bool = False, text_lengths: bool = False) -> FusedMosiStep:
         """The cached FusedMosiStep for (optimizer, loss group, batch, padded steps) — one captured graph per
         padded length (mosi_data.MOSI.device_loader(step_for=...) gathers straight into its inputs).  ``steps``: an
         ``int`` or a triple (Ta, Tv, Tt); the key is ``norm_steps(steps)``, so ``50`` and ``(50, 50, 50)`` give the
         same object.  ``ragged``: the step whose recurrences read per-sample lengths (``step(..., lengths=...)``) — one
-        captured graph for every batch of this padded length, whatever its real lengths; a separate cache entry."""
+        captured graph for every batch of this padded length, whatever its real lengths; a separate cache entry.
+        ``text_lengths`` (independent of ``ragged``): the step whose TextCNN pooling reads ``lengths["text"]``; one more
+        trailing key element."""
         steps = norm_steps(steps)
-        key = _ragged_key((id(optimizer), id(loss_functions), int(batch), steps), ragged)
+        key = _text_lengths_key(_ragged_key((id(optimizer), id(loss_functions), int(batch), steps), ragged), text_lengths)
         st = self._steps.get(key)
         if st is None:
-            st = FusedMosiStep(self, optimizer, loss_functions, int(batch), steps, ragged=ragged)
+            st = FusedMosiStep(self, optimizer, loss_functions, int(batch), steps, ragged=ragged,
+                               text_lengths=text_lengths)
             self._steps[key] = st
         return st
 
@@ -1238,7 +1291,8 @@ class UttFusionModel(nn.Module):
         is the zeroed tensor the dataset delivers, data/base_dataset.py:61-74).  ``lengths`` (this project's addition):
         ``{"audio": int tensor [B], "video": int tensor [B]}``, either key optional — the LSTM encoders then freeze each
         row's state at its own last step (``pack_padded_sequence`` semantics), so the embedding no longer depends on the
-        padding; the text modality has no length input."""
+        padding.  A ``"text"`` key (optional, alone or with the others) gives the TextCNN each row's length: the time-max
+        runs over the row's own windows, so the text embedding no longer depends on the (zero) padding either."""
         assert not all((A is None, V is None, T is None)), "At least one of A, V, T must be provided"
         assert not all([is_embd_A, is_embd_V, is_embd_T]), "Cannot have all embeddings as True"
         if A is None or V is None or T is None or is_embd_A or is_embd_V or is_embd_T:
@@ -1250,7 +1304,7 @@ class UttFusionModel(nn.Module):
         if self.training and torch.is_grad_enabled():
             params = list(self.parameters())
             return _UttFn.apply(A, V, T, self, lengths, *params)
-        eng = self._engine(A.shape[0], _batch_steps(A, V, T), A.device, lengths is not None)
+        eng = self._engine(A.shape[0], _batch_steps(A, V, T), A.device, *_split_lengths(lengths))
         eng.load(A, V, T)
         eng.set_lengths(lengths)
         eng.forward(L.stream_handle(), self.training)
@@ -1276,8 +1330,9 @@ class UttFusionModel(nn.Module):
                    else L.regress_head_supported(A.shape[0], self.netC.widths[-1]))
         lengths = batch.get("lengths")  # per-sample lengths (mosi_data.MOSI(use_lengths=True)): the ragged step
         if isinstance(optimizer, FusedAdam) and head_ok and A.is_cuda:
-            out = self.fused_step(optimizer, loss_functions, A.shape[0], _batch_steps(A, V, T),
-                                  ragged=lengths is not None).step(A, V, T, labels, lengths)
+            ragged, tl = _split_lengths(lengths)
+            out = self.fused_step(optimizer, loss_functions, A.shape[0], _batch_steps(A, V, T), ragged=ragged,
+                                  text_lengths=tl).step(A, V, T, labels, lengths)
             logits, loss = out["logits"], out["loss"]
         else:
             self.train()
@@ -1310,7 +1365,7 @@ class UttFusionModel(nn.Module):
         labels = batch["label"].to(device)
         miss = np.array(batch.get("pattern_name", []))
         lengths = batch.get("lengths")
-        eng = self._engine(A.shape[0], _batch_steps(A, V, T), A.device, lengths is not None)
+        eng = self._engine(A.shape[0], _batch_steps(A, V, T), A.device, *_split_lengths(lengths))
         reg = _regress_mode(self, loss_functions)
         if reg is not None:
             labels = labels.float()
@@ -1361,7 +1416,7 @@ class UttFusionModel(nn.Module):
             V = _modality(batch, "video").to(device).float()
             T = _modality(batch, "text").to(device).float()
             lengths = batch.get("lengths")
-            eng = self._engine(A.shape[0], _batch_steps(A, V, T), A.device, lengths is not None)
+            eng = self._engine(A.shape[0], _batch_steps(A, V, T), A.device, *_split_lengths(lengths))
             eng.load(A, V, T)
             eng.set_lengths(lengths)
             eng.forward(L.stream_handle(), False)

@@ -41,7 +41,7 @@ from . import _lib as L
 MODALITIES = ("audio", "video", "text")
 _PICKLE_KEYS = {"audio": "audio", "video": "vision", "text": "text"}  # data/mosi.py:135-138
 PATTERNS = ["atv", "at", "av", "tv", "a", "t", "v"]  # data/mosi.py:61-69 order
-LENGTH_MODALITIES = ("audio", "video")  # the LSTM encoders take per-sample lengths; the TextCNN has no length input
+LENGTH_MODALITIES = ("audio", "video")  # what use_lengths covers (the LSTM encoders); "text" joins with text_lengths
 
 
 def pad_of(pad_to, modality: str) -> int:
@@ -221,7 +221,8 @@ class MOSI(torch.utils.data.Dataset):
                  missing_patterns=None, selected_patterns: Optional[List[str]] = None,
                  labels_key: str = "classification_labels", aligned: bool = False, length: Optional[int] = None,
                  num_classes: Optional[int] = None, batch_size: int = 1, corpus: Optional[MosiCorpus] = None,
-                 device=None, seed: int = 0, allow_pickle: bool = False, use_lengths: bool = False) -> None:
+                 device=None, seed: int = 0, allow_pickle: bool = False, use_lengths: bool = False,
+                 text_lengths: bool = False) -> None:
         split = split.lower()
         if split not in self.VALID_SPLITS:
             raise AssertionError(f"Invalid split provided, must be one of {self.VALID_SPLITS}")
@@ -244,8 +245,13 @@ class MOSI(torch.utils.data.Dataset):
         self.allow_pickle = allow_pickle
         # use_lengths: batches carry each sample's true audio / video length (``"lengths"``, or written into a ragged
         # step's length buffers) and an unaligned file is trimmed to its audio_lengths / vision_lengths; the LSTM
-        # encoders then stop at each sample's own last frame.  The text modality has no length input.
+        # encoders then stop at each sample's own last frame.  text_lengths (with use_lengths): the batches carry the
+        # text lengths too (``"lengths"["text"]``, or written into a text_lengths step's buffer) and the TextCNN pools
+        # over each sample's own windows; padding rows are zero either way.
         self.use_lengths = bool(use_lengths)
+        self.text_lengths = bool(text_lengths)
+        if self.text_lengths and not self.use_lengths:
+            raise L.TspmError("MOSI: text_lengths=True goes with use_lengths=True")
         if corpus is None:
             corpus = self._load(data_fp)
         self.corpus = corpus
@@ -333,6 +339,12 @@ class MOSI(torch.utils.data.Dataset):
         return {m: k[:, j].contiguous().to(self.device, non_blocking=True)
                 for j, m in enumerate(MODALITIES) if not bool((k[:, j] == 1.0).all())}
 
+    def _length_modalities(self) -> Sequence[str]:
+        """The modalities whose lengths a batch carries: none, the LSTM encoders', or with ``text_lengths`` all three."""
+        if not self.use_lengths:
+            return ()
+        return LENGTH_MODALITIES + (("text",) if self.text_lengths else ())
+
     def _want(self) -> Sequence[str]:
         """The modalities a batch carries (data.AVMNIST._want's rule)."""
         return MODALITIES if self.target_modality == "multimodal" else (self.target_modality,)
@@ -346,16 +358,17 @@ class MOSI(torch.utils.data.Dataset):
         index = torch.from_numpy(rows).to(self.device, non_blocking=True)
         masks = {k: v for k, v in self._masks(pid).items() if k == m}
         names = [self.selected_patterns[p] for p in pid]
-        ragged = self.use_lengths and m in LENGTH_MODALITIES
+        ragged = m in self._length_modalities()
         if step is not None:
             if (step.N, step.T) != (b, tpad):
                 raise L.TspmError(f"step planned for (B={step.N}, T={step.T}), batch is (B={b}, T={tpad})")
             lab = step.labels_f if dc.float_labels else step.labels
             lens = None
             if ragged:
-                lens = getattr(step.eng, "lens", None)
+                lens = getattr(step.eng, "text_lens" if m == "text" else "lens", None)
                 if lens is None:
-                    raise L.TspmError("use_lengths: the step was built without ragged=True (no length buffer)")
+                    raise L.TspmError("use_lengths: the step was built without ragged=True (text: text_lengths=True) "
+                                      "(no length buffer)")
             dc.gather(index, tpad, {m: step.X}, True, masks, lab, {m: lens} if ragged else None)
             return {m: step.X, "label": lab, "pattern_name": names, **({"lengths": lens} if ragged else {})}
         out = torch.empty(b, tpad, dc.feat[m], device=self.device)
@@ -382,12 +395,17 @@ class MOSI(torch.utils.data.Dataset):
                 if getattr(e, "lens", None) is None:
                     raise L.TspmError("use_lengths: the step was built without ragged=True (no length buffers)")
                 lens = {"audio": e.lens["a"], "video": e.lens["v"]}
+                if self.text_lengths:
+                    if getattr(e, "text_lens", None) is None:
+                        raise L.TspmError("text_lengths: the step was built without text_lengths=True (no text length "
+                                          "buffer)")
+                    lens["text"] = e.text_lens
             dc.gather(index, tpad, {"audio": e.A, "video": e.V, "text": e.X}, True, masks, lab, lens)
             return {"audio": e.A, "video": e.V, "text": e.X, "label": lab, "pattern_name": names,
                     "steps": tpad, "time_major": True, **({"lengths": lens} if lens is not None else {})}
         out = {m: torch.empty(b, steps_of(tpad, m), dc.feat[m], device=self.device) for m in MODALITIES}
         lab = torch.empty(b, dtype=dc.label_dtype, device=self.device)
-        lens = ({m: torch.empty(b, dtype=torch.int32, device=self.device) for m in LENGTH_MODALITIES}
+        lens = ({m: torch.empty(b, dtype=torch.int32, device=self.device) for m in self._length_modalities()}
                 if self.use_lengths else None)
         dc.gather(index, tpad, out, False, masks, lab, lens)
         return {"audio": out["audio"], "video": out["video"], "text": out["text"], "label": lab,
