@@ -56,7 +56,9 @@ enum {
  * tspm_lstm_fwd_t16 / tspm_lstm_bwd_t16, those recurrences with a 16-bit "maxpool" time index (up to 65535 steps);
  * tspm_lstm_fwd_len / tspm_lstm_bwd_len, the recurrences with per-sample sequence lengths read on the device
  * (pack_padded_sequence semantics; their own descriptors); tspm_textcnn_pool_fwd_len, the TextCNN pooling over each
- * row's own windows (per-sample text lengths read on the device). */
+ * row's own windows (per-sample text lengths read on the device); tspm_adam_begin_multi / tspm_adam_step_multi /
+ * tspm_grad_clip_coef_multi, the optimizer phase of a step with up to 8 FusedAdam groups in the launches one group
+ * takes. */
 #define TSPM_ABI_VERSION 23
 int tspm_abi_version(void);  /* returns TSPM_ABI_VERSION */
 /* Static string for a status code. */
@@ -495,6 +497,33 @@ int tspm_adam_step(int64_t count, float* param, const float* grad, float* exp_av
  * MML_Suite/models/msa/utt_fusion.py:188-190).  g' = (g * grad_scale) * clip_coef. */
 int tspm_adam_step_clip(int64_t count, float* param, const float* grad, float* exp_avg, float* exp_avg_sq,
                         const tspm_adam_hyper* hyper, const float* clip_coef, tspm_stream_t stream);
+/* Several FusedAdam groups in one launch each (added under ABI 23): `segs` is a HOST array of `count` segments,
+ * 1 <= count <= TSPM_ADAM_MAX_SEGMENTS, copied into the kernel arguments (nothing of it is read after the call
+ * returns).  A segment is one group's flat buffers with its own device tspm_adam_hyper (lr, betas, eps, weight decay,
+ * grad_scale and step all per segment); a segment with count 0 is empty: its buffers are never touched and may be
+ * NULL.  Every non-empty segment needs non-NULL, 16-byte-aligned param / grad / exp_avg / exp_avg_sq and a non-NULL
+ * hyper; any violation, a negative count or a count outside 1..8 is TSPM_ERR_INVALID before any launch.
+ * tspm_adam_begin_multi: hyper->step += 1 for every segment whose hyper is non-NULL (an empty segment's too), one
+ * launch of one thread that takes the segments in order (a hyper named by two segments advances twice).
+ * tspm_adam_step_multi: every non-empty segment updated in ONE launch.  Each workgroup belongs to exactly one
+ * segment: the host gives a segment cdiv(count/4 + 1, 256) workgroups (tspm_adam_step's grid), scaled down
+ * proportionally to about 2048 in total with at least one per non-empty segment, and passes the prefix of that
+ * partition in the kernel arguments; a workgroup finds its segment by scanning those <= 8 entries and runs
+ * tspm_adam_step's element loop (f32x4 body, scalar tail for count & 3) with that segment's constants.  No atomics,
+ * no communication between workgroups, no table in memory.  Adam is element-wise, so each segment's param / exp_avg /
+ * exp_avg_sq are bitwise those of tspm_adam_step on it alone — with clip_coef (device scalar, nullable) those of
+ * tspm_adam_step_clip.  Segments must not overlap.  With every segment empty the call launches nothing. */
+#define TSPM_ADAM_MAX_SEGMENTS 8
+typedef struct tspm_adam_seg {
+  float* param;
+  const float* grad;
+  float* exp_avg;
+  float* exp_avg_sq;
+  int64_t count;           /* >= 0; 0 = an empty segment, skipped */
+  tspm_adam_hyper* hyper;  /* device */
+} tspm_adam_seg;
+int tspm_adam_begin_multi(int32_t count, const tspm_adam_seg* segs, tspm_stream_t stream);
+int tspm_adam_step_multi(int32_t count, const tspm_adam_seg* segs, const float* clip_coef, tspm_stream_t stream);
 
 /* ABI 20: tspm_conv_bwd that also carries an Adam update: `blocks` extra workgroups of the same grid run
  * tspm_adam_step's element loop over `count` elements starting at param / grad / exp_avg / exp_avg_sq (a range of
@@ -886,6 +915,23 @@ int tspm_textcnn_bwd(int32_t batch, int32_t steps, int32_t feat, int32_t nconv, 
 size_t tspm_grad_clip_workspace(void);
 int tspm_grad_clip_coef(int64_t count, const float* grad, float grad_scale, float max_norm, float* coef,
                         float* total_norm, void* workspace, size_t workspace_bytes, tspm_stream_t stream);
+/* clip_grad_norm_ over several gradient buffers (added under ABI 23): total = the 2-norm of all `ranges` together (a
+ * HOST array of `count` ranges, 1 <= count <= TSPM_ADAM_MAX_SEGMENTS, copied into the kernel arguments; a range with
+ * count 0 is skipped and may have a NULL grad), in the two launches of tspm_grad_clip_coef: one sum-of-squares launch
+ * of 512 workgroups writing double partials, each workgroup summing a slice of ONE range, then the same coefficient
+ * kernel.  A non-empty range gets 1 + floor((512 - n) * count / total) workgroups (n = the number of non-empty
+ * ranges, total = the sum of their counts); workgroups left over write a zero partial.  The partition depends on the
+ * counts alone, so equal inputs give equal bits; with count == 1 it is tspm_grad_clip_coef's and *coef and
+ * *total_norm are bitwise that call's.  Otherwise the squares are summed in another order: in double, so only the
+ * final rounding to float can differ.  coef, total_norm, workspace and the status codes as tspm_grad_clip_coef
+ * (TSPM_ERR_INVALID also for a negative count, a NULL grad of a non-empty range, or no element at all). */
+typedef struct tspm_grad_range {
+  const float* grad;
+  int64_t count;
+} tspm_grad_range;
+int tspm_grad_clip_coef_multi(int32_t count, const tspm_grad_range* ranges, float grad_scale, float max_norm,
+                              float* coef, float* total_norm, void* workspace, size_t workspace_bytes,
+                              tspm_stream_t stream);
 /* Padded batch assembly (data/mosi.py:202-232 pad_sequence + the step's .to(device)) from a ragged
  * corpus data[rows][feat] (sample s = rows offsets[s] .. offsets[s]+lengths[s]-1): out[t*stride_t +
  * b*stride_b + f] = sample index[b]'s row t (0 past its length) * row_mask[b] (nullable), for

@@ -90,6 +90,18 @@ class AdamHyper(Structure):
                 ("step", c_int64), ("pad_", c_int64)]
 
 HYPER_STEP_OFFSET = 48  # byte offset of tspm_adam_hyper.step
+ADAM_MAX_SEGMENTS = 8   # TSPM_ADAM_MAX_SEGMENTS: the most groups of tspm_adam_*_multi / tspm_grad_clip_coef_multi
+
+
+class AdamSeg(Structure):
+    """tspm_adam_seg (added under ABI 23): one FusedAdam group's flat buffers and its own device tspm_adam_hyper."""
+    _fields_ = [("param", c_void_p), ("grad", c_void_p), ("exp_avg", c_void_p), ("exp_avg_sq", c_void_p),
+                ("count", c_int64), ("hyper", c_void_p)]
+
+
+class GradRange(Structure):
+    """tspm_grad_range (added under ABI 23): one gradient buffer of tspm_grad_clip_coef_multi."""
+    _fields_ = [("grad", c_void_p), ("count", c_int64)]
 
 
 class LinearBwdDesc(Structure):
@@ -351,6 +363,10 @@ _SIGS = {
     "tspm_grad_clip_coef": (c_int32, [c_int64, _P, c_float, c_float, _P, _P, _P, c_size_t, _P]),
     "tspm_seq_gather": (c_int32, [c_int32, _P, c_int64, _P, _P, _P, c_int32, c_int32, _P, c_int64, c_int64, _P, _P, _P,
                                   _P]),
+    # added under ABI 23: up to 8 FusedAdam groups in the optimizer launches of one (host arrays of segments / ranges)
+    "tspm_adam_begin_multi": (c_int32, [c_int32, POINTER(AdamSeg), _P]),
+    "tspm_adam_step_multi": (c_int32, [c_int32, POINTER(AdamSeg), _P, _P]),
+    "tspm_grad_clip_coef_multi": (c_int32, [c_int32, POINTER(GradRange), c_float, c_float, _P, _P, _P, c_size_t, _P]),
     # ABI 23: the monomodal pre-training head in one launch
     "tspm_mono_head_step": (c_int32, [POINTER(MonoHeadDesc), _P]),
     # added under ABI 23 (no existing signature changed): the multi-label (BCEWithLogits) form of that head, for the MMIMDb encoders

@@ -399,6 +399,69 @@ __global__ __launch_bounds__(256) void k_adam(long long count, float* __restrict
   }
 }
 
+// Several Adam groups in one launch (tspm_adam_step_multi).  The host's partition travels in the kernel arguments:
+// workgroups first[s] .. first[s+1]-1 belong to segment s (an empty segment has none).
+struct AdamSegs {
+  float* p[TSPM_ADAM_MAX_SEGMENTS];
+  const float* g[TSPM_ADAM_MAX_SEGMENTS];
+  float* m[TSPM_ADAM_MAX_SEGMENTS];
+  float* v[TSPM_ADAM_MAX_SEGMENTS];
+  const tspm_adam_hyper* h[TSPM_ADAM_MAX_SEGMENTS];
+  long long count[TSPM_ADAM_MAX_SEGMENTS];
+  int first[TSPM_ADAM_MAX_SEGMENTS + 1];
+  int nseg;
+};
+
+struct AdamHypers {
+  tspm_adam_hyper* h[TSPM_ADAM_MAX_SEGMENTS];
+  int nseg;
+};
+
+__global__ void k_adam_begin_multi(AdamHypers a) {
+#pragma unroll
+  for (int s = 0; s < TSPM_ADAM_MAX_SEGMENTS; ++s)
+    if (s < a.nseg && a.h[s]) a.h[s]->step += 1;
+}
+
+// k_adam's element loop per segment (adam_consts / adam_update: bitwise tspm_adam_step[_clip] on the segment alone)
+__global__ __launch_bounds__(256) void k_adam_multi(AdamSegs a, const float* __restrict__ clip) {
+  int s = 0;  // the last segment whose first workgroup is <= this one (empty segments share the next one's start)
+#pragma unroll
+  for (int i = 1; i < TSPM_ADAM_MAX_SEGMENTS; ++i)
+    if (i < a.nseg && (int)blockIdx.x >= a.first[i]) s = i;
+  const long long count = a.count[s];
+  float* __restrict__ p = a.p[s];
+  const float* __restrict__ g = a.g[s];
+  float* __restrict__ m = a.m[s];
+  float* __restrict__ v = a.v[s];
+  const int blk = (int)blockIdx.x - a.first[s], nblk = a.first[s + 1] - a.first[s];
+  __shared__ AdamConsts sh;
+  if (threadIdx.x == 0) sh = adam_consts(a.h[s]);
+  __syncthreads();
+  const AdamConsts c = sh;
+  const float cc = clip ? clip[0] : 1.f;
+  auto upd = [&](float& pp, float gg, float& mm, float& vv) { adam_update(pp, gg, mm, vv, c, clip != nullptr, cc); };
+  const long long n4 = count >> 2;
+  for (long long i = blk * 256LL + threadIdx.x; i < n4; i += (long long)nblk * 256) {
+    f32x4 pp = ld4(p + 4 * i), gg = ld4(g + 4 * i), mm = ld4(m + 4 * i), vv = ld4(v + 4 * i);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      float x = pp[j], y = mm[j], z = vv[j];
+      upd(x, gg[j], y, z);
+      pp[j] = x; mm[j] = y; vv[j] = z;
+    }
+    st4(p + 4 * i, pp);
+    st4(m + 4 * i, mm);
+    st4(v + 4 * i, vv);
+  }
+  if (blk == 0 && threadIdx.x < (count & 3)) {
+    const long long i = (n4 << 2) + threadIdx.x;
+    float x = p[i], y = m[i], z = v[i];
+    upd(x, g[i], y, z);
+    p[i] = x; m[i] = y; v[i] = z;
+  }
+}
+
 __global__ __launch_bounds__(256) void k_image_lut(long long count, const uint8_t* __restrict__ u8,
                                                    const uint8_t* __restrict__ lut, float* __restrict__ out) {
   for (long long i = blockIdx.x * 256LL + threadIdx.x; i < count; i += (long long)gridDim.x * 256)
@@ -654,6 +717,61 @@ extern "C" int tspm_adam_step_clip(int64_t count, float* param, const float* gra
   if (blocks > 2048) blocks = 2048;
   hipLaunchKernelGGL(k_adam, dim3((int)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), (long long)count, param,
                      grad, exp_avg, exp_avg_sq, hyper, clip_coef);
+  TSPM_LAUNCH_CHECK();
+  return TSPM_OK;
+}
+
+namespace {
+// The checks shared by tspm_adam_begin_multi and tspm_adam_step_multi (before any launch).
+bool adam_segs_valid(int32_t count, const tspm_adam_seg* segs) {
+  if (count < 1 || count > TSPM_ADAM_MAX_SEGMENTS || !segs) return false;
+  for (int s = 0; s < count; ++s) {
+    const tspm_adam_seg& g = segs[s];
+    if (g.count < 0) return false;
+    if (g.count == 0) continue;
+    if (!g.param || !g.grad || !g.exp_avg || !g.exp_avg_sq || !g.hyper) return false;
+    if (!aligned16(g.param) || !aligned16(g.grad) || !aligned16(g.exp_avg) || !aligned16(g.exp_avg_sq)) return false;
+  }
+  return true;
+}
+}  // namespace
+
+extern "C" int tspm_adam_begin_multi(int32_t count, const tspm_adam_seg* segs, tspm_stream_t stream) {
+  if (!adam_segs_valid(count, segs)) return TSPM_ERR_INVALID;
+  AdamHypers a{};
+  a.nseg = count;
+  bool any = false;
+  for (int s = 0; s < count; ++s) any |= (a.h[s] = segs[s].hyper) != nullptr;
+  if (!any) return TSPM_OK;
+  hipLaunchKernelGGL(k_adam_begin_multi, dim3(1), dim3(1), 0, static_cast<hipStream_t>(stream), a);
+  TSPM_LAUNCH_CHECK();
+  return TSPM_OK;
+}
+
+extern "C" int tspm_adam_step_multi(int32_t count, const tspm_adam_seg* segs, const float* clip_coef,
+                                    tspm_stream_t stream) {
+  if (!adam_segs_valid(count, segs)) return TSPM_ERR_INVALID;
+  constexpr long long kMaxBlocks = 2048;  // tspm_adam_step's grid limit, here for all segments together
+  long long want[TSPM_ADAM_MAX_SEGMENTS], sum = 0;
+  for (int s = 0; s < count; ++s) {
+    want[s] = segs[s].count > 0 ? std::min<long long>(cdiv64(segs[s].count / 4 + 1, 256), kMaxBlocks) : 0;
+    sum += want[s];
+  }
+  if (sum == 0) return TSPM_OK;
+  AdamSegs a{};
+  a.nseg = count;
+  int at = 0;
+  for (int s = 0; s < count; ++s) {
+    const tspm_adam_seg& g = segs[s];
+    a.p[s] = g.param; a.g[s] = g.grad; a.m[s] = g.exp_avg; a.v[s] = g.exp_avg_sq; a.h[s] = g.hyper;
+    a.count[s] = g.count;
+    a.first[s] = at;
+    long long b = want[s];
+    if (sum > kMaxBlocks && b > 0) b = std::max<long long>(1, b * kMaxBlocks / sum);  // proportional, <= 2048 in all
+    at += (int)b;
+  }
+  for (int s = count; s <= TSPM_ADAM_MAX_SEGMENTS; ++s) a.first[s] = at;
+  hipLaunchKernelGGL(k_adam_multi, dim3(at), dim3(256), 0, static_cast<hipStream_t>(stream), a, clip_coef);
   TSPM_LAUNCH_CHECK();
   return TSPM_OK;
 }

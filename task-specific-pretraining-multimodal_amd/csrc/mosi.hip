@@ -554,6 +554,39 @@ __global__ __launch_bounds__(256) void k_sumsq(long long count, const float* __r
   if (threadIdx.x == 0) partial[blockIdx.x] = red[0];
 }
 
+// k_sumsq over several buffers (tspm_grad_clip_coef_multi): workgroups first[r] .. first[r+1]-1 sum range r with
+// k_sumsq's loop and tree (one range over all kClipBlocks workgroups is k_sumsq bit for bit); the workgroups past
+// first[nrange] write a zero partial, so k_clip_coef always reads kClipBlocks of them.
+struct GradRanges {
+  const float* g[TSPM_ADAM_MAX_SEGMENTS];
+  long long count[TSPM_ADAM_MAX_SEGMENTS];
+  int first[TSPM_ADAM_MAX_SEGMENTS + 1];
+  int nrange;
+};
+
+__global__ __launch_bounds__(256) void k_sumsq_multi(GradRanges a, float gs, double* __restrict__ partial) {
+  __shared__ double red[256];
+  int r = 0;  // the last range whose first workgroup is <= this one (empty ranges share the next one's start)
+#pragma unroll
+  for (int i = 1; i < TSPM_ADAM_MAX_SEGMENTS; ++i)
+    if (i < a.nrange && (int)blockIdx.x >= a.first[i]) r = i;
+  const int blk = (int)blockIdx.x - a.first[r], nblk = a.first[r + 1] - a.first[r];
+  const long long count = blk < nblk ? a.count[r] : 0;  // a left-over workgroup sums nothing
+  const float* __restrict__ g = a.g[r];
+  double s = 0.0;
+  for (long long i = blk * 256LL + threadIdx.x; i < count; i += (long long)nblk * 256) {
+    const double v = (double)(g[i] * gs);
+    s += v * v;
+  }
+  red[threadIdx.x] = s;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if (threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) partial[blockIdx.x] = red[0];
+}
+
 // one workgroup: strided partial sums then a fixed-order LDS tree (deterministic; all loads in flight
 // together instead of one thread's dependent chain)
 __global__ __launch_bounds__(256) void k_clip_coef(int nparts, const double* __restrict__ partial, float max_norm,
@@ -878,6 +911,39 @@ extern "C" int tspm_grad_clip_coef(int64_t count, const float* grad, float grad_
   hipStream_t st = static_cast<hipStream_t>(stream);
   double* part = static_cast<double*>(workspace);
   hipLaunchKernelGGL(k_sumsq, dim3(kClipBlocks), dim3(256), 0, st, (long long)count, grad, grad_scale, part);
+  TSPM_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_clip_coef, dim3(1), dim3(256), 0, st, kClipBlocks, part, max_norm, coef, total_norm);
+  TSPM_LAUNCH_CHECK();
+  return TSPM_OK;
+}
+
+extern "C" int tspm_grad_clip_coef_multi(int32_t count, const tspm_grad_range* ranges, float grad_scale, float max_norm,
+                                         float* coef, float* total_norm, void* workspace, size_t workspace_bytes,
+                                         tspm_stream_t stream) {
+  if (count < 1 || count > TSPM_ADAM_MAX_SEGMENTS || !ranges || !coef || !(max_norm > 0.f)) return TSPM_ERR_INVALID;
+  int nonempty = 0;
+  unsigned long long total = 0;
+  for (int r = 0; r < count; ++r) {
+    if (ranges[r].count < 0 || (ranges[r].count > 0 && !ranges[r].grad)) return TSPM_ERR_INVALID;
+    if (ranges[r].count > 0) { ++nonempty; total += (unsigned long long)ranges[r].count; }
+  }
+  if (nonempty == 0) return TSPM_ERR_INVALID;
+  if (!workspace || workspace_bytes < tspm_grad_clip_workspace()) return TSPM_ERR_WORKSPACE;
+  // the partition, from the counts alone: one workgroup per non-empty range, the rest in proportion (rounded down)
+  GradRanges a{};
+  a.nrange = count;
+  int at = 0;
+  for (int r = 0; r < count; ++r) {
+    a.g[r] = ranges[r].grad;
+    a.count[r] = ranges[r].count;
+    a.first[r] = at;
+    if (ranges[r].count > 0)  // exact: the shares sum to at most kClipBlocks - nonempty
+      at += 1 + (int)((unsigned __int128)(kClipBlocks - nonempty) * (unsigned long long)ranges[r].count / total);
+  }
+  for (int r = count; r <= TSPM_ADAM_MAX_SEGMENTS; ++r) a.first[r] = at;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  double* part = static_cast<double*>(workspace);
+  hipLaunchKernelGGL(k_sumsq_multi, dim3(kClipBlocks), dim3(256), 0, st, a, grad_scale, part);
   TSPM_LAUNCH_CHECK();
   hipLaunchKernelGGL(k_clip_coef, dim3(1), dim3(256), 0, st, kClipBlocks, part, max_norm, coef, total_norm);
   TSPM_LAUNCH_CHECK();

@@ -46,6 +46,17 @@ lengths)``): the pooling runs in ``tspm_textcnn_pool_fwd_len`` over each row's o
 — the TextCNN of the row's first ``L_b`` steps, whatever the padding — independent of ``ragged`` and a further trailing
 key element.  The loaders' zero padding is a precondition for rows shorter than a kernel height (include/tspm.h).
 
+Frozen encoders and several Adam groups (the second stage on pre-trained encoders): an encoder module (``netA`` /
+``netV`` / ``netT``) none of whose parameters has ``requires_grad`` is frozen — PyTorch's semantics: the forward is
+unchanged (the training-mode TextCNN dropout of a frozen ``netT`` included), its backward is skipped and its parameters
+get no gradient and no update.  ``MosiEngine`` learns the frozen set when it is built (a trailing ``("frozen", names)``
+element of the engine and ``fused_step`` keys, only when something is frozen); ``FusedMosiStep`` takes a ``FusedAdam`` of
+1..8 param groups (``finetune_param_groups`` builds the usual ones) and keeps the optimizer phase at four launches for
+any number of them (``tspm_grad_clip_coef_multi``, ``tspm_adam_begin_multi``, ``tspm_adam_step_multi``).  Mixed flags
+inside a module, a ``netC`` that is not fully trainable, a trainable parameter in no group, ``allreduce`` with several
+groups, and a ``FusedAdam`` whose flat buffers (fixed when it was built) are not exactly the parameters that train now
+are refused (``check_param_groups``): set the flags first, then build the optimizer.
+
 Sentiment regression (this project's addition; the reference's YAMLs train the three-class variant only): a
 one-output ``netC.fc_out`` (``build_utt_fusion(name, output_dim=1)``) with a single mean ``nn.L1Loss`` / ``nn.MSELoss``
 term (``_regress_term``) on the float32 ``regression_labels`` runs the same steps with the head — ``fc_out``, the loss,
@@ -336,6 +347,122 @@ def _text_lengths_key(key: tuple, text_lengths: bool) -> tuple:
     return key + ("text_lengths",) if text_lengths else key
 
 
+ENCODER_MODULES = (("audio", "netA"), ("video", "netV"), ("text", "netT"))  # modality -> attribute, in key order
+
+
+def _frozen_state(model: "UttFusionModel"):
+    """(frozen, error): ``frozen`` = the modalities, in audio / video / text order, whose encoder module has no
+    parameter with ``requires_grad``; ``error`` = why the model cannot be TRAINED on this path (an encoder with mixed
+    flags — freezing inside a module is not built — or a ``netC`` that is not fully trainable), or None.  Forward-only
+    users never see the error."""
+    frozen, error = [], None
+    for name, attr in ENCODER_MODULES:
+        flags = [(n, p.requires_grad) for n, p in getattr(model, attr).named_parameters()]
+        if not any(f for _, f in flags):
+            frozen.append(name)
+        elif not all(f for _, f in flags) and error is None:
+            off = [n for n, f in flags if not f]
+            error = (f"{attr}: mixed requires_grad flags ({attr}.{off[0]} is frozen, others are not) - an encoder is "
+                     f"trained or frozen as a whole")
+    off = [n for n, p in model.netC.named_parameters() if not p.requires_grad]
+    if off and error is None:
+        error = f"netC: every classifier parameter must be trainable (netC.{off[0]} is frozen)"
+    return tuple(frozen), error
+
+
+def frozen_encoders(model: "UttFusionModel") -> tuple:
+    """The frozen encoders of a model to be trained, as modality names in audio / video / text order (``()``: everything
+    trains).  An encoder module (``netA`` / ``netV`` / ``netT``) is frozen when none of its parameters has
+    ``requires_grad``.  Raises ``TspmError`` naming the module for an encoder with mixed flags or a ``netC`` that is not
+    fully trainable."""
+    frozen, error = _frozen_state(model)
+    if error is not None:
+        raise L.TspmError(f"UttFusionModel HIP path: {error}")
+    return frozen
+
+
+def _frozen_key(key: tuple, frozen: tuple) -> tuple:
+    """A cache key with the frozen set in it, after the ragged / text_lengths elements: unchanged when nothing is
+    frozen."""
+    return key + (("frozen", tuple(frozen)),) if frozen else key
+
+
+def check_param_groups(model: "UttFusionModel", param_groups, allreduce=None, flat_groups=None) -> tuple:
+    """What FusedMosiStep asks of (model, optimizer.param_groups, optimizer.flat_groups()) before it builds anything; →
+    the frozen set.  Refused with a ``TspmError`` that names the module or parameter: an encoder with mixed flags, a
+    ``netC`` not fully trainable (``frozen_encoders``), a trainable parameter in no group (it would get a gradient and
+    never an update), a parameter in two groups, more than ``L.ADAM_MAX_SEGMENTS`` groups with trainable parameters, and
+    ``allreduce`` with more than one such group (data parallelism with several groups is not built).  ``flat_groups``
+    (``FusedAdam.flat_groups()``; None: the groups' parameters by their current flags) is what the kernels update and
+    what the clip norm spans: FusedAdam moved the parameters that were trainable WHEN IT WAS BUILT into its flat buffers,
+    so those must be exactly the model's trainable parameters now — a parameter frozen since would still be updated
+    (weight decay, stale gradients in the norm), one unfrozen since has no gradient buffer; both are refused."""
+    frozen = frozen_encoders(model)
+    seen: Dict[int, int] = {}
+    names = {id(p): n for n, p in model.named_parameters()}
+    if flat_groups is None:
+        updated = [[p for p in group["params"] if p.requires_grad] for group in param_groups]
+        updated = [ps for ps in updated if ps]
+    else:
+        updated = [list(fg.params) for fg in flat_groups]
+    live = len(updated)
+    for gi, group in enumerate(param_groups):
+        for p in group["params"]:
+            if id(p) in seen:
+                raise L.TspmError(f"FusedMosiStep: parameter {names.get(id(p), '?')} is in parameter groups {seen[id(p)]} "
+                                  f"and {gi}")
+            seen[id(p)] = gi
+    for n, p in model.named_parameters():
+        if p.requires_grad and id(p) not in seen:
+            raise L.TspmError(f"FusedMosiStep: trainable parameter {n} is in no FusedAdam parameter group (freeze its "
+                              f"module with requires_grad_(False) or give it to the optimizer)")
+    flat = {id(p) for ps in updated for p in ps}
+    for ps in updated:
+        for p in ps:
+            if not p.requires_grad or id(p) not in names:
+                raise L.TspmError(f"FusedMosiStep: parameter {names.get(id(p), '(not of this model)')} is in FusedAdam's "
+                                  f"flat buffers but is not a trainable parameter of the model - frozen after the "
+                                  f"optimizer was built? It would still be updated: rebuild FusedAdam")
+    for n, p in model.named_parameters():
+        if p.requires_grad and id(p) not in flat:
+            raise L.TspmError(f"FusedMosiStep: trainable parameter {n} is not in FusedAdam's flat buffers - unfrozen "
+                              f"after the optimizer was built? It has no gradient buffer: rebuild FusedAdam")
+    if not 1 <= live <= L.ADAM_MAX_SEGMENTS:
+        raise L.TspmError(f"FusedMosiStep: 1..{L.ADAM_MAX_SEGMENTS} FusedAdam parameter groups with trainable parameters "
+                          f"(one optimizer phase for all of them), got {live}")
+    if allreduce is not None and live > 1:
+        raise L.TspmError("FusedMosiStep: allreduce (data parallelism) with more than one parameter group is not built")
+    return frozen
+
+
+def finetune_param_groups(model: "UttFusionModel", *, lr: float, weight_decay: float, encoder_lr: Optional[float] = None,
+                          encoder_weight_decay: Optional[float] = None, freeze: Sequence[str] = ()) -> List[Dict[str, Any]]:
+    """The second-stage experiments on pre-trained encoders as ``FusedAdam`` param groups.  ``freeze``: a subset of
+    ("audio", "video", "text") - those encoders get ``requires_grad_(False)`` (the step then skips their backward and
+    they are in no group).  → ``[classifier group]`` with the remaining encoders folded in when ``encoder_lr`` and
+    ``encoder_weight_decay`` are both None, else ``[classifier group, encoder group]`` with the encoders at
+    ``encoder_lr`` / ``encoder_weight_decay`` (each defaulting to the classifier's value) - the reference's
+    ``training.encoder_optimizer`` form.  With every encoder frozen there is no encoder group."""
+    mods = dict(ENCODER_MODULES)
+    bad = [f for f in freeze if f not in mods]
+    if bad or len(set(freeze)) != len(tuple(freeze)):
+        raise L.TspmError(f"finetune_param_groups: freeze is a subset of {tuple(mods)}, got {tuple(freeze)!r}")
+    enc: List[torch.Tensor] = []
+    for name, attr in ENCODER_MODULES:
+        if name in freeze:
+            getattr(model, attr).requires_grad_(False)
+        else:
+            enc += list(getattr(model, attr).parameters())
+    head = dict(params=list(model.netC.parameters()), lr=float(lr), weight_decay=float(weight_decay))
+    if encoder_lr is None and encoder_weight_decay is None:
+        head["params"] = enc + head["params"]  # model.parameters() order: encoders, then netC
+        return [head]
+    if not enc:
+        return [head]
+    return [head, dict(params=enc, lr=float(lr if encoder_lr is None else encoder_lr),
+                       weight_decay=float(weight_decay if encoder_weight_decay is None else encoder_weight_decay))]
+
+
 def _split_lengths(lengths) -> tuple:
     """(ragged, text_lengths) of a ``lengths`` argument: a ``"text"`` key asks for the TextCNN's length input; anything
     else — an empty dict too, as before — for the ragged LSTM recurrences.  ``{"text": ...}`` alone is text-only."""
@@ -531,6 +658,11 @@ class MosiEngine:
                  text_lengths: bool = False):
         self.m, self.B, self.T, self.device = model, batch, norm_steps(steps), device
         self.ragged, self.text_lengths = bool(ragged), bool(text_lengths)
+        # the frozen encoders (no parameter with requires_grad): their backward is skipped.  What cannot be trained (mixed
+        # flags, a frozen netC) is looked up by ``backward``, from the flags of that moment - the forward runs whatever
+        # the flags are
+        self.frozen = _frozen_state(model)[0]
+        self.trains = {k: nm not in self.frozen for k, nm in (("a", "audio"), ("v", "video"), ("t", "text"))}
         a, v, t, c = model.netA, model.netV, model.netT, model.netC
         f = dict(device=device, dtype=torch.float32)
         B = batch
@@ -548,8 +680,8 @@ class MosiEngine:
         self.fused = torch.zeros(B, self.E, **f)
         # one launch runs both recurrences: 16-bit index buffers for both when either is "maxpool" past 256 steps
         self.wide = L.lstm_wide_index(((a.embd_method, Ta), (v.embd_method, Tv)))
-        self.lstm = {name: _lstm_alloc(enc, B, T_m, device, wide=self.wide)
-                     for name, enc, T_m in (("a", a, Ta), ("v", v, Tv))}
+        self.lstm = {name: _lstm_alloc(enc, B, T_m, device, backward=self.trains[name], wide=self.wide)
+                     for name, enc, T_m in (("a", a, Ta), ("v", v, Tv))}  # a frozen LSTM keeps no dg buffer
         # ragged mode: one persistent int32 [B] length buffer per LSTM encoder, read by tspm_lstm_fwd_len / _bwd_len
         self.lens = {"a": _length_buffer(B, Ta, device), "v": _length_buffer(B, Tv, device)} if self.ragged else None
         # text_lengths: the TextCNN's own persistent int32 [B] length buffer, read by tspm_textcnn_pool_fwd_len
@@ -583,8 +715,11 @@ class MosiEngine:
         self.keep_override: Optional[Dict[str, torch.Tensor]] = None
         self.rng_ctr_ptr: Optional[int] = None
         self._host_ctr: Optional[torch.Tensor] = None
-        (sa, sv), self.wg_ws = _lstm_wgrad_plan(B, ((a, Ta), (v, Tv)), device)
-        self.wg_splits = {"a": sa, "v": sv}
+        plans = [(name, enc, T_m) for name, enc, T_m in (("a", a, Ta), ("v", v, Tv)) if self.trains[name]]
+        self.wg_splits, self.wg_ws = {}, None  # the weight-gradient GEMMs of the trainable LSTMs
+        if plans:
+            sps, self.wg_ws = _lstm_wgrad_plan(B, [(enc, T_m) for _, enc, T_m in plans], device)
+            self.wg_splits = {name: sp for (name, _, _), sp in zip(plans, sps)}
         self.concurrent = os.environ.get("TSPM_MOSI_SERIAL", "0") != "1"
         self.side: Optional[torch.cuda.Stream] = None
         self.clip_coef = torch.ones(1, **f)
@@ -778,7 +913,16 @@ class MosiEngine:
 
     # -- backward -----------------------------------------------------------------------------------
     def backward(self, sh: int, from_head: bool = True) -> None:
-        """``from_head=False``: ``dh[-1]`` and ``fc_out``'s gradients are already written (``head_regress``)."""
+        """``from_head=False``: ``dh[-1]`` and ``fc_out``'s gradients are already written (``head_regress``).  A frozen
+        encoder's backward is skipped: no tspm_lstm_bwd* problem, weight-gradient GEMMs or ``dg`` buffer for a frozen
+        LSTM (no launch and no side-stream fork with both frozen), no ``_text_backward`` for a frozen ``netT``, and with
+        all three frozen layer 0's ``linear_bwd`` gets no ``dx``: ``dfused`` is never written."""
+        frozen, error = self.m.flag_state()[1]  # the flags now, not those of the engine's construction
+        if error is not None:
+            raise L.TspmError(f"UttFusionModel HIP path: {error}")
+        if frozen != self.frozen:
+            raise L.TspmError(f"MosiEngine: requires_grad flags changed since this engine was planned (frozen then: "
+                              f"{self.frozen}, now: {frozen})")
         lib, m, g = L.lib(), self.m, self.grad_of
         B = self.B
         c = m.netC
@@ -806,8 +950,17 @@ class MosiEngine:
                 dy = self.dh[j]
             xin, fin = (self.h[j - 1], self.widths[j - 1]) if j > 0 else (self.fused, self.E)
             dx, lddx = (self.dh[j - 1], self.widths[j - 1]) if j > 0 else (self.dfused, self.E)
+            if j == 0 and not any(self.trains.values()):
+                dx = None  # every encoder frozen: nothing reads the embeddings' gradient
             linear_bwd(B, fin, w, xin.data_ptr(), fin, dy.data_ptr(), w, lins[j].weight.data_ptr(),
-                       g(lins[j].weight).data_ptr(), g(lins[j].bias).data_ptr(), dx.data_ptr(), lddx, sh)
+                       g(lins[j].weight).data_ptr(), g(lins[j].bias).data_ptr(), L.ptr(dx), lddx, sh)
+        lstm, text = self.trains["a"] or self.trains["v"], self.trains["t"]
+        if not (lstm and text):  # a frozen half: the other one (if any) on the caller's stream, no fork
+            if text:
+                self._backward_text(sh)
+            if lstm:
+                self._backward_lstm(sh)
+            return
         if self.concurrent:
             side, sh_side = self._fork()
             with torch.cuda.stream(side):
@@ -829,15 +982,28 @@ class MosiEngine:
         lib, m, g = L.lib(), self.m, self.grad_of
         B, (Ta, Tv, _) = self.B, self.Ts
         # LSTMs: backward through time (one launch for both), then the weight gradients as GEMMs over T_m*B rows
+        encs = [e for e in (("a", m.netA, self.A, 0, Ta), ("v", m.netV, self.V, m.netA.hidden_size, Tv))
+                if self.trains[e[0]]]  # a frozen LSTM is no problem of the launch
         _lstm_bwd_launch([(enc, self.lstm[name], T_m, self.dfused.data_ptr() + col * 4, self.E,
-                           self.lens[name] if self.ragged else None)
-                          for name, enc, col, T_m in (("a", m.netA, 0, Ta), ("v", m.netV, m.netA.hidden_size, Tv))],
+                           self.lens[name] if self.ragged else None) for name, enc, _, col, T_m in encs],
                          B, sh, self.wide)
-        for name, enc, x, T_m in (("a", m.netA, self.A, Ta), ("v", m.netV, self.V, Tv)):
+        for name, enc, x, _, T_m in encs:
             _lstm_wgrad(enc, x, self.lstm[name], B, T_m, self.wg_splits[name], self.wg_ws, g, sh)
 
-    def clip(self, sh: int, flat_grad: torch.Tensor, grad_scale: float) -> None:
-        """clip_grad_norm_(model.parameters(), clip) coefficient into ``clip_coef`` (utt_fusion.py:188-189)."""
+    def clip(self, sh: int, flat_grad, grad_scale: float) -> None:
+        """clip_grad_norm_(model.parameters(), clip) coefficient into ``clip_coef`` (utt_fusion.py:188-189).
+        ``flat_grad``: the optimizer's flat gradient buffer, or a list of them (one per FusedAdam group) - with more than
+        one the norm spans them all in ``tspm_grad_clip_coef_multi``'s two launches.  A frozen parameter is in no flat
+        buffer, as clip_grad_norm_ skips parameters without gradients."""
+        if isinstance(flat_grad, (list, tuple)) and len(flat_grad) == 1:
+            flat_grad = flat_grad[0]
+        if isinstance(flat_grad, (list, tuple)):
+            ranges = (L.GradRange * len(flat_grad))(*[L.GradRange(t.data_ptr(), t.numel()) for t in flat_grad])
+            L.check(L.lib().tspm_grad_clip_coef_multi(len(flat_grad), ranges, grad_scale, float(self.m.clip),
+                                                      self.clip_coef.data_ptr(), self.total_norm.data_ptr(),
+                                                      self.clip_ws.data_ptr(), self.clip_ws.numel() * 4, sh),
+                    "grad_clip_multi")
+            return
         L.check(L.lib().tspm_grad_clip_coef(flat_grad.numel(), flat_grad.data_ptr(), grad_scale, float(self.m.clip),
                                             self.clip_coef.data_ptr(), self.total_norm.data_ptr(),
                                             self.clip_ws.data_ptr(), self.clip_ws.numel() * 4, sh), "grad_clip")
@@ -1001,9 +1167,12 @@ class FusedMosiStep:
         dev = next(model.parameters()).device
         if dev.type != "cuda":
             raise L.TspmError("FusedMosiStep runs on the MI355X: move the model to cuda first")
+        # 1..8 groups (the clip norm spans all of them); frozen encoders; refusals name the module or parameter
+        # and what FusedAdam's flat buffers hold (fixed when it was built) is exactly what trains now
         fgs = optimizer.flat_groups()
-        if len(fgs) != 1:
-            raise L.TspmError("FusedMosiStep: one FusedAdam parameter group (the clip norm spans all parameters)")
+        self.frozen = check_param_groups(model, optimizer.param_groups, allreduce, fgs)
+        self._flags = model.flag_state()[0]
+        self.multi = len(fgs) > 1
         self.model, self.opt, self.N, self.T = model, optimizer, batch, norm_steps(steps)
         self.weight = _ce_weight(loss_functions)
         self.regress = _regress_mode(model, loss_functions)  # (kind, weight): the one-launch regression head
@@ -1015,6 +1184,7 @@ class FusedMosiStep:
                               "layer of at most 128 units, a multiple of 4")
         self.ragged, self.text_lengths = bool(ragged), bool(text_lengths)
         self.eng = MosiEngine(model, batch, steps, dev, ragged=self.ragged, text_lengths=self.text_lengths)
+        # the dropout counter is group 0's step (all groups advance together)
         self.eng.rng_ctr_ptr = fgs[0].hyper.data_ptr() + L.HYPER_STEP_OFFSET
         if model.clip is not None:
             optimizer.clip_coef = self.eng.clip_coef
@@ -1053,6 +1223,11 @@ class FusedMosiStep:
 
     def _opt(self) -> None:
         sh = L.stream_handle()
+        if self.multi:  # several groups: the same four launches (sum of squares, coefficient, counters, update)
+            if self.model.clip is not None:
+                self.eng.clip(sh, [fg.grad for fg in self.opt.flat_groups()], self.opt.grad_scale)
+            self.opt.launch_multi(sh)
+            return
         if self.model.clip is not None:
             fg = self.opt.flat_groups()[0]
             self.eng.clip(sh, fg.grad, self.opt.grad_scale)
@@ -1073,6 +1248,11 @@ class FusedMosiStep:
         return {"loss": self.eng.loss, "logits": self.eng.logits}
 
     def run(self) -> None:
+        flags, (frozen, _) = self.model.flag_state()
+        if flags != self._flags:
+            raise L.TspmError(f"FusedMosiStep: requires_grad flags changed since this step was built (frozen then: "
+                              f"{self.frozen}, now: {frozen}).  FusedAdam's flat buffers hold what was trainable when it "
+                              f"was built: build a new FusedAdam for the new flags, then take model.fused_step(...) with it")
         self.model.train()
         self.opt.sync_hyper()
         self.eng.apply_keep_override()
@@ -1204,7 +1384,8 @@ class _UttFn(torch.autograd.Function):
                 grads[id(p)] = t
             return t
         for p in model.parameters():  # allocate on this stream before the backward forks its side stream
-            grad_of(p)
+            if p.requires_grad:  # a frozen encoder's backward is skipped: no gradient, None returned
+                grad_of(p)
         eng.grad_of = grad_of
         try:
             eng.backward(L.stream_handle())
@@ -1229,11 +1410,27 @@ class UttFusionModel(nn.Module):
         self._engines: Dict[Any, MosiEngine] = {}
         self._steps: Dict[Any, FusedMosiStep] = {}
         self._fwd_generation = 0
+        self._flag_cache = None
 
     def _apply(self, fn, *args, **kwargs):
         out = super()._apply(fn, *args, **kwargs)
-        self._engines, self._steps = {}, {}
+        self._engines, self._steps, self._flag_cache = {}, {}, None
         return out
+
+    def flag_state(self):
+        """(flags, (frozen, error)): the ``requires_grad`` flags of the encoders' and the classifier's parameters as one
+        tuple, and ``_frozen_state`` of them.  Asked for on every batch (the cache keys, ``FusedMosiStep.run``), so the
+        parameter list is kept per set of modules and the answer per flag tuple: one attribute read per parameter."""
+        md = self._modules
+        mods = (md["netA"], md["netV"], md["netT"], md["netC"])
+        c = self._flag_cache
+        if c is None or c[0] != mods:  # a module swapped in (modules compare by identity)
+            c = self._flag_cache = (mods, [p for m in mods for p in m.parameters()], {})
+        flags = tuple([p.requires_grad for p in c[1]])
+        state = c[2].get(flags)
+        if state is None:
+            state = c[2][flags] = _frozen_state(self)
+        return flags, state
 
     def _engine(self, b: int, t, device, ragged: bool = False, text_lengths: bool = False) -> MosiEngine:
         """The cached MosiEngine for (batch, steps): ``t`` an ``int`` or a triple (Ta, Tv, Tt), keyed by ``norm_steps``;
@@ -1242,7 +1439,7 @@ class UttFusionModel(nn.Module):
         if torch.device(device).type != "cuda":
             raise L.TspmError("UttFusionModel (tspm_amd) runs on the MI355X only (no CPU fallback)")
         t = norm_steps(t)
-        key = _text_lengths_key(_ragged_key((b, t, device), ragged), text_lengths)
+        key = _frozen_key(_text_lengths_key(_ragged_key((b, t, device), ragged), text_lengths), self.flag_state()[1][0])
         eng = self._engines.get(key)
         if eng is None:
             eng = MosiEngine(self, b, t, device, ragged=ragged, text_lengths=text_lengths)
@@ -1259,7 +1456,8 @@ class UttFusionModel(nn.Module):
         ``text_lengths`` (independent of ``ragged``): the step whose TextCNN pooling reads ``lengths["text"]``; one more
         trailing key element."""
         steps = norm_steps(steps)
-        key = _text_lengths_key(_ragged_key((id(optimizer), id(loss_functions), int(batch), steps), ragged), text_lengths)
+        key = _frozen_key(_text_lengths_key(_ragged_key((id(optimizer), id(loss_functions), int(batch), steps), ragged),
+                                            text_lengths), self.flag_state()[1][0])
         st = self._steps.get(key)
         if st is None:
             st = FusedMosiStep(self, optimizer, loss_functions, int(batch), steps, ragged=ragged,

@@ -7,7 +7,10 @@ parameter of a group is moved into one 16-byte-aligned flat fp32 buffer (conv we
 OHWI/channels_last layout inside it) and re-pointed as a view; ``.grad`` becomes a view of a flat
 gradient buffer the HIP backward writes directly.  One ``tspm_adam_step`` launch then updates the
 whole group (28 B/param of HBM traffic).  The step counter lives on the device so a captured HIP
-graph advances the bias correction on every replay.  ``state_dict()`` has torch.optim.Adam's
+graph advances the bias correction on every replay.  ``launch`` takes two launches per param group;
+``launch_multi`` updates up to eight groups, each at its own hyper-parameters, in two launches in all
+(``tspm_adam_begin_multi`` / ``tspm_adam_step_multi``; the MOSI / MOSEI step with more than one group).
+``state_dict()`` has torch.optim.Adam's
 format (``step`` / ``exp_avg`` / ``exp_avg_sq`` per parameter).
 """
 from __future__ import annotations
@@ -131,6 +134,23 @@ class FusedAdam(torch.optim.Optimizer):
                 continue
             L.check(lib.tspm_adam_step(fg.numel, fg.param.data_ptr(), fg.grad.data_ptr(), fg.exp_avg.data_ptr(),
                                        fg.exp_avg_sq.data_ptr(), fg.hyper.data_ptr(), stream_handle), "adam_step")
+
+    def launch_multi(self, stream_handle: int) -> None:
+        """``launch`` for several groups in the launches of one (capturable): ``tspm_adam_begin_multi`` advances every
+        group's step counter and ``tspm_adam_step_multi`` updates every group — each with its own lr / betas / eps /
+        weight decay, all with ``clip_coef`` when set — whatever the number of groups, up to ``L.ADAM_MAX_SEGMENTS``.
+        Bitwise ``launch`` (Adam is element-wise)."""
+        fgs = self.flat_groups()
+        if not 1 <= len(fgs) <= L.ADAM_MAX_SEGMENTS:
+            raise L.TspmError(f"FusedAdam.launch_multi: 1..{L.ADAM_MAX_SEGMENTS} non-empty parameter groups "
+                              f"(tspm_adam_step_multi), got {len(fgs)}")
+        segs = (L.AdamSeg * len(fgs))()
+        for sg, fg in zip(segs, fgs):
+            sg.param, sg.grad, sg.exp_avg = fg.param.data_ptr(), fg.grad.data_ptr(), fg.exp_avg.data_ptr()
+            sg.exp_avg_sq, sg.count, sg.hyper = fg.exp_avg_sq.data_ptr(), fg.numel, fg.hyper.data_ptr()
+        lib = L.lib()
+        L.check(lib.tspm_adam_begin_multi(len(fgs), segs, stream_handle), "adam_begin_multi")
+        L.check(lib.tspm_adam_step_multi(len(fgs), segs, L.ptr(self.clip_coef), stream_handle), "adam_step_multi")
 
     def launch_begin(self, stream_handle: int) -> None:
         """Enqueue the device step-count increment of every group (before launch_ranges)."""
