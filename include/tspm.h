@@ -58,7 +58,8 @@ enum {
  * (pack_padded_sequence semantics; their own descriptors); tspm_textcnn_pool_fwd_len, the TextCNN pooling over each
  * row's own windows (per-sample text lengths read on the device); tspm_adam_begin_multi / tspm_adam_step_multi /
  * tspm_grad_clip_coef_multi, the optimizer phase of a step with up to 8 FusedAdam groups in the launches one group
- * takes. */
+ * takes; tspm_lstm_bwd_seq, the backward recurrence with a gradient at every step, and tspm_attn_pool_fwd /
+ * tspm_attn_pool_bwd, the attention pooling of LSTMEncoder(embd_method="attention"). */
 #define TSPM_ABI_VERSION 23
 int tspm_abi_version(void);  /* returns TSPM_ABI_VERSION */
 /* Static string for a status code. */
@@ -873,6 +874,81 @@ typedef struct tspm_lstm_bwd_len_desc {
 } tspm_lstm_bwd_len_desc;
 int tspm_lstm_fwd_len(int32_t count, const tspm_lstm_fwd_len_desc* descs, tspm_stream_t stream);
 int tspm_lstm_bwd_len(int32_t count, const tspm_lstm_bwd_len_desc* descs, tspm_stream_t stream);
+/* The backward recurrence with a gradient at EVERY step (added under ABI 23, no existing signature changed): what an
+ * embedding that weights all of r_out — LSTMEncoder(embd_method="attention") — hands to the recurrence.  The descriptor
+ * is tspm_lstm_bwd_len_desc without the index fields, plus
+ *   dseq  [steps][batch][hidden], nullable: added to dh_t at every t < L_b;
+ *   wt    [steps][batch], nullable: with dh non-NULL, dh_t += wt[t][b] * dh[b] at every t < L_b (the alpha_t g term of
+ *         the attention pooling without another pass over [steps][batch][hidden]); with wt NULL dh enters at L_b - 1,
+ *         exactly as tspm_lstm_bwd_len's "last" does; with dh NULL wt is not read;
+ *   dh    nullable; at least one of dh / dseq must be given (else TSPM_ERR_INVALID).
+ * lengths (device int32 [batch]) is required and clamped on the device as in tspm_lstm_bwd_len; nothing at t >= L_b is
+ * read from dseq / wt (the padding may hold anything), and dgates[t][b] for L_b <= t < steps is written as +0.0.
+ * hidden, count, tiers, kinds and launch sharing are those of tspm_lstm_bwd_w; every descriptor is validated before
+ * the first launch.  Per step: dh_t = (the recurrent term) [+ wt * dh] [+ dseq], in that order; with dseq and wt NULL
+ * the results are bitwise those of tspm_lstm_bwd_len without an index. */
+typedef struct tspm_lstm_bwd_seq_desc {
+  int32_t batch, steps, hidden, ld_dh;
+  const float* w_hh;
+  const float* gates;
+  const float* cs;
+  const float* dh;   /* nullable */
+  float* dgates;
+  const float* dseq; /* nullable */
+  const float* wt;   /* nullable */
+  const int32_t* lengths;
+} tspm_lstm_bwd_seq_desc;
+int tspm_lstm_bwd_seq(int32_t count, const tspm_lstm_bwd_seq_desc* descs, tspm_stream_t stream);
+/* Attention pooling over the LSTM outputs (added under ABI 23) — LSTMEncoder(embd_method="attention"), the
+ * Hierarchical-Attention embedding of models/msa/networks/lstm.py:21-44.  Row b, L_b = min(max(lengths[b], 1), steps),
+ * r_t = r[t][b] (the recurrence's hs + batch * hidden):
+ *   norm 0 ("time"): s_t = tanh(p_t) . u for t < L_b, alpha_t = exp(s_t - max s) / sum_{tau < L_b} exp(s_tau - max s);
+ *   norm 1 ("unit"): alpha_t = 1 for t < L_b (a softmax over a trailing axis of size 1);
+ *   alpha_t = +0.0 for t >= L_b;  h_out[b] = sum_{t < L_b} alpha_t r_t (row stride ld_out).
+ * p [steps][batch][hidden] comes in as the pre-activation W r_t + c (a tspm_linear_fwd over the steps * batch rows) and
+ * leaves as z = tanh(p) for t < L_b (rows past the length are neither read nor written); with norm 1, p and u are not
+ * read and may be NULL.  alpha is [steps][batch].  One workgroup per batch row; every reduction runs in an order that
+ * depends on L_b (and hidden) alone, so a row's alpha and h_out are bitwise the same whatever the padding and whatever
+ * else is in the batch.  hidden: a multiple of 4 in 4..128; r and p 16-byte aligned; steps * batch within int32; norm
+ * other than 0 / 1, a NULL lengths, count outside 1..2: TSPM_ERR_INVALID before any launch.  Two descriptors share the
+ * one launch. */
+typedef struct tspm_attn_pool_fwd_desc {
+  int32_t batch, steps, hidden, ld_out;
+  int32_t norm, reserved_; /* reserved_: 0 */
+  const float* r;
+  float* p;       /* in: W r + c; out: tanh of it (norm 0; nullable with norm 1) */
+  const float* u; /* [hidden] (norm 0; nullable with norm 1) */
+  float* alpha;
+  float* h_out;
+  const int32_t* lengths;
+} tspm_attn_pool_fwd_desc;
+int tspm_attn_pool_fwd(int32_t count, const tspm_attn_pool_fwd_desc* descs, tspm_stream_t stream);
+/* Its backward for norm 0 (norm 1 has no gradient through the scores: the caller launches nothing and the recurrence
+ * takes wt = alpha, dh = g).  From g = dloss/dh_out (row stride ld_g), alpha, z (the forward's p buffer), r and u:
+ * a_t = g . r_t, D = sum_{t < L_b} alpha_t a_t, ds_t = alpha_t (a_t - D),
+ *   dp[t][b] = ds_t * u * (1 - z_t^2) for t < L_b and +0.0 for t >= L_b ([steps][batch][hidden]: the GEMMs that follow
+ *   — dW = dp^T r, dseq = dp W — read all steps * batch rows);
+ *   du[h] = sum_{b, t < L_b} ds_t z_t[h];
+ *   dc[h] = -u[h] sum_{b, t < L_b} ds_t z_t[h]^2 — the bias gradient sum_{b,t} dp[t][b][h] with its cancelling part
+ *   (sum_t ds_t = 0 in every row) taken out; the column sums of dp in float32 lose 1e-5 .. 1e-4 of it to that part;
+ *   du and dc: per-row sums into rows [batch][2 * hidden] (caller-provided scratch), then a second launch adds the rows
+ *   in index order.  No floating-point atomics: the same inputs give the same bits.
+ * Shapes, alignment (r, z, dp 16-byte aligned), lengths and count as in the forward; norm must be 0. */
+typedef struct tspm_attn_pool_bwd_desc {
+  int32_t batch, steps, hidden, ld_g;
+  int32_t norm, reserved_; /* norm: 0 */
+  const float* g;
+  const float* alpha;
+  const float* z;
+  const float* r;
+  const float* u;
+  float* dp;
+  float* du;
+  float* dc;
+  float* rows;
+  const int32_t* lengths;
+} tspm_attn_pool_bwd_desc;
+int tspm_attn_pool_bwd(int32_t count, const tspm_attn_pool_bwd_desc* descs, tspm_stream_t stream);
 /* TextCNN pooling (models/msa/networks/textcnn.py:56-67): for conv i (kernel height heights[i], output
  * conv_out[i] time-major [steps-heights[i]+1][batch][channels] without bias), bias[i] added, ReLU,
  * max over time (first maximum, F.max_pool1d), concatenated over convs: pooled[b][i*C+c] and the

@@ -47,7 +47,8 @@ SHAPES = {"mosi_aligned": ("mosi", 128, 50), "mosi": ("mosi", 128, (375, 500, 50
           "mosei_aligned": ("mosei", 256, 50), "mosei": ("mosei", 256, (500, 375, 50))}
 T16 = ("tspm_lstm_fwd_t16", "tspm_lstm_bwd_t16")
 LATER = T16 + ("tspm_lstm_fwd_len", "tspm_lstm_bwd_len", "tspm_textcnn_pool_fwd_len", "tspm_adam_begin_multi",
-               "tspm_adam_step_multi", "tspm_grad_clip_coef_multi")  # exports an older build of the library may lack
+               "tspm_adam_step_multi", "tspm_grad_clip_coef_multi", "tspm_lstm_bwd_seq", "tspm_attn_pool_fwd",
+               "tspm_attn_pool_bwd")  # exports an older build of the library may lack
 
 
 def summarise(us):

@@ -146,6 +146,29 @@ class LstmBwdLenDesc(Structure):
     _fields_ = LstmBwdDesc._fields_ + [("lengths", c_void_p), ("index_bits", c_int32), ("reserved_", c_int32)]
 
 
+class LstmBwdSeqDesc(Structure):
+    """tspm_lstm_bwd_seq_desc (added under ABI 23): the backward recurrence with a gradient at every step - ``dseq``
+    [steps][batch][hidden] and / or ``dh`` weighted per step by ``wt`` [steps][batch] (NULL: ``dh`` enters at the row's
+    last step); ``lengths`` required."""
+    _fields_ = [(n, c_int32) for n in ("batch", "steps", "hidden", "ld_dh")] + \
+        [(n, c_void_p) for n in ("w_hh", "gates", "cs", "dh", "dgates", "dseq", "wt", "lengths")]
+
+
+ATTN_NORMS = {"time": 0, "unit": 1}  # tspm_attn_pool_*_desc.norm
+
+
+class AttnPoolFwdDesc(Structure):
+    """tspm_attn_pool_fwd_desc (added under ABI 23): the attention pooling of LSTMEncoder(embd_method="attention")."""
+    _fields_ = [(n, c_int32) for n in ("batch", "steps", "hidden", "ld_out", "norm", "reserved_")] + \
+        [(n, c_void_p) for n in ("r", "p", "u", "alpha", "h_out", "lengths")]
+
+
+class AttnPoolBwdDesc(Structure):
+    """tspm_attn_pool_bwd_desc (added under ABI 23): its backward for the "time" normalisation."""
+    _fields_ = [(n, c_int32) for n in ("batch", "steps", "hidden", "ld_g", "norm", "reserved_")] + \
+        [(n, c_void_p) for n in ("g", "alpha", "z", "r", "u", "dp", "du", "dc", "rows", "lengths")]
+
+
 class MonoHeadDesc(Structure):
     """tspm_mono_head_desc (ABI 23): the monomodal head (classifier, CE, predictions, backward) in one launch."""
     _fields_ = [(n, c_int32) for n in ("n", "hid", "classes", "ld_emb", "ld_demb")] + [("loss_weight", c_float)] + \
@@ -352,6 +375,10 @@ _SIGS = {
     # added under ABI 23: the recurrences with per-sample sequence lengths (device int32 [batch]; their own descriptors)
     "tspm_lstm_fwd_len": (c_int32, [c_int32, POINTER(LstmFwdLenDesc), _P]),
     "tspm_lstm_bwd_len": (c_int32, [c_int32, POINTER(LstmBwdLenDesc), _P]),
+    # added under ABI 23: the backward recurrence with a gradient at every step, and the attention pooling it serves
+    "tspm_lstm_bwd_seq": (c_int32, [c_int32, POINTER(LstmBwdSeqDesc), _P]),
+    "tspm_attn_pool_fwd": (c_int32, [c_int32, POINTER(AttnPoolFwdDesc), _P]),
+    "tspm_attn_pool_bwd": (c_int32, [c_int32, POINTER(AttnPoolBwdDesc), _P]),
     "tspm_textcnn_pool_fwd": (c_int32, [c_int32, c_int32, c_int32, _P, c_int32, _P, _P, _P, c_float, _P, _P, _P,
                                         c_int32, _P]),
     # added under ABI 23: the pooling over each row's own windows (per-sample text lengths, device int32 [batch])

@@ -337,6 +337,130 @@ __global__ __launch_bounds__(4 * HP) void k_lstm_bwd(LstmBwdDesc d0, X... x0, Ls
 }
 
 // ------------------------------------------------------------------------------------------------
+// The same backward with a gradient at EVERY step (tspm_lstm_bwd_seq; the "attention" embedding weights all of r_out):
+// dh_t = (the recurrent term) [+ wt[t][b] * dh[b]] [+ dseq[t][b]] for t < L_b.  It exists with lengths only and needs
+// no time index.  A body and a descriptor of its own, not one more mode of lstm_bwd_body: the two extra pointers would
+// change LstmBwdDesc, the argument list of every existing backward kernel, and those kernels stay instruction for
+// instruction what they were.  The loop is lstm_bwd_body's with Len; with dseq and wt null the arithmetic is the same.
+// ------------------------------------------------------------------------------------------------
+struct LstmBwdSeqDesc {
+  int B, T;
+  const float* whh;    // [4H][H]
+  const float* gates;  // [T][B][4H]
+  const float* cs;     // [T][B][H]
+  const float* dh;     // [B] rows of stride lddh, or null
+  int lddh;
+  float* dgates;       // [T][B][4H] out
+  const float* dseq;   // [T][B][H] or null
+  const float* wt;     // [T][B] or null: dh enters every step with this weight (null: at the row's last step)
+};
+
+template <int HP, int RB, bool Fixed>
+TSPM_DEV void lstm_bwd_seq_body(const LstmBwdSeqDesc& d, const LstmExtra x, int chunk) {
+  const int H = Fixed ? HP : x.H;
+  constexpr int GP = 4 * HP;
+  __shared__ __attribute__((aligned(16))) float dgs[RB][GP];
+  __shared__ float part[4][RB][HP];
+  const int tid = threadIdx.x;
+  const int q = tid / HP, k = tid - (tid / HP) * HP;
+  const bool live = k < H;
+  const int G = 4 * H;
+  const int b0 = chunk * RB;
+  const int B = d.B, T = d.T;
+  float wc[HP];
+#pragma unroll
+  for (int jj = 0; jj < HP; ++jj) wc[jj] = (live && jj < H) ? d.whh[(long long)(q * H + jj) * H + k] : 0.f;
+  const int cr = q, cu = k;
+  const bool cell = tid < RB * HP && live && b0 + cr < B;  // ghost rows and padded lanes compute zeros, write nothing
+  float dc = 0.f, dh = 0.f, gin = 0.f;
+  const LstmLens<RB, true> ln(x.lens, b0, B, T, cr);
+  const int last = ln.mine - 1;
+  const float* wt = d.dh ? d.wt : nullptr;  // without dh there is nothing to weight
+  if (cell && d.dh) gin = d.dh[(long long)(b0 + cr) * d.lddh + cu];
+  if (tid < RB * HP && !cell) {
+    dgs[cr][cu] = 0.f; dgs[cr][HP + cu] = 0.f; dgs[cr][2 * HP + cu] = 0.f; dgs[cr][3 * HP + cu] = 0.f;
+  }
+  // A step's operands — its gates, c_{t-1}, wt and dseq — are fetched one step ahead, after the previous step's stores:
+  // they arrive while the recurrent product below runs instead of standing between the barrier and the cell arithmetic
+  // (fetched at the step itself, behind their own branches, wt and dseq each cost the loop one more memory round trip
+  // per step).  c_t is the previous step's c_{t-1}.  The arithmetic is untouched.
+  float nig = 0.f, nfg = 0.f, ngg = 0.f, nog = 0.f, ncc = 0.f, ncp = 0.f, nwt = 0.f, nds = 0.f;
+  auto fetch = [&](int t) {
+    const long long row = (long long)t * B + b0 + cr;
+    const long long go = row * G + cu;
+    nig = d.gates[go]; nfg = d.gates[go + H]; ngg = d.gates[go + 2 * H]; nog = d.gates[go + 3 * H];
+    ncp = t > 0 ? d.cs[row * H + cu - (long long)B * H] : 0.f;
+    if (wt) nwt = wt[row];
+    if (d.dseq) nds = d.dseq[row * H + cu];
+  };
+  if (cell) {  // the row's first step, L_b - 1: nothing of dseq / wt at t >= L_b is ever read
+    ncc = d.cs[((long long)last * B + b0 + cr) * H + cu];
+    fetch(last);
+  }
+  for (int t = ln.bound(T) - 1; t >= 0; --t) {
+    if (cell && t < ln.mine) {
+      if (t < last)
+        dh = ((part[0][cr][cu] + part[1][cr][cu]) + part[2][cr][cu]) + part[3][cr][cu];
+      else
+        dh = wt ? 0.f : gin;  // the row's last step: where "last" puts the embedding gradient
+      if (wt) dh = fmaf(nwt, gin, dh);
+      if (d.dseq) dh += nds;
+      const long long go = ((long long)t * B + b0 + cr) * G + cu;
+      const float ig = nig, fg = nfg, gg = ngg, og = nog, c = ncc, cp = ncp;
+      const float tc = tanhf(c);
+      const float dog = dh * tc;
+      const float dcc = dc + dh * og * (1.f - tc * tc);
+      const float dig = dcc * gg, dgg = dcc * ig, dfg = dcc * cp;
+      dc = dcc * fg;
+      const float ai = dig * ig * (1.f - ig), af = dfg * fg * (1.f - fg);
+      const float ag = dgg * (1.f - gg * gg), ao = dog * og * (1.f - og);
+      dgs[cr][cu] = ai; dgs[cr][HP + cu] = af; dgs[cr][2 * HP + cu] = ag; dgs[cr][3 * HP + cu] = ao;
+      d.dgates[go] = ai; d.dgates[go + H] = af; d.dgates[go + 2 * H] = ag; d.dgates[go + 3 * H] = ao;
+      if (t > 0) {
+        ncc = cp;
+        fetch(t - 1);
+      }
+    }
+    __syncthreads();
+    if (t > 0) {
+#pragma unroll
+      for (int r = 0; r < RB; ++r) {
+        if (!ln.row_runs(r, t)) continue;  // workgroup-uniform: the row has not started yet
+        float a4[4] = {0.f, 0.f, 0.f, 0.f};  // interleaved partial sums, as in the forward
+#pragma unroll
+        for (int j0 = 0; j0 < HP; j0 += kLstmChunk) {
+          if (j0 < H) {  // wave-uniform: a chunk wholly past the width is skipped
+#pragma unroll
+            for (int jj = j0; jj < j0 + kLstmChunk; jj += 4) {
+              const f32x4 dv = *reinterpret_cast<const f32x4*>(&dgs[r][q * HP + jj]);
+#pragma unroll
+              for (int v = 0; v < 4; ++v) a4[v] = fmaf(dv[v], wc[jj + v], a4[v]);
+            }
+          }
+        }
+        part[q][r][k] = (a4[0] + a4[1]) + (a4[2] + a4[3]);
+      }
+    }
+    __syncthreads();
+  }
+  if (cell) {  // gate gradients past the row's length: zeros, so the weight-gradient GEMMs keep all T*B rows
+    for (int t = ln.mine; t < T; ++t) {
+      const long long go = ((long long)t * B + b0 + cr) * G + cu;
+      d.dgates[go] = 0.f; d.dgates[go + H] = 0.f; d.dgates[go + 2 * H] = 0.f; d.dgates[go + 3 * H] = 0.f;
+    }
+  }
+}
+
+template <int HP, int RB, typename... X>
+__global__ __launch_bounds__(4 * HP) void k_lstm_bwd_seq(LstmBwdSeqDesc d0, X... x0, LstmBwdSeqDesc d1, X... x1, int nb0) {
+  static_assert(RB <= 4 && kLstmLen<X...>, "cell threads are the first RB gate quarters; the lengths are required");
+  if ((int)blockIdx.x < nb0)
+    lstm_bwd_seq_body<HP, RB, kLstmFixed<X...>>(d0, lstm_extra(x0...), blockIdx.x);
+  else
+    lstm_bwd_seq_body<HP, RB, kLstmFixed<X...>>(d1, lstm_extra(x1...), blockIdx.x - nb0);
+}
+
+// ------------------------------------------------------------------------------------------------
 // TextCNN pooling: conv_i [Tout_i][B][C] (+ bias) -> ReLU -> max over time (first maximum, as
 // F.max_pool1d) for every (b, conv i, channel); the result (and its dropout, textcnn.py:66) goes to
 // the embedding Linear's input.  The argmax time index and the pooled value are kept for the backward.
@@ -644,7 +768,7 @@ int grid_for(long long work) {
 }
 
 // ------------------------------------------------------------------------------------------------
-// LSTM host path: each of the eight entry points fills one LstmProb per descriptor, validates it against the entry
+// LSTM host path: each of the nine entry points fills one LstmProb per descriptor, validates it against the entry
 // point's rules and hands the problems to lstm_dispatch.
 // ------------------------------------------------------------------------------------------------
 constexpr int kLstmRB = 2;  // batch rows per workgroup (B = 128: 64 workgroups per LSTM)
@@ -665,6 +789,7 @@ struct LstmProb {
 };
 using LstmFwdProb = LstmProb<LstmFwdDesc>;
 using LstmBwdProb = LstmProb<LstmBwdDesc>;
+using LstmBwdSeqProb = LstmProb<LstmBwdSeqDesc>;
 
 // tspm_lstm_fwd_desc / _fwd_len_desc and the two backward descriptors agree on these fields.
 template <typename S>
@@ -699,6 +824,12 @@ bool lstm_valid(const LstmBwdProb& p, LstmRules r) {
   return lstm_shape_ok(d.B, d.T, p.H, d.lddh, d.arg, p.bits, p.lens, r) && d.whh && d.gates && d.cs && d.dh && d.dgates;
 }
 
+bool lstm_valid(const LstmBwdSeqProb& p, LstmRules r) {  // dh or dseq (or both); no index
+  const LstmBwdSeqDesc& d = p.d;
+  return lstm_shape_ok(d.B, d.T, p.H, d.dh ? d.lddh : p.H, nullptr, 0, p.lens, r) && d.whh && d.gates && d.cs &&
+         d.dgates && (d.dh || d.dseq);
+}
+
 // The one place that names the kernels: X is the kernel's pack of per-problem extras, A the arguments after d0.
 template <int HP, typename Ix, typename... X, typename... A>
 void lstm_kernel(dim3 grid, hipStream_t st, const LstmFwdDesc& d0, A... rest) {
@@ -707,6 +838,12 @@ void lstm_kernel(dim3 grid, hipStream_t st, const LstmFwdDesc& d0, A... rest) {
 template <int HP, typename Ix, typename... X, typename... A>
 void lstm_kernel(dim3 grid, hipStream_t st, const LstmBwdDesc& d0, A... rest) {
   hipLaunchKernelGGL((k_lstm_bwd<HP, kLstmRB, Ix, X...>), grid, dim3(4 * HP), 0, st, d0, rest...);
+}
+
+template <int HP, typename Ix, typename... X, typename... A>
+void lstm_kernel(dim3 grid, hipStream_t st, const LstmBwdSeqDesc& d0, A... rest) {
+  if constexpr (kLstmLen<X...>)  // the per-step form exists with lengths only (and has no index: Ix is not used)
+    hipLaunchKernelGGL((k_lstm_bwd_seq<HP, kLstmRB, X...>), grid, dim3(4 * HP), 0, st, d0, rest...);
 }
 
 template <int HP, bool Fixed, typename Ix, bool Len, typename Desc>
@@ -815,6 +952,13 @@ extern "C" int tspm_lstm_fwd_len(int32_t count, const tspm_lstm_fwd_len_desc* de
 extern "C" int tspm_lstm_bwd_len(int32_t count, const tspm_lstm_bwd_len_desc* descs, tspm_stream_t stream) {
   return lstm_entry<LstmBwdDesc>(count, descs, stream, kRulesLen, [](const tspm_lstm_bwd_len_desc& s) {
     return lstm_bwd_prob(s, s.argmax ? s.index_bits : 0, s.lengths);
+  });
+}
+
+extern "C" int tspm_lstm_bwd_seq(int32_t count, const tspm_lstm_bwd_seq_desc* descs, tspm_stream_t stream) {
+  return lstm_entry<LstmBwdSeqDesc>(count, descs, stream, kRulesLen, [](const tspm_lstm_bwd_seq_desc& s) {
+    return LstmBwdSeqProb{{s.batch, s.steps, s.w_hh, s.gates, s.cs, s.dh, s.ld_dh, s.dgates, s.dseq, s.wt},
+                          s.hidden, 0, s.lengths};
   });
 }
 

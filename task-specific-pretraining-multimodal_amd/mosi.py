@@ -4,7 +4,7 @@ Drop-ins for the reference's classes, same constructor arguments, attribute name
 keys (MML_Suite paths):
 
 * ``LSTMEncoder``     models/msa/networks/lstm.py:8-67   (``rnn`` = nn.LSTM parameter container, "last" /
-                      "maxpool")
+                      "maxpool" / "attention")
 * ``TextCNN``         models/msa/networks/textcnn.py:10-69
 * ``FcClassifier``    models/msa/networks/classifier.py:83-117
 * ``UttFusionModel``  models/msa/utt_fusion.py:25-294 (forward, train_step with clip_grad_norm_,
@@ -57,6 +57,13 @@ inside a module, a ``netC`` that is not fully trainable, a trainable parameter i
 groups, and a ``FusedAdam`` whose flat buffers (fixed when it was built) are not exactly the parameters that train now
 are refused (``check_param_groups``): set the flags first, then build the optimizer.
 
+The "attention" embedding of the LSTM encoders (lstm.py:21-44): ``LSTMEncoder(..., embd_method="attention",
+attention_norm="time" | "unit")`` pools every LSTM output, e = sum_t alpha_t r_t, in ``tspm_attn_pool_fwd`` after the recurrence
+(with "time" the score projection tanh(W r_t + c) . u runs on ``tspm_linear_fwd`` over the T*B rows first); the backward is
+``tspm_attn_pool_bwd``, the projection's two gradient GEMMs and ``tspm_lstm_bwd_seq``, the backward through time with a
+gradient at every step.  Such an encoder always runs the length-taking entry points (its length buffer stays at the padded
+length without ``ragged``); the encoders' methods are fixed at construction, so no cache key changes.
+
 Sentiment regression (this project's addition; the reference's YAMLs train the three-class variant only): a
 one-output ``netC.fc_out`` (``build_utt_fusion(name, output_dim=1)``) with a single mean ``nn.L1Loss`` / ``nn.MSELoss``
 term (``_regress_term``) on the float32 ``regression_labels`` runs the same steps with the head — ``fc_out``, the loss,
@@ -95,17 +102,22 @@ YAML_CONFIGS = {
 
 
 def build_utt_fusion(name: str = "mosi", output_dim: int = 3,
-                     embd_sizes: Sequence[int] = (64, 64, 64)) -> "UttFusionModel":
+                     embd_sizes: Sequence[int] = (64, 64, 64), embd_method: Optional[str] = None,
+                     attention_norm: Optional[str] = None) -> "UttFusionModel":
     """UttFusionModel of the named YAML (netA, netV, netT, netC constructed in the YAML's order, so a
     ``torch.manual_seed`` before the call gives the reference's initial weights).  ``output_dim=1`` builds the
     sentiment-regression model (``regression_labels``: a continuous score in [-3, 3]); only ``netC.fc_out``, the last
     module constructed, differs from the default build of the same seed.  ``embd_sizes`` = the (audio, video, text)
     embedding widths (the YAMLs' ``hidden_size`` / ``embd_size`` fields; the LSTM widths within
-    ``L.lstm_width_supported``); the classifier's input is their sum."""
+    ``L.lstm_width_supported``); the classifier's input is their sum.  ``embd_method`` (default: the YAML's) and
+    ``attention_norm`` go to both LSTM encoders (``LSTMEncoder``: "attention" needs ``attention_norm`` "time" or
+    "unit")."""
     c = YAML_CONFIGS[name]
     ha, hv, ht = (int(w) for w in embd_sizes)
-    netA = LSTMEncoder(input_size=c["audio_dim"], hidden_size=ha, embd_method=c["embd_method"])
-    netV = LSTMEncoder(input_size=c["video_dim"], hidden_size=hv, embd_method=c["embd_method"])
+    method = c["embd_method"] if embd_method is None else embd_method
+    kw = {} if attention_norm is None else dict(attention_norm=attention_norm)  # the two-argument call as it was
+    netA = LSTMEncoder(input_size=c["audio_dim"], hidden_size=ha, embd_method=method, **kw)
+    netV = LSTMEncoder(input_size=c["video_dim"], hidden_size=hv, embd_method=method, **kw)
     netT = TextCNN(input_size=c["text_dim"], embd_size=ht, dropout=c["text_dropout"], in_channels=1, out_channels=128,
                    kernel_heights=[3, 4, 5])
     netC = FcClassifier(input_dim=ha + hv + ht, layers=list(c["cls_layers"]), output_dim=output_dim, dropout=c["cls_dropout"],
@@ -116,20 +128,54 @@ def build_utt_fusion(name: str = "mosi", output_dim: int = 3,
 # ------------------------------------------------------------------------------------------------
 # parameter containers (reference attribute names / state_dict keys / construction order)
 # ------------------------------------------------------------------------------------------------
+ATTENTION_NORMS = ("time", "unit")
+_ATTENTION_VECTOR_SEED = 0x5EED_A77E  # the private generator that fills attention_vector_weight
+
+
 class LSTMEncoder(nn.Module):
     """lstm.py:8-67: one-directional nn.LSTM(batch_first=True); embd "last" = h_n, "maxpool" = max over
-    time of r_out (lstm.py:47-52, F.max_pool1d: first maximum)."""
+    time of r_out (lstm.py:47-52, F.max_pool1d: first maximum), "attention" = sum_t alpha_t r_t (lstm.py:21-44).
 
-    def __init__(self, input_size: int, hidden_size: int, embd_method: str = "last"):
+    "attention" (DESIGN §3.16): s_t = tanh(W r_t + c) . u with ``attention_layer`` = Sequential(Linear(H, H), Tanh())
+    and ``attention_vector_weight`` [H, 1] (the reference's names, shapes and construction order, so the ``state_dict``
+    keys are its own).  The normalisation of the scores must be chosen with ``attention_norm``:
+
+    * ``"time"``  alpha = softmax of s over the row's time steps - the Hierarchical-Attention formula the reference's
+      docstring describes;
+    * ``"unit"``  alpha_t = 1 on every valid step, the embedding is the plain time-sum - what a softmax over the
+      trailing size-1 axis of [B, T, 1] scores computes (the reference's code as recalled; checkpoint interoperability).
+
+    Without ``attention_norm`` the method keeps raising ``NotImplementedError``.  ``attention_layer``'s Linear draws from
+    the global RNG in its place; the vector, which the reference leaves uninitialised (``torch.Tensor(H, 1)``), is filled
+    U(-1/sqrt(H), 1/sqrt(H)) from a private generator of fixed seed and consumes no global RNG."""
+
+    def __init__(self, input_size: int, hidden_size: int, embd_method: str = "last",
+                 attention_norm: Optional[str] = None):
         super().__init__()
         self.input_size = input_size
         self.hidden_size = hidden_size
         self.rnn = nn.LSTM(self.input_size, self.hidden_size, batch_first=True)
         assert embd_method in ["maxpool", "attention", "last"]
+        if attention_norm is not None and embd_method != "attention":
+            raise L.TspmError(f"LSTMEncoder: attention_norm={attention_norm!r} goes with embd_method='attention', not "
+                              f"{embd_method!r}")
         if embd_method == "attention":
-            raise NotImplementedError("LSTMEncoder HIP path: embd_method 'last' or 'maxpool' (the MOSI / MOSEI "
-                                      "UTT-Fusion configs)")
+            if attention_norm is None:
+                raise NotImplementedError(
+                    "LSTMEncoder HIP path: embd_method='attention' needs attention_norm - choose 'time' (softmax of the "
+                    "scores over the row's time steps, the formula of the reference's docstring) or 'unit' (every weight "
+                    "1, the plain time-sum: what the reference's Softmax(dim=-1) over [B, T, 1] scores computes)")
+            if attention_norm not in ATTENTION_NORMS:
+                raise L.TspmError(f"LSTMEncoder: attention_norm is one of {ATTENTION_NORMS}, got {attention_norm!r}")
+            self.attention_vector_weight = nn.Parameter(torch.empty(self.hidden_size, 1))
+            self.attention_layer = nn.Sequential(nn.Linear(self.hidden_size, self.hidden_size), nn.Tanh())
+            self.softmax = nn.Softmax(dim=-1)
+            bound = 1.0 / float(self.hidden_size) ** 0.5
+            with torch.no_grad():
+                self.attention_vector_weight.uniform_(
+                    -bound, bound, generator=torch.Generator().manual_seed(_ATTENTION_VECTOR_SEED))
         self.embd_method = embd_method
+        self.attention_norm = attention_norm
 
     def forward(self, x: torch.Tensor, lengths: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Inference embedding h_T of x [B, T, input] (gradients flow through UttFusionModel only).  ``lengths`` (int
@@ -298,6 +344,19 @@ def _lstm_alloc(enc: "LSTMEncoder", B: int, T: int, device, backward: bool = Tru
                 cs=torch.empty(T * B, H, **f), hs=torch.empty((T + 1) * B, H, **f),
                 dg=torch.empty(T * B, 4 * H, **f) if backward else None)
     bufs["arg"] = (torch.zeros(B, H, dtype=torch.int16 if wide else torch.uint8, device=device) if indexed else None)
+    if _is_attention(enc):
+        # the attention pooling: alpha [T, B], the recurrence's own h_out (a scratch: the embedding is the pooling's),
+        # with "time" p / z [T*B, H]; to train it, dp and dseq [T*B, H], the per-row du / dc sums and the split-K workspace
+        # of dW = dp^T r (a frozen encoder keeps none of these)
+        time = enc.attention_norm == "time"
+        bufs["alpha"], bufs["hout"] = torch.empty(T, B, **f), torch.empty(B, H, **f)
+        bufs["p"] = torch.empty(T * B, H, **f) if time else None
+        if backward and time:
+            bufs["dp"], bufs["dseq"] = torch.empty(T * B, H, **f), torch.empty(T * B, H, **f)
+            bufs["rows"] = torch.empty(B, 2 * H, **f)
+            bufs["attn_split"] = sp = max(1, min(32, (T * B) // 128))  # as _lstm_wgrad_plan
+            wsb = int(L.lib().tspm_linear_bwd_weight_splitk_workspace(T * B, H, H, sp))
+            bufs["attn_ws"] = torch.empty(max(wsb // 4, 1), **f)
     return bufs
 
 
@@ -530,6 +589,92 @@ def _lstm_bwd_launch(probs, B: int, sh: int, wide: bool) -> None:
     L.check(rc, "lstm_bwd_len" if ragged else "lstm_bwd")
 
 
+def _is_attention(enc) -> bool:
+    return getattr(enc, "embd_method", None) == "attention"
+
+
+def _attn_fwd_launch(probs, B: int, sh: int) -> None:
+    """The attention pooling after the recurrences: per "attention" LSTM (encoder, buffers, T, embedding pointer,
+    ld_out, length buffer); with "time" the score projection p = r W^T + c over the T*B rows first (tspm_linear_fwd;
+    "unit" needs no scores), then ONE tspm_attn_pool_fwd for all of them."""
+    if not probs:
+        return
+    lib = L.lib()
+    descs = (L.AttnPoolFwdDesc * len(probs))()
+    for i, (enc, bufs, T, out, ld_out, lens) in enumerate(probs):
+        d, H = descs[i], enc.hidden_size
+        r = bufs["hs"].data_ptr() + B * H * 4  # r_t = hs[t + 1]
+        if enc.attention_norm == "time":
+            lin = enc.attention_layer[0]
+            L.check(lib.tspm_linear_fwd(T * B, H, H, r, H, lin.weight.data_ptr(), lin.bias.data_ptr(), 0, None, 1.0,
+                                        bufs["p"].data_ptr(), H, sh), "attention projection")
+        d.batch, d.steps, d.hidden, d.ld_out, d.norm = B, T, H, ld_out, L.ATTN_NORMS[enc.attention_norm]
+        d.r, d.p, d.u = r, L.ptr(bufs["p"]), enc.attention_vector_weight.data_ptr()
+        d.alpha, d.h_out, d.lengths = bufs["alpha"].data_ptr(), out, lens.data_ptr()
+    L.check(lib.tspm_attn_pool_fwd(len(probs), descs, sh), "attn_pool_fwd")
+
+
+def _attn_bwd_launch(probs, B: int, sh: int, g) -> None:
+    """The attention pooling's backward, before the recurrences': per trainable "attention" LSTM (encoder, buffers, T,
+    gradient pointer, ld_g, length buffer).  "time": ONE tspm_attn_pool_bwd (dp, du, dc), then per
+    encoder dW = the split-K weight gradient of dp over the T*B rows and dseq = dp W.  "unit": no gradient reaches
+    the scores - nothing is launched here and the three parameters' gradients are written as zeros (they still belong
+    to their Adam group; the flat buffers hold the previous step's values)."""
+    lib = L.lib()
+    timed = [p for p in probs if p[0].attention_norm == "time"]
+    if timed:
+        descs = (L.AttnPoolBwdDesc * len(timed))()
+        for i, (enc, bufs, T, dout, ld_g, lens) in enumerate(timed):
+            d, H = descs[i], enc.hidden_size
+            d.batch, d.steps, d.hidden, d.ld_g, d.norm = B, T, H, ld_g, 0
+            d.g, d.alpha, d.z = dout, bufs["alpha"].data_ptr(), bufs["p"].data_ptr()
+            d.r, d.u = bufs["hs"].data_ptr() + B * H * 4, enc.attention_vector_weight.data_ptr()
+            d.dp, d.rows = bufs["dp"].data_ptr(), bufs["rows"].data_ptr()
+            d.du, d.dc = g(enc.attention_vector_weight).data_ptr(), g(enc.attention_layer[0].bias).data_ptr()
+            d.lengths = lens.data_ptr()
+        L.check(lib.tspm_attn_pool_bwd(len(timed), descs, sh), "attn_pool_bwd")
+        for enc, bufs, T, *_ in timed:
+            H, lin = enc.hidden_size, enc.attention_layer[0]
+            r, ws = bufs["hs"].data_ptr() + B * H * 4, bufs["attn_ws"]
+            L.check(lib.tspm_linear_bwd_weight_splitk(T * B, H, H, r, H, bufs["dp"].data_ptr(), H,
+                                                      g(lin.weight).data_ptr(), None,  # dc is the pooling backward's
+                                                      bufs["attn_split"], ws.data_ptr(), ws.numel() * 4, sh),
+                    "attention dW")
+            L.check(lib.tspm_linear_bwd_data(T * B, H, H, bufs["dp"].data_ptr(), H, lin.weight.data_ptr(),
+                                             bufs["dseq"].data_ptr(), H, sh), "attention dseq")
+    for enc, *_ in probs:
+        if enc.attention_norm == "unit":
+            for p in (enc.attention_vector_weight, enc.attention_layer[0].weight, enc.attention_layer[0].bias):
+                g(p).zero_()  # on the current stream, which is the one `sh` names (captured with the step)
+
+
+def _lstm_bwd_seq_launch(probs, B: int, sh: int) -> None:
+    """ONE tspm_lstm_bwd_seq call for the trainable "attention" LSTMs: per LSTM (encoder, buffers, T, dh pointer, ld_dh,
+    length buffer).  Every step takes alpha_t g through ``wt`` = alpha and, with "time", dseq on top."""
+    descs = (L.LstmBwdSeqDesc * len(probs))()
+    for i, (enc, bufs, T, dh, ld_dh, lens) in enumerate(probs):
+        d, rnn = descs[i], enc.rnn
+        d.batch, d.steps, d.hidden, d.ld_dh = B, T, enc.hidden_size, ld_dh
+        d.w_hh, d.gates, d.cs = rnn.weight_hh_l0.data_ptr(), bufs["gates"].data_ptr(), bufs["cs"].data_ptr()
+        d.dh, d.dgates, d.wt = dh, bufs["dg"].data_ptr(), bufs["alpha"].data_ptr()
+        d.dseq = L.ptr(bufs.get("dseq"))
+        d.lengths = lens.data_ptr()
+    L.check(L.lib().tspm_lstm_bwd_seq(len(probs), descs, sh), "lstm_bwd_seq")
+
+
+def _lstm_backward(encs, B: int, sh: int, wide: bool, g) -> None:
+    """The backward of the trainable LSTMs of one launch group: per LSTM (encoder, buffers, T, gradient pointer, ld_g,
+    length buffer or None).  "attention" encoders: the pooling's backward, then ONE
+    tspm_lstm_bwd_seq; the others ONE tspm_lstm_bwd* call as before."""
+    attn = [e for e in encs if _is_attention(e[0])]
+    rest = [e for e in encs if not _is_attention(e[0])]
+    if attn:
+        _attn_bwd_launch(attn, B, sh, g)
+        _lstm_bwd_seq_launch(attn, B, sh)
+    if rest:
+        _lstm_bwd_launch(rest, B, sh, wide)
+
+
 def _lstm_wgrad(enc: "LSTMEncoder", x: torch.Tensor, bufs, B: int, T: int, split: int,
                 wg_ws: torch.Tensor, g, sh: int) -> None:
     """The LSTM weight gradients as GEMMs over the T*B rows of dgates (after tspm_lstm_bwd)."""
@@ -683,7 +828,11 @@ class MosiEngine:
         self.lstm = {name: _lstm_alloc(enc, B, T_m, device, backward=self.trains[name], wide=self.wide)
                      for name, enc, T_m in (("a", a, Ta), ("v", v, Tv))}  # a frozen LSTM keeps no dg buffer
         # ragged mode: one persistent int32 [B] length buffer per LSTM encoder, read by tspm_lstm_fwd_len / _bwd_len
-        self.lens = {"a": _length_buffer(B, Ta, device), "v": _length_buffer(B, Tv, device)} if self.ragged else None
+        # an "attention" encoder always runs the length-taking entry points (its pooling reads lengths): such an engine
+        # keeps the buffers, at the padded length, without ragged too - and both recurrences go through the one call
+        self.attn = {"a": _is_attention(a), "v": _is_attention(v)}
+        self.lens = ({"a": _length_buffer(B, Ta, device), "v": _length_buffer(B, Tv, device)}
+                     if self.ragged or any(self.attn.values()) else None)
         # text_lengths: the TextCNN's own persistent int32 [B] length buffer, read by tspm_textcnn_pool_fwd_len
         self.text_lens = _length_buffer(B, Tt, device) if self.text_lengths else None
         _text_alloc(self, t, B, Tt, device)
@@ -830,11 +979,15 @@ class MosiEngine:
         lib, m = L.lib(), self.m
         B, (Ta, Tv, _) = self.B, self.Ts
         # LSTM input projections over each encoder's T_m*B rows, then both recurrences in one launch
-        _lstm_fwd_launch([(enc, x, self.lstm[name], T_m, self.fused.data_ptr() + col * 4, self.E,
-                           self.lens[name] if self.ragged else None)
-                          for name, enc, x, col, T_m in (("a", m.netA, self.A, 0, Ta),
-                                                         ("v", m.netV, self.V, m.netA.hidden_size, Tv))],
-                         B, sh, self.wide)
+        # (an "attention" encoder's recurrence writes its h_out to a scratch; the pooling that follows writes the embedding)
+        encs = (("a", m.netA, self.A, 0, Ta), ("v", m.netV, self.V, m.netA.hidden_size, Tv))
+        _lstm_fwd_launch([(enc, x, self.lstm[name], T_m,
+                           *((self.lstm[name]["hout"].data_ptr(), enc.hidden_size) if self.attn[name]
+                             else (self.fused.data_ptr() + col * 4, self.E)),
+                           self.lens[name] if self.lens is not None else None)
+                          for name, enc, x, col, T_m in encs], B, sh, self.wide)
+        _attn_fwd_launch([(enc, self.lstm[name], T_m, self.fused.data_ptr() + col * 4, self.E, self.lens[name])
+                          for name, enc, _, col, T_m in encs if self.attn[name]], B, sh)
 
     def _forward_text(self, sh: int, train: bool) -> None:
         m, t = self.m, self.m.netT
@@ -984,9 +1137,9 @@ class MosiEngine:
         # LSTMs: backward through time (one launch for both), then the weight gradients as GEMMs over T_m*B rows
         encs = [e for e in (("a", m.netA, self.A, 0, Ta), ("v", m.netV, self.V, m.netA.hidden_size, Tv))
                 if self.trains[e[0]]]  # a frozen LSTM is no problem of the launch
-        _lstm_bwd_launch([(enc, self.lstm[name], T_m, self.dfused.data_ptr() + col * 4, self.E,
-                           self.lens[name] if self.ragged else None) for name, enc, _, col, T_m in encs],
-                         B, sh, self.wide)
+        _lstm_backward([(enc, self.lstm[name], T_m, self.dfused.data_ptr() + col * 4, self.E,
+                         self.lens[name] if self.lens is not None else None)
+                        for name, enc, _, col, T_m in encs], B, sh, self.wide, g)
         for name, enc, x, _, T_m in encs:
             _lstm_wgrad(enc, x, self.lstm[name], B, T_m, self.wg_splits[name], self.wg_ws, g, sh)
 
@@ -1031,7 +1184,8 @@ class MosiEncoderEngine:
         if self.text_lengths and not isinstance(enc, TextCNN):
             raise L.TspmError("MosiEncoderEngine: text_lengths is the TextCNN's length input (an LSTMEncoder takes "
                               "ragged=True)")
-        self.lens = _length_buffer(self.B, self.T, device) if self.ragged else None
+        # (an "attention" LSTMEncoder keeps the buffer, at the padded length, without ragged too: its entry points read it)
+        self.lens = _length_buffer(self.B, self.T, device) if self.ragged or _is_attention(enc) else None
         # text_lengths: the TextCNN's persistent int32 [B] length buffer, read by tspm_textcnn_pool_fwd_len
         self.text_lens = _length_buffer(self.B, self.T, device) if self.text_lengths else None
         B, T = self.B, self.T
@@ -1104,6 +1258,11 @@ class MosiEncoderEngine:
         if self.is_text:
             _text_forward(self, self.enc, sh, self._keep_mask(train, sh), self.emb.data_ptr(), self.hidden)
             return
+        if _is_attention(self.enc):  # the recurrence's h_out to a scratch, the embedding from the pooling
+            _lstm_fwd_launch([(self.enc, self.X, self.bufs, T, self.bufs["hout"].data_ptr(), self.hidden, self.lens)], B,
+                             sh, self.wide)
+            _attn_fwd_launch([(self.enc, self.bufs, T, self.emb.data_ptr(), self.hidden, self.lens)], B, sh)
+            return
         _lstm_fwd_launch([(self.enc, self.X, self.bufs, T, self.emb.data_ptr(), self.hidden, self.lens)], B, sh,
                          self.wide)
 
@@ -1115,7 +1274,8 @@ class MosiEncoderEngine:
             _text_backward(self, self.enc, sh, keep, self.demb.data_ptr(), self.hidden, self.emb.data_ptr(),
                            self.hidden, self.grad_of)
             return
-        _lstm_bwd_launch([(self.enc, self.bufs, T, self.demb.data_ptr(), self.hidden, self.lens)], B, sh, self.wide)
+        _lstm_backward([(self.enc, self.bufs, T, self.demb.data_ptr(), self.hidden, self.lens)], B, sh, self.wide,
+                       self.grad_of)
         _lstm_wgrad(self.enc, self.X, self.bufs, B, T, self.wg_split, self.wg_ws, self.grad_of, sh)
 
 
@@ -1638,9 +1798,13 @@ def _encode_lstm(enc: LSTMEncoder, x: torch.Tensor, lengths: Optional[torch.Tens
     out = torch.empty(B, enc.hidden_size, device=x.device, dtype=torch.float32)
     sh = L.stream_handle()
     wide = L.lstm_wide_index(((enc.embd_method, T),))
-    lens = None if lengths is None else _length_buffer(B, T, x.device)
-    if lens is not None:
+    attn = _is_attention(enc)  # always the length-taking entry points (at the padded length without ``lengths``)
+    lens = None if lengths is None and not attn else _length_buffer(B, T, x.device)
+    if lengths is not None:
         _set_lengths(lens, lengths.to(x.device), T, "input")
-    _lstm_fwd_launch([(enc, xt, _lstm_alloc(enc, B, T, x.device, backward=False, wide=wide), T, out.data_ptr(),
-                       enc.hidden_size, lens)], B, sh, wide)
+    bufs = _lstm_alloc(enc, B, T, x.device, backward=False, wide=wide)
+    h_out = bufs["hout"] if attn else out
+    _lstm_fwd_launch([(enc, xt, bufs, T, h_out.data_ptr(), enc.hidden_size, lens)], B, sh, wide)
+    if attn:
+        _attn_fwd_launch([(enc, bufs, T, out.data_ptr(), enc.hidden_size, lens)], B, sh)
     return out
