@@ -1017,6 +1017,25 @@ int tspm_seq_gather(int32_t count, const int64_t* index, int64_t n_samples, cons
                     const int64_t* offsets, const int32_t* lengths, int32_t feat, int32_t steps_pad, float* out,
                     int64_t stride_t, int64_t stride_b, const float* row_mask, const int64_t* labels,
                     int64_t* labels_out, tspm_stream_t stream);
+/* Missing-modality pattern expansion (added under ABI 23) — every pattern of a batch from ONE encoder pass over 2*batch
+ * rows.  emb [2*batch][ld_emb]: rows [0, batch) are the embeddings cat(audio, video, text) of the real inputs, rows
+ * [batch, 2*batch) those of the zeroed inputs of the same rows (a zeroed tensor through the encoder, not a zero
+ * embedding).  In one launch, for p < npat and b < batch, with row = p*batch + b:
+ *   out[row*ld_out + c]  = emb[(keep[3p + m] ? b : batch + b)*ld_emb + c]  for every column c of modality m
+ *   labels_out[row]      = labels[b]         (label_bytes = 8: int64 class labels, 4: float32 scores; copied as bytes)
+ *   groups_out[row]      = group_id[p]       (int32)
+ * keep ([npat][3], the (audio, video, text) flags of a pattern, non-zero = kept) and group_id ([npat]) are HOST
+ * arrays copied into the kernel arguments (nothing of them is read after the call returns).  Plain loads and stores,
+ * 16 bytes wide for a modality whose width and column offset are multiples of 4 when ld_emb and ld_out are too and
+ * emb / out are 16-byte aligned, else one float each; no atomics; nothing but the elements named above is written
+ * (padding columns of out keep their content).  TSPM_ERR_INVALID before any launch: batch <= 0, npat outside
+ * 1..TSPM_MAX_PATTERNS, a non-positive width, ld_emb or ld_out below the width sum, a pattern that keeps nothing, a
+ * NULL pointer, label_bytes other than 4 or 8. */
+#define TSPM_MAX_PATTERNS 7
+int tspm_pattern_expand(int32_t batch, int32_t npat, const int32_t* keep, const int32_t* group_id, int32_t w_audio,
+                        int32_t w_video, int32_t w_text, const float* emb, int64_t ld_emb, float* out, int64_t ld_out,
+                        const void* labels, void* labels_out, int32_t label_bytes, int32_t* groups_out,
+                        tspm_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Monomodal pre-training head (ABI 23) — train_monomodal.MonomodalEncoder's `classifier = nn.Linear(hid,

@@ -91,6 +91,7 @@ class AdamHyper(Structure):
 
 HYPER_STEP_OFFSET = 48  # byte offset of tspm_adam_hyper.step
 ADAM_MAX_SEGMENTS = 8   # TSPM_ADAM_MAX_SEGMENTS: the most groups of tspm_adam_*_multi / tspm_grad_clip_coef_multi
+MAX_PATTERNS = 7        # TSPM_MAX_PATTERNS: the most patterns of one tspm_pattern_expand launch
 
 
 class AdamSeg(Structure):
@@ -401,6 +402,9 @@ _SIGS = {
     "tspm_mono_head_bce_step": (c_int32, [POINTER(MonoHeadBceDesc), _P]),
     # added under ABI 23: the scalar-output regression head (MOSI / MOSEI sentiment score) in one launch
     "tspm_regress_head_step": (c_int32, [POINTER(RegressHeadDesc), _P]),
+    # added under ABI 23: every missing-modality pattern of a batch from one 2B-row encoder pass (host keep / group arrays)
+    "tspm_pattern_expand": (c_int32, [c_int32, c_int32, POINTER(c_int32), POINTER(c_int32), c_int32, c_int32, c_int32,
+                                      _P, c_int64, _P, c_int64, _P, _P, c_int32, _P, _P]),
 }
 
 EXPORTED = tuple(_SIGS)

@@ -768,6 +768,51 @@ int grid_for(long long work) {
 }
 
 // ------------------------------------------------------------------------------------------------
+// Missing-modality pattern expansion: emb [2B][ld_emb] holds the embeddings of the real inputs (rows [0, B)) and of
+// the zeroed inputs (rows [B, 2B)) as cat(audio, video, text); row (p, b) of out takes each modality's columns from
+// row b when pattern p keeps it, else from row B + b.  A thread moves one unit of a row: a float4 of a segment whose
+// width, column offset and both row strides are multiples of 4 (both bases 16-byte aligned), else one float.  Unit 0
+// of a row also copies the row's label (4 or 8 bytes) and writes its group id.  The per-pattern tables ride in the
+// kernel's arguments (as PoolSet does).
+// ------------------------------------------------------------------------------------------------
+struct PatternSet {
+  int keep[TSPM_MAX_PATTERNS];   // bit m: modality m (audio, video, text) comes from the real row
+  int group[TSPM_MAX_PATTERNS];
+  int width[3], col[3], units[3], vec[3];
+};
+
+__global__ __launch_bounds__(256) void k_pattern_expand(int B, int npat, PatternSet ps, const float* __restrict__ emb,
+                                                        long long ld_emb, float* __restrict__ out, long long ld_out,
+                                                        const void* __restrict__ lab_in, void* __restrict__ lab_out,
+                                                        int lab_bytes, int32_t* __restrict__ groups_out) {
+  const int u0 = ps.units[0], u01 = u0 + ps.units[1], upr = u01 + ps.units[2];
+  const long long total = (long long)npat * B * upr;
+  for (long long e = blockIdx.x * 256LL + threadIdx.x; e < total; e += (long long)gridDim.x * 256) {
+    const int u = (int)(e % upr);
+    const long long row = e / upr;  // p * B + b
+    const int b = (int)(row % B), p = (int)(row / B);
+    const int m = u < u0 ? 0 : (u < u01 ? 1 : 2);
+    const int uu = u - (m == 0 ? 0 : (m == 1 ? u0 : u01));
+    const long long src = ((ps.keep[p] >> m) & 1) ? b : (long long)B + b;
+    const float* s = emb + src * ld_emb + ps.col[m];
+    float* d = out + row * ld_out + ps.col[m];
+    if (ps.vec[m]) {
+      reinterpret_cast<float4*>(d)[uu] = reinterpret_cast<const float4*>(s)[uu];
+    } else {
+      d[uu] = s[uu];
+    }
+    if (u == 0) {
+      if (lab_bytes == 8) {
+        static_cast<unsigned long long*>(lab_out)[row] = static_cast<const unsigned long long*>(lab_in)[b];
+      } else {
+        static_cast<unsigned*>(lab_out)[row] = static_cast<const unsigned*>(lab_in)[b];
+      }
+      groups_out[row] = ps.group[p];
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
 // LSTM host path: each of the nine entry points fills one LstmProb per descriptor, validates it against the entry
 // point's rules and hands the problems to lstm_dispatch.
 // ------------------------------------------------------------------------------------------------
@@ -1104,6 +1149,42 @@ extern "C" int tspm_seq_gather(int32_t count, const int64_t* index, int64_t n_sa
   hipLaunchKernelGGL(k_seq_gather, dim3(grid_for((long long)steps_pad * count * feat)), dim3(256), 0,
                      static_cast<hipStream_t>(stream), count, index, (long long)n_samples, data, offsets, lengths, feat,
                      steps_pad, out, (long long)stride_t, (long long)stride_b, row_mask, labels, labels_out);
+  TSPM_LAUNCH_CHECK();
+  return TSPM_OK;
+}
+
+extern "C" int tspm_pattern_expand(int32_t batch, int32_t npat, const int32_t* keep, const int32_t* group_id,
+                                   int32_t w_audio, int32_t w_video, int32_t w_text, const float* emb, int64_t ld_emb,
+                                   float* out, int64_t ld_out, const void* labels, void* labels_out,
+                                   int32_t label_bytes, int32_t* groups_out, tspm_stream_t stream) {
+  if (batch <= 0 || npat < 1 || npat > TSPM_MAX_PATTERNS || w_audio <= 0 || w_video <= 0 || w_text <= 0)
+    return TSPM_ERR_INVALID;
+  if (!keep || !group_id || !emb || !out || !labels || !labels_out || !groups_out) return TSPM_ERR_INVALID;
+  if (label_bytes != 4 && label_bytes != 8) return TSPM_ERR_INVALID;
+  const long long sum = (long long)w_audio + w_video + w_text;
+  if (ld_emb < sum || ld_out < sum || sum > INT32_MAX / 2) return TSPM_ERR_INVALID;
+  PatternSet ps{};
+  for (int p = 0; p < npat; ++p) {
+    const int bits = (keep[3 * p] ? 1 : 0) | (keep[3 * p + 1] ? 2 : 0) | (keep[3 * p + 2] ? 4 : 0);
+    if (bits == 0) return TSPM_ERR_INVALID;  // a pattern keeps at least one modality
+    ps.keep[p] = bits;
+    ps.group[p] = group_id[p];
+  }
+  const int w[3] = {w_audio, w_video, w_text};
+  const bool wide_ok = ld_emb % 4 == 0 && ld_out % 4 == 0 &&
+                       ((reinterpret_cast<uintptr_t>(emb) | reinterpret_cast<uintptr_t>(out)) & 15) == 0;
+  int col = 0;
+  for (int m = 0; m < 3; ++m) {
+    ps.width[m] = w[m];
+    ps.col[m] = col;
+    ps.vec[m] = (wide_ok && w[m] % 4 == 0 && col % 4 == 0) ? 1 : 0;
+    ps.units[m] = ps.vec[m] ? w[m] / 4 : w[m];
+    col += w[m];
+  }
+  const long long upr = (long long)ps.units[0] + ps.units[1] + ps.units[2];
+  hipLaunchKernelGGL(k_pattern_expand, dim3(grid_for((long long)npat * batch * upr)), dim3(256), 0,
+                     static_cast<hipStream_t>(stream), batch, npat, ps, emb, (long long)ld_emb, out, (long long)ld_out,
+                     labels, labels_out, label_bytes, groups_out);
   TSPM_LAUNCH_CHECK();
   return TSPM_OK;
 }

@@ -184,7 +184,9 @@ class MosiEpochRunner:
     (``MosiDeviceLoader`` with ``step_for`` pointed here by ``loader_for``) — or, for valid / test, the
     pattern-grouped ``{pattern: sub-batch}`` of data/mosi.py:236-251; each group is one ``validation_step`` (one
     ``FusedMosiEvalStep`` replay: its loss is one entry of the epoch's loss log, its rows go to the confusion
-    counts of their pattern).  Per-pattern metrics come from ``DeviceMetricRecorder`` with the YAML's MSA and
+    counts of their pattern).  A ``"fused_patterns"`` batch (``MOSI.loader(fuse_patterns=True)``: the samples once,
+    unmasked) is one ``FusedMosiPatternEvalStep`` replay that writes the same per-pattern entries and counts from one
+    encoder pass.  Per-pattern metrics come from ``DeviceMetricRecorder`` with the YAML's MSA and
     confusion-matrix functions (keys ``MSA_Has0_Accuracy_ATV`` ...; metric_recorder.py:147-209)."""
 
     def __init__(self, model, optimizer, loss_functions, metric_config=None, device=None, log_capacity: int = 1 << 16):
@@ -204,6 +206,7 @@ class MosiEpochRunner:
         self.eval_steps: Dict[Tuple[int, int], Any] = {}
         self.ragged = False  # the loader's dataset carries per-sample lengths (mosi_data.MOSI(use_lengths=True))
         self.text_lengths = False  # ... and the text lengths too (mosi_data.MOSI(text_lengths=True))
+        self.patterns = None  # the selected patterns of a fuse_patterns loader (loader_for)
 
     def train_step_for(self, b: int, t, ragged: Optional[bool] = None, text_lengths: Optional[bool] = None):
         """The model's cached FusedMosiStep for (b, t); ``t`` an ``int`` or a triple (Ta, Tv, Tt) (``mosi.norm_steps``).
@@ -231,15 +234,50 @@ class MosiEpochRunner:
             self.eval_steps[key] = st
         return st
 
+    def pattern_eval_step_for(self, b: int, t, patterns=None, ragged: Optional[bool] = None,
+                              text_lengths: Optional[bool] = None):
+        """The cached FusedMosiPatternEvalStep for (patterns, b, t) — every pattern of a batch from one encoder pass
+        (``mosi_data.MOSI.loader(fuse_patterns=True)``).  ``patterns`` (default: the current fused loader's
+        ``selected_patterns``, else all seven).  Cached in ``eval_steps`` under ``eval_step_for``'s key behind a
+        ("patterns", names) head, which no per-pattern key has; rebuilt like those when the model dropped its engines."""
+        from .mosi import FusedMosiPatternEvalStep, norm_patterns, norm_steps
+        t, pats = norm_steps(t), norm_patterns(self.patterns if patterns is None else patterns)
+        ragged = self.ragged if ragged is None else bool(ragged)
+        tl = self.text_lengths if text_lengths is None else bool(text_lengths)
+        key = (("patterns", pats),) + ((b, t, "ragged") if ragged else (b, t)) + (("text_lengths",) if tl else ())
+        st = self.eval_steps.get(key)
+        if st is None or st.eng is not self.model._pattern_engine(b, t, self.device, pats, ragged, tl):
+            st = FusedMosiPatternEvalStep(self.model, self.loss_functions, b, t, self.log, patterns=pats, ragged=ragged,
+                                          text_lengths=tl)
+            self.eval_steps[key] = st
+        return st
+
     def loader_for(self, loader, train: bool):
-        """Point a ``MosiDeviceLoader`` at this runner's steps (batches gathered straight into their inputs)."""
+        """Point a ``MosiDeviceLoader`` at this runner's steps (batches gathered straight into their inputs): a
+        ``fuse_patterns`` loader at ``pattern_eval_step_for`` with its dataset's selected patterns."""
         self.ragged = bool(getattr(getattr(loader, "ds", None), "use_lengths", False))
         self.text_lengths = bool(getattr(getattr(loader, "ds", None), "text_lengths", False))
+        fused = bool(getattr(loader, "fuse_patterns", False)) and not train
+        self.patterns = tuple(loader.ds.selected_patterns) if fused else None
         if hasattr(loader, "step_for"):
-            loader.step_for = self.train_step_for if train else self.eval_step_for
+            loader.step_for = (self.train_step_for if train else
+                               self.pattern_eval_step_for if fused else self.eval_step_for)
         return loader
 
+    def _eval_step_of(self, b: Dict[str, Any]):
+        """The eval step a batch asks for: the fused-pattern step for a ``"fused_patterns"`` batch, else the per-pattern
+        one."""
+        if b.get("fused_patterns"):
+            return self.pattern_eval_step_for(*self._shape(b), patterns=b["patterns"], **self._modes(b))
+        return self.eval_step_for(*self._shape(b), **self._modes(b))
+
     def _run(self, st, b: Dict[str, Any]) -> None:
+        if b.get("fused_patterns"):  # the step expands labels and group ids on the device
+            if b.get("time_major") and b["audio"] is st.eng.A:
+                st.run()
+            else:
+                st.step(b["audio"], b["video"], b["text"], b["label"], b.get("lengths"))
+            return
         st.eng.groups.copy_(self.log.group_ids(b.get("pattern_name") or b["pattern_names"]), non_blocking=True)
         if b.get("time_major") and b["audio"] is st.eng.A:
             st.run()  # the gather wrote the inputs (and, for a ragged step, the length buffers) in place
@@ -294,7 +332,7 @@ class MosiEpochRunner:
         try:
             for b in self.loader_for(loader, False):
                 for g in self._groups(b):
-                    self._run(self.eval_step_for(*self._shape(g), **self._modes(g)), g)
+                    self._run(self._eval_step_of(g), g)
         finally:
             self.model.train()
         return self._finish(t0)

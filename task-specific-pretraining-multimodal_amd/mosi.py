@@ -64,6 +64,13 @@ attention_norm="time" | "unit")`` pools every LSTM output, e = sum_t alpha_t r_t
 gradient at every step.  Such an encoder always runs the length-taking entry points (its length buffer stays at the padded
 length without ``ragged``); the encoders' methods are fixed at construction, so no cache key changes.
 
+Every missing-modality pattern of a batch from one eval pass (this project's addition, opt-in, eval only):
+under any pattern a modality is the real input or the zeroed input, so ``MosiPatternEngine`` runs the encoders once over
+2B rows (the batch and zero rows), ``tspm_pattern_expand`` builds the P*B classifier rows, labels and group ids, and the
+classifier runs once on them — ``UttFusionModel.forward_patterns``, ``FusedMosiPatternEvalStep`` (the per-pattern loss and
+metrics launches on row slices: the same log entries as P replays of ``FusedMosiEvalStep``) and
+``mosi_data.MOSI.loader(fuse_patterns=True)``.  Its cache keys start with a ("patterns", names) element; no other changes.
+
 Sentiment regression (this project's addition; the reference's YAMLs train the three-class variant only): a
 one-output ``netC.fc_out`` (``build_utt_fusion(name, output_dim=1)``) with a single mean ``nn.L1Loss`` / ``nn.MSELoss``
 term (``_regress_term``) on the float32 ``regression_labels`` runs the same steps with the head — ``fc_out``, the loss,
@@ -782,15 +789,16 @@ def _text_backward(o, t: "TextCNN", sh: int, keep: Optional[int], dout: int, ld_
 
 def _seq_load(src: torch.Tensor, dst: torch.Tensor, B: int, T: int, index, offs, lens, nm: str, sh: int) -> None:
     """A batch-first [B, T, F] tensor → the time-major buffer `dst` (one tspm_seq_gather: the dense batch seen
-    as B sequences of length T)."""
+    as B sequences of length T).  `dst` may hold more than B rows per step (``MosiPatternEngine``'s 2B): the batch
+    goes to the first B, the others are not written."""
     L.require_cuda_f32(src, nm)
     if tuple(src.shape) != (B, T, dst.shape[2]):
         raise L.TspmError(f"{nm} batch shape {tuple(src.shape)} != planned {(B, T, dst.shape[2])} (batch, {nm} "
                           f"steps, features)")
     src = src.contiguous()
     L.check(L.lib().tspm_seq_gather(B, index.data_ptr(), B, src.data_ptr(), offs.data_ptr(), lens.data_ptr(),
-                                    dst.shape[2], T, dst.data_ptr(), B * dst.shape[2], dst.shape[2], None, None, None,
-                                    sh), "seq_gather")
+                                    dst.shape[2], T, dst.data_ptr(), dst.shape[1] * dst.shape[2], dst.shape[2], None,
+                                    None, None, sh), "seq_gather")
 
 
 class MosiEngine:
@@ -800,29 +808,48 @@ class MosiEngine:
     are planned at its own length (``Ts``); ``T`` is the normalised value (the ``int`` on aligned data)."""
 
     def __init__(self, model: "UttFusionModel", batch: int, steps, device: torch.device, ragged: bool = False,
-                 text_lengths: bool = False):
+                 text_lengths: bool = False, *, encoders: bool = True, classifier: bool = True, backward: bool = True):
+        """``encoders`` / ``classifier`` / ``backward`` (all on: the train step's engine, as always): a forward-only
+        half — ``classifier=False, backward=False`` plans the three encoders up to ``fused`` and nothing after it,
+        ``encoders=False, backward=False`` the classifier from ``fused`` on with no LSTM or TextCNN buffer
+        (``MosiPatternEngine`` runs one of each, at different row counts)."""
         self.m, self.B, self.T, self.device = model, batch, norm_steps(steps), device
         self.ragged, self.text_lengths = bool(ragged), bool(text_lengths)
         # the frozen encoders (no parameter with requires_grad): their backward is skipped.  What cannot be trained (mixed
         # flags, a frozen netC) is looked up by ``backward``, from the flags of that moment - the forward runs whatever
         # the flags are
         self.frozen = _frozen_state(model)[0]
-        self.trains = {k: nm not in self.frozen for k, nm in (("a", "audio"), ("v", "video"), ("t", "text"))}
+        self.trains = {k: backward and nm not in self.frozen for k, nm in (("a", "audio"), ("v", "video"), ("t", "text"))}
         a, v, t, c = model.netA, model.netV, model.netT, model.netC
         f = dict(device=device, dtype=torch.float32)
-        B = batch
-        Ta, Tv, Tt = self.Ts = steps_triple(self.T)
+        self.Ts = steps_triple(self.T)
+        self.E = a.hidden_size + v.hidden_size + t.hidden_size
+        if c.linears()[0].in_features != self.E:
+            raise L.TspmError("FcClassifier input_dim must equal the sum of the three embedding sizes")
+        self.fused = torch.zeros(batch, self.E, **f)
+        self.keep_override: Optional[Dict[str, torch.Tensor]] = None
+        self.rng_ctr_ptr: Optional[int] = None
+        self._host_ctr: Optional[torch.Tensor] = None
+        self.concurrent = os.environ.get("TSPM_MOSI_SERIAL", "0") != "1"
+        self.side: Optional[torch.cuda.Stream] = None
+        self.grad_of = lambda p: p.grad  # noqa: E731  (FusedAdam's flat gradient views)
+        if encoders:
+            self._plan_encoders()
+        if classifier:
+            self._plan_classifier(backward)
+        if backward:
+            self._plan_backward()
+
+    def _plan_encoders(self) -> None:
+        """The encoders' half: time-major inputs, the LSTMs' saved activations, the length buffers, the TextCNN plan."""
+        m, B, device = self.m, self.B, self.device
+        a, v, t = m.netA, m.netV, m.netT
+        f = dict(device=device, dtype=torch.float32)
+        Ta, Tv, Tt = self.Ts
         self.fa, self.fv, self.ft = a.input_size, v.input_size, t.input_size
         self.A = torch.zeros(Ta, B, self.fa, **f)          # time-major inputs, each at its own length
         self.V = torch.zeros(Tv, B, self.fv, **f)
         self.X = torch.zeros(Tt, B, self.ft, **f)
-        self.labels = torch.zeros(B, dtype=torch.int64, device=device)
-        self.labels_f = torch.zeros(B, **f)               # the regression head's float32 labels
-        self.groups = torch.zeros(B, dtype=torch.int32, device=device)
-        self.E = a.hidden_size + v.hidden_size + t.hidden_size
-        if c.linears()[0].in_features != self.E:
-            raise L.TspmError("FcClassifier input_dim must equal the sum of the three embedding sizes")
-        self.fused = torch.zeros(B, self.E, **f)
         # one launch runs both recurrences: 16-bit index buffers for both when either is "maxpool" past 256 steps
         self.wide = L.lstm_wide_index(((a.embd_method, Ta), (v.embd_method, Tv)))
         self.lstm = {name: _lstm_alloc(enc, B, T_m, device, backward=self.trains[name], wide=self.wide)
@@ -836,13 +863,24 @@ class MosiEngine:
         # text_lengths: the TextCNN's own persistent int32 [B] length buffer, read by tspm_textcnn_pool_fwd_len
         self.text_lens = _length_buffer(B, Tt, device) if self.text_lengths else None
         _text_alloc(self, t, B, Tt, device)
-        nc = self.nc
-        lib = L.lib()
+        self._index = torch.arange(B, dtype=torch.int64, device=device)
+        # the dense batch seen as B sequences of length T_m: per modality (equal lengths share one pair)
+        self._lens, self._offs = {}, {}
+        for T_m in dict.fromkeys(self.Ts):
+            self._lens[T_m] = torch.full((B,), T_m, dtype=torch.int32, device=device)
+            self._offs[T_m] = torch.arange(B, dtype=torch.int64, device=device) * T_m
+
+    def _plan_classifier(self, backward: bool = True) -> None:
+        """The classifier's half, from ``fused`` on: labels, groups, the layers' outputs, logits, loss (``backward``: the
+        gradient buffers too)."""
+        B, device, c = self.B, self.device, self.m.netC
+        f = dict(device=device, dtype=torch.float32)
+        self.labels = torch.zeros(B, dtype=torch.int64, device=device)
+        self.labels_f = torch.zeros(B, **f)               # the regression head's float32 labels
+        self.groups = torch.zeros(B, dtype=torch.int32, device=device)
         self.widths = c.widths
         self.h = [torch.empty(B, w, **f) for w in self.widths]
         self.logits = torch.empty(B, c.fc_out.out_features, **f)
-        self.dlogits = torch.empty_like(self.logits)
-        self.dh = [torch.empty(B, w, **f) for w in self.widths]
         # FcClassifier(use_bn): per layer the ReLU output r (the BatchNorm input), its batch statistics and the
         # gradient of r's Linear (the BN backward writes it with the ReLU mask applied)
         self.use_bn = c.use_bn
@@ -850,37 +888,35 @@ class MosiEngine:
             self.r = [torch.empty(B, w, **f) for w in self.widths]
             self.bn_mean = [torch.empty(w, **f) for w in self.widths]
             self.bn_inv = [torch.empty(w, **f) for w in self.widths]
-            self.dr = [torch.empty(B, w, **f) for w in self.widths]
-        self.dfused = torch.empty(B, self.E, **f)
         self.loss = torch.zeros(1, **f)
         self.stats = torch.zeros(4, **f)
+        if backward:
+            self.dlogits = torch.empty_like(self.logits)
+            self.dh = [torch.empty(B, w, **f) for w in self.widths]
+            if self.use_bn:
+                self.dr = [torch.empty(B, w, **f) for w in self.widths]
+            self.dfused = torch.empty(B, self.E, **f)
+
+    def _plan_backward(self) -> None:
+        """What only a training engine keeps: the dropout keep masks, the LSTM weight-gradient plan, the clip buffers."""
+        m, B, device = self.m, self.B, self.device
+        f = dict(device=device, dtype=torch.float32)
         # dropout keep masks: TextCNN (before the embedding Linear) + one per classifier layer
-        sizes = [nc] + self.widths
+        sizes = [self.nc] + self.widths
         self.keep_all = torch.ones(B * sum(sizes), dtype=torch.uint8, device=device)
         self.keeps, off = [], 0
         for w in sizes:
             self.keeps.append(self.keep_all[off:off + B * w].view(B, w))
             off += B * w
-        self.keep_override: Optional[Dict[str, torch.Tensor]] = None
-        self.rng_ctr_ptr: Optional[int] = None
-        self._host_ctr: Optional[torch.Tensor] = None
-        plans = [(name, enc, T_m) for name, enc, T_m in (("a", a, Ta), ("v", v, Tv)) if self.trains[name]]
+        Ta, Tv, _ = self.Ts
+        plans = [(name, enc, T_m) for name, enc, T_m in (("a", m.netA, Ta), ("v", m.netV, Tv)) if self.trains[name]]
         self.wg_splits, self.wg_ws = {}, None  # the weight-gradient GEMMs of the trainable LSTMs
         if plans:
             sps, self.wg_ws = _lstm_wgrad_plan(B, [(enc, T_m) for _, enc, T_m in plans], device)
             self.wg_splits = {name: sp for (name, _, _), sp in zip(plans, sps)}
-        self.concurrent = os.environ.get("TSPM_MOSI_SERIAL", "0") != "1"
-        self.side: Optional[torch.cuda.Stream] = None
         self.clip_coef = torch.ones(1, **f)
         self.total_norm = torch.zeros(1, **f)
-        self.clip_ws = torch.zeros(int(lib.tspm_grad_clip_workspace()) // 4 + 1, **f)
-        self.grad_of = lambda p: p.grad  # noqa: E731  (FusedAdam's flat gradient views)
-        self._index = torch.arange(B, dtype=torch.int64, device=device)
-        # the dense batch seen as B sequences of length T_m: per modality (equal lengths share one pair)
-        self._lens, self._offs = {}, {}
-        for T_m in dict.fromkeys(self.Ts):
-            self._lens[T_m] = torch.full((B,), T_m, dtype=torch.int32, device=device)
-            self._offs[T_m] = torch.arange(B, dtype=torch.int64, device=device) * T_m
+        self.clip_ws = torch.zeros(int(L.lib().tspm_grad_clip_workspace()) // 4 + 1, **f)
 
     # -- inputs -------------------------------------------------------------------------------------
     def set_lengths(self, lengths: Optional[Dict[str, torch.Tensor]]) -> None:
@@ -964,6 +1000,11 @@ class MosiEngine:
         stream), joined before the classifier; everything graph-capturable.  ``head=False`` stops before
         ``fc_out`` (``head_regress`` runs it)."""
         self._keep_masks(train, sh)
+        self._forward_encoders(sh, train)
+        self._forward_classifier(sh, train, head)
+
+    def _forward_encoders(self, sh: int, train: bool) -> None:
+        """The three encoders into ``fused``: the LSTM half on the side stream, the TextCNN half on the caller's, joined."""
         if self.concurrent:
             side, sh_side = self._fork()
             with torch.cuda.stream(side):
@@ -973,7 +1014,6 @@ class MosiEngine:
         else:
             self._forward_lstm(sh)
             self._forward_text(sh, train)
-        self._forward_classifier(sh, train, head)
 
     def _forward_lstm(self, sh: int) -> None:
         lib, m = L.lib(), self.m
@@ -1037,30 +1077,52 @@ class MosiEngine:
                                     fo.bias.data_ptr(), 0, None, 1.0, self.logits.data_ptr(), fo.out_features, sh),
                 "classifier out")
 
-    def loss_fn(self, sh: int, weight: float, with_grad: bool, stats: bool = False) -> None:
-        L.check(L.lib().tspm_cross_entropy(self.B, self.logits.shape[1], self.logits.data_ptr(), self.labels.data_ptr(),
-                                           self.loss.data_ptr(), self.dlogits.data_ptr() if with_grad else None, weight,
+    def loss_fn(self, sh: int, weight: float, with_grad: bool, stats: bool = False, rows=None, loss=None) -> None:
+        """``rows`` = (first row, count): the cross-entropy of that row slice alone (forward only), written to ``loss``
+        (a one-element tensor; default: the engine's)."""
+        r0, n = rows if rows is not None else (0, self.B)
+        if with_grad and rows is not None:
+            raise L.TspmError("MosiEngine.loss_fn: a row slice has no gradient (the mean is over the slice)")
+        C = self.logits.shape[1]
+        L.check(L.lib().tspm_cross_entropy(n, C, self.logits.data_ptr() + r0 * C * 4, self.labels.data_ptr() + r0 * 8,
+                                           (self.loss if loss is None else loss).data_ptr(),
+                                           self.dlogits.data_ptr() if with_grad else None, weight,
                                            self.stats.data_ptr() if stats else None, sh), "cross_entropy")
 
-    def head_regress(self, sh: int, train: bool, kind: int, weight: float, log=None) -> None:
+    def classify_update(self, sh: int, lg, rows=None, loss=None) -> None:
+        """``tspm_classify_update`` of the rows (default: all) into the ClassificationLog ``lg``: confusion counts by
+        group, the loss appended to the epoch's log."""
+        r0, n = rows if rows is not None else (0, self.B)
+        C = self.logits.shape[1]
+        L.check(L.lib().tspm_classify_update(n, C, self.logits.data_ptr() + r0 * C * 4, self.labels.data_ptr() + r0 * 8,
+                                             self.groups.data_ptr() + r0 * 4, len(lg.groups), lg.conf.data_ptr(), None,
+                                             (self.loss if loss is None else loss).data_ptr(), lg.loss_log.data_ptr(),
+                                             lg.counters.data_ptr(), lg.capacity, sh), "classify_update")
+
+    def head_regress(self, sh: int, train: bool, kind: int, weight: float, log=None, rows=None, loss=None) -> None:
         """The regression head in ONE launch (``tspm_regress_head_step``) in place of ``fc_out``'s tspm_linear_fwd,
         tspm_cross_entropy, tspm_classify_update and ``fc_out``'s tspm_linear_bwd: predictions into ``logits``
         [B, 1], the weighted L1 / MSE loss against ``labels_f`` into ``loss``, with ``train`` the gradients of
         ``fc_out`` and ``dh[-1]`` (``backward(sh, from_head=False)`` continues from it), with ``log`` (a
-        metrics.RegressionLog) the epoch's per-pattern accumulators and loss log."""
+        metrics.RegressionLog) the epoch's per-pattern accumulators and loss log.  ``rows`` = (first row, count): the
+        head of that row slice alone (forward only), its loss written to ``loss`` (default: the engine's)."""
         fo, w = self.m.netC.fc_out, self.widths[-1]
-        if fo.out_features != 1 or not L.regress_head_supported(self.B, w):
+        r0, n = rows if rows is not None else (0, self.B)
+        if train and rows is not None:
+            raise L.TspmError("MosiEngine.head_regress: a row slice runs forward only")
+        if fo.out_features != 1 or not L.regress_head_supported(n, w):
             raise L.TspmError(f"regression head: fc_out must be Linear(hid, 1) with hid <= 128 and a multiple of 4 and "
-                              f"at most 1024 rows (got Linear({w}, {fo.out_features}), {self.B} rows)")
+                              f"at most 1024 rows (got Linear({w}, {fo.out_features}), {n} rows)")
         g = self.grad_of
-        d = L.RegressHeadDesc(n=self.B, hid=w, ld_emb=w, ld_demb=w, kind=int(kind), n_groups=1,
+        d = L.RegressHeadDesc(n=n, hid=w, ld_emb=w, ld_demb=w, kind=int(kind), n_groups=1,
                               loss_weight=float(weight))
-        d.emb, d.w, d.b = self.h[-1].data_ptr(), fo.weight.data_ptr(), fo.bias.data_ptr()
-        d.labels, d.pred, d.loss = self.labels_f.data_ptr(), self.logits.data_ptr(), self.loss.data_ptr()
+        d.emb, d.w, d.b = self.h[-1].data_ptr() + r0 * w * 4, fo.weight.data_ptr(), fo.bias.data_ptr()
+        d.labels, d.pred = self.labels_f.data_ptr() + r0 * 4, self.logits.data_ptr() + r0 * 4
+        d.loss = (self.loss if loss is None else loss).data_ptr()
         if train:
             d.dw, d.db, d.demb = g(fo.weight).data_ptr(), g(fo.bias).data_ptr(), self.dh[-1].data_ptr()
         if log is not None:
-            d.groups, d.n_groups, d.stats = self.groups.data_ptr(), len(log.groups), log.records.data_ptr()
+            d.groups, d.n_groups, d.stats = self.groups.data_ptr() + r0 * 4, len(log.groups), log.records.data_ptr()
             d.loss_log, d.counters, d.log_capacity = log.loss_log.data_ptr(), log.counters.data_ptr(), log.capacity
         L.check(L.lib().tspm_regress_head_step(ctypes.byref(d), sh), "regress_head_step")
 
@@ -1496,6 +1558,193 @@ class FusedMosiEvalStep:
 
 
 # ------------------------------------------------------------------------------------------------
+# every missing-modality pattern of a batch from one encoder pass
+# ------------------------------------------------------------------------------------------------
+ALL_PATTERNS = tuple(PATTERNS)  # "atv", "at", "av", "tv", "a", "t", "v": data/mosi.py:61-69 order (mosi_data.PATTERNS)
+
+
+def norm_patterns(patterns=None) -> tuple:
+    """The patterns of a fused-pattern pass as a tuple of names: all seven in ``ALL_PATTERNS`` order by default, or the
+    given subset in the given order.  Unknown names raise ``ValueError`` (as the dataset's constructor does); an empty or
+    repeating selection too."""
+    if patterns is None:
+        return ALL_PATTERNS
+    pats = tuple(str(p) for p in patterns)
+    bad = set(pats) - set(ALL_PATTERNS)
+    if bad:
+        raise ValueError(f"Invalid patterns: {bad}")
+    if not pats or len(set(pats)) != len(pats):
+        raise ValueError(f"patterns: 1..{len(ALL_PATTERNS)} distinct names among {ALL_PATTERNS}, got {pats!r}")
+    return pats
+
+
+def _pattern_key(key: tuple, patterns: tuple) -> tuple:
+    """The cache key of a fused-pattern engine or step: the plain key behind a ("patterns", names) head.  Every other
+    key of these caches starts with an int (a batch size or an ``id``), so the two families cannot collide."""
+    return (("patterns", tuple(patterns)),) + key
+
+
+class MosiPatternEngine:
+    """The eval-mode forward of a batch under ``patterns`` (P of the seven missing-modality patterns) from ONE encoder
+    pass.  Under any pattern a modality is the real input or the zeroed input, so the encoders run once over 2B rows —
+    rows [0, B) of the three time-major inputs hold the batch, rows [B, 2B) are zero (zeroed at allocation, never
+    written) — and ``enc.fused`` [2B, E] then holds every embedding the patterns need.  ``tspm_pattern_expand`` builds
+    the P*B classifier rows (pattern-major: row p*B + b), their labels and group ids in one launch, and the classifier
+    runs once on them (no dropout, running statistics in the BatchNorm1d).  ``enc`` is a forward-only ``MosiEngine``
+    without a classifier at 2B rows, ``cls`` one without encoders at P*B rows: no LSTM or TextCNN buffer grows with P.
+    With ``ragged`` / ``text_lengths`` the length buffers are 2B long and both halves carry the batch's lengths (a zero
+    row runs exactly as long as its real row): callers write the first B (``set_lengths``, or the loader's gather), the
+    forward mirrors them."""
+
+    def __init__(self, model: "UttFusionModel", batch: int, steps, device: torch.device, patterns=None,
+                 ragged: bool = False, text_lengths: bool = False, groups: Optional[Sequence[str]] = None):
+        if torch.device(device).type != "cuda":
+            raise L.TspmError("UttFusionModel (tspm_amd) runs on the MI355X only (no CPU fallback)")
+        self.m, self.B, self.T, self.device = model, int(batch), norm_steps(steps), device
+        self.patterns = norm_patterns(patterns)
+        self.P = P = len(self.patterns)
+        self.ragged, self.text_lengths = bool(ragged), bool(text_lengths)
+        B = self.B
+        self.enc = MosiEngine(model, 2 * B, steps, device, ragged=ragged, text_lengths=text_lengths, classifier=False,
+                              backward=False)
+        self.cls = MosiEngine(model, P * B, steps, device, encoders=False, backward=False)
+        self.Ts, self.E = self.enc.Ts, self.enc.E
+        self.A, self.V, self.X = self.enc.A, self.enc.V, self.enc.X   # [T_m, 2B, F]: the batch in rows [0, B)
+        self.labels = torch.zeros(B, dtype=torch.int64, device=device)
+        self.labels_f = torch.zeros(B, dtype=torch.float32, device=device)
+        # the first halves of the 2B-long length buffers: what set_lengths and the loader's gather write
+        self._len_bufs = ([(self.enc.lens["a"], "audio", self.Ts[0]), (self.enc.lens["v"], "video", self.Ts[1])]
+                          if self.ragged else [])
+        if self.text_lengths:
+            self._len_bufs.append((self.enc.text_lens, "text", self.Ts[2]))
+        self.lens = {"a": self.enc.lens["a"][:B], "v": self.enc.lens["v"][:B]} if self.ragged else None
+        self.text_lens = self.enc.text_lens[:B] if self.text_lengths else None
+        self.logits = self.cls.logits.view(P, B, -1)
+        self.losses = torch.zeros(P, dtype=torch.float32, device=device)  # one loss per pattern, in pattern order
+        self._keep = (ctypes.c_int32 * (3 * P))(*[int(ch in p) for p in self.patterns for ch in "avt"])
+        self.set_groups(groups)
+        eng = self.enc
+        self._index = torch.arange(B, dtype=torch.int64, device=device)
+        self._lens = {T_m: eng._lens[T_m][:B] for T_m in eng._lens}
+        self._offs = {T_m: eng._offs[T_m][:B] for T_m in eng._offs}
+
+    def set_groups(self, groups: Optional[Sequence[str]]) -> None:
+        """The group id of each pattern = its index in ``groups`` (a log's group names; default: ``ALL_PATTERNS``).  Host
+        values copied into the launch: set them before a graph is captured."""
+        names = list(ALL_PATTERNS if groups is None else groups)
+        try:
+            self._group = (ctypes.c_int32 * self.P)(*[names.index(p) for p in self.patterns])
+        except ValueError:
+            raise L.TspmError(f"patterns {self.patterns} are not all among the log's groups {names}") from None
+        self.group_names = tuple(names)
+
+    def set_lengths(self, lengths: Optional[Dict[str, torch.Tensor]]) -> None:
+        """The batch's B lengths into the first half of each 2B-long length buffer (``MosiEngine.set_lengths``'s rules);
+        the forward copies them to the second half."""
+        if not self.ragged and not self.text_lengths:
+            if lengths is not None:
+                raise L.TspmError("MosiPatternEngine: lengths given to an engine built without ragged=True")
+            return
+        lengths = lengths or {}
+        _check_lengths_arg(lengths, self.ragged, self.text_lengths)
+        for buf, nm, T_m in self._len_bufs:
+            _set_lengths(buf[:self.B], lengths.get(nm), T_m, nm)
+
+    def load(self, A: torch.Tensor, V: torch.Tensor, T: torch.Tensor, labels: Optional[torch.Tensor] = None,
+             regress: bool = False) -> None:
+        """Batch-first [B, T_m, F] tensors → rows [0, B) of the time-major buffers (``MosiEngine.load``'s launches at
+        the 2B-row time stride); ``labels`` as there."""
+        sh = L.stream_handle()
+        for src, dst, nm, T_m in zip((A, V, T), (self.A, self.V, self.X), _MODALITY_ORDER, self.Ts):
+            _seq_load(src, dst, self.B, T_m, self._index, self._offs[T_m], self._lens[T_m], nm, sh)
+        if labels is not None:
+            dst = self.labels_f if regress else self.labels
+            if labels.data_ptr() != dst.data_ptr():
+                dst.copy_(labels.reshape(-1).to(dst.dtype), non_blocking=True)
+
+    def forward(self, sh: int, head: bool = True, regress: bool = False) -> None:
+        """Length mirror, the encoders over 2B rows, ``tspm_pattern_expand``, the classifier over P*B rows (``head=False``
+        stops before ``fc_out``); everything on the caller's stream (the LSTM half forks as in ``MosiEngine``),
+        graph-capturable.  ``regress``: the float32 labels travel instead of the int64 ones."""
+        B, e, c = self.B, self.enc, self.cls
+        for buf, _, _ in self._len_bufs:
+            buf[B:].copy_(buf[:B])  # on the current stream, which is the one `sh` names
+        e._forward_encoders(sh, False)
+        a, v, t = self.m.netA, self.m.netV, self.m.netT
+        src, dst = (self.labels_f, c.labels_f) if regress else (self.labels, c.labels)
+        L.check(L.lib().tspm_pattern_expand(B, self.P, self._keep, self._group, a.hidden_size, v.hidden_size,
+                                            t.hidden_size, e.fused.data_ptr(), self.E, c.fused.data_ptr(), self.E,
+                                            src.data_ptr(), dst.data_ptr(), src.element_size(), c.groups.data_ptr(), sh),
+                "pattern_expand")
+        c._forward_classifier(sh, False, head)
+
+
+class FusedMosiPatternEvalStep:
+    """``FusedMosiEvalStep`` for every pattern of a batch at once (``MosiPatternEngine``): the batch arrives unmasked,
+    once; one HIP graph runs the 2B-row encoder pass, the expansion, the classifier on P*B rows and then, for each
+    pattern in order, the existing loss and metrics launches on its B rows (``tspm_cross_entropy`` +
+    ``tspm_classify_update``, or ``tspm_regress_head_step`` forward-only in regression mode) — so the epoch's log gets
+    the same P loss entries, in pattern order, that P replays of the per-pattern step write, and the per-pattern
+    accumulators are filled through the expanded group ids.  First call eager, second captured, later ones replays; no
+    host synchronisation; the refusals of ``FusedMosiEvalStep``.  ``step`` takes a batch-first batch, ``run`` serves
+    inputs gathered in place (``mosi_data.MOSI.loader(fuse_patterns=True)``)."""
+
+    def __init__(self, model: "UttFusionModel", loss_functions, batch: int, steps, log, patterns=None,
+                 use_graph: bool = True, ragged: bool = False, text_lengths: bool = False):
+        dev = next(model.parameters()).device
+        self.ragged, self.text_lengths = bool(ragged), bool(text_lengths)
+        self.model, self.N, self.T, self.log = model, int(batch), norm_steps(steps), log
+        self.patterns = norm_patterns(patterns)
+        self.weight = _ce_weight(loss_functions)
+        self.regress = _regress_mode(model, loss_functions)
+        if self.regress is None and self.weight is None:
+            raise L.TspmError("FusedMosiPatternEvalStep: the loss group must be a single cross-entropy term (or, with a "
+                              "one-output fc_out, a single mean L1 / MSE term)")
+        if self.regress is not None and not L.regress_head_supported(batch, model.netC.widths[-1]):
+            raise L.TspmError("FusedMosiPatternEvalStep: the regression head takes at most 1024 rows and a last "
+                              "classifier layer of at most 128 units, a multiple of 4")
+        self.eng = model._pattern_engine(batch, steps, dev, self.patterns, self.ragged, self.text_lengths)
+        self.use_graph = use_graph and not os.environ.get("TSPM_NO_GRAPH")
+        self.graph: Optional[torch.cuda.CUDAGraph] = None
+        self.calls = 0
+
+    def _all(self) -> None:
+        sh, e, lg, B = L.stream_handle(), self.eng, self.log, self.N
+        if self.regress is not None:
+            _check_regress_log(lg)
+            e.forward(sh, head=False, regress=True)
+            for p in range(e.P):
+                e.cls.head_regress(sh, False, *self.regress, lg, rows=(p * B, B), loss=e.losses[p:p + 1])
+            return
+        e.forward(sh)
+        for p in range(e.P):
+            e.cls.loss_fn(sh, self.weight, False, rows=(p * B, B), loss=e.losses[p:p + 1])
+            e.cls.classify_update(sh, lg, rows=(p * B, B), loss=e.losses[p:p + 1])
+
+    def step(self, A, V, T, labels, lengths: Optional[Dict[str, torch.Tensor]] = None) -> None:
+        self.eng.load(A, V, T, labels, self.regress is not None)
+        self.eng.set_lengths(lengths)
+        self.run()
+
+    def run(self) -> None:
+        self.model.eval()
+        if self.eng.group_names != tuple(self.log.groups):  # the log's group order decides the ids the launch carries
+            self.eng.set_groups(self.log.groups)
+            self.graph = None
+        if not self.use_graph or self.calls == 0:
+            self._all()
+        else:
+            if self.graph is None:
+                torch.cuda.synchronize()
+                g = torch.cuda.CUDAGraph()
+                with L.graph_capture(g):
+                    self._all()
+                self.graph = g
+            self.graph.replay()
+        self.calls += 1
+
+
+# ------------------------------------------------------------------------------------------------
 # the model
 # ------------------------------------------------------------------------------------------------
 def _modality(batch: Dict[Any, Any], name: str):
@@ -1605,6 +1854,40 @@ class UttFusionModel(nn.Module):
             eng = MosiEngine(self, b, t, device, ragged=ragged, text_lengths=text_lengths)
             self._engines[key] = eng
         return eng
+
+    def _pattern_engine(self, b: int, t, device, patterns=None, ragged: bool = False,
+                        text_lengths: bool = False) -> "MosiPatternEngine":
+        """The cached MosiPatternEngine for (patterns, batch, steps): ``_engine``'s key behind a ("patterns", names)
+        head (``_pattern_key``), in the same cache — dropped with the others on ``.to()``."""
+        if torch.device(device).type != "cuda":
+            raise L.TspmError("UttFusionModel (tspm_amd) runs on the MI355X only (no CPU fallback)")
+        t, pats = norm_steps(t), norm_patterns(patterns)
+        key = _pattern_key(_text_lengths_key(_ragged_key((b, t, device), ragged), text_lengths), pats)
+        eng = self._engines.get(key)
+        if eng is None:
+            eng = self._engines[key] = MosiPatternEngine(self, b, t, device, pats, ragged=ragged,
+                                                         text_lengths=text_lengths)
+        return eng
+
+    @torch.no_grad()
+    def forward_patterns(self, A: torch.Tensor, V: torch.Tensor, T: torch.Tensor, patterns=None,
+                         lengths: Optional[Dict[str, torch.Tensor]] = None) -> torch.Tensor:
+        """The eval-mode logits of the batch under every missing-modality pattern, [P, B, C], from one encoder pass
+        (``MosiPatternEngine``): ``out[p]`` is what ``model.eval()(A * ka, V * kv, T * kt)`` gives for the keep factors
+        of ``patterns[p]`` — a missing modality is the zeroed tensor through its encoder — up to summation order (the
+        dense kernels' paths depend on the row count).  ``patterns``: all seven in ``ALL_PATTERNS`` order by default, or
+        a subset in any order (unknown names: ``ValueError``).  ``A``, ``V``, ``T`` are the unmasked [B, T_m, F]
+        sequences; ``lengths`` as in ``forward``.  The module's training flag is not changed."""
+        pats = norm_patterns(patterns)
+        A, V, T = A.float(), V.float(), T.float()
+        if not (A.is_cuda and V.is_cuda and T.is_cuda):
+            raise L.TspmError("UttFusionModel (tspm_amd) runs on the MI355X only; move the model and inputs to the "
+                              "ROCm device (there is no CPU fallback)")
+        eng = self._pattern_engine(A.shape[0], _batch_steps(A, V, T), A.device, pats, *_split_lengths(lengths))
+        eng.load(A, V, T)
+        eng.set_lengths(lengths)
+        eng.forward(L.stream_handle())
+        return eng.logits.clone()
 
     def fused_step(self, optimizer: FusedAdam, loss_functions, batch: int, steps,
                    ragged: bool = False, text_lengths: bool = False) -> FusedMosiStep:

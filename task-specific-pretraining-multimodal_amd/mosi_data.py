@@ -174,7 +174,7 @@ class DeviceMosiCorpus:
 
     def gather(self, index: torch.Tensor, steps_pad, out: Dict[str, torch.Tensor], time_major: bool,
                masks: Optional[Dict[str, torch.Tensor]] = None, labels_out: Optional[torch.Tensor] = None,
-               lengths_out: Optional[Dict[str, torch.Tensor]] = None) -> None:
+               lengths_out: Optional[Dict[str, torch.Tensor]] = None, rows: Optional[int] = None) -> None:
         """Write the batch ``index`` (device int64) into ``out[m]``: [T, B, F] (time_major) or [B, T, F], for
         the modalities ``out`` names (all three for the fusion step, one for encoder pre-training); int64 labels
         ride on the first launch, float32 labels (``labels_out`` float32 [B]) take one ``tspm_avmnist_gather``
@@ -182,9 +182,14 @@ class DeviceMosiCorpus:
         length, or the (audio, video, text) triple of an unaligned batch — each modality's launch pads to its own.
         ``lengths_out``: ``{modality: int32 [B]}`` device buffers filled with the batch's true lengths
         (``self.lengths[m][index]``, on the device, no host sync) — a ragged step's length buffers, or a batch's
-        ``"lengths"``."""
+        ``"lengths"``.  ``rows`` (time-major only): ``out[m]`` holds that many rows per step, at least the batch's; the
+        batch goes to the first ``len(index)`` of them and the others are not written (a fused-pattern step's 2B-row
+        inputs)."""
         lib, sh = L.lib(), L.stream_handle()
         b = int(index.numel())
+        nrows = b if rows is None else int(rows)
+        if nrows < b or (rows is not None and not time_major):
+            raise L.TspmError(f"rows={rows}: a time-major output of at least {b} rows per step")
         for m, buf in (lengths_out or {}).items():
             if buf.dtype != torch.int32 or tuple(buf.shape) != (b,):
                 raise L.TspmError(f"lengths_out[{m!r}]: an int32 [{b}] device buffer")
@@ -197,10 +202,10 @@ class DeviceMosiCorpus:
             labels_out = None
         for j, m in enumerate([m for m in MODALITIES if m in out]):
             f, dst, tp = self.feat[m], out[m], steps_of(steps_pad, m)
-            shape = (tp, b, f) if time_major else (b, tp, f)
+            shape = (tp, nrows, f) if time_major else (b, tp, f)
             if tuple(dst.shape) != shape or not dst.is_contiguous() or dst.dtype != torch.float32:
                 raise L.TspmError(f"{m}: output {tuple(dst.shape)} != {shape} (contiguous f32)")
-            st_t, st_b = (b * f, f) if time_major else (f, tp * f)
+            st_t, st_b = (nrows * f, f) if time_major else (f, tp * f)
             mk = masks.get(m) if masks else None
             L.check(lib.tspm_seq_gather(b, index.data_ptr(), self.n, self.data[m].data_ptr(), self.offsets[m].data_ptr(),
                                         self.lengths[m].data_ptr(), f, tp, dst.data_ptr(), st_t, st_b,
@@ -377,6 +382,19 @@ class MOSI(torch.utils.data.Dataset):
         dc.gather(index, tpad, {m: out}, False, masks, lab, {m: lens} if ragged else None)
         return {m: out, "label": lab, "pattern_name": names, **({"lengths": lens} if ragged else {})}
 
+    def _length_buffers_of(self, e) -> Optional[Dict[str, torch.Tensor]]:
+        """The length buffers of a step's engine that this dataset's batches fill (None without ``use_lengths``)."""
+        if not self.use_lengths:
+            return None
+        if getattr(e, "lens", None) is None:
+            raise L.TspmError("use_lengths: the step was built without ragged=True (no length buffers)")
+        lens = {"audio": e.lens["a"], "video": e.lens["v"]}
+        if self.text_lengths:
+            if getattr(e, "text_lens", None) is None:
+                raise L.TspmError("text_lengths: the step was built without text_lengths=True (no text length buffer)")
+            lens["text"] = e.text_lens
+        return lens
+
     def _collate(self, rows: np.ndarray, pid: np.ndarray, step=None, pad_to: int = 0) -> Dict[str, Any]:
         if self.target_modality != "multimodal":
             return self._collate_mono(rows, pid, step, pad_to)
@@ -390,16 +408,7 @@ class MOSI(torch.utils.data.Dataset):
             if (e.B, e.T) != (b, tpad):
                 raise L.TspmError(f"step planned for (B={e.B}, T={e.T}), batch is (B={b}, T={tpad})")
             lab = e.labels_f if dc.float_labels else e.labels
-            lens = None
-            if self.use_lengths:
-                if getattr(e, "lens", None) is None:
-                    raise L.TspmError("use_lengths: the step was built without ragged=True (no length buffers)")
-                lens = {"audio": e.lens["a"], "video": e.lens["v"]}
-                if self.text_lengths:
-                    if getattr(e, "text_lens", None) is None:
-                        raise L.TspmError("text_lengths: the step was built without text_lengths=True (no text length "
-                                          "buffer)")
-                    lens["text"] = e.text_lens
+            lens = self._length_buffers_of(e)
             dc.gather(index, tpad, {"audio": e.A, "video": e.V, "text": e.X}, True, masks, lab, lens)
             return {"audio": e.A, "video": e.V, "text": e.X, "label": lab, "pattern_name": names,
                     "steps": tpad, "time_major": True, **({"lengths": lens} if lens is not None else {})}
@@ -412,9 +421,43 @@ class MOSI(torch.utils.data.Dataset):
                 "pattern_name": names, "pattern_names": names, "steps": tpad,
                 **({"lengths": lens} if lens is not None else {})}
 
+    def _check_fuse_patterns(self) -> None:
+        if self.split == "train" or self.target_modality != "multimodal":
+            raise L.TspmError(f"fuse_patterns=True is for the multimodal valid / test splits (every sample under every "
+                              f"selected pattern); this dataset is split {self.split!r}, target_modality "
+                              f"{self.target_modality!r}")
+
+    def _collate_fused(self, rows: np.ndarray, step=None, pad_to: int = 0) -> Dict[str, Any]:
+        """A fused-pattern batch: the samples once, unmasked, with ``"patterns"`` (the selected patterns, which the step
+        expands on the device) and ``"fused_patterns": True`` in place of ``pattern_name``.  With ``step`` (a
+        ``FusedMosiPatternEvalStep``) the gather writes rows [0, B) of its 2B-row time-major inputs, its label buffer
+        and the first halves of its length buffers."""
+        dc = self.device_corpus
+        b, tpad = len(rows), dc.batch_steps(rows, pad_to)
+        index = torch.from_numpy(rows).to(self.device, non_blocking=True)
+        extra = {"patterns": list(self.selected_patterns), "fused_patterns": True, "steps": tpad}
+        if step is not None:
+            e = step.eng
+            if (e.B, e.T) != (b, tpad) or list(e.patterns) != list(self.selected_patterns):
+                raise L.TspmError(f"step planned for (B={e.B}, T={e.T}, patterns={list(e.patterns)}), batch is (B={b}, "
+                                  f"T={tpad}, patterns={self.selected_patterns})")
+            lab = e.labels_f if dc.float_labels else e.labels
+            lens = self._length_buffers_of(e)
+            dc.gather(index, tpad, {"audio": e.A, "video": e.V, "text": e.X}, True, None, lab, lens, rows=2 * b)
+            return {"audio": e.A, "video": e.V, "text": e.X, "label": lab, "time_major": True, **extra,
+                    **({"lengths": lens} if lens is not None else {})}
+        out = {m: torch.empty(b, steps_of(tpad, m), dc.feat[m], device=self.device) for m in MODALITIES}
+        lab = torch.empty(b, dtype=dc.label_dtype, device=self.device)
+        lens = ({m: torch.empty(b, dtype=torch.int32, device=self.device) for m in self._length_modalities()}
+                if self.use_lengths else None)
+        dc.gather(index, tpad, out, False, None, lab, lens)
+        return {"audio": out["audio"], "video": out["video"], "text": out["text"], "label": lab, **extra,
+                **({"lengths": lens} if lens is not None else {})}
+
     def device_loader(self, batch_size: int, shuffle: bool = False, drop_last: bool = False,
                       generator: Optional[torch.Generator] = None, step_for=None,
-                      pad_to: int = 0, group_patterns: Optional[bool] = None) -> Iterator[Dict[str, Any]]:
+                      pad_to: int = 0, group_patterns: Optional[bool] = None,
+                      fuse_patterns: bool = False) -> Iterator[Dict[str, Any]]:
         """One epoch of batches gathered on device.  ``step_for(B, T) -> FusedMosiStep`` (or
         ``FusedMosiEvalStep``): gather each batch time-major straight into that step's input buffers.
         ``pad_to``: pad every batch to at least this many steps (the aligned length, e.g. 50 for aligned_50:
@@ -425,7 +468,22 @@ class MOSI(torch.utils.data.Dataset):
         ``pad_to`` that covers the corpus gives one step shape, hence one graph, for the epoch.
         ``group_patterns`` (default: valid / test splits, as collate_fn):
         each batch is ``{pattern: sub-batch}`` in first-seen order (data/mosi.py:236-251); with a single target
-        modality the default is flat batches (``step_for`` then returns the monomodal train / eval step)."""
+        modality the default is flat batches (``step_for`` then returns the monomodal train / eval step).
+        ``fuse_patterns`` (multimodal valid / test splits only): each sample is yielded ONCE, unmasked, in sample order,
+        in batches that carry ``"patterns": list(selected_patterns)`` and ``"fused_patterns": True`` and no
+        ``pattern_name`` — ``step_for(B, T)`` then returns a ``FusedMosiPatternEvalStep``, which evaluates every
+        pattern of the batch from one encoder pass."""
+        if fuse_patterns:
+            self._check_fuse_patterns()
+            ns = self.num_samples
+            order = torch.randperm(ns, generator=generator).numpy() if shuffle else np.arange(ns)
+            for s in range(0, ns, batch_size):
+                rows = order[s:s + batch_size].astype(np.int64)
+                if drop_last and len(rows) < batch_size:
+                    break
+                step = step_for(len(rows), self.device_corpus.batch_steps(rows, pad_to)) if step_for is not None else None
+                yield self._collate_fused(rows, step, pad_to)
+            return
         n = len(self)
         grouped = ((self.split != "train" and self.target_modality == "multimodal") if group_patterns is None
                    else bool(group_patterns))
@@ -454,9 +512,14 @@ class MOSI(torch.utils.data.Dataset):
                 yield out if grouped else out[None]
 
     def loader(self, batch_size: int, shuffle: bool = False, drop_last: bool = False, seed: Optional[int] = None,
-               step_for=None, pad_to: int = 0, group_patterns: Optional[bool] = None) -> "MosiDeviceLoader":
-        """A re-iterable epoch loader (one ``device_loader`` pass per ``iter``), as a DataLoader is."""
-        return MosiDeviceLoader(self, batch_size, shuffle, drop_last, seed, step_for, pad_to, group_patterns)
+               step_for=None, pad_to: int = 0, group_patterns: Optional[bool] = None,
+               fuse_patterns: bool = False) -> "MosiDeviceLoader":
+        """A re-iterable epoch loader (one ``device_loader`` pass per ``iter``), as a DataLoader is.  ``fuse_patterns``:
+        see ``device_loader`` (refused here already for a train or single-modality dataset)."""
+        if fuse_patterns:
+            self._check_fuse_patterns()
+        return MosiDeviceLoader(self, batch_size, shuffle, drop_last, seed, step_for, pad_to, group_patterns,
+                                fuse_patterns)
 
     def get_split(self) -> str:
         return self.split
@@ -483,13 +546,14 @@ class MosiDeviceLoader:
     (the harness points it at its own train / eval steps)."""
 
     def __init__(self, ds: MOSI, batch_size: int, shuffle: bool, drop_last: bool, seed: Optional[int], step_for,
-                 pad_to: int, group_patterns: Optional[bool]):
+                 pad_to: int, group_patterns: Optional[bool], fuse_patterns: bool = False):
         self.ds, self.batch_size, self.shuffle, self.drop_last = ds, batch_size, shuffle, drop_last
         self.seed, self.step_for, self.pad_to, self.group_patterns = seed, step_for, pad_to, group_patterns
+        self.fuse_patterns = bool(fuse_patterns)
         self.epoch = 0
 
     def __len__(self) -> int:
-        n = len(self.ds)
+        n = self.ds.num_samples if self.fuse_patterns else len(self.ds)
         return n // self.batch_size if self.drop_last else -(-n // self.batch_size)
 
     def __iter__(self):
@@ -499,4 +563,4 @@ class MosiDeviceLoader:
             gen.manual_seed((self.seed if self.seed is not None else 0) + self.epoch)
         self.epoch += 1
         return self.ds.device_loader(self.batch_size, self.shuffle, self.drop_last, gen, self.step_for, self.pad_to,
-                                     self.group_patterns)
+                                     self.group_patterns, self.fuse_patterns)
