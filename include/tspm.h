@@ -1036,6 +1036,21 @@ int tspm_pattern_expand(int32_t batch, int32_t npat, const int32_t* keep, const 
                         int32_t w_video, int32_t w_text, const float* emb, int64_t ld_emb, float* out, int64_t ld_out,
                         const void* labels, void* labels_out, int32_t label_bytes, int32_t* groups_out,
                         tspm_stream_t stream);
+/* The adjoint of tspm_pattern_expand (added under ABI 23), for training every pattern of a batch in one step: folds
+ * the classifier-input gradient dout [npat*batch][ld_dout] (row p*batch + b) back onto the 2*batch encoder rows.  For
+ * each modality m whose bit is set in modalities (bit 0 audio, 1 video, 2 text), b < batch and column c of m:
+ *   demb[b*ld_demb + c]           = sum over the p with keep[3p + m] != 0 of dout[(p*batch + b)*ld_dout + c]
+ *   demb[(batch + b)*ld_demb + c] = sum over the p with keep[3p + m] == 0 of the same
+ * Each sum starts from +0.0 and adds in ascending p with plain fp32 adds (nothing to contract, no atomics: one thread
+ * owns one output unit), so it is deterministic and a host loop restates it bit for bit; a slot no pattern uses is
+ * written +0.0.  Columns of a modality whose bit is clear (a frozen encoder, whose gradient nobody reads) and padding
+ * columns keep their content.  keep is a HOST array as above.  16 bytes per thread under tspm_pattern_expand's rule
+ * (applied to dout / ld_dout and demb / ld_demb), else one float.  TSPM_ERR_INVALID before any launch: everything
+ * tspm_pattern_expand refuses (batch <= 0, npat outside 1..TSPM_MAX_PATTERNS, a non-positive width, ld_dout or
+ * ld_demb below the width sum, a pattern that keeps nothing, a NULL pointer) and modalities outside 1..7. */
+int tspm_pattern_expand_bwd(int32_t batch, int32_t npat, const int32_t* keep, int32_t w_audio, int32_t w_video,
+                            int32_t w_text, const float* dout, int64_t ld_dout, float* demb, int64_t ld_demb,
+                            int32_t modalities, tspm_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Monomodal pre-training head (ABI 23) — train_monomodal.MonomodalEncoder's `classifier = nn.Linear(hid,

@@ -405,6 +405,8 @@ _SIGS = {
     # added under ABI 23: every missing-modality pattern of a batch from one 2B-row encoder pass (host keep / group arrays)
     "tspm_pattern_expand": (c_int32, [c_int32, c_int32, POINTER(c_int32), POINTER(c_int32), c_int32, c_int32, c_int32,
                                       _P, c_int64, _P, c_int64, _P, _P, c_int32, _P, _P]),
+    "tspm_pattern_expand_bwd": (c_int32, [c_int32, c_int32, POINTER(c_int32), c_int32, c_int32, c_int32,
+                                          _P, c_int64, _P, c_int64, c_int32, _P]),
 }
 
 EXPORTED = tuple(_SIGS)

@@ -812,6 +812,47 @@ __global__ __launch_bounds__(256) void k_pattern_expand(int B, int npat, Pattern
   }
 }
 
+// The adjoint of k_pattern_expand: demb [2B][ld_demb] row b takes, per modality, the sum of dout's rows (p, b) over the
+// patterns that keep the modality, row B + b the sum over those that drop it.  One thread owns one unit of demb (the
+// unit rule above) and adds the patterns in ascending p from +0.0 — plain fp32 adds, no atomics, so the host can
+// restate it bit for bit; a slot no pattern uses is written +0.0.  Units of a modality whose bit in mods is clear are
+// skipped: their columns keep their content.
+__global__ __launch_bounds__(256) void k_pattern_expand_bwd(int B, int npat, PatternSet ps,
+                                                            const float* __restrict__ dout, long long ld_dout,
+                                                            float* __restrict__ demb, long long ld_demb, int mods) {
+  const int u0 = ps.units[0], u01 = u0 + ps.units[1], upr = u01 + ps.units[2];
+  const long long total = 2LL * B * upr;
+  for (long long e = blockIdx.x * 256LL + threadIdx.x; e < total; e += (long long)gridDim.x * 256) {
+    const int u = (int)(e % upr);
+    const long long row = e / upr;  // half * B + b
+    const int b = (int)(row % B), want = row < B ? 1 : 0;
+    const int m = u < u0 ? 0 : (u < u01 ? 1 : 2);
+    if (!((mods >> m) & 1)) continue;
+    const int uu = u - (m == 0 ? 0 : (m == 1 ? u0 : u01));
+    const float* s = dout + b * ld_dout + ps.col[m];
+    float* d = demb + row * ld_demb + ps.col[m];
+    if (ps.vec[m]) {
+      float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+      for (int p = 0; p < npat; ++p) {
+        if (((ps.keep[p] >> m) & 1) != want) continue;
+        const float4 g = reinterpret_cast<const float4*>(s + (long long)p * B * ld_dout)[uu];
+        acc.x += g.x;
+        acc.y += g.y;
+        acc.z += g.z;
+        acc.w += g.w;
+      }
+      reinterpret_cast<float4*>(d)[uu] = acc;
+    } else {
+      float acc = 0.f;
+      for (int p = 0; p < npat; ++p) {
+        if (((ps.keep[p] >> m) & 1) != want) continue;
+        acc += s[(long long)p * B * ld_dout + uu];
+      }
+      d[uu] = acc;
+    }
+  }
+}
+
 // ------------------------------------------------------------------------------------------------
 // LSTM host path: each of the nine entry points fills one LstmProb per descriptor, validates it against the entry
 // point's rules and hands the problems to lstm_dispatch.
@@ -1153,6 +1194,31 @@ extern "C" int tspm_seq_gather(int32_t count, const int64_t* index, int64_t n_sa
   return TSPM_OK;
 }
 
+// Fills ps from the host tables (group_id may be null) and picks each modality's unit: a float4 where strides4 holds
+// (both row strides multiples of 4), both bases are 16-byte aligned and the width and column offset are multiples of 4.
+// False for a pattern that keeps nothing.
+static bool pattern_set_fill(PatternSet& ps, int npat, const int32_t* keep, const int32_t* group_id, int w_audio,
+                             int w_video, int w_text, bool strides4, const void* base_a, const void* base_b) {
+  for (int p = 0; p < npat; ++p) {
+    const int bits = (keep[3 * p] ? 1 : 0) | (keep[3 * p + 1] ? 2 : 0) | (keep[3 * p + 2] ? 4 : 0);
+    if (bits == 0) return false;  // a pattern keeps at least one modality
+    ps.keep[p] = bits;
+    ps.group[p] = group_id ? group_id[p] : 0;
+  }
+  const int w[3] = {w_audio, w_video, w_text};
+  const bool wide_ok =
+      strides4 && ((reinterpret_cast<uintptr_t>(base_a) | reinterpret_cast<uintptr_t>(base_b)) & 15) == 0;
+  int col = 0;
+  for (int m = 0; m < 3; ++m) {
+    ps.width[m] = w[m];
+    ps.col[m] = col;
+    ps.vec[m] = (wide_ok && w[m] % 4 == 0 && col % 4 == 0) ? 1 : 0;
+    ps.units[m] = ps.vec[m] ? w[m] / 4 : w[m];
+    col += w[m];
+  }
+  return true;
+}
+
 extern "C" int tspm_pattern_expand(int32_t batch, int32_t npat, const int32_t* keep, const int32_t* group_id,
                                    int32_t w_audio, int32_t w_video, int32_t w_text, const float* emb, int64_t ld_emb,
                                    float* out, int64_t ld_out, const void* labels, void* labels_out,
@@ -1164,27 +1230,32 @@ extern "C" int tspm_pattern_expand(int32_t batch, int32_t npat, const int32_t* k
   const long long sum = (long long)w_audio + w_video + w_text;
   if (ld_emb < sum || ld_out < sum || sum > INT32_MAX / 2) return TSPM_ERR_INVALID;
   PatternSet ps{};
-  for (int p = 0; p < npat; ++p) {
-    const int bits = (keep[3 * p] ? 1 : 0) | (keep[3 * p + 1] ? 2 : 0) | (keep[3 * p + 2] ? 4 : 0);
-    if (bits == 0) return TSPM_ERR_INVALID;  // a pattern keeps at least one modality
-    ps.keep[p] = bits;
-    ps.group[p] = group_id[p];
-  }
-  const int w[3] = {w_audio, w_video, w_text};
-  const bool wide_ok = ld_emb % 4 == 0 && ld_out % 4 == 0 &&
-                       ((reinterpret_cast<uintptr_t>(emb) | reinterpret_cast<uintptr_t>(out)) & 15) == 0;
-  int col = 0;
-  for (int m = 0; m < 3; ++m) {
-    ps.width[m] = w[m];
-    ps.col[m] = col;
-    ps.vec[m] = (wide_ok && w[m] % 4 == 0 && col % 4 == 0) ? 1 : 0;
-    ps.units[m] = ps.vec[m] ? w[m] / 4 : w[m];
-    col += w[m];
-  }
+  if (!pattern_set_fill(ps, npat, keep, group_id, w_audio, w_video, w_text, ld_emb % 4 == 0 && ld_out % 4 == 0, emb, out))
+    return TSPM_ERR_INVALID;
   const long long upr = (long long)ps.units[0] + ps.units[1] + ps.units[2];
   hipLaunchKernelGGL(k_pattern_expand, dim3(grid_for((long long)npat * batch * upr)), dim3(256), 0,
                      static_cast<hipStream_t>(stream), batch, npat, ps, emb, (long long)ld_emb, out, (long long)ld_out,
                      labels, labels_out, label_bytes, groups_out);
+  TSPM_LAUNCH_CHECK();
+  return TSPM_OK;
+}
+
+extern "C" int tspm_pattern_expand_bwd(int32_t batch, int32_t npat, const int32_t* keep, int32_t w_audio,
+                                       int32_t w_video, int32_t w_text, const float* dout, int64_t ld_dout,
+                                       float* demb, int64_t ld_demb, int32_t modalities, tspm_stream_t stream) {
+  if (batch <= 0 || npat < 1 || npat > TSPM_MAX_PATTERNS || w_audio <= 0 || w_video <= 0 || w_text <= 0)
+    return TSPM_ERR_INVALID;
+  if (!keep || !dout || !demb || modalities < 1 || modalities > 7) return TSPM_ERR_INVALID;
+  const long long sum = (long long)w_audio + w_video + w_text;
+  if (ld_dout < sum || ld_demb < sum || sum > INT32_MAX / 2) return TSPM_ERR_INVALID;
+  PatternSet ps{};
+  if (!pattern_set_fill(ps, npat, keep, nullptr, w_audio, w_video, w_text, ld_dout % 4 == 0 && ld_demb % 4 == 0, dout,
+                        demb))
+    return TSPM_ERR_INVALID;
+  const long long upr = (long long)ps.units[0] + ps.units[1] + ps.units[2];
+  hipLaunchKernelGGL(k_pattern_expand_bwd, dim3(grid_for(2LL * batch * upr)), dim3(256), 0,
+                     static_cast<hipStream_t>(stream), batch, npat, ps, dout, (long long)ld_dout, demb,
+                     (long long)ld_demb, modalities);
   TSPM_LAUNCH_CHECK();
   return TSPM_OK;
 }

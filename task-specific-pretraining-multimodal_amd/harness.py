@@ -252,17 +252,40 @@ class MosiEpochRunner:
             self.eval_steps[key] = st
         return st
 
+    def train_pattern_step_for(self, b: int, t, patterns=None, ragged: Optional[bool] = None,
+                               text_lengths: Optional[bool] = None):
+        """The model's cached FusedMosiPatternStep for (patterns, b, t) - every pattern of a batch trained in one step
+        (``mosi_data.MOSI.loader(all_patterns=True)``), with this runner's log attached as ``train_step_for`` attaches
+        it.  ``patterns`` (default: the current all-pattern loader's ``selected_patterns``, else all seven)."""
+        from .mosi import norm_patterns
+        ragged = self.ragged if ragged is None else bool(ragged)
+        tl = self.text_lengths if text_lengths is None else bool(text_lengths)
+        pats = getattr(self, "patterns", None) if patterns is None else patterns
+        st = self.model.fused_pattern_step(self.optimizer, self.loss_functions, b, t, norm_patterns(pats), ragged=ragged,
+                                           text_lengths=tl)
+        if st.log is not self.log:
+            st.log, st.graph = self.log, None  # the captured graph must record into this log
+        return st
+
     def loader_for(self, loader, train: bool):
         """Point a ``MosiDeviceLoader`` at this runner's steps (batches gathered straight into their inputs): a
-        ``fuse_patterns`` loader at ``pattern_eval_step_for`` with its dataset's selected patterns."""
+        ``fuse_patterns`` loader at ``pattern_eval_step_for``, a train ``all_patterns`` loader at
+        ``train_pattern_step_for``, each with its dataset's selected patterns."""
         self.ragged = bool(getattr(getattr(loader, "ds", None), "use_lengths", False))
         self.text_lengths = bool(getattr(getattr(loader, "ds", None), "text_lengths", False))
         fused = bool(getattr(loader, "fuse_patterns", False)) and not train
-        self.patterns = tuple(loader.ds.selected_patterns) if fused else None
+        allp = bool(getattr(loader, "all_patterns", False)) and train
+        self.patterns = tuple(loader.ds.selected_patterns) if fused or allp else None
         if hasattr(loader, "step_for"):
-            loader.step_for = (self.train_step_for if train else
+            loader.step_for = (self.train_pattern_step_for if allp else self.train_step_for if train else
                                self.pattern_eval_step_for if fused else self.eval_step_for)
         return loader
+
+    def _train_step_of(self, b: Dict[str, Any]):
+        """The train step a batch asks for: the all-pattern step for an ``"all_patterns"`` batch, else the plain one."""
+        if b.get("all_patterns"):
+            return self.train_pattern_step_for(*self._shape(b), patterns=b["patterns"], **self._modes(b))
+        return self.train_step_for(*self._shape(b), **self._modes(b))
 
     def _eval_step_of(self, b: Dict[str, Any]):
         """The eval step a batch asks for: the fused-pattern step for a ``"fused_patterns"`` batch, else the per-pattern
@@ -272,7 +295,7 @@ class MosiEpochRunner:
         return self.eval_step_for(*self._shape(b), **self._modes(b))
 
     def _run(self, st, b: Dict[str, Any]) -> None:
-        if b.get("fused_patterns"):  # the step expands labels and group ids on the device
+        if b.get("fused_patterns") or b.get("all_patterns"):  # the step expands labels and group ids on the device
             if b.get("time_major") and b["audio"] is st.eng.A:
                 st.run()
             else:
@@ -321,7 +344,7 @@ class MosiEpochRunner:
         t0 = time.time()
         for b in self.loader_for(loader, True):
             for g in self._groups(b):
-                self._run(self.train_step_for(*self._shape(g), **self._modes(g)), g)
+                self._run(self._train_step_of(g), g)
         return self._finish(t0)
 
     @torch.no_grad()

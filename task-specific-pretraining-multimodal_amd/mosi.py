@@ -71,6 +71,16 @@ classifier runs once on them — ``UttFusionModel.forward_patterns``, ``FusedMos
 metrics launches on row slices: the same log entries as P replays of ``FusedMosiEvalStep``) and
 ``mosi_data.MOSI.loader(fuse_patterns=True)``.  Its cache keys start with a ("patterns", names) element; no other changes.
 
+Training every pattern of a batch in one step (this project's addition, opt-in; the reference draws one random
+pattern per sample, and that path is unchanged): ``FusedMosiPatternStep`` (``UttFusionModel.fused_pattern_step``, an
+``"all_patterns"`` batch in ``train_step``, ``mosi_data.MOSI.loader(all_patterns=True)``) runs ``MosiPatternEngine(backward=
+True)`` - the encoders forward and backward over the same 2B rows, the classifier over the P*B expanded rows, and between
+them ``tspm_pattern_expand_bwd``, the expansion's adjoint, which folds the [P*B, E] classifier-input gradient onto the
+[2B, E] encoder rows (ascending-p fp32 sums, no atomics; a frozen encoder's columns untouched).  The loss is the weighted
+mean over all P*B rows - a plain step on the replicated batch cat_p(A*ka_p, V*kv_p, T*kt_p); BatchNorm1d takes its
+statistics over the P*B rows and updates its running statistics once per step; the TextCNN dropout mask is drawn per
+encoder row (2B; shared by the patterns that read the row), the classifier masks per classifier row (P*B).
+
 Sentiment regression (this project's addition; the reference's YAMLs train the three-class variant only): a
 one-output ``netC.fc_out`` (``build_utt_fusion(name, output_dim=1)``) with a single mean ``nn.L1Loss`` / ``nn.MSELoss``
 term (``_regress_term``) on the float32 ``regression_labels`` runs the same steps with the head — ``fc_out``, the loss,
@@ -812,7 +822,10 @@ class MosiEngine:
         """``encoders`` / ``classifier`` / ``backward`` (all on: the train step's engine, as always): a forward-only
         half — ``classifier=False, backward=False`` plans the three encoders up to ``fused`` and nothing after it,
         ``encoders=False, backward=False`` the classifier from ``fused`` on with no LSTM or TextCNN buffer
-        (``MosiPatternEngine`` runs one of each, at different row counts)."""
+        (``MosiPatternEngine`` runs one of each, at different row counts).  A half with ``backward`` plans only its own
+        masks and gradient buffers: the encoder half ``dfused``, the TextCNN keep mask, the LSTM ``dg`` buffers and
+        weight-gradient plan; the classifier half ``dlogits`` / ``dh`` / ``dr`` / ``dfused``, its layers' keep masks and
+        the clip buffers."""
         self.m, self.B, self.T, self.device = model, batch, norm_steps(steps), device
         self.ragged, self.text_lengths = bool(ragged), bool(text_lengths)
         # the frozen encoders (no parameter with requires_grad): their backward is skipped.  What cannot be trained (mixed
@@ -833,6 +846,7 @@ class MosiEngine:
         self.concurrent = os.environ.get("TSPM_MOSI_SERIAL", "0") != "1"
         self.side: Optional[torch.cuda.Stream] = None
         self.grad_of = lambda p: p.grad  # noqa: E731  (FusedAdam's flat gradient views)
+        self.has_encoders, self.has_classifier = bool(encoders), bool(classifier)
         if encoders:
             self._plan_encoders()
         if classifier:
@@ -898,22 +912,28 @@ class MosiEngine:
             self.dfused = torch.empty(B, self.E, **f)
 
     def _plan_backward(self) -> None:
-        """What only a training engine keeps: the dropout keep masks, the LSTM weight-gradient plan, the clip buffers."""
+        """What only a training engine keeps: the dropout keep masks, the LSTM weight-gradient plan, the clip buffers —
+        of the halves this engine holds (a half alone: ``keeps[0]`` is empty without the encoders, there are no
+        ``keeps[1:]`` without the classifier; ``dfused`` is the classifier half's, or the encoder half's own)."""
         m, B, device = self.m, self.B, self.device
         f = dict(device=device, dtype=torch.float32)
         # dropout keep masks: TextCNN (before the embedding Linear) + one per classifier layer
-        sizes = [self.nc] + self.widths
+        sizes = [self.nc if self.has_encoders else 0] + (self.widths if self.has_classifier else [])
         self.keep_all = torch.ones(B * sum(sizes), dtype=torch.uint8, device=device)
         self.keeps, off = [], 0
         for w in sizes:
             self.keeps.append(self.keep_all[off:off + B * w].view(B, w))
             off += B * w
         Ta, Tv, _ = self.Ts
-        plans = [(name, enc, T_m) for name, enc, T_m in (("a", m.netA, Ta), ("v", m.netV, Tv)) if self.trains[name]]
+        plans = [(name, enc, T_m) for name, enc, T_m in (("a", m.netA, Ta), ("v", m.netV, Tv))
+                 if self.trains[name] and self.has_encoders]
         self.wg_splits, self.wg_ws = {}, None  # the weight-gradient GEMMs of the trainable LSTMs
         if plans:
             sps, self.wg_ws = _lstm_wgrad_plan(B, [(enc, T_m) for _, enc, T_m in plans], device)
             self.wg_splits = {name: sp for (name, _, _), sp in zip(plans, sps)}
+        if not self.has_classifier:
+            self.dfused = torch.empty(B, self.E, **f)  # the encoder half's own: tspm_pattern_expand_bwd writes it
+            return
         self.clip_coef = torch.ones(1, **f)
         self.total_norm = torch.zeros(1, **f)
         self.clip_ws = torch.zeros(int(L.lib().tspm_grad_clip_workspace()) // 4 + 1, **f)
@@ -1132,12 +1152,21 @@ class MosiEngine:
         encoder's backward is skipped: no tspm_lstm_bwd* problem, weight-gradient GEMMs or ``dg`` buffer for a frozen
         LSTM (no launch and no side-stream fork with both frozen), no ``_text_backward`` for a frozen ``netT``, and with
         all three frozen layer 0's ``linear_bwd`` gets no ``dx``: ``dfused`` is never written."""
+        self._check_flags()
+        self._backward_classifier(sh, from_head)
+        self._backward_encoders(sh)
+
+    def _check_flags(self) -> None:
         frozen, error = self.m.flag_state()[1]  # the flags now, not those of the engine's construction
         if error is not None:
             raise L.TspmError(f"UttFusionModel HIP path: {error}")
         if frozen != self.frozen:
             raise L.TspmError(f"MosiEngine: requires_grad flags changed since this engine was planned (frozen then: "
                               f"{self.frozen}, now: {frozen})")
+
+    def _backward_classifier(self, sh: int, from_head: bool = True) -> None:
+        """``fc_out`` (``from_head``) and the classifier layers, down to ``dfused`` (not written with every encoder
+        frozen)."""
         lib, m, g = L.lib(), self.m, self.grad_of
         B = self.B
         c = m.netC
@@ -1169,6 +1198,9 @@ class MosiEngine:
                 dx = None  # every encoder frozen: nothing reads the embeddings' gradient
             linear_bwd(B, fin, w, xin.data_ptr(), fin, dy.data_ptr(), w, lins[j].weight.data_ptr(),
                        g(lins[j].weight).data_ptr(), g(lins[j].bias).data_ptr(), L.ptr(dx), lddx, sh)
+
+    def _backward_encoders(self, sh: int) -> None:
+        """The trainable encoders' backward from ``dfused``: the LSTM half on the side stream when both halves train."""
         lstm, text = self.trains["a"] or self.trains["v"], self.trains["t"]
         if not (lstm and text):  # a frozen half: the other one (if any) on the caller's stream, no fork
             if text:
@@ -1401,11 +1433,11 @@ class FusedMosiStep:
         if self.regress is None and self.weight is None:
             raise L.TspmError("FusedMosiStep: the loss group must be a single cross-entropy term (or, with a "
                               "one-output fc_out, a single mean L1 / MSE term)")
-        if self.regress is not None and not L.regress_head_supported(batch, model.netC.widths[-1]):
+        if self.regress is not None and not L.regress_head_supported(self._head_rows(batch), model.netC.widths[-1]):
             raise L.TspmError("FusedMosiStep: the regression head takes at most 1024 rows and a last classifier "
                               "layer of at most 128 units, a multiple of 4")
         self.ragged, self.text_lengths = bool(ragged), bool(text_lengths)
-        self.eng = MosiEngine(model, batch, steps, dev, ragged=self.ragged, text_lengths=self.text_lengths)
+        self.eng = self._build_engine(dev, steps)
         # the dropout counter is group 0's step (all groups advance together)
         self.eng.rng_ctr_ptr = fgs[0].hyper.data_ptr() + L.HYPER_STEP_OFFSET
         if model.clip is not None:
@@ -1415,6 +1447,13 @@ class FusedMosiStep:
         self.graph: Optional[torch.cuda.CUDAGraph] = None
         self.calls = 0
         self.log = None  # metrics.ClassificationLog (train predictions on the device); RegressionLog in regression mode
+
+    def _head_rows(self, batch: int) -> int:
+        """The rows the head runs over (the regression head's limit applies to them)."""
+        return batch
+
+    def _build_engine(self, dev, steps):
+        return MosiEngine(self.model, self.N, steps, dev, ragged=self.ragged, text_lengths=self.text_lengths)
 
     @property
     def keep_override(self):
@@ -1495,6 +1534,69 @@ class FusedMosiStep:
             self._opt()
         self.opt.note_steps(1)
         self.calls += 1
+
+
+class FusedMosiPatternStep(FusedMosiStep):
+    """``FusedMosiStep`` that trains every batch row under each of ``patterns`` (P of the seven missing-modality
+    patterns; default all) in one step (``MosiPatternEngine(backward=True)``): the batch arrives
+    unmasked, once; the encoders run forward and backward over 2B rows (the batch and zero rows), the classifier over
+    the P*B expanded rows.  ``FusedMosiStep``'s order — ``check_param_groups`` (1..8 groups, frozen encoders), forward,
+    the loss with its gradient, ``tspm_classify_update`` over the P*B rows with the expanded group ids when a log is
+    attached (ONE loss entry per step, confusion counts per pattern), backward, clip, Adam; first call eager, second
+    captured, later ones replays; the dropout counter is group 0's step.  The loss is the weighted mean cross-entropy
+    over all P*B rows, i.e. a plain step on the replicated batch cat_p(A*ka_p, V*kv_p, T*kt_p) with labels and lengths
+    tiled P times; BatchNorm1d (MOSEI) takes its statistics over the P*B rows and updates its running statistics once;
+    the TextCNN dropout mask is per encoder row (2B; shared by the patterns that read the row), the classifier masks
+    per classifier row (``keep_override``: ``"text"`` [2B, nc], ``"cls{j}"`` [P*B, w_j]).  Regression mode runs
+    ``head_regress`` over the P*B rows, so P*B is within the head's 1024 rows or the step is refused.  ``step`` returns
+    ``{"loss", "logits"}`` with ``logits`` [P, B, C]; ``run`` serves inputs gathered in place
+    (``mosi_data.MOSI.loader(all_patterns=True)``).  ``allreduce`` is refused: data parallelism is not built for this
+    step."""
+
+    def __init__(self, model: "UttFusionModel", optimizer: FusedAdam, loss_functions, batch: int, steps, patterns=None,
+                 use_graph: bool = True, ragged: bool = False, text_lengths: bool = False, allreduce=None):
+        if allreduce is not None:
+            raise L.TspmError("FusedMosiPatternStep: allreduce (data parallelism) is not built for the all-pattern step; "
+                              "it runs on one device")
+        self.patterns = norm_patterns(patterns)
+        super().__init__(model, optimizer, loss_functions, batch, steps, use_graph=use_graph, ragged=ragged,
+                         text_lengths=text_lengths)
+
+    def _head_rows(self, batch: int) -> int:
+        return len(self.patterns) * batch
+
+    def _build_engine(self, dev, steps):
+        return MosiPatternEngine(self.model, self.N, steps, dev, self.patterns, ragged=self.ragged,
+                                 text_lengths=self.text_lengths, backward=True)
+
+    def _fwd_bwd(self) -> None:
+        sh, e = L.stream_handle(), self.eng
+        if self.regress is not None:
+            _check_regress_log(self.log)
+            e.forward(sh, head=False, regress=True, train=True)
+            e.cls.head_regress(sh, True, *self.regress, self.log)
+            e.backward(sh, from_head=False)
+            return
+        e.forward(sh, train=True)
+        e.cls.loss_fn(sh, self.weight, True, True)
+        if self.log is not None:
+            e.cls.classify_update(sh, self.log)
+        e.backward(sh)
+
+    def step(self, A, V, T, labels, lengths: Optional[Dict[str, torch.Tensor]] = None) -> Dict[str, torch.Tensor]:
+        """The unmasked batch ([B, T_m, F] each, B labels); ``lengths`` as in ``FusedMosiStep.step`` (B per modality:
+        the zero rows run as long as their real rows).  → ``{"loss": [1], "logits": [P, B, C]}``."""
+        self.eng.load(A, V, T, labels, self.regress is not None)
+        self.eng.set_lengths(lengths)
+        self.run()
+        return {"loss": self.eng.cls.loss, "logits": self.eng.logits}
+
+    def run(self) -> None:
+        # the log's group order decides the ids the expansion writes (host values of the launch)
+        if self.log is not None and self.eng.group_names != tuple(self.log.groups):
+            self.eng.set_groups(self.log.groups)
+            self.graph = None
+        super().run()
 
 
 class FusedMosiEvalStep:
@@ -1594,10 +1696,25 @@ class MosiPatternEngine:
     without a classifier at 2B rows, ``cls`` one without encoders at P*B rows: no LSTM or TextCNN buffer grows with P.
     With ``ragged`` / ``text_lengths`` the length buffers are 2B long and both halves carry the batch's lengths (a zero
     row runs exactly as long as its real row): callers write the first B (``set_lengths``, or the loader's gather), the
-    forward mirrors them."""
+    forward mirrors them.
+
+    ``backward=True`` is the training form (``FusedMosiPatternStep``): both halves plan their backward —
+    ``enc`` at 2B rows ``dfused`` [2B, E], the LSTM ``dg`` buffers, the weight-gradient plan and the TextCNN keep mask
+    [2B, nc]; ``cls`` at P*B rows ``dlogits``, ``dh``, ``dr``, ``dfused`` [P*B, E], its layers' keep masks [P*B, w] and
+    the clip buffers.  ``forward(train=True)`` draws the masks and runs both halves in training mode; ``backward`` runs
+    the classifier's backward over the P*B rows, ``tspm_pattern_expand_bwd`` (the expansion's adjoint: ``cls.dfused``
+    folded onto the 2B rows of ``enc.dfused``, the trainable encoders' columns only) and the encoders' backward over 2B
+    rows.  Defined semantics: the loss is the weighted mean over all P*B rows — a plain step on the replicated batch
+    cat_p(A*ka_p, V*kv_p, T*kt_p); the MOSEI classifier's BatchNorm1d takes its batch statistics over the P*B rows and
+    updates its running statistics once per step, as on the replicated batch; the TextCNN dropout mask is drawn per
+    ENCODER row (2B rows: a row's mask is shared by every pattern that reads the row), the classifier masks per
+    classifier row (P*B); ``keep_override`` takes ``"text"`` as [2B, nc] and ``"cls{j}"`` as [P*B, w_j].  Real rows and
+    zero rows both contribute to every encoder parameter's gradient (a zero row's embedding depends on the biases and,
+    with lengths, on the row's own length)."""
 
     def __init__(self, model: "UttFusionModel", batch: int, steps, device: torch.device, patterns=None,
-                 ragged: bool = False, text_lengths: bool = False, groups: Optional[Sequence[str]] = None):
+                 ragged: bool = False, text_lengths: bool = False, groups: Optional[Sequence[str]] = None,
+                 backward: bool = False):
         if torch.device(device).type != "cuda":
             raise L.TspmError("UttFusionModel (tspm_amd) runs on the MI355X only (no CPU fallback)")
         self.m, self.B, self.T, self.device = model, int(batch), norm_steps(steps), device
@@ -1605,9 +1722,15 @@ class MosiPatternEngine:
         self.P = P = len(self.patterns)
         self.ragged, self.text_lengths = bool(ragged), bool(text_lengths)
         B = self.B
+        self.trainable = bool(backward)
         self.enc = MosiEngine(model, 2 * B, steps, device, ragged=ragged, text_lengths=text_lengths, classifier=False,
-                              backward=False)
-        self.cls = MosiEngine(model, P * B, steps, device, encoders=False, backward=False)
+                              backward=self.trainable)
+        self.cls = MosiEngine(model, P * B, steps, device, encoders=False, backward=self.trainable)
+        self.keep_override: Optional[Dict[str, torch.Tensor]] = None
+        self.rng_ctr_ptr: Optional[int] = None
+        self._host_ctr: Optional[torch.Tensor] = None
+        if self.trainable:  # the clip buffers live on the classifier half
+            self.clip, self.clip_coef, self.total_norm = self.cls.clip, self.cls.clip_coef, self.cls.total_norm
         self.Ts, self.E = self.enc.Ts, self.enc.E
         self.A, self.V, self.X = self.enc.A, self.enc.V, self.enc.X   # [T_m, 2B, F]: the batch in rows [0, B)
         self.labels = torch.zeros(B, dtype=torch.int64, device=device)
@@ -1662,21 +1785,72 @@ class MosiPatternEngine:
             if labels.data_ptr() != dst.data_ptr():
                 dst.copy_(labels.reshape(-1).to(dst.dtype), non_blocking=True)
 
-    def forward(self, sh: int, head: bool = True, regress: bool = False) -> None:
+    def apply_keep_override(self) -> None:
+        """Copy injected dropout masks (parity hook) into the keep buffers of the two halves: ``"text"`` [2B, nc] (one
+        mask per encoder row), ``"cls{j}"`` [P*B, w_j]; called before the step runs, outside any captured graph."""
+        if self.keep_override is None:
+            return
+        dsts = [("text", self.enc.keeps[0])] + [(f"cls{j}", k) for j, k in enumerate(self.cls.keeps[1:])]
+        for k, dst in dsts:
+            dst.copy_(self.keep_override[k].reshape(dst.shape).to(torch.uint8), non_blocking=True)
+
+    def _keep_masks(self, sh: int) -> None:
+        """Fresh keep masks for one training forward (``MosiEngine._keep_masks``'s seeds, rates and counter): the TextCNN
+        mask over the 2B encoder rows, the classifier masks over the P*B classifier rows."""
+        pt, pc = float(self.m.netT.dropout.p), float(self.m.netC.dropout_p)
+        if (pt <= 0 and pc <= 0) or self.keep_override is not None:
+            return
+        if self.rng_ctr_ptr is None:
+            self._host_ctr = torch.zeros(1, dtype=torch.int64, device=self.device)
+            self.rng_ctr_ptr = self._host_ctr.data_ptr()
+        lib, seed = L.lib(), self.m._rng_seed
+        if pt > 0:
+            L.check(lib.tspm_dropout_mask(self.enc.keep_all.numel(), pt, seed, self.rng_ctr_ptr,
+                                          self.enc.keep_all.data_ptr(), sh), "dropout_mask (text)")
+        if pc > 0:
+            L.check(lib.tspm_dropout_mask(self.cls.keep_all.numel(), pc, seed ^ _CLS_SEED_SALT, self.rng_ctr_ptr,
+                                          self.cls.keep_all.data_ptr(), sh), "dropout_mask (classifier)")
+        if self._host_ctr is not None and self.rng_ctr_ptr == self._host_ctr.data_ptr():
+            self._host_ctr.add_(1)  # outside FusedMosiPatternStep nothing else advances the counter
+
+    def forward(self, sh: int, head: bool = True, regress: bool = False, train: bool = False) -> None:
         """Length mirror, the encoders over 2B rows, ``tspm_pattern_expand``, the classifier over P*B rows (``head=False``
         stops before ``fc_out``); everything on the caller's stream (the LSTM half forks as in ``MosiEngine``),
-        graph-capturable.  ``regress``: the float32 labels travel instead of the int64 ones."""
+        graph-capturable.  ``regress``: the float32 labels travel instead of the int64 ones.  ``train`` (a
+        ``backward=True`` engine): the dropout masks are drawn first and both halves run in training mode."""
         B, e, c = self.B, self.enc, self.cls
+        if train and not self.trainable:
+            raise L.TspmError("MosiPatternEngine: a training forward needs an engine built with backward=True")
         for buf, _, _ in self._len_bufs:
             buf[B:].copy_(buf[:B])  # on the current stream, which is the one `sh` names
-        e._forward_encoders(sh, False)
+        if train:
+            self._keep_masks(sh)
+        e._forward_encoders(sh, train)
         a, v, t = self.m.netA, self.m.netV, self.m.netT
         src, dst = (self.labels_f, c.labels_f) if regress else (self.labels, c.labels)
         L.check(L.lib().tspm_pattern_expand(B, self.P, self._keep, self._group, a.hidden_size, v.hidden_size,
                                             t.hidden_size, e.fused.data_ptr(), self.E, c.fused.data_ptr(), self.E,
                                             src.data_ptr(), dst.data_ptr(), src.element_size(), c.groups.data_ptr(), sh),
                 "pattern_expand")
-        c._forward_classifier(sh, False, head)
+        c._forward_classifier(sh, train, head)
+
+    def backward(self, sh: int, from_head: bool = True) -> None:
+        """The classifier's backward over the P*B rows into ``cls.dfused``, ``tspm_pattern_expand_bwd`` into
+        ``enc.dfused`` (``modalities`` = the trainable encoders), the encoders' backward over the 2B rows
+        (``MosiEngine``'s, side-stream fork included).  ``from_head=False``: ``cls.head_regress`` wrote ``dh[-1]`` and
+        ``fc_out``'s gradients.  With every encoder frozen layer 0's ``linear_bwd`` gets no ``dx`` and neither the
+        adjoint nor any encoder backward is launched; ``MosiEngine.backward``'s flag checks."""
+        e, c = self.enc, self.cls
+        c._check_flags()
+        c._backward_classifier(sh, from_head)
+        mods = sum(1 << i for i, k in enumerate("avt") if e.trains[k])
+        if not mods:
+            return
+        a, v, t = self.m.netA, self.m.netV, self.m.netT
+        L.check(L.lib().tspm_pattern_expand_bwd(self.B, self.P, self._keep, a.hidden_size, v.hidden_size, t.hidden_size,
+                                                c.dfused.data_ptr(), self.E, e.dfused.data_ptr(), self.E, mods, sh),
+                "pattern_expand_bwd")
+        e._backward_encoders(sh)
 
 
 class FusedMosiPatternEvalStep:
@@ -1898,14 +2072,35 @@ class UttFusionModel(nn.Module):
         captured graph for every batch of this padded length, whatever its real lengths; a separate cache entry.
         ``text_lengths`` (independent of ``ragged``): the step whose TextCNN pooling reads ``lengths["text"]``; one more
         trailing key element."""
-        steps = norm_steps(steps)
-        key = _frozen_key(_text_lengths_key(_ragged_key((id(optimizer), id(loss_functions), int(batch), steps), ragged),
-                                            text_lengths), self.flag_state()[1][0])
+        key = self._fused_step_key(optimizer, loss_functions, batch, steps, ragged, text_lengths)
         st = self._steps.get(key)
         if st is None:
-            st = FusedMosiStep(self, optimizer, loss_functions, int(batch), steps, ragged=ragged,
+            st = FusedMosiStep(self, optimizer, loss_functions, int(batch), norm_steps(steps), ragged=ragged,
                                text_lengths=text_lengths)
             self._steps[key] = st
+        return st
+
+    def _fused_step_key(self, optimizer, loss_functions, batch: int, steps, ragged: bool = False,
+                        text_lengths: bool = False, patterns=None) -> tuple:
+        """``fused_step``'s cache key; with ``patterns`` the same key behind ``_pattern_key``'s ("patterns", names)
+        head (``fused_pattern_step``)."""
+        key = _frozen_key(_text_lengths_key(_ragged_key((id(optimizer), id(loss_functions), int(batch),
+                                                         norm_steps(steps)), ragged), text_lengths),
+                          self.flag_state()[1][0])
+        return key if patterns is None else _pattern_key(key, norm_patterns(patterns))
+
+    def fused_pattern_step(self, optimizer: FusedAdam, loss_functions, batch: int, steps, patterns=None,
+                           ragged: bool = False, text_lengths: bool = False) -> "FusedMosiPatternStep":
+        """The cached ``FusedMosiPatternStep`` for (patterns, optimizer, loss group, batch, padded steps): every row of
+        a batch trained under each of ``patterns`` (names among ``ALL_PATTERNS``, default all seven) in one step.  Its
+        key is ``fused_step``'s behind a ("patterns", names) head, in the same cache; ``fused_step``'s own keys and
+        objects are unchanged."""
+        pats = norm_patterns(patterns)
+        key = self._fused_step_key(optimizer, loss_functions, batch, steps, ragged, text_lengths, pats)
+        st = self._steps.get(key)
+        if st is None:
+            st = self._steps[key] = FusedMosiPatternStep(self, optimizer, loss_functions, int(batch), norm_steps(steps),
+                                                         pats, ragged=ragged, text_lengths=text_lengths)
         return st
 
     def load_pretrained(self) -> None:
@@ -1958,7 +2153,11 @@ class UttFusionModel(nn.Module):
         on the HIP forward/backward (one autograd node).  Regression mode — a one-output ``netC.fc_out`` with a
         single mean L1 / MSE term: float32 labels, the fused step with the one-launch regression head (the autograd
         sequence when the head is outside the kernel's limits), and the float predictions recorded under the
-        ``"regression"`` group (this package's name for it)."""
+        ``"regression"`` group (this package's name for it).  A batch carrying ``"all_patterns": True`` and
+        ``"patterns"`` (``mosi_data.MOSI.loader(all_patterns=True)``: the samples once, unmasked) trains every row under
+        every one of those patterns in one ``FusedMosiPatternStep`` and records the P*B predictions against the tiled
+        targets with ``m_types`` = the expanded pattern names; that runs on the fused step only (``FusedAdam``) - no
+        autograd node is built for it."""
         A = _modality(batch, "audio").to(device).float()
         V = _modality(batch, "video").to(device).float()
         T = _modality(batch, "text").to(device).float()
@@ -1967,6 +2166,25 @@ class UttFusionModel(nn.Module):
         reg = _regress_mode(self, loss_functions)
         if reg is not None:
             labels = labels.float()
+        if batch.get("all_patterns"):
+            if not isinstance(optimizer, FusedAdam) or not A.is_cuda:
+                raise L.TspmError("UttFusionModel.train_step: all-pattern training (an \"all_patterns\" batch) runs on "
+                                  "the fused step only - FusedAdam on the ROCm device; there is no autograd node for it")
+            pats = norm_patterns(batch["patterns"])
+            lengths = batch.get("lengths")
+            ragged, tl = _split_lengths(lengths)
+            out = self.fused_pattern_step(optimizer, loss_functions, A.shape[0], _batch_steps(A, V, T), pats,
+                                          ragged=ragged, text_lengths=tl).step(A, V, T, labels, lengths)
+            if metric_recorder is not None:
+                names = np.array([p for p in pats for _ in range(A.shape[0])])
+                targets = labels.reshape(-1).detach().cpu().numpy()
+                if reg is not None:
+                    preds = out["logits"].detach().reshape(-1).cpu().numpy()
+                else:
+                    preds = torch.softmax(out["logits"].detach(), dim=-1).argmax(dim=-1).reshape(-1).cpu().numpy()
+                metric_recorder.update_group_all("regression" if reg is not None else "classification",
+                                                 predictions=preds, targets=np.tile(targets, len(pats)), m_types=names)
+            return {"loss": float(out["loss"].item())}
         head_ok = (_ce_weight(loss_functions) is not None if reg is None
                    else L.regress_head_supported(A.shape[0], self.netC.widths[-1]))
         lengths = batch.get("lengths")  # per-sample lengths (mosi_data.MOSI(use_lengths=True)): the ragged step

@@ -427,15 +427,30 @@ class MOSI(torch.utils.data.Dataset):
                               f"selected pattern); this dataset is split {self.split!r}, target_modality "
                               f"{self.target_modality!r}")
 
+    def _check_all_patterns(self, fuse_patterns: bool = False) -> None:
+        if self.split != "train" or self.target_modality != "multimodal" or fuse_patterns:
+            raise L.TspmError(f"all_patterns=True is for the multimodal train split (every sample trained under every "
+                              f"selected pattern in one step) and excludes fuse_patterns, the valid / test form; this "
+                              f"dataset is split {self.split!r}, target_modality {self.target_modality!r}, "
+                              f"fuse_patterns={bool(fuse_patterns)}")
+
     def _collate_fused(self, rows: np.ndarray, step=None, pad_to: int = 0) -> Dict[str, Any]:
         """A fused-pattern batch: the samples once, unmasked, with ``"patterns"`` (the selected patterns, which the step
         expands on the device) and ``"fused_patterns": True`` in place of ``pattern_name``.  With ``step`` (a
         ``FusedMosiPatternEvalStep``) the gather writes rows [0, B) of its 2B-row time-major inputs, its label buffer
         and the first halves of its length buffers."""
+        return self._collate_unmasked(rows, step, pad_to, "fused_patterns")
+
+    def _collate_all(self, rows: np.ndarray, step=None, pad_to: int = 0) -> Dict[str, Any]:
+        """A train ``all_patterns`` batch: ``_collate_fused``'s batch with ``"all_patterns": True`` in place of
+        ``"fused_patterns"``; ``step`` is a ``FusedMosiPatternStep`` (the same 2B-row inputs and buffers)."""
+        return self._collate_unmasked(rows, step, pad_to, "all_patterns")
+
+    def _collate_unmasked(self, rows: np.ndarray, step, pad_to, flag: str) -> Dict[str, Any]:
         dc = self.device_corpus
         b, tpad = len(rows), dc.batch_steps(rows, pad_to)
         index = torch.from_numpy(rows).to(self.device, non_blocking=True)
-        extra = {"patterns": list(self.selected_patterns), "fused_patterns": True, "steps": tpad}
+        extra = {"patterns": list(self.selected_patterns), flag: True, "steps": tpad}
         if step is not None:
             e = step.eng
             if (e.B, e.T) != (b, tpad) or list(e.patterns) != list(self.selected_patterns):
@@ -457,7 +472,7 @@ class MOSI(torch.utils.data.Dataset):
     def device_loader(self, batch_size: int, shuffle: bool = False, drop_last: bool = False,
                       generator: Optional[torch.Generator] = None, step_for=None,
                       pad_to: int = 0, group_patterns: Optional[bool] = None,
-                      fuse_patterns: bool = False) -> Iterator[Dict[str, Any]]:
+                      fuse_patterns: bool = False, all_patterns: bool = False) -> Iterator[Dict[str, Any]]:
         """One epoch of batches gathered on device.  ``step_for(B, T) -> FusedMosiStep`` (or
         ``FusedMosiEvalStep``): gather each batch time-major straight into that step's input buffers.
         ``pad_to``: pad every batch to at least this many steps (the aligned length, e.g. 50 for aligned_50:
@@ -472,9 +487,16 @@ class MOSI(torch.utils.data.Dataset):
         ``fuse_patterns`` (multimodal valid / test splits only): each sample is yielded ONCE, unmasked, in sample order,
         in batches that carry ``"patterns": list(selected_patterns)`` and ``"fused_patterns": True`` and no
         ``pattern_name`` — ``step_for(B, T)`` then returns a ``FusedMosiPatternEvalStep``, which evaluates every
-        pattern of the batch from one encoder pass."""
-        if fuse_patterns:
-            self._check_fuse_patterns()
+        pattern of the batch from one encoder pass.
+        ``all_patterns`` (the multimodal train split only; not with ``fuse_patterns``): the train form of the same — each
+        sample ONCE per epoch, unmasked, in the loader's usual (shuffled) order, in batches that carry ``"patterns"`` and
+        ``"all_patterns": True`` and neither ``pattern_name`` nor ``fused_patterns``; ``step_for(B, T)`` then returns a
+        ``FusedMosiPatternStep``, which trains every pattern of the batch in one step."""
+        if all_patterns:
+            self._check_all_patterns(fuse_patterns)
+        if fuse_patterns or all_patterns:
+            if fuse_patterns:
+                self._check_fuse_patterns()
             ns = self.num_samples
             order = torch.randperm(ns, generator=generator).numpy() if shuffle else np.arange(ns)
             for s in range(0, ns, batch_size):
@@ -482,7 +504,7 @@ class MOSI(torch.utils.data.Dataset):
                 if drop_last and len(rows) < batch_size:
                     break
                 step = step_for(len(rows), self.device_corpus.batch_steps(rows, pad_to)) if step_for is not None else None
-                yield self._collate_fused(rows, step, pad_to)
+                yield (self._collate_all if all_patterns else self._collate_fused)(rows, step, pad_to)
             return
         n = len(self)
         grouped = ((self.split != "train" and self.target_modality == "multimodal") if group_patterns is None
@@ -513,13 +535,15 @@ class MOSI(torch.utils.data.Dataset):
 
     def loader(self, batch_size: int, shuffle: bool = False, drop_last: bool = False, seed: Optional[int] = None,
                step_for=None, pad_to: int = 0, group_patterns: Optional[bool] = None,
-               fuse_patterns: bool = False) -> "MosiDeviceLoader":
-        """A re-iterable epoch loader (one ``device_loader`` pass per ``iter``), as a DataLoader is.  ``fuse_patterns``:
-        see ``device_loader`` (refused here already for a train or single-modality dataset)."""
+               fuse_patterns: bool = False, all_patterns: bool = False) -> "MosiDeviceLoader":
+        """A re-iterable epoch loader (one ``device_loader`` pass per ``iter``), as a DataLoader is.  ``fuse_patterns`` /
+        ``all_patterns``: see ``device_loader`` (refused here already for a dataset they are not for)."""
+        if all_patterns:
+            self._check_all_patterns(fuse_patterns)
         if fuse_patterns:
             self._check_fuse_patterns()
         return MosiDeviceLoader(self, batch_size, shuffle, drop_last, seed, step_for, pad_to, group_patterns,
-                                fuse_patterns)
+                                fuse_patterns, all_patterns)
 
     def get_split(self) -> str:
         return self.split
@@ -546,10 +570,11 @@ class MosiDeviceLoader:
     (the harness points it at its own train / eval steps)."""
 
     def __init__(self, ds: MOSI, batch_size: int, shuffle: bool, drop_last: bool, seed: Optional[int], step_for,
-                 pad_to: int, group_patterns: Optional[bool], fuse_patterns: bool = False):
+                 pad_to: int, group_patterns: Optional[bool], fuse_patterns: bool = False, all_patterns: bool = False):
         self.ds, self.batch_size, self.shuffle, self.drop_last = ds, batch_size, shuffle, drop_last
         self.seed, self.step_for, self.pad_to, self.group_patterns = seed, step_for, pad_to, group_patterns
         self.fuse_patterns = bool(fuse_patterns)
+        self.all_patterns = bool(all_patterns)
         self.epoch = 0
 
     def __len__(self) -> int:
@@ -563,4 +588,4 @@ class MosiDeviceLoader:
             gen.manual_seed((self.seed if self.seed is not None else 0) + self.epoch)
         self.epoch += 1
         return self.ds.device_loader(self.batch_size, self.shuffle, self.drop_last, gen, self.step_for, self.pad_to,
-                                     self.group_patterns, self.fuse_patterns)
+                                     self.group_patterns, self.fuse_patterns, self.all_patterns)
