@@ -1052,6 +1052,62 @@ int tspm_pattern_expand_bwd(int32_t batch, int32_t npat, const int32_t* keep, in
                             int32_t w_text, const float* dout, int64_t ld_dout, float* demb, int64_t ld_demb,
                             int32_t modalities, tspm_stream_t stream);
 
+/* All-pattern evaluation head (added under ABI 23) — AVMNIST's classifier `net` (tspm_head_train_step's three Linears,
+ * no dropout), the loss group's weighted cross-entropy and tspm_classify_update's bookkeeping for EVERY missing-modality
+ * pattern of a batch in one call.  In eval mode an encoder's output row depends on that row's input and the weights
+ * only, so the embedding of a zeroed modality is one constant row: x0 [in] holds both encoders' zero-input embeddings
+ * (columns [0, w_audio) the audio encoder's, [w_audio, in) the image encoder's) and x [batch][ldx] the embeddings of the
+ * real inputs.  For p < npat and b < batch, row = p*batch + b:
+ *   input  = per modality m (0 audio, 1 image) x[b]'s columns when keep[2p + m] != 0, else x0's
+ *   logits[row] = Linear(w5,b5)(relu(Linear(w3,b3)(relu(Linear(w0,b0)(input)))))
+ *   preds[row]  = first argmax of softmax(logits[row])            (TSPM_ARGMAX_SOFTMAX; preds nullable)
+ *   confusion[group_id[p]][labels[b]][pred] += 1                  (integer atomics; a row whose label is outside
+ *                                                                   [0, classes) or whose group is outside
+ *                                                                   [0, n_groups) is not counted; confusion nullable)
+ *   loss[p] = loss_weight * mean_b CE(logits[p*batch + b], labels[b])   (an out-of-range label: NaN, nothing read out of
+ *                                                                   bounds)
+ * and once per call, when counters is given: loss_log[counters[0] + p] = loss[p] for every p with that index below
+ * log_capacity (loss_log nullable), then counters[0] += npat, counters[1] += npat*batch — what npat calls of
+ * tspm_cross_entropy + tspm_classify_update on the row slices leave behind, in pattern order.
+ * keep ([npat][2]) and group_id ([npat]) are HOST arrays copied into the launch arguments, as in tspm_pattern_expand.
+ * Two launches.  (1) One workgroup of 512 threads per sample (at most 256 workgroups, each walking its samples), the
+ * three weight matrices staged in LDS as tspm_head_train_step stages them.  fc0 is linear in the concatenated input, so
+ * the workgroup forms the audio-half and the image-half product of x0 once and of each sample once and adds the two
+ * halves a pattern selects; fc3, fc5, the row's cross-entropy term, its prediction and its confusion count follow
+ * per (pattern, sample) row.  A row's logits depend on x[b], x0, the weights and keep[p] only — not on batch, npat or
+ * the other rows (bitwise).  (2) One workgroup adds each pattern's per-row terms from the workspace in a fixed order
+ * (tspm_cross_entropy's: strided partial sums and a tree, in double) and writes loss, the log entries and the counters.
+ * No floating-point atomics; two calls on the same inputs are bitwise equal.
+ * Limits (tspm_head_train_step's): in <= 256, hidden <= 256, hidden2 <= 128, classes <= 16; in, w_audio, hidden,
+ * hidden2 multiples of 4, 0 < w_audio < in; ldx >= in and a multiple of 4; x, x0, w0, w3, w5 16-byte aligned; 1 <= npat
+ * <= TSPM_PATTERN_HEAD_MAX_PATTERNS; weights plus row buffers within 160 KiB of LDS.  x0 may be NULL when every pattern
+ * keeps both modalities.  loss_log needs counters; confusion needs n_groups >= 1; log_capacity >= 0.  Anything else, or
+ * a NULL among x, keep, group_id, the six weights, labels, logits, loss: TSPM_ERR_INVALID; a missing or short workspace
+ * with the other arguments valid: TSPM_ERR_WORKSPACE.  Nothing is launched on error. */
+#define TSPM_PATTERN_HEAD_MAX_PATTERNS 8
+typedef struct tspm_pattern_head_eval_desc {
+  int32_t batch, npat, in, w_audio, hidden, hidden2, classes, ldx;
+  const float* x;           /* [batch, ldx] */
+  const float* x0;          /* [in] */
+  const int32_t* keep;      /* HOST [npat][2]: (audio, image), non-zero = the real input */
+  const int32_t* group_id;  /* HOST [npat] */
+  const float *w0, *b0, *w3, *b3, *w5, *b5;
+  const int64_t* labels;    /* [batch] */
+  float loss_weight;        /* the cross-entropy term's weight */
+  int32_t n_groups;
+  float* logits;            /* [npat*batch, classes] */
+  int64_t* preds;           /* nullable: [npat*batch] */
+  float* loss;              /* [npat] */
+  int64_t* confusion;       /* nullable: [n_groups][classes][classes] */
+  float* loss_log;          /* nullable */
+  int64_t* counters;        /* nullable: {entries, samples} */
+  int64_t log_capacity;
+  void* workspace;          /* tspm_pattern_head_eval_workspace(batch, npat) bytes, 16-byte aligned */
+  size_t workspace_bytes;
+} tspm_pattern_head_eval_desc;
+size_t tspm_pattern_head_eval_workspace(int32_t batch, int32_t npat);
+int tspm_pattern_head_eval(const tspm_pattern_head_eval_desc* desc, tspm_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Monomodal pre-training head (ABI 23) — train_monomodal.MonomodalEncoder's `classifier = nn.Linear(hid,
  * classes)` forward, the loss group's weighted cross-entropy, the argmax(logits, 1) predictions

@@ -92,6 +92,7 @@ class AdamHyper(Structure):
 HYPER_STEP_OFFSET = 48  # byte offset of tspm_adam_hyper.step
 ADAM_MAX_SEGMENTS = 8   # TSPM_ADAM_MAX_SEGMENTS: the most groups of tspm_adam_*_multi / tspm_grad_clip_coef_multi
 MAX_PATTERNS = 7        # TSPM_MAX_PATTERNS: the most patterns of one tspm_pattern_expand launch
+PATTERN_HEAD_MAX_PATTERNS = 8  # TSPM_PATTERN_HEAD_MAX_PATTERNS: the most patterns of one tspm_pattern_head_eval call
 
 
 class AdamSeg(Structure):
@@ -183,6 +184,31 @@ class MonoHeadBceDesc(Structure):
         [("loss_weight", c_float), ("threshold", c_float)] + \
         [(n, c_void_p) for n in ("emb", "w", "b", "targets", "logits", "loss", "preds", "dw", "db", "demb", "stats",
                                  "workspace")] + [("workspace_bytes", c_size_t)]
+
+
+class PatternHeadEvalDesc(Structure):
+    """tspm_pattern_head_eval_desc (added under ABI 23): AVMNIST's fusion head, cross-entropy and classification log for
+    every missing-modality pattern of a batch in one call; ``keep`` / ``group_id`` are host int32 arrays."""
+    _fields_ = [(n, c_int32) for n in ("batch", "npat", "in_", "w_audio", "hidden", "hidden2", "classes", "ldx")] + \
+        [("x", c_void_p), ("x0", c_void_p), ("keep", POINTER(c_int32)), ("group_id", POINTER(c_int32))] + \
+        [(n, c_void_p) for n in ("w0", "b0", "w3", "b3", "w5", "b5", "labels")] + \
+        [("loss_weight", c_float), ("n_groups", c_int32)] + \
+        [(n, c_void_p) for n in ("logits", "preds", "loss", "confusion", "loss_log", "counters")] + \
+        [("log_capacity", c_int64), ("workspace", c_void_p), ("workspace_bytes", c_size_t)]
+
+
+def pattern_head_eval_supported(in_: int, w_audio: int, hidden: int, hidden2: int, classes: int, npat: int) -> bool:
+    """Python mirror of tspm_pattern_head_eval's shape checks (csrc/misc.hip: tspm_head_train_step's limits, sizes
+    % 4, 1..8 patterns, weights + row buffers in at most 160 KiB of LDS): False = the call would return
+    TSPM_ERR_INVALID for this head whatever the pointers."""
+    F, WA, H, H2, C, P = (int(v) for v in (in_, w_audio, hidden, hidden2, classes, npat))
+    if not (0 < F <= 256 and 0 < H <= 256 and 0 < H2 <= 128 and 0 < C <= 16 and 1 <= P <= PATTERN_HEAD_MAX_PATTERNS):
+        return False
+    if F % 4 or H % 4 or H2 % 4 or WA % 4 or not 0 < WA < F:
+        return False
+    ldc = ((C + 3) & ~3) + 4
+    floats = H * (F + 4) + H2 * (H + 4) + C * (H2 + 4) + 2 * (F + 4) + 4 * H + P * ((H + 4) + (H2 + 4) + ldc) + H + H2 + C
+    return floats * 4 <= 160 * 1024
 
 
 REGRESS_L1, REGRESS_MSE = 0, 1
@@ -407,6 +433,9 @@ _SIGS = {
                                       _P, c_int64, _P, c_int64, _P, _P, c_int32, _P, _P]),
     "tspm_pattern_expand_bwd": (c_int32, [c_int32, c_int32, POINTER(c_int32), c_int32, c_int32, c_int32,
                                           _P, c_int64, _P, c_int64, c_int32, _P]),
+    # added under ABI 23: AVMNIST's eval head + cross-entropy + classification log for every pattern of a batch
+    "tspm_pattern_head_eval_workspace": (c_size_t, [c_int32, c_int32]),
+    "tspm_pattern_head_eval": (c_int32, [POINTER(PatternHeadEvalDesc), _P]),
 }
 
 EXPORTED = tuple(_SIGS)

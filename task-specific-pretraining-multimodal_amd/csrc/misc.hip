@@ -1281,6 +1281,237 @@ extern "C" int tspm_head_train_step(const tspm_head_desc* desc, tspm_stream_t st
 }
 
 // ------------------------------------------------------------------------------------------------
+// All-pattern evaluation head (tspm_pattern_head_eval, added under ABI 23): the fusion head, the cross-entropy and
+// tspm_classify_update's bookkeeping for every missing-modality pattern of a batch.
+// Launch 1 (k_pattern_head_rows): one workgroup per sample (at most PH_MAXGRID, each walking its samples), weights in
+// LDS through k_head_rows' staging.  fc0 is linear in the concatenated input: the audio-half and image-half products
+// of x0 are formed once per workgroup and those of a sample once per sample (sums in head_xwT's order over the half's
+// columns), and pattern p's h1 is relu((half_a + half_i) + b0) with each half taken from the sample or from x0 —
+// 2 products per sample instead of P.  fc3 / fc5 run on the P rows; wave lanes in groups of 16 per row then do the
+// row's softmax (k_head_rows' layout), its cross-entropy term, the prediction (k_classify_update's rule: first
+// maximum of the softmax values) and the confusion count.
+// Launch 2 (k_pattern_head_loss): one workgroup; per pattern k_cross_entropy's reduction of the per-row terms, then
+// thread 0 writes the P log entries in pattern order and advances the counters.
+// ------------------------------------------------------------------------------------------------
+namespace {
+constexpr int PH_THREADS = 512, PH_MAXP = TSPM_PATTERN_HEAD_MAX_PATTERNS, PH_MAXGRID = 256;
+
+struct PatHeadArgs {
+  tspm_pattern_head_eval_desc d;  // keep / group_id (host pointers) are not read on the device
+  int keep[PH_MAXP][2];
+  int group[PH_MAXP];
+  float* row_ce;                  // workspace: [npat * batch] per-row cross-entropy terms
+};
+
+// LDS floats of k_pattern_head_rows: weights (rows padded by 4), x and x0, the four half products, P rows of h1 / hh /
+// logits, biases
+size_t pat_head_lds_floats(int F, int H, int H2, int C, int P) {
+  return (size_t)H * (F + 4) + (size_t)H2 * (H + 4) + (size_t)C * (H2 + 4) + (size_t)2 * (F + 4) + (size_t)4 * H +
+         (size_t)P * ((H + 4) + (H2 + 4) + head_ldc(C)) + (size_t)(H + H2 + C);
+}
+
+// sum_k x[k] w[k], K % 4 == 0, x and w 16-byte aligned in LDS: head_xwT's sum (even / odd 4-element chunks)
+TSPM_DEV float pat_dot(const float* x, const float* w, int K) {
+  float a0 = 0.f, a1 = 0.f;
+  int k = 0;
+#pragma unroll 2
+  for (; k + 8 <= K; k += 8) {
+    const f32x4 w0 = ld4(w + k), w1 = ld4(w + k + 4), x0 = ld4(x + k), x1 = ld4(x + k + 4);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      a0 = fmaf(x0[j], w0[j], a0);
+      a1 = fmaf(x1[j], w1[j], a1);
+    }
+  }
+  if (k < K) {
+    const f32x4 w0 = ld4(w + k), x0 = ld4(x + k);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) a0 = fmaf(x0[j], w0[j], a0);
+  }
+  return a0 + a1;
+}
+
+__global__ __launch_bounds__(PH_THREADS) void k_pattern_head_rows(PatHeadArgs a) {
+  const tspm_pattern_head_eval_desc& d = a.d;
+  extern __shared__ float lds[];
+  const int F = d.in, H = d.hidden, H2 = d.hidden2, C = d.classes, P = d.npat, WA = d.w_audio, B = d.batch;
+  const int ldx = F + 4, ldh = H + 4, ldh2 = H2 + 4, ldc = head_ldc(C);
+  float* sw0 = lds;                 // [H][F + 4]
+  float* sw3 = sw0 + H * ldx;       // [H2][H + 4]
+  float* sw5 = sw3 + H2 * ldh;      // [C][H2 + 4]
+  float* sx = sw5 + C * ldh2;       // [2][F + 4]: the sample's row, x0
+  float* spart = sx + 2 * ldx;      // [2][2][H]: (sample | x0) x (audio half | image half) of fc0
+  float* sh1 = spart + 4 * H;       // [P][H + 4]
+  float* shh = sh1 + P * ldh;       // [P][H2 + 4]
+  float* sz = shh + P * ldh2;       // [P][ldc]
+  float* sb0 = sz + P * ldc;        // biases [H], [H2], [C]
+  float* sb3 = sb0 + H;
+  float* sb5 = sb3 + H2;
+  const int t = threadIdx.x;
+  {
+    const HeadSeg g0{d.w0, sw0, H, F / 4, H, F}, g3{d.w3, sw3, H2, H / 4, H2, H}, g5{d.w5, sw5, C, H2 / 4, C, H2};
+    constexpr int U0 = (128 * 192 / 4 + PH_THREADS - 1) / PH_THREADS, U3 = (64 * 128 / 4 + PH_THREADS - 1) / PH_THREADS;
+    f32x4 v0[U0], v3[U3], v5[1];
+    head_load(g0, v0);
+    head_load(g3, v3);
+    head_load(g5, v5);
+    head_store(g0, v0);
+    head_store(g3, v3);
+    head_store(g5, v5);
+    for (int i = t; i < H + H2 + C; i += PH_THREADS)
+      sb0[i] = i < H ? d.b0[i] : i < H + H2 ? d.b3[i - H] : d.b5[i - H - H2];
+    for (int i = t; i < F / 4; i += PH_THREADS)
+      st4(sx + ldx + 4 * i, d.x0 ? ld4(d.x0 + 4 * i) : f32x4{0.f, 0.f, 0.f, 0.f});
+  }
+  head_sync();
+  // the two halves of fc0 on row `xr` -> dst[half * H + o]
+  auto halves = [&](const float* xr, float* dst) {
+    for (int item = t; item < 2 * H; item += PH_THREADS) {
+      const int half = item >= H ? 1 : 0, o = item - half * H;
+      const int k0 = half ? WA : 0, K = half ? F - WA : WA;
+      dst[item] = pat_dot(xr + k0, sw0 + o * ldx + k0, K);
+    }
+  };
+  halves(sx + ldx, spart + 2 * H);
+  for (int b = blockIdx.x; b < B; b += gridDim.x) {
+    // sx row 0 was last read before the previous sample's barriers
+    for (int i = t; i < F / 4; i += PH_THREADS) st4(sx + 4 * i, ld4(d.x + (long long)b * d.ldx + 4 * i));
+    head_sync();
+    halves(sx, spart);
+    head_sync();
+    for (int item = t; item < P * H; item += PH_THREADS) {
+      const int p = item / H, o = item - p * H;
+      const float pa = spart[(a.keep[p][0] ? 0 : 2 * H) + o], pi = spart[(a.keep[p][1] ? 0 : 2 * H) + H + o];
+      sh1[p * ldh + o] = relu_f((pa + pi) + sb0[o]);
+    }
+    head_sync();
+    for (int item = t; item < P * H2; item += PH_THREADS) {
+      const int p = item / H2, o = item - p * H2;
+      shh[p * ldh2 + o] = relu_f(pat_dot(sh1 + p * ldh, sw3 + o * ldh, H) + sb3[o]);
+    }
+    head_sync();
+    for (int item = t; item < P * C; item += PH_THREADS) {
+      const int p = item / C, o = item - p * C;
+      const float v = pat_dot(shh + p * ldh2, sw5 + o * ldh2, H2) + sb5[o];
+      sz[p * ldc + o] = v;
+      d.logits[((long long)p * B + b) * C + o] = v;
+    }
+    head_sync();
+    // 16 lanes per row, lane k owns class k; the scans run in class order in every lane of the row
+    if (t < 16 * P) {
+      const int p = t >> 4, k = t & 15, l0 = (t & 63) & ~15;
+      const float* z = sz + p * ldc;
+      float mx = z[0];
+      for (int j = 1; j < C; ++j) mx = z[j] > mx ? z[j] : mx;
+      const float e = k < C ? expf(z[k] - mx) : 0.f;
+      float se = 0.f;
+      for (int j = 0; j < C; ++j) se += __shfl(e, l0 + j, 64);
+      const float pk = e / se;
+      float best = __shfl(pk, l0, 64);
+      int am = 0;
+      for (int j = 1; j < C; ++j) {
+        const float pj = __shfl(pk, l0 + j, 64);
+        if (pj > best) { best = pj; am = j; }
+      }
+      if (k == 0) {
+        const long long row = (long long)p * B + b;
+        const long long lab64 = d.labels[b];
+        const bool lok = lab64 >= 0 && lab64 < C;
+        const int lab = lok ? (int)lab64 : 0;
+        a.row_ce[row] = lok ? logf(se) - (z[lab] - mx) : __builtin_nanf("");
+        if (d.preds) d.preds[row] = am;
+        const int g = a.group[p];
+        if (d.confusion && lok && g >= 0 && g < d.n_groups)
+          atomicAdd(reinterpret_cast<unsigned long long*>(d.confusion) + ((long long)g * C + lab) * C + am, 1ULL);
+      }
+    }
+    // the next sample writes sx / spart / sh1 / shh / sz only behind barriers that follow every read above
+  }
+}
+
+__global__ __launch_bounds__(256) void k_pattern_head_loss(PatHeadArgs a) {
+  const tspm_pattern_head_eval_desc& d = a.d;
+  __shared__ double sl[256];
+  __shared__ float sloss[PH_MAXP];
+  const int t = threadIdx.x;
+  for (int p = 0; p < d.npat; ++p) {
+    double s = 0.0;
+    for (int n = t; n < d.batch; n += 256) s += (double)a.row_ce[(long long)p * d.batch + n];
+    sl[t] = s;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+      if (t < w) sl[t] += sl[t + w];
+      __syncthreads();
+    }
+    if (t == 0) {
+      const float l = (float)(sl[0] / (double)d.batch) * d.loss_weight;
+      sloss[p] = l;
+      d.loss[p] = l;
+    }
+    __syncthreads();
+  }
+  if (t == 0 && d.counters) {
+    const long long base = d.counters[0];
+    if (d.loss_log)
+      for (int p = 0; p < d.npat; ++p)
+        if (base + p < d.log_capacity) d.loss_log[base + p] = sloss[p];
+    d.counters[0] = base + d.npat;
+    d.counters[1] += (long long)d.npat * d.batch;
+  }
+}
+
+size_t pat_head_ws_bytes(int batch, int npat) { return (((size_t)batch * npat * sizeof(float)) + 15) & ~(size_t)15; }
+
+}  // namespace
+
+extern "C" size_t tspm_pattern_head_eval_workspace(int32_t batch, int32_t npat) {
+  if (batch <= 0 || npat <= 0 || npat > PH_MAXP) return 0;
+  return pat_head_ws_bytes(batch, npat);
+}
+
+extern "C" int tspm_pattern_head_eval(const tspm_pattern_head_eval_desc* desc, tspm_stream_t stream) {
+  if (!desc) return TSPM_ERR_INVALID;
+  const tspm_pattern_head_eval_desc& d = *desc;
+  if (d.batch <= 0 || d.npat <= 0 || d.npat > PH_MAXP) return TSPM_ERR_INVALID;
+  if (d.in <= 0 || d.hidden <= 0 || d.hidden2 <= 0 || d.classes <= 0) return TSPM_ERR_INVALID;
+  if (d.in > HEAD_MAXIN || d.hidden > HEAD_MAXH || d.hidden2 > HEAD_MAXH2 || d.classes > HEAD_MAXC)
+    return TSPM_ERR_INVALID;
+  if (d.in % 4 || d.hidden % 4 || d.hidden2 % 4 || d.w_audio % 4 || d.w_audio <= 0 || d.w_audio >= d.in)
+    return TSPM_ERR_INVALID;
+  if (d.ldx < d.in || d.ldx % 4) return TSPM_ERR_INVALID;
+  if (!d.x || !d.keep || !d.group_id || !d.w0 || !d.b0 || !d.w3 || !d.b3 || !d.w5 || !d.b5 || !d.labels ||
+      !d.logits || !d.loss)
+    return TSPM_ERR_INVALID;
+  if (!aligned16(d.x) || !aligned16(d.x0) || !aligned16(d.w0) || !aligned16(d.w3) || !aligned16(d.w5))
+    return TSPM_ERR_INVALID;
+  if (d.log_capacity < 0 || (d.loss_log && !d.counters) || (d.confusion && d.n_groups <= 0)) return TSPM_ERR_INVALID;
+  PatHeadArgs a{};
+  a.d = d;
+  bool drops = false;
+  for (int p = 0; p < d.npat; ++p) {
+    a.keep[p][0] = d.keep[2 * p] != 0;
+    a.keep[p][1] = d.keep[2 * p + 1] != 0;
+    a.group[p] = d.group_id[p];
+    drops = drops || !a.keep[p][0] || !a.keep[p][1];
+  }
+  if (drops && !d.x0) return TSPM_ERR_INVALID;
+  const size_t lds = pat_head_lds_floats(d.in, d.hidden, d.hidden2, d.classes, d.npat) * sizeof(float);
+  if (lds > 160 * 1024) return TSPM_ERR_INVALID;
+  if (!d.workspace || !aligned16(d.workspace) || d.workspace_bytes < pat_head_ws_bytes(d.batch, d.npat))
+    return TSPM_ERR_WORKSPACE;
+  a.row_ce = static_cast<float*>(d.workspace);
+  a.d.keep = nullptr;
+  a.d.group_id = nullptr;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const int grid = d.batch < PH_MAXGRID ? d.batch : PH_MAXGRID;
+  hipLaunchKernelGGL(k_pattern_head_rows, dim3(grid), dim3(PH_THREADS), lds, st, a);
+  TSPM_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_pattern_head_loss, dim3(1), dim3(256), 0, st, a);
+  TSPM_LAUNCH_CHECK();
+  return TSPM_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
 // Monomodal head step (ABI 23): classifier Linear forward, weighted cross-entropy, argmax(logits) and the
 // Linear's whole backward in ONE launch of ONE workgroup.  The problem is launch-bound ([128,64] x [64,3] at
 // the MOSI shapes), so the rows are not spread over workgroups: the workgroup walks the batch in chunks of

@@ -541,9 +541,26 @@ class AVMNIST(torch.utils.data.Dataset):
     def device_loader(self, batch_size: int, shuffle: bool = False, drop_last: bool = False,
                       generator: Optional[torch.Generator] = None, *, rank: int = 0, world_size: int = 1,
                       distributed: Optional[bool] = None, seed: int = 0, pattern: Optional[str] = None,
-                      out=None) -> "DeviceLoader":
+                      out=None, fuse_patterns: bool = False) -> "DeviceLoader":
+        """``fuse_patterns`` (valid / test splits of the multimodal target): see :class:`DeviceLoader`."""
         return DeviceLoader(self, batch_size, shuffle, drop_last, generator, rank=rank, world_size=world_size,
-                            distributed=distributed, seed=seed, pattern=pattern, out=out)
+                            distributed=distributed, seed=seed, pattern=pattern, out=out, fuse_patterns=fuse_patterns)
+
+    def _check_fuse_patterns(self, pattern: Optional[str] = None) -> None:
+        """A fused-pattern loader yields every sample once, unmasked; the step rebuilds each selected pattern from the
+        real embedding or the zero-input one, which is exact only for 0 / 1 masks."""
+        if self.split == "train" or self.target_modality != "multimodal":
+            raise L.TspmError(f"fuse_patterns=True is for the multimodal valid / test splits (every sample under every "
+                              f"selected pattern); this dataset is split {self.split!r}, target_modality "
+                              f"{self.target_modality!r}")
+        if pattern is not None:
+            raise L.TspmError("fuse_patterns=True evaluates every selected pattern of a batch; it excludes pattern=")
+        for p in self.selected_patterns:
+            probs = self.missing_patterns[p]
+            want = {m: (1.0 if m[0] in p else 0.0) for m in MODALITIES}
+            if any(probs.get(m, 1.0) != want[m] for m in MODALITIES):
+                raise L.TspmError(f"fuse_patterns=True needs 0 / 1 presence probabilities that match the pattern's name; "
+                                  f"pattern {p!r} has {probs}")
 
     def get_split(self) -> str:
         return self.split
@@ -579,15 +596,25 @@ class DeviceLoader:
     Batches equal those of ``DataLoader(dataset, batch_size, shuffle, drop_last, collate_fn=
     dataset.collate_fn)`` for the same item order.
 
+    ``fuse_patterns=True`` (valid / test splits of the multimodal target; refused for train, a single-modality target,
+    together with ``pattern=``, and for fractional presence probabilities): each sample is yielded ONCE, unmasked, in
+    sample order, in batches that carry ``"patterns": list(selected_patterns)`` and ``"fused_patterns": True`` and no
+    ``pattern_name`` / ``pattern_ids`` — ``step.FusedPatternEvalStep`` evaluates every pattern of such a batch from
+    one encoder pass.  ``len`` counts these batches; distributed sharding is over the N samples.
+
     ``out=(audio, image, labels)``: full batches are written into these caller-owned buffers (e.g. a
     ``FusedTrainStep``'s static inputs, so the step consumes the gather's output in place) and the
     yielded dict holds those same tensors — consume each batch before advancing the iterator."""
 
     def __init__(self, dataset: AVMNIST, batch_size: int, shuffle: bool = False, drop_last: bool = False,
                  generator: Optional[torch.Generator] = None, *, rank: int = 0, world_size: int = 1,
-                 distributed: Optional[bool] = None, seed: int = 0, pattern: Optional[str] = None, out=None):
+                 distributed: Optional[bool] = None, seed: int = 0, pattern: Optional[str] = None, out=None,
+                 fuse_patterns: bool = False):
         if batch_size <= 0:
             raise ValueError("batch_size must be positive")
+        self.fuse_patterns = bool(fuse_patterns)
+        if self.fuse_patterns:
+            dataset._check_fuse_patterns(pattern)
         self.out = out
         self.ds, self.batch_size, self.shuffle, self.drop_last = dataset, batch_size, shuffle, drop_last
         self.generator, self.rank, self.world_size, self.seed = generator, rank, world_size, seed
@@ -599,7 +626,7 @@ class DeviceLoader:
         self.epoch = epoch
 
     def _n_items(self) -> int:
-        return self.ds.num_samples if self.pattern is not None else len(self.ds)
+        return self.ds.num_samples if (self.pattern is not None or self.fuse_patterns) else len(self.ds)
 
     def items(self) -> np.ndarray:
         """The epoch's item order, drawing from the RNGs exactly as ``iter(DataLoader(...))`` does: the
@@ -634,6 +661,9 @@ class DeviceLoader:
         if nb == 0:
             return
         order = order[:nb * self.batch_size] if self.drop_last else order
+        if self.fuse_patterns:
+            yield from self._iter_fused(order, nb)
+            return
         samples, names, am, im = self.ds._resolve(order)
         dc = self.ds.device_corpus
         idx_d = torch.from_numpy(samples).pin_memory().to(dc.device, non_blocking=True)
@@ -646,3 +676,16 @@ class DeviceLoader:
             out = self.out if (self.out is not None and hi - lo == self.batch_size) else None
             a, imt, lab = dc.gather(idx_d[lo:hi], am_d[lo:hi], im_d[lo:hi], want_audio=wa, want_image=wi, out=out)
             yield self.ds._pack(a, imt, lab, names[lo:hi], pid_d[lo:hi])
+
+    def _iter_fused(self, order: np.ndarray, nb: int) -> Iterator[Dict[Any, Any]]:
+        """The fused-pattern epoch: each sample once, unmasked (null masks), with the selected patterns named."""
+        dc = self.ds.device_corpus
+        idx_d = torch.from_numpy(np.ascontiguousarray(order, dtype=np.int64)).pin_memory().to(dc.device, non_blocking=True)
+        pats = list(self.ds.selected_patterns)
+        for b in range(nb):
+            lo, hi = b * self.batch_size, min(len(order), (b + 1) * self.batch_size)
+            out = self.out if (self.out is not None and hi - lo == self.batch_size) else None
+            a, imt, lab = dc.gather(idx_d[lo:hi], None, None, out=out)
+            batch: Dict[Any, Any] = {"labels": lab, "missing_masks": {}, "patterns": list(pats), "fused_patterns": True,
+                                     self.ds.keys["audio"]: a, self.ds.keys["image"]: imt}
+            yield batch

@@ -32,7 +32,7 @@ import torch
 from . import _lib as L
 from .metrics import ClassificationLog, DeviceMetricRecorder, RegressionLog, RegressionMetricRecorder
 from .modules import modality_key
-from .step import FusedEvalStep, FusedTrainStep
+from .step import FusedEvalStep, FusedPatternEvalStep, FusedTrainStep, norm_avmnist_patterns
 
 # the AVMNIST YAML's metric block (configs/avmnist/centralised/train_avmnist_resnet.yaml:105-166)
 AVMNIST_METRICS = {
@@ -118,7 +118,9 @@ class CheckpointManager:
 class EpochRunner:
     """train_epoch / validate_epoch on the fused steps.  ``loader`` yields collate_fn-style batch dicts
     on the device (data.DeviceLoader / the drop-in DataLoader); batches of the runner's size are fed
-    through the static buffers of one captured graph, a smaller last batch through a second one."""
+    through the static buffers of one captured graph, a smaller last batch through a second one.  A
+    ``"fused_patterns"`` batch (the samples once, unmasked) is one ``FusedPatternEvalStep`` replay that writes one loss
+    entry per pattern, in pattern order, and every row's count under its pattern."""
 
     def __init__(self, model, optimizer, loss_functions, metric_config=None, device=None, log_capacity: int = 1 << 16):
         self.model, self.optimizer, self.loss_functions = model, optimizer, loss_functions
@@ -127,6 +129,7 @@ class EpochRunner:
         self.recorder = DeviceMetricRecorder(metric_config or AVMNIST_METRICS, self.log)
         self.train_steps: Dict[int, FusedTrainStep] = {}
         self.eval_steps: Dict[int, FusedEvalStep] = {}
+        self.pattern_eval_steps: Dict[Tuple[Tuple[str, ...], int], FusedPatternEvalStep] = {}
 
     def _train_step(self, n: int) -> FusedTrainStep:
         st = self.train_steps.get(n)
@@ -141,6 +144,17 @@ class EpochRunner:
         if st is None:
             st = FusedEvalStep(self.model, self.loss_functions, n, self.log)
             self.eval_steps[n] = st
+        st.log = self.log
+        return st
+
+    def pattern_eval_step_for(self, n: int, patterns=None) -> FusedPatternEvalStep:
+        """The cached FusedPatternEvalStep for (patterns, batch size) — every pattern of a ``"fused_patterns"`` batch
+        (``data.AVMNIST.device_loader(fuse_patterns=True)``) from one encoder pass; kept apart from ``eval_steps``."""
+        key = (norm_avmnist_patterns(patterns), n)
+        st = self.pattern_eval_steps.get(key)
+        if st is None or st.eng_a is not self.model.audio_encoder.engine_for(st.A):  # the model dropped its engines
+            st = FusedPatternEvalStep(self.model, self.loss_functions, n, self.log, patterns=key[0])
+            self.pattern_eval_steps[key] = st
         st.log = self.log
         return st
 
@@ -171,7 +185,14 @@ class EpochRunner:
         self.log.reset()
         t0 = time.time()
         self.model.eval()
+        fresh_zero = False  # the zero-input embeddings: refreshed once per epoch (no weight changes inside it)
         for b in loader:
+            if b.get("fused_patterns"):
+                a, i = b[modality_key(b, "audio")], b[modality_key(b, "image")]
+                st = self.pattern_eval_step_for(a.shape[0], b["patterns"])
+                st.step(a, i, b["labels"], refresh_zero=not fresh_zero)
+                fresh_zero = True
+                continue
             a, i, lab, g = self._unpack(b)
             self._eval_step(a.shape[0]).step(a, i, lab, g)
         return self._finish(t0)

@@ -407,10 +407,91 @@ class AVMNIST(nn.Module):
         st.log = log
         return st
 
+    # -- every missing-modality pattern of a batch from one encoder pass --------------------------------
+    def _apply(self, fn, *args, **kwargs):
+        out = super()._apply(fn, *args, **kwargs)
+        # parameters moved (the encoders drop their engines here too): the zero-input embeddings and the steps
+        # whose graphs read them are bound to the old storage
+        self.__dict__.pop("_zero_emb", None)
+        self.__dict__.pop("_fused_pattern_eval", None)
+        return out
+
+    def zero_embeddings(self, refresh: bool = True, audio_hw=(32, 94), image_hw=(28, 28)) -> torch.Tensor:
+        """``[embd_size_A + embd_size_I]``: each encoder's eval-mode embedding of an all-zero input (what a pattern
+        that drops the modality feeds the head; with BatchNorm on running statistics it is the same row for every
+        sample).  One device buffer per model with a stable address (captured graphs read it), dropped with the
+        encoders' engines when the parameters move.  ``refresh``: recompute it — each encoder's forward on a one-row
+        zero input, the two encoders on two streams; a new buffer is always filled.  FusedAdam writes parameters
+        through raw pointers, so nothing here can tell whether the weights changed: callers refresh unless they know
+        they did not (inside one evaluation epoch)."""
+        dev = next(self.parameters()).device
+        key = (tuple(audio_hw), tuple(image_hw))
+        z = self.__dict__.get("_zero_emb")
+        if z is None or z["key"] != key or z["emb"].device != dev:
+            f32 = dict(device=dev, dtype=torch.float32)
+            z = {"key": key, "emb": torch.zeros(1, self.embd_size_A + self.embd_size_I, **f32),
+                 "A": torch.zeros(1, *audio_hw, **f32), "I": torch.zeros(1, 1, *image_hw, **f32)}
+            self._zero_emb = z
+            refresh = True
+        if refresh:
+            F, ea = z["emb"].shape[1], self.embd_size_A  # train=False below: running statistics, whatever the mode flag
+            main, side = torch.cuda.current_stream(), L.shared_streams(dev, 1)[0]
+            with torch.no_grad():
+                side.wait_stream(main)
+                with torch.cuda.stream(side):
+                    self.image_encoder.engine_for(z["I"]).forward(z["I"], z["emb"][:, ea:], F, train=False)
+                self.audio_encoder.engine_for(z["A"]).forward(z["A"], z["emb"], F, train=False)
+                main.wait_stream(side)
+        return z["emb"][0]
+
+    def pattern_eval_step_for(self, loss_functions, batch: int, log=None, patterns=None, head: Optional[str] = None):
+        """The cached FusedPatternEvalStep for (patterns, head, batch size) — kept apart from ``eval_step_for``'s."""
+        from .step import DEFAULT_PATTERN_HEAD, FusedPatternEvalStep, norm_avmnist_patterns
+        pats = norm_avmnist_patterns(patterns)
+        key = (pats, head or DEFAULT_PATTERN_HEAD, batch)
+        cache = self.__dict__.setdefault("_fused_pattern_eval", {})
+        st = cache.get(key)
+        if st is None or st.ce_weight != _ce_weight_of(loss_functions):
+            st = FusedPatternEvalStep(self, loss_functions, batch, log, patterns=pats, head=head)
+            cache[key] = st
+        st.log = log
+        return st
+
+    def forward_patterns(self, A: torch.Tensor, I: torch.Tensor, patterns=None) -> torch.Tensor:
+        """Eval-mode logits ``[P, B, C]`` of the batch under each of ``patterns`` (default ``("a", "ai", "i")``; a
+        subset in any order) from one encoder pass, under ``no_grad``; the zero embeddings are refreshed first."""
+        dev = next(self.parameters()).device
+        was_training = self.training
+        try:
+            with torch.no_grad():
+                A = A.to(dev, non_blocking=True).float()
+                I = I.to(dev, non_blocking=True).float()
+                st = self.pattern_eval_step_for(None, A.shape[0], None, patterns)
+                labels = torch.zeros(A.shape[0], dtype=torch.int64, device=dev)
+                return st.step(A, I, labels, refresh_zero=True)["logits"].clone()
+        finally:
+            if was_training:
+                self.train()
+
+    def _validation_step_patterns(self, batch, loss_functions, device, metric_recorder):
+        """A ``"fused_patterns"`` batch (data.AVMNIST.device_loader(fuse_patterns=True): the samples once, unmasked)."""
+        dlog = self._device_log(metric_recorder)
+        if dlog is None:
+            raise L.TspmError("a fused-pattern batch records its per-pattern losses and predictions on the device: "
+                              "validation_step needs a metrics.DeviceMetricRecorder (or use the default loader)")
+        self.eval()
+        with torch.no_grad():
+            A, I, labels, _ = self._unpack(batch, device)
+            st = self.pattern_eval_step_for(loss_functions, A.shape[0], dlog, batch["patterns"])
+            out = st.step(A, I, labels, refresh_zero=True)
+            return {"loss": float(out["loss"].mean().item())}
+
     def validation_step(self, batch, loss_functions, device, metric_recorder, return_test_info: bool = False):
         """models/avmnist.py:312-360 (eval-mode BN running stats, dropout off).  With a single
         cross-entropy loss group the batch runs as one FusedEvalStep graph (predictions recorded on the
         device when metric_recorder is a metrics.DeviceMetricRecorder)."""
+        if batch.get("fused_patterns"):
+            return self._validation_step_patterns(batch, loss_functions, device, metric_recorder)
         self.eval()
         with torch.no_grad():
             A, I, labels, miss_type = self._unpack(batch, device)

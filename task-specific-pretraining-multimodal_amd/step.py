@@ -17,6 +17,7 @@ zero_grad pass); with world_size > 1 the flat buffer is all-reduced between back
 from __future__ import annotations
 
 import contextlib
+import ctypes
 import os
 import time
 from typing import Dict, List, Optional, Tuple
@@ -704,3 +705,197 @@ class FusedEvalStep:
         self.load_batch(A, I, labels, groups)
         self.run()
         return {"loss": self.loss, "logits": self.logits, "preds": self.preds}
+
+
+# the AVMNIST missing-modality patterns in ``data.AVMNIST.get_all_possible_patterns()`` order (the classification log's
+# group order) and the (audio, image) inputs each keeps
+AVMNIST_PATTERNS = ("a", "ai", "i")
+PATTERN_KEEP = {"a": (1, 0), "ai": (1, 1), "i": (0, 1)}
+
+
+def norm_avmnist_patterns(patterns=None) -> Tuple[str, ...]:
+    """The patterns of a fused-pattern pass as a tuple of names: all three in ``AVMNIST_PATTERNS`` order by default, or
+    the given subset in the given order.  Unknown names raise ``ValueError``; an empty or repeating selection too."""
+    if patterns is None:
+        return AVMNIST_PATTERNS
+    pats = tuple(str(p) for p in patterns)
+    bad = set(pats) - set(AVMNIST_PATTERNS)
+    if bad:
+        raise ValueError(f"Invalid patterns: {bad}\nValid patterns are: {list(AVMNIST_PATTERNS)}")
+    if not pats or len(set(pats)) != len(pats):
+        raise ValueError(f"patterns: 1..{len(AVMNIST_PATTERNS)} distinct names among {AVMNIST_PATTERNS}, got {pats!r}")
+    return pats
+
+
+# the head of a FusedPatternEvalStep built without head=: "kernel" (tspm_pattern_head_eval) or "launches" (the same
+# result from tspm_pattern_expand + tspm_linear_fwd + tspm_cross_entropy + tspm_classify_update); the leg
+# that measured faster at batch 128 (profiles/avmnist_patterns.json, DESIGN §3.19)
+DEFAULT_PATTERN_HEAD = "kernel"
+
+
+class FusedPatternEvalStep:
+    """AVMNIST.validation_step for EVERY missing-modality pattern of a batch from one encoder pass, as one HIP graph.
+    In eval mode an encoder's output row depends on that row's input and the weights only, so the embedding of a zeroed
+    spectrogram / image is one constant row per encoder (``AVMNIST.zero_embeddings``): the graph holds both encoders
+    over the B real rows (two streams) into ``fused [B, F]``, then the head over the P·B (pattern, sample) rows —
+    ``head="kernel"``: one ``tspm_pattern_head_eval`` call; ``head="launches"``: a copy-expand to ``[P·B, F]``, three
+    ``tspm_linear_fwd`` and per pattern ``tspm_cross_entropy`` + ``tspm_classify_update`` on the row slice (the A/B leg,
+    and the fallback for a head outside the kernel's limits).  Either way the log receives P loss entries per batch in
+    pattern order and every row's confusion count under its pattern's group.
+
+    ``step(A, I, labels, refresh_zero=True)`` → ``{"loss": [P], "logits": [P, B, C], "preds": [P, B]}`` (views of the
+    static outputs).  The zero embeddings are refreshed before each step unless ``refresh_zero=False`` (an evaluation
+    epoch refreshes once: weights do not change inside it)."""
+
+    def __init__(self, model, loss_functions, batch: int, log=None, patterns=None, head: Optional[str] = None,
+                 audio_hw=(32, 94), image_hw=(28, 28), use_graph: bool = True):
+        self.model, self.N, self.log = model, batch, log
+        self.ce_weight = _ce_weight(loss_functions)
+        if self.ce_weight is None:
+            raise L.TspmError("FusedPatternEvalStep: the loss group must be a single cross-entropy term")
+        self.patterns = norm_avmnist_patterns(patterns)
+        self.P = P = len(self.patterns)
+        ea, ei = int(model.embd_size_A), int(model.embd_size_I)
+        self.ea, self.F, self.hd, self.h2 = ea, ea + ei, int(model.hidden_dim), int(model.hidden_dim) // 2
+        head = DEFAULT_PATTERN_HEAD if head is None else head
+        if head not in ("kernel", "launches"):
+            raise ValueError(f"head: 'kernel' or 'launches', got {head!r}")
+        if head == "kernel" and not L.pattern_head_eval_supported(self.F, ea, self.hd, self.h2, NUM_CLASSES, P):
+            head = "launches"
+        self.head = head
+        self.use_graph = use_graph and not os.environ.get("TSPM_NO_GRAPH")
+        dev = next(model.parameters()).device
+        self.device = dev
+        self.audio_hw, self.image_hw = tuple(audio_hw), tuple(image_hw)
+        f32 = dict(device=dev, dtype=torch.float32)
+        self.A = torch.zeros(batch, audio_hw[0], audio_hw[1], **f32)
+        self.I = torch.zeros(batch, 1, image_hw[0], image_hw[1], **f32)
+        self.labels = torch.zeros(batch, dtype=torch.int64, device=dev)
+        self.eng_a = model.audio_encoder.engine_for(self.A)
+        self.eng_i = model.image_encoder.engine_for(self.I)
+        self.x0 = model.zero_embeddings(refresh=False, audio_hw=self.audio_hw, image_hw=self.image_hw)
+        self.logits = torch.empty(P * batch, NUM_CLASSES, **f32)
+        self.loss = torch.zeros(P, **f32)
+        self.preds = torch.zeros(P * batch, dtype=torch.int64, device=dev)
+        # host arrays of the launch arguments (read at enqueue time only)
+        self._keep = (ctypes.c_int32 * (2 * P))(*[k for p in self.patterns for k in PATTERN_KEEP[p]])
+        self._gid = (ctypes.c_int32 * P)()
+        if head == "kernel":
+            self.fused = torch.empty(batch, self.F, **f32)
+            need = int(L.lib().tspm_pattern_head_eval_workspace(batch, P))
+            self.ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+        else:
+            # tspm_pattern_expand's layout: rows [0, B) the real embeddings (the encoders write them), rows [B, 2B)
+            # the zero-input embeddings of the same rows — here one constant row, broadcast.  The entry point takes
+            # three modality widths: the image embedding's columns go in as two halves under the same keep flag
+            self.emb2 = torch.empty(2 * batch, self.F, **f32)
+            self.fused = self.emb2[:batch]
+            self._widths = (ea, ei // 2, ei - ei // 2)
+            self._keep3 = (ctypes.c_int32 * (3 * P))(*[k for p in self.patterns
+                                                        for k in (PATTERN_KEEP[p][0],) + (PATTERN_KEEP[p][1],) * 2])
+            self.x = torch.empty(P * batch, self.F, **f32)
+            self.h1 = torch.empty(P * batch, self.hd, **f32)
+            self.hh = torch.empty(P * batch, self.h2, **f32)
+            self.labels_x = torch.zeros(P * batch, dtype=torch.int64, device=dev)
+            self.groups = torch.zeros(P * batch, dtype=torch.int32, device=dev)
+        self.side = L.shared_streams(dev, 1)[0]
+        self.graph: Optional[torch.cuda.CUDAGraph] = None
+        self._graph_log = None
+        self.calls = 0
+
+    def _group_ids(self) -> List[int]:
+        """Each pattern's group in the log (its position among the log's groups; without a log, among all patterns)."""
+        gid = self.log.gid if self.log is not None else {p: i for i, p in enumerate(AVMNIST_PATTERNS)}
+        try:
+            return [int(gid[p]) for p in self.patterns]
+        except KeyError as e:
+            raise L.TspmError(f"pattern {e} is not one of this log's groups {self.log.groups}") from None
+
+    def load_batch(self, A: torch.Tensor, I: torch.Tensor, labels: torch.Tensor) -> None:
+        for dst, src in ((self.A, A), (self.I, I), (self.labels, labels)):
+            if src.data_ptr() != dst.data_ptr():
+                dst.copy_(src.reshape(dst.shape), non_blocking=True)
+
+    def _head_kernel(self, sh: int) -> None:
+        net, log, g = self.model.net, self.log, (lambda t: t.data_ptr())
+        d = L.PatternHeadEvalDesc(
+            batch=self.N, npat=self.P, in_=self.F, w_audio=self.ea, hidden=self.hd, hidden2=self.h2, classes=NUM_CLASSES,
+            ldx=self.F, x=g(self.fused), x0=g(self.x0), keep=self._keep, group_id=self._gid,
+            w0=g(net[0].weight), b0=g(net[0].bias), w3=g(net[3].weight), b3=g(net[3].bias), w5=g(net[5].weight),
+            b5=g(net[5].bias), labels=g(self.labels), loss_weight=self.ce_weight,
+            n_groups=len(log.groups) if log is not None else 1, logits=g(self.logits), preds=g(self.preds),
+            loss=g(self.loss), confusion=g(log.conf) if log is not None else None,
+            loss_log=g(log.loss_log) if log is not None else None, counters=g(log.counters) if log is not None else None,
+            log_capacity=log.capacity if log is not None else 0, workspace=g(self.ws), workspace_bytes=self.ws.numel())
+        L.check(L.lib().tspm_pattern_head_eval(d, sh), "pattern_head_eval")
+
+    def _head_launches(self, sh: int) -> None:
+        lib, net, log = L.lib(), self.model.net, self.log
+        n, F, hd, h2, B = self.P * self.N, self.F, self.hd, self.h2, self.N
+        self.emb2[B:].copy_(self.x0.expand(B, F))
+        wa, wv, wt = self._widths
+        L.check(lib.tspm_pattern_expand(B, self.P, self._keep3, self._gid, wa, wv, wt, self.emb2.data_ptr(), F,
+                                        self.x.data_ptr(), F, self.labels.data_ptr(), self.labels_x.data_ptr(), 8,
+                                        self.groups.data_ptr(), sh), "pattern eval expand")
+        L.check(lib.tspm_linear_fwd(n, F, hd, self.x.data_ptr(), F, net[0].weight.data_ptr(), net[0].bias.data_ptr(), 1,
+                                    None, 1.0, self.h1.data_ptr(), hd, sh), "pattern eval fc0")
+        L.check(lib.tspm_linear_fwd(n, hd, h2, self.h1.data_ptr(), hd, net[3].weight.data_ptr(), net[3].bias.data_ptr(),
+                                    1, None, 1.0, self.hh.data_ptr(), h2, sh), "pattern eval fc3")
+        L.check(lib.tspm_linear_fwd(n, h2, NUM_CLASSES, self.hh.data_ptr(), h2, net[5].weight.data_ptr(),
+                                    net[5].bias.data_ptr(), 0, None, 1.0, self.logits.data_ptr(), NUM_CLASSES, sh),
+                "pattern eval fc5")
+        for p in range(self.P):
+            lg, ls = self.logits[p * B:(p + 1) * B], self.loss[p:p + 1]
+            L.check(lib.tspm_cross_entropy(B, NUM_CLASSES, lg.data_ptr(), self.labels.data_ptr(), ls.data_ptr(), None,
+                                           self.ce_weight, None, sh), "pattern eval cross_entropy")
+            L.check(lib.tspm_classify_update(
+                B, NUM_CLASSES, lg.data_ptr(), self.labels.data_ptr(), self.groups[p * B:(p + 1) * B].data_ptr(),
+                len(log.groups) if log is not None else 1, log.conf.data_ptr() if log is not None else None,
+                self.preds[p * B:(p + 1) * B].data_ptr(), ls.data_ptr(),
+                log.loss_log.data_ptr() if log is not None else None,
+                log.counters.data_ptr() if log is not None else None, log.capacity if log is not None else 0, sh),
+                "pattern eval classify_update")
+
+    def _enqueue(self) -> None:
+        main = torch.cuda.current_stream()
+        self.side.wait_stream(main)
+        with torch.cuda.stream(self.side):
+            self.eng_i.forward(self.I, self.fused[:, self.ea:], self.F, train=False)
+        self.eng_a.forward(self.A, self.fused, self.F, train=False)
+        main.wait_stream(self.side)
+        if self.head == "kernel":
+            self._head_kernel(main.cuda_stream)
+        else:
+            self._head_launches(main.cuda_stream)
+
+    def _bind_log(self) -> None:
+        """Group ids of the patterns in the current log, into the launch arguments, before the enqueue that bakes them
+        into the graph."""
+        for p, g in enumerate(self._group_ids()):
+            self._gid[p] = g
+
+    def run(self, refresh_zero: bool = True) -> None:
+        """Evaluate the batch in the static input buffers under every pattern (logits, loss, preds; log updated)."""
+        self.model.eval()
+        x0 = self.model.zero_embeddings(refresh=refresh_zero, audio_hw=self.audio_hw, image_hw=self.image_hw)
+        if x0.data_ptr() != self.x0.data_ptr():  # the model dropped its buffer (moved): the graph read the old one
+            self.x0, self.graph = x0, None
+        if not self.use_graph or self.calls == 0:
+            self._bind_log()
+            self._enqueue()
+        else:
+            if self.graph is None or self._graph_log is not self.log:
+                self._bind_log()
+                torch.cuda.synchronize(self.device)
+                g = torch.cuda.CUDAGraph()
+                with L.graph_capture(g):
+                    self._enqueue()
+                self.graph, self._graph_log = g, self.log
+            self.graph.replay()
+        self.calls += 1
+
+    def step(self, A, I, labels, refresh_zero: bool = True) -> Dict[str, torch.Tensor]:
+        self.load_batch(A, I, labels)
+        self.run(refresh_zero)
+        return {"loss": self.loss, "logits": self.logits.view(self.P, self.N, NUM_CLASSES),
+                "preds": self.preds.view(self.P, self.N)}
