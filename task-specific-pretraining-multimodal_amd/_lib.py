@@ -580,3 +580,57 @@ def graph_capture(graph: "torch.cuda.CUDAGraph"):
     the process aborted (round 4's abort in destroy_process_group, reproduced and read in round 5:
     gpurun_out/r5a_phased.err).  Thread-local mode forbids the unsafe calls only in the capturing thread."""
     return torch.cuda.graph(graph, capture_error_mode="thread_local")
+
+
+_PLAIN_KEY_TYPES = (bool, int, float, str, bytes, tuple, type(None))
+
+
+def _same_key(a: tuple, b: tuple) -> bool:
+    """Graph keys element by element: plain values (bools, numbers, strings, tuples of them, None) by ``==``, any
+    other object — a metrics log — by identity."""
+    return len(a) == len(b) and all(x is y or (isinstance(x, _PLAIN_KEY_TYPES) and isinstance(y, _PLAIN_KEY_TYPES)
+                                               and x == y) for x, y in zip(a, b))
+
+
+class GraphRunner:
+    """The capture-and-replay lifecycle of every fused step, as a mixin.  A step's first ``run()`` enqueues its
+    launches eagerly (lazy plans and workspaces get built outside a capture), the second captures them into a HIP
+    graph, later ones replay it — until something the graph baked in changes.  What a step's graph bakes in is its
+    KEY, a tuple handed to ``replay_or_enqueue``: the metrics log (raw pointers into it are launch arguments), host
+    values copied into launches (a keep-mask mode, a group order), a buffer's address.  The key of the last capture is
+    stored; a call whose key differs re-captures first.  Objects in the stored key are held by reference, so a log a
+    graph still points into cannot be freed, nor its ``id`` reused, under that graph.
+
+    ``graph`` and ``calls`` are plain attributes: ``graph = None`` forces a re-capture (the manual override for what no
+    key covers); ``calls`` counts completed ``run()``s and is incremented by the step as the last statement of its
+    ``run``, so a ``run()`` that raises leaves it unchanged.  ``use_graph`` is False for a step built with
+    ``use_graph=False`` or under ``TSPM_NO_GRAPH`` (any non-empty value): such a step enqueues eagerly every time."""
+
+    def _init_graph(self, use_graph: bool, device) -> None:
+        self.use_graph = bool(use_graph) and not os.environ.get("TSPM_NO_GRAPH")
+        self.device = device
+        self.graph: Optional[torch.cuda.CUDAGraph] = None
+        self._captured_key: tuple = ()
+        self.calls = 0
+
+    def capture_graph(self, enqueue) -> "torch.cuda.CUDAGraph":
+        """``enqueue()`` captured into a new graph (the step's device synchronized first); returns the graph."""
+        torch.cuda.synchronize(self.device)
+        g = torch.cuda.CUDAGraph()
+        with graph_capture(g):
+            enqueue()
+        return g
+
+    def replay_or_enqueue(self, enqueue, key: tuple = ()) -> bool:
+        """One execution of ``enqueue``'s launches: eagerly when graphs are off or on the first call; otherwise a
+        replay of ``graph``, re-captured first when it is None or ``key`` differs from the key of its capture.
+        Returns True when this call captured (a step with a second graph re-captures that one too).  An ``enqueue``
+        that raises leaves ``graph`` and the stored key as they were."""
+        if not self.use_graph or self.calls == 0:
+            enqueue()
+            return False
+        captured = self.graph is None or not _same_key(self._captured_key, key)
+        if captured:
+            self.graph, self._captured_key = self.capture_graph(enqueue), key
+        self.graph.replay()
+        return captured

@@ -237,7 +237,7 @@ class MosiEpochRunner:
         tl = self.text_lengths if text_lengths is None else bool(text_lengths)
         st = self.model.fused_step(self.optimizer, self.loss_functions, b, t, ragged=ragged, text_lengths=tl)
         if st.log is not self.log:
-            st.log, st.graph = self.log, None  # the captured graph must record into this log
+            st.log, st.graph = self.log, None  # (the step's graph key holds the log: it would re-capture anyway)
         return st
 
     def eval_step_for(self, b: int, t, ragged: Optional[bool] = None, text_lengths: Optional[bool] = None):
@@ -285,7 +285,7 @@ class MosiEpochRunner:
         st = self.model.fused_pattern_step(self.optimizer, self.loss_functions, b, t, norm_patterns(pats), ragged=ragged,
                                            text_lengths=tl)
         if st.log is not self.log:
-            st.log, st.graph = self.log, None  # the captured graph must record into this log
+            st.log, st.graph = self.log, None  # (the step's graph key holds the log: it would re-capture anyway)
         return st
 
     def loader_for(self, loader, train: bool):

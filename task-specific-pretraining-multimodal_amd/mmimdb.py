@@ -670,9 +670,9 @@ def _record(rec, logits, labels, patterns, threshold):
                          m_types=np.array(patterns if patterns is not None else ["it"] * len(preds)))
 
 
-class FusedMMIMDbStep:
+class FusedMMIMDbStep(L.GraphRunner):
     """One MMIMDb train step (zero_grad-free: the backward overwrites every gradient) — forward, BCE,
-    backward and Adam — as one HIP graph replayed per batch (captured on the second call)."""
+    backward and Adam — as one HIP graph replayed per batch (``_lib.GraphRunner``, empty key)."""
 
     def __init__(self, model: MMIMDb, optimizer: FusedAdam, loss_functions, batch: int, use_graph: bool = True,
                  allreduce=None):
@@ -688,9 +688,8 @@ class FusedMMIMDbStep:
         fgs = optimizer.flat_groups()
         self.eng.rng_ctr_ptr = fgs[0].hyper.data_ptr() + L.HYPER_STEP_OFFSET
         self.nbt = shared_batches_tracked(model, dev, (nn.BatchNorm1d,))
-        self.use_graph, self.allreduce = use_graph, allreduce
-        self.graph: Optional[torch.cuda.CUDAGraph] = None
-        self.calls = 0
+        self._init_graph(use_graph, dev)
+        self.allreduce = allreduce
         self.log_stats = False
 
     @property
@@ -729,16 +728,7 @@ class FusedMMIMDbStep:
         if self.eng.pool is not None and self.eng.pool_keep_override is not None:
             self.eng.keep_pool.copy_(self.eng.pool_keep_override.reshape(self.eng.keep_pool.shape).to(torch.uint8),
                                      non_blocking=True)
-        if not self.use_graph or self.calls == 0:
-            self._all()
-        else:
-            if self.graph is None:
-                torch.cuda.synchronize()
-                g = torch.cuda.CUDAGraph()
-                with L.graph_capture(g):
-                    self._all()
-                self.graph = g
-            self.graph.replay()
+        self.replay_or_enqueue(self._all)
         if self.allreduce is not None:
             self.allreduce()
             self.opt.launch(L.stream_handle())

@@ -173,8 +173,8 @@ class _LinearFn(torch.autograd.Function):
         return gx, gw, gb
 
 
-class _MonoBuffers:
-    """Static device buffers + graph bookkeeping shared by the fused train and eval steps."""
+class _MonoBuffers(L.GraphRunner):
+    """Static device buffers shared by the fused train and eval steps, on the graph runner (key: the log)."""
 
     def _init_buffers(self, model, x_shape: Tuple[int, ...], log, batch: Optional[int] = None) -> None:
         enc, cls = model.encoder, model.classifier
@@ -193,9 +193,6 @@ class _MonoBuffers:
         self.logits = torch.empty(self.N, self.K, **f32)
         self.loss = torch.zeros(1, **f32)
         self.preds = torch.zeros(self.N, dtype=torch.int64, device=dev)
-        self.graph: Optional[torch.cuda.CUDAGraph] = None
-        self._graph_log = None
-        self.calls = 0
 
     def _classify(self, lib, sh: int) -> None:
         log = self.log
@@ -206,18 +203,7 @@ class _MonoBuffers:
             log.capacity if log else 0, ARGMAX_LOGITS, sh), "classify_update")
 
     def _replay_or_enqueue(self) -> None:
-        if self._graph_log is not self.log:  # the metrics log is baked into the captured graph
-            self.graph, self._graph_log = None, self.log
-        if not self.use_graph or self.calls == 0:
-            self._enqueue()
-        else:
-            if self.graph is None:
-                torch.cuda.synchronize(self.device)
-                g = torch.cuda.CUDAGraph()
-                with L.graph_capture(g):
-                    self._enqueue()
-                self.graph = g
-            self.graph.replay()
+        self.replay_or_enqueue(self._enqueue, (self.log,))  # the metrics log is baked into the captured graph
         self.calls += 1
 
     def load_batch(self, x: torch.Tensor, labels: torch.Tensor) -> None:
@@ -237,8 +223,8 @@ class FusedMonoStep(_MonoBuffers):
         encoder fwd → classifier → CE → argmax(logits) → classifier bwd → encoder bwd → FusedAdam
 
     Weight gradients go straight into FusedAdam's flat gradient buffer (overwrite — no zero_grad
-    pass).  First call eager, second captures, later calls copy the batch into the static buffers
-    (no copy when the caller gathered into them) and replay."""
+    pass).  ``_lib.GraphRunner``'s lifecycle: first call eager, second captures, later calls copy the batch
+    into the static buffers (no copy when the caller gathered into them) and replay."""
 
     def __init__(self, model, optimizer: FusedAdam, loss_functions, x_shape, use_graph: bool = True, log=None):
         self.ce_weight = _ce_weight(loss_functions)
@@ -249,7 +235,7 @@ class FusedMonoStep(_MonoBuffers):
         x_shape = tuple(int(v) for v in x_shape)
         self._init_buffers(model, x_shape, log)
         self.opt = optimizer
-        self.use_graph = use_graph and not os.environ.get("TSPM_NO_GRAPH")
+        self._init_graph(use_graph, self.device)
         model.train()
         prepare_encoder_layout(model.encoder)
         for p in model.parameters():
@@ -307,7 +293,7 @@ class FusedMonoEvalStep(_MonoBuffers):
             raise L.TspmError("FusedMonoEvalStep: the loss group must be a single cross-entropy term")
         x_shape = tuple(int(v) for v in x_shape)
         self._init_buffers(model, x_shape, log)
-        self.use_graph = use_graph and not os.environ.get("TSPM_NO_GRAPH")
+        self._init_graph(use_graph, self.device)
         self.eng = model.encoder.engine_for(self.X)
 
     def _enqueue(self) -> None:
@@ -463,7 +449,7 @@ class FusedMosiMonoStep(_MosiMonoBuffers):
                 raise L.TspmError("FusedMosiMonoStep: parameter without a FusedAdam gradient view")
         self._init_mosi(model, x_shape, log, fused_head, ragged, text_lengths)
         self.opt = optimizer
-        self.use_graph = use_graph and not os.environ.get("TSPM_NO_GRAPH")
+        self._init_graph(use_graph, self.device)
         self.eng.rng_ctr_ptr = optimizer.flat_groups()[0].hyper.data_ptr() + L.HYPER_STEP_OFFSET
         f32 = dict(device=self.device, dtype=torch.float32)
         self.dlogits = torch.empty(self.N, self.K, **f32)
@@ -510,7 +496,7 @@ class FusedMosiMonoEvalStep(_MosiMonoBuffers):
             raise L.TspmError("FusedMosiMonoEvalStep: the loss group must be a single cross-entropy term (or, under "
                               "a one-output classifier, a single mean L1 / MSE term)")
         self._init_mosi(model, x_shape, log, fused_head, ragged, text_lengths)
-        self.use_graph = use_graph and not os.environ.get("TSPM_NO_GRAPH")
+        self._init_graph(use_graph, self.device)
 
     def _enqueue(self) -> None:
         sh = torch.cuda.current_stream().cuda_stream
@@ -552,10 +538,10 @@ def bce_head_choice(requested: Optional[bool], n: int, hid: int, classes: int) -
     return bool(requested) and bce_head_supported(n, hid, classes)
 
 
-class _MMIMDbMonoBuffers:
-    """What the MMIMDb-encoder train and eval steps share: the static buffers for one (batch, in), the graph
-    bookkeeping and the multi-label head — ``tspm_mono_head_bce_step`` or the separate launches
-    (``tspm_linear_fwd``, ``tspm_bce_logits``, ``tspm_linear_bwd``)."""
+class _MMIMDbMonoBuffers(L.GraphRunner):
+    """What the MMIMDb-encoder train and eval steps share: the static buffers for one (batch, in), the graph runner
+    (empty key: nothing replaceable is baked in) and the multi-label head — ``tspm_mono_head_bce_step`` or the
+    separate launches (``tspm_linear_fwd``, ``tspm_bce_logits``, ``tspm_linear_bwd``)."""
 
     THRESHOLD = 0.5  # train_monomodal.py: torch.sigmoid(logits) > 0.5
 
@@ -595,8 +581,6 @@ class _MMIMDbMonoBuffers:
         self.splits = 4 if (fin >= 2048 and tiles < 256) else 1
         wsb = lib.tspm_linear_fwd_splitk_workspace(n, fin, self.hid, self.splits) if self.splits > 1 else 0
         self.ws = torch.zeros(max(int(wsb) // 4, 4), **f32)
-        self.graph: Optional[torch.cuda.CUDAGraph] = None
-        self.calls = 0
         self.log = None  # the multi-label counts live in ``stats``; no ClassificationLog on this path
 
     @property
@@ -642,16 +626,7 @@ class _MMIMDbMonoBuffers:
                        cls.weight.grad.data_ptr(), cls.bias.grad.data_ptr(), self.demb.data_ptr(), hid, sh)
 
     def _replay_or_enqueue(self) -> None:
-        if not self.use_graph or self.calls == 0:
-            self._enqueue()
-        else:
-            if self.graph is None:
-                torch.cuda.synchronize(self.device)
-                g = torch.cuda.CUDAGraph()
-                with L.graph_capture(g):
-                    self._enqueue()
-                self.graph = g
-            self.graph.replay()
+        self.replay_or_enqueue(self._enqueue)
         self.calls += 1
 
     def load_batch(self, x: torch.Tensor, labels: torch.Tensor) -> None:
@@ -679,7 +654,7 @@ class FusedMMIMDbMonoStep(_MMIMDbMonoBuffers):
 
     ``x_shape`` is (batch, in).  ``fused_head=False`` runs the head as ``tspm_linear_fwd``, ``tspm_bce_logits`` and
     ``tspm_linear_bwd`` (also taken for shapes outside the head kernel's limits).  Gradients go straight into
-    FusedAdam's flat views (overwritten).  First call eager, second captures, later calls replay."""
+    FusedAdam's flat views (overwritten).  ``_lib.GraphRunner``'s lifecycle: eager, capture, replays."""
 
     def __init__(self, model, optimizer: FusedAdam, loss_functions, x_shape, use_graph: bool = True, log=None,
                  fused_head: Optional[bool] = None):
@@ -694,7 +669,7 @@ class FusedMMIMDbMonoStep(_MMIMDbMonoBuffers):
             if p.requires_grad and p.grad is None:
                 raise L.TspmError("FusedMMIMDbMonoStep: parameter without a FusedAdam gradient view")
         self.opt = optimizer
-        self.use_graph = use_graph and not os.environ.get("TSPM_NO_GRAPH")
+        self._init_graph(use_graph, self.device)
         f32 = dict(device=self.device, dtype=torch.float32)
         self.mean, self.inv = torch.zeros(self.fin, **f32), torch.zeros(self.fin, **f32)
         self.demb = torch.empty(self.N, self.hid, **f32)
@@ -744,7 +719,7 @@ class FusedMMIMDbMonoEvalStep(_MMIMDbMonoBuffers):
     def __init__(self, model, loss_functions, x_shape, log=None, use_graph: bool = True,
                  fused_head: Optional[bool] = None):
         self._init_mmimdb(model, loss_functions, x_shape, fused_head, "FusedMMIMDbMonoEvalStep")
-        self.use_graph = use_graph and not os.environ.get("TSPM_NO_GRAPH")
+        self._init_graph(use_graph, self.device)
 
     def _enqueue(self) -> None:
         from .mmimdb import _bn

@@ -1401,15 +1401,29 @@ def _regress_mode(model: "UttFusionModel", loss_functions):
     return _regress_term(loss_functions) if model.netC.fc_out.out_features == 1 else None
 
 
+def _loss_mode(who: str, model: "UttFusionModel", loss_functions, head_rows: int):
+    """``(weight, regress)`` of the fused step ``who`` whose head runs over ``head_rows`` rows: the weight of a single
+    cross-entropy term (else None) and ``_regress_mode``'s (kind, weight) of the one-launch regression head (else None).
+    A loss group that is neither, and a regression head outside ``tspm_regress_head_step``'s limits, are refused."""
+    weight, regress = _ce_weight(loss_functions), _regress_mode(model, loss_functions)
+    if regress is None and weight is None:
+        raise L.TspmError(f"{who}: the loss group must be a single cross-entropy term (or, with a one-output fc_out, "
+                          f"a single mean L1 / MSE term)")
+    if regress is not None and not L.regress_head_supported(head_rows, model.netC.widths[-1]):
+        raise L.TspmError(f"{who}: the regression head takes at most 1024 rows and a last classifier layer of at most "
+                          f"128 units, a multiple of 4")
+    return weight, regress
+
+
 def _check_regress_log(log) -> None:
     from .metrics import RegressionLog
     if log is not None and not isinstance(log, RegressionLog):
         raise L.TspmError("the regression head records into a metrics.RegressionLog")
 
 
-class FusedMosiStep:
+class FusedMosiStep(L.GraphRunner):
     """One UTT-Fusion train step — forward, cross-entropy, backward, gradient clip, Adam — as one HIP
-    graph (captured on the second call; the backward overwrites every gradient, no zero_grad pass).  With a
+    graph (``_lib.GraphRunner``, key: the log; the backward overwrites every gradient, no zero_grad pass).  With a
     one-output ``netC.fc_out`` and a single mean L1 / MSE term (sentiment regression on float32 labels) the head —
     ``fc_out``, the loss, the per-pattern epoch accumulators, the loss log and ``fc_out``'s backward — is the one
     launch of ``MosiEngine.head_regress``; everything else is the classification step's schedule."""
@@ -1428,24 +1442,16 @@ class FusedMosiStep:
         self._flags = model.flag_state()[0]
         self.multi = len(fgs) > 1
         self.model, self.opt, self.N, self.T = model, optimizer, batch, norm_steps(steps)
-        self.weight = _ce_weight(loss_functions)
-        self.regress = _regress_mode(model, loss_functions)  # (kind, weight): the one-launch regression head
-        if self.regress is None and self.weight is None:
-            raise L.TspmError("FusedMosiStep: the loss group must be a single cross-entropy term (or, with a "
-                              "one-output fc_out, a single mean L1 / MSE term)")
-        if self.regress is not None and not L.regress_head_supported(self._head_rows(batch), model.netC.widths[-1]):
-            raise L.TspmError("FusedMosiStep: the regression head takes at most 1024 rows and a last classifier "
-                              "layer of at most 128 units, a multiple of 4")
+        # regress = (kind, weight): the one-launch regression head
+        self.weight, self.regress = _loss_mode("FusedMosiStep", model, loss_functions, self._head_rows(batch))
         self.ragged, self.text_lengths = bool(ragged), bool(text_lengths)
         self.eng = self._build_engine(dev, steps)
         # the dropout counter is group 0's step (all groups advance together)
         self.eng.rng_ctr_ptr = fgs[0].hyper.data_ptr() + L.HYPER_STEP_OFFSET
         if model.clip is not None:
             optimizer.clip_coef = self.eng.clip_coef
-        self.use_graph = use_graph and not os.environ.get("TSPM_NO_GRAPH")
+        self._init_graph(use_graph, dev)
         self.allreduce = allreduce
-        self.graph: Optional[torch.cuda.CUDAGraph] = None
-        self.calls = 0
         self.log = None  # metrics.ClassificationLog (train predictions on the device); RegressionLog in regression mode
 
     def _head_rows(self, batch: int) -> int:
@@ -1475,11 +1481,7 @@ class FusedMosiStep:
         e.forward(sh, True)
         e.loss_fn(sh, self.weight, True, True)
         if self.log is not None:
-            lg = self.log
-            L.check(L.lib().tspm_classify_update(self.N, e.logits.shape[1], e.logits.data_ptr(), e.labels.data_ptr(),
-                                                 e.groups.data_ptr(), len(lg.groups), lg.conf.data_ptr(), None,
-                                                 e.loss.data_ptr(), lg.loss_log.data_ptr(), lg.counters.data_ptr(),
-                                                 lg.capacity, sh), "classify_update")
+            e.classify_update(sh, self.log)
         e.backward(sh)
 
     def _opt(self) -> None:
@@ -1508,6 +1510,11 @@ class FusedMosiStep:
         self.run()
         return {"loss": self.eng.loss, "logits": self.eng.logits}
 
+    def _bind_log(self) -> tuple:
+        """The graph's key, after anything host-side the current log decides is in place: here the log alone (the
+        launches carry raw pointers into it)."""
+        return (self.log,)
+
     def run(self) -> None:
         flags, (frozen, _) = self.model.flag_state()
         if flags != self._flags:
@@ -1519,16 +1526,7 @@ class FusedMosiStep:
         self.eng.apply_keep_override()
         if self.model.clip is not None:
             self.opt.clip_coef = self.eng.clip_coef
-        if not self.use_graph or self.calls == 0:
-            self._all()
-        else:
-            if self.graph is None:
-                torch.cuda.synchronize()
-                g = torch.cuda.CUDAGraph()
-                with L.graph_capture(g):
-                    self._all()
-                self.graph = g
-            self.graph.replay()
+        self.replay_or_enqueue(self._all, self._bind_log())
         if self.allreduce is not None:
             self.allreduce()
             self._opt()
@@ -1542,10 +1540,10 @@ class FusedMosiPatternStep(FusedMosiStep):
     unmasked, once; the encoders run forward and backward over 2B rows (the batch and zero rows), the classifier over
     the P*B expanded rows.  ``FusedMosiStep``'s order — ``check_param_groups`` (1..8 groups, frozen encoders), forward,
     the loss with its gradient, ``tspm_classify_update`` over the P*B rows with the expanded group ids when a log is
-    attached (ONE loss entry per step, confusion counts per pattern), backward, clip, Adam; first call eager, second
-    captured, later ones replays; the dropout counter is group 0's step.  The loss is the weighted mean cross-entropy
-    over all P*B rows, i.e. a plain step on the replicated batch cat_p(A*ka_p, V*kv_p, T*kt_p) with labels and lengths
-    tiled P times; BatchNorm1d (MOSEI) takes its statistics over the P*B rows and updates its running statistics once;
+    attached (ONE loss entry per step, confusion counts per pattern), backward, clip, Adam; the graph runner's
+    lifecycle (key: the log and its group order); the dropout counter is group 0's step.  The loss is the weighted
+    mean cross-entropy over all P*B rows, i.e. a plain step on the replicated batch cat_p(A*ka_p, V*kv_p, T*kt_p) with
+    labels and lengths tiled P times; BatchNorm1d (MOSEI) takes its statistics over the P*B rows and updates its running statistics once;
     the TextCNN dropout mask is per encoder row (2B; shared by the patterns that read the row), the classifier masks
     per classifier row (``keep_override``: ``"text"`` [2B, nc], ``"cls{j}"`` [P*B, w_j]).  Regression mode runs
     ``head_regress`` over the P*B rows, so P*B is within the head's 1024 rows or the step is refused.  ``step`` returns
@@ -1591,15 +1589,14 @@ class FusedMosiPatternStep(FusedMosiStep):
         self.run()
         return {"loss": self.eng.cls.loss, "logits": self.eng.logits}
 
-    def run(self) -> None:
+    def _bind_log(self) -> tuple:
         # the log's group order decides the ids the expansion writes (host values of the launch)
         if self.log is not None and self.eng.group_names != tuple(self.log.groups):
             self.eng.set_groups(self.log.groups)
-            self.graph = None
-        super().run()
+        return (self.log, self.eng.group_names)
 
 
-class FusedMosiEvalStep:
+class FusedMosiEvalStep(L.GraphRunner):
     """``validation_step``'s device work (utt_fusion.py:202-244) for one (batch, steps) shape as one HIP graph:
     eval-mode forward (no dropout; running statistics in the MOSEI classifier BatchNorm1d), the loss group's
     cross-entropy, and ``tspm_classify_update`` (softmax argmax, per-pattern confusion counts, the batch loss
@@ -1612,18 +1609,16 @@ class FusedMosiEvalStep:
         dev = next(model.parameters()).device
         self.ragged, self.text_lengths = bool(ragged), bool(text_lengths)
         self.model, self.N, self.T, self.log = model, batch, norm_steps(steps), log
-        self.weight = _ce_weight(loss_functions)
-        self.regress = _regress_mode(model, loss_functions)
-        if self.regress is None and self.weight is None:
-            raise L.TspmError("FusedMosiEvalStep: the loss group must be a single cross-entropy term (or, with a "
-                              "one-output fc_out, a single mean L1 / MSE term)")
-        if self.regress is not None and not L.regress_head_supported(batch, model.netC.widths[-1]):
-            raise L.TspmError("FusedMosiEvalStep: the regression head takes at most 1024 rows and a last classifier "
-                              "layer of at most 128 units, a multiple of 4")
-        self.eng = model._engine(batch, steps, dev, self.ragged, self.text_lengths)
-        self.use_graph = use_graph and not os.environ.get("TSPM_NO_GRAPH")
-        self.graph: Optional[torch.cuda.CUDAGraph] = None
-        self.calls = 0
+        self.weight, self.regress = _loss_mode(type(self).__name__, model, loss_functions, batch)
+        self.eng = self._build_engine(dev, steps)
+        self._init_graph(use_graph, dev)
+
+    def _build_engine(self, dev, steps):
+        return self.model._engine(self.N, steps, dev, self.ragged, self.text_lengths)
+
+    def _bind_log(self) -> tuple:
+        """As ``FusedMosiStep._bind_log``: the graph's key is the log."""
+        return (self.log,)
 
     def _all(self) -> None:
         sh, e, lg = L.stream_handle(), self.eng, self.log
@@ -1634,10 +1629,7 @@ class FusedMosiEvalStep:
             return
         e.forward(sh, False)
         e.loss_fn(sh, self.weight, False)
-        L.check(L.lib().tspm_classify_update(self.N, e.logits.shape[1], e.logits.data_ptr(), e.labels.data_ptr(),
-                                             e.groups.data_ptr(), len(lg.groups), lg.conf.data_ptr(), None,
-                                             e.loss.data_ptr(), lg.loss_log.data_ptr(), lg.counters.data_ptr(),
-                                             lg.capacity, sh), "classify_update")
+        e.classify_update(sh, lg)
 
     def step(self, A, V, T, labels, lengths: Optional[Dict[str, torch.Tensor]] = None) -> None:
         self.eng.load(A, V, T, labels, self.regress is not None)
@@ -1646,16 +1638,7 @@ class FusedMosiEvalStep:
 
     def run(self) -> None:
         self.model.eval()
-        if not self.use_graph or self.calls == 0:
-            self._all()
-        else:
-            if self.graph is None:
-                torch.cuda.synchronize()
-                g = torch.cuda.CUDAGraph()
-                with L.graph_capture(g):
-                    self._all()
-                self.graph = g
-            self.graph.replay()
+        self.replay_or_enqueue(self._all, self._bind_log())
         self.calls += 1
 
 
@@ -1853,34 +1836,29 @@ class MosiPatternEngine:
         e._backward_encoders(sh)
 
 
-class FusedMosiPatternEvalStep:
+class FusedMosiPatternEvalStep(FusedMosiEvalStep):
     """``FusedMosiEvalStep`` for every pattern of a batch at once (``MosiPatternEngine``): the batch arrives unmasked,
     once; one HIP graph runs the 2B-row encoder pass, the expansion, the classifier on P*B rows and then, for each
     pattern in order, the existing loss and metrics launches on its B rows (``tspm_cross_entropy`` +
     ``tspm_classify_update``, or ``tspm_regress_head_step`` forward-only in regression mode) — so the epoch's log gets
     the same P loss entries, in pattern order, that P replays of the per-pattern step write, and the per-pattern
-    accumulators are filled through the expanded group ids.  First call eager, second captured, later ones replays; no
-    host synchronisation; the refusals of ``FusedMosiEvalStep``.  ``step`` takes a batch-first batch, ``run`` serves
-    inputs gathered in place (``mosi_data.MOSI.loader(fuse_patterns=True)``)."""
+    accumulators are filled through the expanded group ids.  The graph runner's lifecycle (key: the log and its group
+    order); no host synchronisation; the refusals of ``FusedMosiEvalStep``.  ``step`` takes a batch-first batch,
+    ``run`` serves inputs gathered in place (``mosi_data.MOSI.loader(fuse_patterns=True)``)."""
 
     def __init__(self, model: "UttFusionModel", loss_functions, batch: int, steps, log, patterns=None,
                  use_graph: bool = True, ragged: bool = False, text_lengths: bool = False):
-        dev = next(model.parameters()).device
-        self.ragged, self.text_lengths = bool(ragged), bool(text_lengths)
-        self.model, self.N, self.T, self.log = model, int(batch), norm_steps(steps), log
         self.patterns = norm_patterns(patterns)
-        self.weight = _ce_weight(loss_functions)
-        self.regress = _regress_mode(model, loss_functions)
-        if self.regress is None and self.weight is None:
-            raise L.TspmError("FusedMosiPatternEvalStep: the loss group must be a single cross-entropy term (or, with a "
-                              "one-output fc_out, a single mean L1 / MSE term)")
-        if self.regress is not None and not L.regress_head_supported(batch, model.netC.widths[-1]):
-            raise L.TspmError("FusedMosiPatternEvalStep: the regression head takes at most 1024 rows and a last "
-                              "classifier layer of at most 128 units, a multiple of 4")
-        self.eng = model._pattern_engine(batch, steps, dev, self.patterns, self.ragged, self.text_lengths)
-        self.use_graph = use_graph and not os.environ.get("TSPM_NO_GRAPH")
-        self.graph: Optional[torch.cuda.CUDAGraph] = None
-        self.calls = 0
+        super().__init__(model, loss_functions, int(batch), steps, log, use_graph=use_graph, ragged=ragged,
+                         text_lengths=text_lengths)
+
+    def _build_engine(self, dev, steps):
+        return self.model._pattern_engine(self.N, steps, dev, self.patterns, self.ragged, self.text_lengths)
+
+    def _bind_log(self) -> tuple:
+        if self.eng.group_names != tuple(self.log.groups):  # the log's group order decides the ids the launch carries
+            self.eng.set_groups(self.log.groups)
+        return (self.log, self.eng.group_names)
 
     def _all(self) -> None:
         sh, e, lg, B = L.stream_handle(), self.eng, self.log, self.N
@@ -1894,28 +1872,6 @@ class FusedMosiPatternEvalStep:
         for p in range(e.P):
             e.cls.loss_fn(sh, self.weight, False, rows=(p * B, B), loss=e.losses[p:p + 1])
             e.cls.classify_update(sh, lg, rows=(p * B, B), loss=e.losses[p:p + 1])
-
-    def step(self, A, V, T, labels, lengths: Optional[Dict[str, torch.Tensor]] = None) -> None:
-        self.eng.load(A, V, T, labels, self.regress is not None)
-        self.eng.set_lengths(lengths)
-        self.run()
-
-    def run(self) -> None:
-        self.model.eval()
-        if self.eng.group_names != tuple(self.log.groups):  # the log's group order decides the ids the launch carries
-            self.eng.set_groups(self.log.groups)
-            self.graph = None
-        if not self.use_graph or self.calls == 0:
-            self._all()
-        else:
-            if self.graph is None:
-                torch.cuda.synchronize()
-                g = torch.cuda.CUDAGraph()
-                with L.graph_capture(g):
-                    self._all()
-                self.graph = g
-            self.graph.replay()
-        self.calls += 1
 
 
 # ------------------------------------------------------------------------------------------------

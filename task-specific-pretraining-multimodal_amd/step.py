@@ -187,7 +187,7 @@ class AdamCarry:
         return [out] + list(ranges[1:])
 
 
-class FusedTrainStep:
+class FusedTrainStep(L.GraphRunner):
     def __init__(self, model, optimizer: FusedAdam, loss_functions, batch: int, audio_hw=(32, 94), image_hw=(28, 28),
                  use_graph: bool = True, allreduce=None, adam_split=True):
         self.model = model
@@ -198,11 +198,10 @@ class FusedTrainStep:
             raise L.TspmError("FusedTrainStep: the fusion head's shape is outside tspm_head_train_step's limits "
                               "(use AVMNIST.train_step, which routes such heads to the autograd path)")
         self.N = batch
-        self.use_graph = use_graph and not os.environ.get("TSPM_NO_GRAPH")
         self.allreduce = allreduce
         p0 = next(model.parameters())
         dev = p0.device
-        self.device = dev
+        self._init_graph(use_graph, dev)  # graph: forward + backward (+ Adam on one GPU); key (log, keep-mask mode)
         model.train()
         prepare_encoder_layout(model.audio_encoder)
         prepare_encoder_layout(model.image_encoder)
@@ -224,7 +223,6 @@ class FusedTrainStep:
         # metrics.ClassificationLog: when set, the step also records predictions / confusion counts /
         # the batch loss on the device (train metrics of the epoch, train_multimodal.py:478-491,607-612)
         self.log = None
-        self._graph_log = None
         self.fused = torch.empty(batch, self.F, **f32)
         self.h1 = torch.empty(batch, hd, **f32)
         self.hh = torch.empty(batch, self.h2, **f32)
@@ -261,8 +259,7 @@ class FusedTrainStep:
         # the head's samples per workgroup (tspm_head_desc.rows_per_block, ABI 21): 0 = the library's default (1 up
         # to 256 rows, else 4); TSPM_HEAD_RB=1 / 4 forces one for A/B (read here, not inside the library)
         self.head_rows_per_block = int(os.environ.get("TSPM_HEAD_RB", "0"))
-        self.graph: Optional[torch.cuda.CUDAGraph] = None
-        self.graph_opt: Optional[torch.cuda.CUDAGraph] = None
+        self.graph_opt: Optional[torch.cuda.CUDAGraph] = None  # plain DP step: Adam, replayed behind the all-reduce
         # single-GPU step (adam_split): each encoder's parameters updated by Adam on that encoder's stream right
         # after its own backward (the image encoder's beside the audio chain's tail), the head's with the audio
         # encoder's; bitwise the one-launch update (Adam is element-wise).  A cross-stream edge in the middle of
@@ -273,9 +270,7 @@ class FusedTrainStep:
         # the two step flags and a pair of events (graph end, step end) bracketing the exposed exchange tail
         self.exchange_probe: Optional[list] = None
         self._split_ranges = None
-        self._graph_gen_keep = True
         self._head_bumps_step = False
-        self.calls = 0
         self._sig = (id(optimizer), id(loss_functions), batch)
         # dropout RNG counter = FusedAdam's device step counter (distinct per step, graph-safe)
         fgs = optimizer.flat_groups()
@@ -453,22 +448,11 @@ class FusedTrainStep:
             # the per-phase Adam ranges have no clip-coefficient form: refuse instead of ignoring it
             raise L.TspmError("phased DP step: FusedAdam.clip_coef is set, but the per-phase Adam ranges cannot "
                               "apply a clip coefficient; use the plain DP step (allreduce=GradAllReduce)")
-        eager = not self.use_graph or self.calls == 0
         if getattr(self, "_marks", None) is None:
             self._marks = (L.DeviceFlag(), L.DeviceFlag())
         if getattr(self, "_phase_ranges", None) is None:
             raise L.TspmError("phased step: build the exchange with FusedTrainStep.phased_allreduce()")
-        if eager:
-            self._fwd_bwd(marks=self._marks)
-        else:
-            if self.graph is None:
-                torch.cuda.synchronize(self.device)
-                g = torch.cuda.CUDAGraph()
-                with L.graph_capture(g):
-                    self._fwd_bwd(marks=self._marks)
-                self.graph, self.graph_opt = g, None
-                self._graph_gen_keep = self.keep_override is None
-            self.graph.replay()
+        self._replay_step(lambda: self._fwd_bwd(marks=self._marks), opt_graph=False)
         # each flag is bumped once per step, after (in graph order) everything main ran before this step
         # (batch upload, the previous step's Adam reading the gradients): once the host has seen it, the
         # gradients it covers are complete, so the exchange launched then needs no device-side wait
@@ -567,25 +551,14 @@ class FusedTrainStep:
             raise L.TspmError("FusedTrainStep.run after close()")
         self.model.train()
         self.opt.sync_hyper()
-        if self._graph_log is not self.log:  # the metrics log is baked into the captured graphs
-            self.graph, self.graph_opt = None, None
-            self._graph_log = self.log
         if self.keep_override is not None:
             self.keep.copy_(self.keep_override.reshape(self.keep.shape).to(torch.uint8), non_blocking=True)
-        # the captured head either draws its keep mask or reads the copied-in one: re-capture on a change
-        if self.graph is not None and self._graph_gen_keep != (self.keep_override is None):
-            self.graph, self.graph_opt = None, None
         if isinstance(self.allreduce, PhasedGradAllReduce):
             self._run_phased()
             self.opt.note_steps(1)
             self.calls += 1
             return
-        if not self.use_graph or self.calls == 0:
-            self._enqueue_all()
-        else:
-            if self.graph is None:
-                self._capture()
-            self.graph.replay()
+        self._replay_step(self._enqueue_all, opt_graph=self.allreduce is not None)
         if self.allreduce is not None:
             self.allreduce()
             if self.use_graph and self.graph_opt is not None:
@@ -595,24 +568,17 @@ class FusedTrainStep:
         self.opt.note_steps(1)
         self.calls += 1
 
-    def _capture(self) -> None:
-        torch.cuda.synchronize(self.device)
-        g = torch.cuda.CUDAGraph()
-        with L.graph_capture(g):
-            if self.allreduce is None:
-                self._enqueue_all()
-            else:
-                self._fwd_bwd()
-        self.graph = g
-        self._graph_gen_keep = self.keep_override is None
-        if self.allreduce is not None:
-            go = torch.cuda.CUDAGraph()
-            with L.graph_capture(go):
-                self._opt()
-            self.graph_opt = go
+    def _replay_step(self, enqueue, opt_graph: bool) -> None:
+        """``enqueue`` through the runner.  The graph bakes in the metrics log and whether the head draws its keep mask
+        or reads the copied-in one.  ``graph_opt`` (``opt_graph``: Adam alone, for the plain DP step) lives and dies
+        with ``graph``: dropped when that is found None, captured again right after it."""
+        if self.graph is None:
+            self.graph_opt = None
+        if self.replay_or_enqueue(enqueue, (self.log, self.keep_override is None)):
+            self.graph_opt = self.capture_graph(self._opt) if opt_graph else None
 
 
-class FusedEvalStep:
+class FusedEvalStep(L.GraphRunner):
     """AVMNIST.validation_step (MML_Suite/models/avmnist.py:312-360) as one HIP graph: both encoders in
     eval mode (BatchNorm running statistics) on two streams, the fusion head without dropout, the loss
     (LossFunctionGroup total = weight × CE) and ``tspm_classify_update`` — predictions, per-pattern
@@ -626,9 +592,8 @@ class FusedEvalStep:
         self.ce_weight = _ce_weight(loss_functions)
         if self.ce_weight is None:
             raise L.TspmError("FusedEvalStep: the loss group must be a single cross-entropy term")
-        self.use_graph = use_graph and not os.environ.get("TSPM_NO_GRAPH")
         dev = next(model.parameters()).device
-        self.device = dev
+        self._init_graph(use_graph, dev)  # key: (log,)
         f32 = dict(device=dev, dtype=torch.float32)
         self.A = torch.zeros(batch, audio_hw[0], audio_hw[1], **f32)
         self.I = torch.zeros(batch, 1, image_hw[0], image_hw[1], **f32)
@@ -645,9 +610,6 @@ class FusedEvalStep:
         self.loss = torch.zeros(1, **f32)
         self.preds = torch.zeros(batch, dtype=torch.int64, device=dev)
         self.side = L.shared_streams(dev, 1)[0]
-        self.graph: Optional[torch.cuda.CUDAGraph] = None
-        self._graph_log = None
-        self.calls = 0
 
     def load_batch(self, A: torch.Tensor, I: torch.Tensor, labels: torch.Tensor,
                    groups: Optional[torch.Tensor] = None) -> None:
@@ -689,16 +651,7 @@ class FusedEvalStep:
     def run(self) -> None:
         """Evaluate the batch in the static input buffers (logits, loss, preds; log updated)."""
         self.model.eval()
-        if not self.use_graph or self.calls == 0:
-            self._enqueue()
-        else:
-            if self.graph is None or self._graph_log is not self.log:
-                torch.cuda.synchronize(self.device)
-                g = torch.cuda.CUDAGraph()
-                with L.graph_capture(g):
-                    self._enqueue()
-                self.graph, self._graph_log = g, self.log
-            self.graph.replay()
+        self.replay_or_enqueue(self._enqueue, (self.log,))
         self.calls += 1
 
     def step(self, A, I, labels, groups=None) -> Dict[str, torch.Tensor]:
@@ -733,7 +686,7 @@ def norm_avmnist_patterns(patterns=None) -> Tuple[str, ...]:
 DEFAULT_PATTERN_HEAD = "kernel"
 
 
-class FusedPatternEvalStep:
+class FusedPatternEvalStep(L.GraphRunner):
     """AVMNIST.validation_step for EVERY missing-modality pattern of a batch from one encoder pass, as one HIP graph.
     In eval mode an encoder's output row depends on that row's input and the weights only, so the embedding of a zeroed
     spectrogram / image is one constant row per encoder (``AVMNIST.zero_embeddings``): the graph holds both encoders
@@ -763,9 +716,8 @@ class FusedPatternEvalStep:
         if head == "kernel" and not L.pattern_head_eval_supported(self.F, ea, self.hd, self.h2, NUM_CLASSES, P):
             head = "launches"
         self.head = head
-        self.use_graph = use_graph and not os.environ.get("TSPM_NO_GRAPH")
         dev = next(model.parameters()).device
-        self.device = dev
+        self._init_graph(use_graph, dev)  # key: (log, the zero-row buffer's address)
         self.audio_hw, self.image_hw = tuple(audio_hw), tuple(image_hw)
         f32 = dict(device=dev, dtype=torch.float32)
         self.A = torch.zeros(batch, audio_hw[0], audio_hw[1], **f32)
@@ -799,9 +751,6 @@ class FusedPatternEvalStep:
             self.labels_x = torch.zeros(P * batch, dtype=torch.int64, device=dev)
             self.groups = torch.zeros(P * batch, dtype=torch.int32, device=dev)
         self.side = L.shared_streams(dev, 1)[0]
-        self.graph: Optional[torch.cuda.CUDAGraph] = None
-        self._graph_log = None
-        self.calls = 0
 
     def _group_ids(self) -> List[int]:
         """Each pattern's group in the log (its position among the log's groups; without a log, among all patterns)."""
@@ -857,6 +806,7 @@ class FusedPatternEvalStep:
                 "pattern eval classify_update")
 
     def _enqueue(self) -> None:
+        self._bind_log()
         main = torch.cuda.current_stream()
         self.side.wait_stream(main)
         with torch.cuda.stream(self.side):
@@ -869,29 +819,17 @@ class FusedPatternEvalStep:
             self._head_launches(main.cuda_stream)
 
     def _bind_log(self) -> None:
-        """Group ids of the patterns in the current log, into the launch arguments, before the enqueue that bakes them
-        into the graph."""
+        """Group ids of the patterns in the current log, into the launch arguments (host values only), at the top of
+        the enqueue that bakes them into the graph."""
         for p, g in enumerate(self._group_ids()):
             self._gid[p] = g
 
     def run(self, refresh_zero: bool = True) -> None:
         """Evaluate the batch in the static input buffers under every pattern (logits, loss, preds; log updated)."""
         self.model.eval()
-        x0 = self.model.zero_embeddings(refresh=refresh_zero, audio_hw=self.audio_hw, image_hw=self.image_hw)
-        if x0.data_ptr() != self.x0.data_ptr():  # the model dropped its buffer (moved): the graph read the old one
-            self.x0, self.graph = x0, None
-        if not self.use_graph or self.calls == 0:
-            self._bind_log()
-            self._enqueue()
-        else:
-            if self.graph is None or self._graph_log is not self.log:
-                self._bind_log()
-                torch.cuda.synchronize(self.device)
-                g = torch.cuda.CUDAGraph()
-                with L.graph_capture(g):
-                    self._enqueue()
-                self.graph, self._graph_log = g, self.log
-            self.graph.replay()
+        # the graph reads the zero-row buffer by address: a model that dropped its buffer (moved) hands out another
+        self.x0 = self.model.zero_embeddings(refresh=refresh_zero, audio_hw=self.audio_hw, image_hw=self.image_hw)
+        self.replay_or_enqueue(self._enqueue, (self.log, self.x0.data_ptr()))
         self.calls += 1
 
     def step(self, A, I, labels, refresh_zero: bool = True) -> Dict[str, torch.Tensor]:
