@@ -1108,6 +1108,41 @@ typedef struct tspm_pattern_head_eval_desc {
 size_t tspm_pattern_head_eval_workspace(int32_t batch, int32_t npat);
 int tspm_pattern_head_eval(const tspm_pattern_head_eval_desc* desc, tspm_stream_t stream);
 
+/* All-pattern MMIMDb fusion (added under ABI 23) — tspm_gmu_fwd for EVERY missing-modality pattern of a batch in one
+ * launch.  In eval mode an encoder's output row depends on that row's input and the weights only, and fc_one / fc_two
+ * each act on one modality, so a zeroed modality is one constant half of the projection buffer: u [batch][ldu] holds
+ * [fc_one(image) | fc_two(text)] of the real inputs, u0 [2d] that of an all-zero input.  For p < npat and b < batch,
+ * row = p*batch + b:
+ *   input[row]  = columns [0, d) of u[b] when keep[2p] != 0, else of u0; columns [d, 2d) by keep[2p + 1] likewise
+ *   h[row], gate[row], z[row] = tspm_gmu_fwd's of that input row  (h [npat*batch][ldh] and gate [npat*batch] nullable:
+ *                               evaluation needs neither and h is three quarters of the writes)
+ * BITWISE what tspm_gmu_fwd writes for the explicitly expanded rows: one 256-thread workgroup per sample (at most 1024
+ * workgroups, each walking its samples) forms tanh(u[b]) and tanh(u0) once in LDS (4d + 4 floats), then runs, per
+ * pattern, tspm_gmu_fwd's own per-thread fmaf chain, block sum and mix.  A row depends on u[b], u0, wz and keep[p]
+ * only — not on batch, npat or the other rows.  Plain loads and stores, no atomics; nothing but the named elements is
+ * written (padding columns keep their content).  keep ([npat][2], the (image, text) flags, non-zero = the real input)
+ * is a HOST array copied into the launch arguments, as in tspm_pattern_expand.  u0 may be NULL when every pattern
+ * keeps both modalities.  TSPM_ERR_INVALID before any launch: batch <= 0, npat outside 1..TSPM_MAX_PATTERNS, a pattern
+ * that keeps nothing, d outside 1..TSPM_GMU_PATTERN_MAX_D (the 64 KiB LDS carve: (4d + 4) floats), ldu < 2d, ldz < d,
+ * ldh < 2d with h given, a NULL among keep / u / wz / z, a NULL u0 with a dropped modality. */
+#define TSPM_GMU_PATTERN_MAX_D 4095
+int tspm_gmu_pattern_fwd(int32_t batch, int32_t npat, const int32_t* keep, int32_t d, const float* u, int32_t ldu,
+                         const float* u0, const float* wz, float* h, int32_t ldh, float* gate, float* z, int32_t ldz,
+                         tspm_stream_t stream);
+/* tspm_bce_logits for every pattern of a batch in one call (added under ABI 23; no gradient): logits
+ * [npat*batch][classes] (row p*batch + b), targets [batch][classes] shared by the patterns (not replicated).  Workgroup
+ * p runs tspm_bce_logits' code on its row slice: loss[p] and stats[p] (stats [npat][3 + 3*classes], tspm_bce_logits'
+ * layout, ACCUMULATED into; nullable) are BITWISE what npat calls of tspm_bce_logits on the slices leave.  Then, once
+ * per call and when counters (int64 {entries, samples}) is given, a one-thread launch writes
+ * loss_log[counters[0] + p] = loss[p] for every p with that index below log_capacity (loss_log nullable) and adds
+ * npat to counters[0] and npat*batch to counters[1] — tspm_pattern_head_eval's log semantics.  No floating-point
+ * atomics; two calls on the same inputs are bitwise equal.  TSPM_ERR_INVALID before any launch: batch <= 0, npat
+ * outside 1..TSPM_MAX_PATTERNS, classes <= 0, a NULL among logits / targets / loss, loss_log without counters,
+ * log_capacity < 0. */
+int tspm_bce_logits_patterns(int32_t batch, int32_t npat, int32_t classes, const float* logits, const float* targets,
+                             float grad_scale, float threshold, float* loss, float* stats, float* loss_log,
+                             int64_t* counters, int64_t log_capacity, tspm_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Monomodal pre-training head (ABI 23) — train_monomodal.MonomodalEncoder's `classifier = nn.Linear(hid,
  * classes)` forward, the loss group's weighted cross-entropy, the argmax(logits, 1) predictions

@@ -211,6 +211,15 @@ def pattern_head_eval_supported(in_: int, w_audio: int, hidden: int, hidden2: in
     return floats * 4 <= 160 * 1024
 
 
+GMU_PATTERN_MAX_D = 4095  # TSPM_GMU_PATTERN_MAX_D: (4d + 4) floats of LDS within 64 KiB
+
+
+def gmu_pattern_supported(d: int, npat: int) -> bool:
+    """Python mirror of tspm_gmu_pattern_fwd's shape checks: False = the call would return TSPM_ERR_INVALID for this
+    GMU width and pattern count whatever the pointers."""
+    return 1 <= int(d) <= GMU_PATTERN_MAX_D and 1 <= int(npat) <= MAX_PATTERNS
+
+
 REGRESS_L1, REGRESS_MSE = 0, 1
 REGRESS_STATS_WORDS = 66  # sizeof(tspm_regress_stats) / 8
 
@@ -436,6 +445,11 @@ _SIGS = {
     # added under ABI 23: AVMNIST's eval head + cross-entropy + classification log for every pattern of a batch
     "tspm_pattern_head_eval_workspace": (c_size_t, [c_int32, c_int32]),
     "tspm_pattern_head_eval": (c_int32, [POINTER(PatternHeadEvalDesc), _P]),
+    # added under ABI 23: MMIMDb's GMU and BCEWithLogits for every pattern of a batch
+    "tspm_gmu_pattern_fwd": (c_int32, [c_int32, c_int32, POINTER(c_int32), c_int32, _P, c_int32, _P, _P, _P, c_int32,
+                                       _P, _P, c_int32, _P]),
+    "tspm_bce_logits_patterns": (c_int32, [c_int32, c_int32, c_int32, _P, _P, c_float, c_float, _P, _P, _P, _P,
+                                           c_int64, _P]),
 }
 
 EXPORTED = tuple(_SIGS)

@@ -7,7 +7,9 @@
 //     gradient in half, as ATen's derivative of maximum does);
 //   * BCEWithLogitsLoss(mean) (experiment_utils/loss.py:52) with on-device multilabel counts for the
 //     f1_{samples,macro,weighted,micro} metrics of configs/mmimdb/centralised/mmimdb_baseline.yaml
-//     (prediction = sigmoid(x) > threshold, models/mmimdb.py:236-237).
+//     (prediction = sigmoid(x) > threshold, models/mmimdb.py:236-237);
+//   * the GMU forward and that loss for every missing-modality pattern of a batch in one call each
+//     (k_gmu_pattern_fwd, k_bce_logits_patterns: bitwise the per-row / per-pattern kernels above).
 // Every kernel is HBM/latency bound (a few hundred KB per launch); rows map to workgroups so the
 // row reductions are wave shuffles + one LDS step in a fixed order (deterministic).
 #include "common.h"
@@ -16,6 +18,7 @@ namespace {
 
 constexpr int kRowThreads = 256;
 constexpr int kLossThreads = 1024;
+constexpr int kGmuPatternGrid = 1024;  // k_gmu_pattern_fwd: at most this many workgroups, each walking its samples
 
 // Block-wide sum in a fixed order: wave shuffle tree, then wave 0 adds the 4 wave totals.
 template <int NT = kRowThreads>
@@ -135,12 +138,12 @@ __global__ __launch_bounds__(256) void k_maxout_bwd(int n, int d, const float* _
   }
 }
 
-// Single workgroup: loss (mean over n*c), dlogits, and the metric counts.
-__global__ __launch_bounds__(kLossThreads) void k_bce_logits(int n, int c, const float* __restrict__ x,
-                                                            const float* __restrict__ t, float* __restrict__ loss,
-                                                            float* __restrict__ dx, float grad_scale, float threshold,
-                                                            float* __restrict__ stats) {
-  __shared__ float red[kLossThreads / 64];
+// One workgroup's BCEWithLogits over n rows: loss (mean over n*c), dlogits, and the metric counts.  The body of
+// k_bce_logits (the whole batch) and of k_bce_logits_patterns (one pattern's row slice per workgroup): one
+// statement list, so both sum and contract alike.
+TSPM_DEV void bce_logits_rows(int n, int c, const float* __restrict__ x, const float* __restrict__ t,
+                              float* __restrict__ loss, float* __restrict__ dx, float grad_scale, float threshold,
+                              float* __restrict__ stats, float* red) {
   const long long total = (long long)n * c;
   const float inv = 1.f / (float)total;
   float acc = 0.f;
@@ -190,6 +193,87 @@ __global__ __launch_bounds__(kLossThreads) void k_bce_logits(int n, int c, const
     stats[3 + 3 * k] += tp;
     stats[4 + 3 * k] += fp;
     stats[5 + 3 * k] += fn;
+  }
+}
+
+// Single workgroup: the whole batch.
+__global__ __launch_bounds__(kLossThreads) void k_bce_logits(int n, int c, const float* __restrict__ x,
+                                                            const float* __restrict__ t, float* __restrict__ loss,
+                                                            float* __restrict__ dx, float grad_scale, float threshold,
+                                                            float* __restrict__ stats) {
+  __shared__ float red[kLossThreads / 64];
+  bce_logits_rows(n, c, x, t, loss, dx, grad_scale, threshold, stats, red);
+}
+
+// Every missing-modality pattern of a batch: workgroup p runs k_bce_logits' code on rows [p*n, (p+1)*n) of x against
+// the n target rows all patterns share, into loss[p] and stats[p] (3 + 3c floats each).
+__global__ __launch_bounds__(kLossThreads) void k_bce_logits_patterns(int n, int c, const float* __restrict__ x,
+                                                                     const float* __restrict__ t,
+                                                                     float* __restrict__ loss, float grad_scale,
+                                                                     float threshold, float* __restrict__ stats) {
+  __shared__ float red[kLossThreads / 64];
+  const long long p = blockIdx.x;
+  bce_logits_rows(n, c, x + p * n * c, t, loss + p, nullptr, grad_scale, threshold,
+                  stats ? stats + p * (3 + 3 * c) : nullptr, red);
+}
+
+// The loss log of one all-pattern call (tspm_pattern_head_eval's semantics): P entries in pattern order, then the
+// counters.  One thread; runs after k_bce_logits_patterns in the same stream.
+__global__ __launch_bounds__(64) void k_pattern_loss_log(int npat, long long rows, const float* __restrict__ loss,
+                                                         float* __restrict__ loss_log, long long* __restrict__ counters,
+                                                         long long cap) {
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  const long long base = counters[0];
+  if (loss_log)
+    for (int p = 0; p < npat; ++p)
+      if (base + p >= 0 && base + p < cap) loss_log[base + p] = loss[p];
+  counters[0] = base + npat;
+  counters[1] += rows;
+}
+
+// tspm_gmu_fwd for every missing-modality pattern of a batch.  u [batch, ldu] holds the projections of the real
+// inputs, u0 [2d] those of an all-zero input (one constant row in eval mode); row p*batch + b takes its image half
+// (columns [0, d)) from u[b] or u0 and its text half likewise.  One workgroup per sample (walking samples above the
+// grid cap): tanh(u[b]) and tanh(u0) once into LDS, then per pattern k_gmu_fwd's own fmaf chain over
+// j = tid, tid + 256, ..., its block_sum and its mix line — so every row is bitwise what k_gmu_fwd writes for the
+// explicitly expanded row.  LDS: 4d + 4 floats.
+struct GmuPatternSet {
+  int keep[TSPM_MAX_PATTERNS];  // bit 0: the image half comes from u[b], bit 1: the text half
+};
+
+__global__ __launch_bounds__(kRowThreads) void k_gmu_pattern_fwd(int batch, int npat, GmuPatternSet ps, int d,
+                                                                 const float* __restrict__ u, int ldu,
+                                                                 const float* __restrict__ u0,
+                                                                 const float* __restrict__ wz, float* __restrict__ h,
+                                                                 int ldh, float* __restrict__ gate,
+                                                                 float* __restrict__ z, int ldz) {
+  extern __shared__ __attribute__((aligned(16))) float gmu_lds[];  // no static LDS in this kernel: the base stays aligned
+  float* th = gmu_lds;           // tanh(u[b])  [2d]
+  float* th0 = gmu_lds + 2 * d;  // tanh(u0)    [2d]
+  float* red = gmu_lds + 4 * d;  // block_sum's wave totals
+  for (int j = threadIdx.x; j < 2 * d; j += kRowThreads) th0[j] = u0 ? tanhf(u0[j]) : 0.f;
+  for (int b = blockIdx.x; b < batch; b += gridDim.x) {
+    const float* ur = u + (long long)b * ldu;
+    for (int j = threadIdx.x; j < 2 * d; j += kRowThreads) th[j] = tanhf(ur[j]);
+    __syncthreads();
+    for (int p = 0; p < npat; ++p) {
+      const float* h1 = (ps.keep[p] & 1) ? th : th0;
+      const float* h2 = ((ps.keep[p] & 2) ? th : th0) + d;
+      const long long r = (long long)p * batch + b;
+      float s = 0.f;
+      for (int j = threadIdx.x; j < 2 * d; j += kRowThreads) {
+        const float t = j < d ? h1[j] : h2[j - d];
+        if (h) h[r * ldh + j] = t;
+        s = fmaf(wz[j], t, s);
+      }
+      s = block_sum(s, red);
+      const float g = 1.f / (1.f + expf(-s));
+      if (gate && threadIdx.x == 0) gate[r] = g;
+      const float g1 = 1.f - g;
+      float* zr = z + r * ldz;
+      for (int j = threadIdx.x; j < d; j += kRowThreads) zr[j] = g * h1[j] + g1 * h2[j];
+    }
+    __syncthreads();  // every wave is done with th before the next sample overwrites it
   }
 }
 
@@ -897,6 +981,43 @@ extern "C" int tspm_bce_logits(int32_t n, int32_t classes, const float* logits, 
   if (n <= 0 || classes <= 0 || !logits || !targets || !loss) return TSPM_ERR_INVALID;
   hipLaunchKernelGGL(k_bce_logits, dim3(1), dim3(kLossThreads), 0, static_cast<hipStream_t>(stream), n, classes, logits,
                      targets, loss, dlogits, grad_scale, threshold, stats);
+  TSPM_LAUNCH_CHECK();
+  return TSPM_OK;
+}
+
+extern "C" int tspm_bce_logits_patterns(int32_t batch, int32_t npat, int32_t classes, const float* logits,
+                                        const float* targets, float grad_scale, float threshold, float* loss,
+                                        float* stats, float* loss_log, int64_t* counters, int64_t log_capacity,
+                                        tspm_stream_t stream) {
+  if (batch <= 0 || npat < 1 || npat > TSPM_MAX_PATTERNS || classes <= 0 || !logits || !targets || !loss)
+    return TSPM_ERR_INVALID;
+  if (log_capacity < 0 || (loss_log && !counters)) return TSPM_ERR_INVALID;
+  hipLaunchKernelGGL(k_bce_logits_patterns, dim3(npat), dim3(kLossThreads), 0, static_cast<hipStream_t>(stream), batch,
+                     classes, logits, targets, loss, grad_scale, threshold, stats);
+  TSPM_LAUNCH_CHECK();
+  if (counters) {
+    hipLaunchKernelGGL(k_pattern_loss_log, dim3(1), dim3(64), 0, static_cast<hipStream_t>(stream), npat,
+                       (long long)npat * batch, loss, loss_log, reinterpret_cast<long long*>(counters),
+                       (long long)log_capacity);
+    TSPM_LAUNCH_CHECK();
+  }
+  return TSPM_OK;
+}
+
+extern "C" int tspm_gmu_pattern_fwd(int32_t batch, int32_t npat, const int32_t* keep, int32_t d, const float* u,
+                                    int32_t ldu, const float* u0, const float* wz, float* h, int32_t ldh, float* gate,
+                                    float* z, int32_t ldz, tspm_stream_t stream) {
+  if (batch <= 0 || npat < 1 || npat > TSPM_MAX_PATTERNS || d <= 0 || d > TSPM_GMU_PATTERN_MAX_D)
+    return TSPM_ERR_INVALID;
+  if (!keep || !u || !wz || !z || ldu < 2 * d || ldz < d || (h && ldh < 2 * d)) return TSPM_ERR_INVALID;
+  GmuPatternSet ps{};
+  for (int p = 0; p < npat; ++p) {
+    ps.keep[p] = (keep[2 * p] ? 1 : 0) | (keep[2 * p + 1] ? 2 : 0);
+    if (ps.keep[p] == 0 || (ps.keep[p] != 3 && !u0)) return TSPM_ERR_INVALID;
+  }
+  const size_t lds = (size_t)(4 * d + 4) * sizeof(float);
+  hipLaunchKernelGGL(k_gmu_pattern_fwd, dim3(batch < kGmuPatternGrid ? batch : kGmuPatternGrid), dim3(kRowThreads), lds,
+                     static_cast<hipStream_t>(stream), batch, npat, ps, d, u, ldu, u0, wz, h, ldh, gate, z, ldz);
   TSPM_LAUNCH_CHECK();
   return TSPM_OK;
 }

@@ -16,14 +16,21 @@ BCEWithLogits = ``tspm_gmu_*``, ``tspm_maxout_*``, ``tspm_bce_logits``, Adam = `
 ``FusedMMIMDbStep`` captures forward + loss + backward + Adam in one HIP graph.  No CPU or ATen
 fallback: a CPU tensor raises ``TspmError``.
 
+Evaluation of every missing-modality pattern of a batch from ONE encoder pass (opt-in): the fusion's two
+projections each act on one modality, so in eval mode a zeroed modality is one constant half-row of the projection
+buffer — ``MMIMDb.zero_projections`` / ``forward_patterns``, ``FusedMMIMDbPatternEvalStep`` (``tspm_gmu_pattern_fwd`` +
+``tspm_bce_logits_patterns``, or the same result from existing launches), ``evaluate_patterns``,
+``fit_mmimdb(fuse_patterns=True)``.
+
 Supported configuration = the reference's MMIMDb configs: GMU fusion or ``multimodal_pooling``
 (``MultimodalPooling``, models/pooling.py: max / avg / sum / attention / gated; ``tspm_pool_*``),
 MaxOut with 2 units and no bias, Dropout 0.5, biasless GMU.
 """
 from __future__ import annotations
 
+import ctypes
 import os
-from typing import Any, Dict, List, Optional
+from typing import Any, Dict, List, Optional, Tuple
 
 import torch
 from torch import nn
@@ -191,6 +198,40 @@ class MMIMDbEngine:
         if n < 2:
             raise L.TspmError("BatchNorm1d in training mode needs more than one sample per batch")
         self.model, self.n, self.dev = model, n, device
+        self._configure(model)
+        f = dict(device=device, dtype=torch.float32)
+        e, d, h, c = self.e, self.d, self.h, self.c
+        z = lambda *s: torch.zeros(*s, **f)
+        self.I, self.T, self.labels = z(n, self.di), z(n, self.dt), z(n, c)
+        self.XnI, self.XnT, self.EI, self.ET = z(n, self.di), z(n, self.dt), z(n, e), z(n, e)
+        self.U, self.H, self.gate, self.Z, self.Zn = z(n, 2 * d), z(n, 2 * d), z(n), z(n, d), z(n, d)
+        self.A1, self.Y1, self.Y1n = z(n, 2 * h), z(n, h), z(n, h)
+        self.A2, self.Y2, self.Y2n = z(n, 2 * h), z(n, h), z(n, h)
+        self.logits, self.loss, self.dlogits = z(n, c), z(1), z(n, c)
+        self.dY2n, self.dY2, self.dA2, self.dY1n, self.dY1, self.dA1 = z(n, h), z(n, h), z(n, 2 * h), z(n, h), \
+            z(n, h), z(n, 2 * h)
+        self.dZn, self.dZ, self.dU, self.ds = z(n, d), z(n, d), z(n, 2 * d), z(n)
+        self.dEI, self.dET = z(n, e), z(n, e)
+        if self.pool is not None:  # U = [proj_a | proj_b], TU = tanh(U), H = dropout(TU) = [a | b]
+            hd = self.hd
+            self.TU, self.Hpre, self.Hh, self.wts = z(n, 2 * d), z(n, hd), z(n, hd), z(n, 2)
+            self.dAB2, self.dS, self.dHpre = z(n, 2 * d), z(n, 2), z(n, hd)
+            self.keep_pool = torch.ones(n, 2 * d, dtype=torch.uint8, device=device)
+            self.pool_keep_override: Optional[torch.Tensor] = None
+        self.dXn, self.dXnT = z(n, self.di), z(n, self.dt)
+        # one stream: the text branch on a side stream measured 0.4385 vs 0.4278 ms at batch 256, 0.373 vs
+        # 0.365 at 128, 0.859 vs 0.876 at 1024 — the two stream edges cost about what the overlap saves
+        self.side = None
+        self.keep = torch.ones(2, n, h, dtype=torch.uint8, device=device)
+        widths = (self.di, self.dt, d, h)
+        self.stat = {k: (z(w), z(w)) for k, w in zip(("i", "t", "b0", "b1", "b2"), widths + (h,))}
+        self.stats = z(3 + 3 * c)
+        self._plan_encoder_splits()
+        self.keep_override: Optional[torch.Tensor] = None
+        self.rng_ctr_ptr: Optional[int] = None
+
+    def _configure(self, model: "MMIMDb") -> None:
+        """The model's widths (di, dt, e, d, h, c, the pooling's hd) and the configuration checks."""
         ie, te, gmu, clf = model.image_model, model.text_model, model.fusion_module, model.mm_mlp
         self.di, self.dt = ie.net[0].num_features, te.net[0].num_features
         self.e = ie.net[1].out_features
@@ -219,43 +260,17 @@ class MMIMDbEngine:
         for c in (self.di, self.dt, self.d, self.h):
             if c % 4:
                 raise L.TspmError("MMIMDb HIP engine: feature widths must be multiples of 4")
-        f = dict(device=device, dtype=torch.float32)
-        e, d, h, c = self.e, self.d, self.h, self.c
-        z = lambda *s: torch.zeros(*s, **f)
-        self.I, self.T, self.labels = z(n, self.di), z(n, self.dt), z(n, c)
-        self.XnI, self.XnT, self.EI, self.ET = z(n, self.di), z(n, self.dt), z(n, e), z(n, e)
-        self.U, self.H, self.gate, self.Z, self.Zn = z(n, 2 * d), z(n, 2 * d), z(n), z(n, d), z(n, d)
-        self.A1, self.Y1, self.Y1n = z(n, 2 * h), z(n, h), z(n, h)
-        self.A2, self.Y2, self.Y2n = z(n, 2 * h), z(n, h), z(n, h)
-        self.logits, self.loss, self.dlogits = z(n, c), z(1), z(n, c)
-        self.dY2n, self.dY2, self.dA2, self.dY1n, self.dY1, self.dA1 = z(n, h), z(n, h), z(n, 2 * h), z(n, h), \
-            z(n, h), z(n, 2 * h)
-        self.dZn, self.dZ, self.dU, self.ds = z(n, d), z(n, d), z(n, 2 * d), z(n)
-        self.dEI, self.dET = z(n, e), z(n, e)
-        if self.pool is not None:  # U = [proj_a | proj_b], TU = tanh(U), H = dropout(TU) = [a | b]
-            hd = self.hd
-            self.TU, self.Hpre, self.Hh, self.wts = z(n, 2 * d), z(n, hd), z(n, hd), z(n, 2)
-            self.dAB2, self.dS, self.dHpre = z(n, 2 * d), z(n, 2), z(n, hd)
-            self.keep_pool = torch.ones(n, 2 * d, dtype=torch.uint8, device=device)
-            self.pool_keep_override: Optional[torch.Tensor] = None
-        self.dXn, self.dXnT = z(n, self.di), z(n, self.dt)
-        # one stream: the text branch on a side stream measured 0.4385 vs 0.4278 ms at batch 256, 0.373 vs
-        # 0.365 at 128, 0.859 vs 0.876 at 1024 — the two stream edges cost about what the overlap saves
-        self.side = None
-        self.keep = torch.ones(2, n, h, dtype=torch.uint8, device=device)
-        widths = (self.di, self.dt, d, h)
-        self.stat = {k: (z(w), z(w)) for k, w in zip(("i", "t", "b0", "b1", "b2"), widths + (h,))}
-        self.stats = z(3 + 3 * c)
-        # split-K for the long encoder Linear when its output tiles cannot fill the chip
+
+    def _plan_encoder_splits(self) -> None:
+        """Split-K for the long encoder Linear when its output tiles cannot fill the chip, and its workspace."""
+        n, e = self.n, self.e
         self.enc_splits = 4
         tiles = -(-n // 32) * -(-e // 32)
         if self.di < 2048 or tiles >= 256:
             self.enc_splits = 1
         wsb = L.lib().tspm_linear_fwd_splitk_workspace(n, self.di, e, self.enc_splits) if self.enc_splits > 1 else 0
-        self.ws = torch.zeros(max(int(wsb) // 4, 4), **f)
+        self.ws = torch.zeros(max(int(wsb) // 4, 4), device=self.dev, dtype=torch.float32)
         self.ws_bytes = self.ws.numel() * 4
-        self.keep_override: Optional[torch.Tensor] = None
-        self.rng_ctr_ptr: Optional[int] = None
 
     @staticmethod
     def _adjacent(mo: MaxOut) -> bool:
@@ -336,13 +351,24 @@ class MMIMDbEngine:
 
     # -- forward ------------------------------------------------------------------------------------
     def forward(self, sh: int, train: bool) -> None:
-        lib = L.lib()
-        m = self.model
-        n, e, d, h, c = self.n, self.e, self.d, self.h, self.c
-        ie, te, gmu, net = m.image_model.net, m.text_model.net, m.fusion_module, m.mm_mlp.net
+        """The whole forward: its three parts in order (the all-pattern eval step runs them at different row
+        counts, on two engines)."""
+        self.forward_encoders(sh, train)
+        self.forward_fusion(sh, train)
+        self.forward_classifier(sh, train)
+
+    def _bn_fn(self, sh: int, train: bool):
         bn_s = (lambda k, mod, x, w, o, st: self._bn_train(k, mod, x, w, o, st)) if train else \
             (lambda k, mod, x, w, o, st: self._bn_eval(mod, x, w, o, st))
-        bn = lambda k, mod, x, w, o: bn_s(k, mod, x, w, o, sh)
+        return bn_s, (lambda k, mod, x, w, o: bn_s(k, mod, x, w, o, sh))
+
+    def forward_encoders(self, sh: int, train: bool) -> None:
+        """I, T → the fusion's projection buffer U = [fc_one(image) | fc_two(text)] (proj_a | proj_b)."""
+        lib = L.lib()
+        m = self.model
+        n, e, d = self.n, self.e, self.d
+        ie, te, gmu = m.image_model.net, m.text_model.net, m.fusion_module
+        bn_s, bn = self._bn_fn(sh, train)
         # encoders: BatchNorm1d → Linear (models/mmimdb.py:78-93), then the GMU projections into
         # U = [fc_one | fc_two]; the text branch runs on the side stream (joined before the gate)
         pairs = _PAIRS and self.side is None
@@ -379,12 +405,25 @@ class MMIMDbEngine:
                 L.check(lib.tspm_linear_fwd(n, e, d, self.EI.data_ptr(), e, gmu.fc_one.weight.data_ptr(), None, 0,
                                             None, 1.0, self.U.data_ptr(), 2 * d, sh), "gmu fc_one")
             self._join()
+        if self.pool is not None:
+            self._pool_proj(sh)
+
+    def forward_fusion(self, sh: int, train: bool) -> None:
+        """U → Z: the GMU, or the pooling after its projections."""
+        n, d = self.n, self.d
         if self.pool is None:
-            L.check(lib.tspm_gmu_fwd(n, d, self.U.data_ptr(), 2 * d, gmu.hidden_sigmoid.weight.data_ptr(),
-                                     self.H.data_ptr(), 2 * d, self.gate.data_ptr(), self.Z.data_ptr(), d, sh), "gmu")
+            L.check(L.lib().tspm_gmu_fwd(n, d, self.U.data_ptr(), 2 * d,
+                                         self.model.fusion_module.hidden_sigmoid.weight.data_ptr(), self.H.data_ptr(),
+                                         2 * d, self.gate.data_ptr(), self.Z.data_ptr(), d, sh), "gmu")
         else:
-            self._pool_fwd(sh, train)
-        # classifier (models/mmimdb.py:38-47)
+            self._pool_mix(sh, train)
+
+    def forward_classifier(self, sh: int, train: bool) -> None:
+        """Z → logits (models/mmimdb.py:38-47)."""
+        lib = L.lib()
+        n, d, h, c = self.n, self.d, self.h, self.c
+        net = self.model.mm_mlp.net
+        _, bn = self._bn_fn(sh, train)
         keep, k1, k2, scale = None, None, None, 1.0
         # in-launch masks: each MaxOut forward draws its half of the mask tspm_dropout_mask would write
         rng = train and self.p > 0 and self.keep_override is None and _RNG_INLAUNCH
@@ -414,16 +453,21 @@ class MMIMDbEngine:
 
     _POOL_SEED_MIX = 0x5DEECE66D  # the pooling dropout's stream, distinct from the classifier's
 
-    def _pool_fwd(self, sh: int, train: bool) -> None:
-        """MultimodalPooling (models/pooling.py:81-127): [proj_a | proj_b] (+ biases) → tanh → dropout →
-        max / avg / sum, or the attention / gate scoring MLP → softmax / sigmoid mix."""
+    def _pool_proj(self, sh: int) -> None:
+        """MultimodalPooling (models/pooling.py:81-127), first half: U = [proj_a | proj_b] (+ biases)."""
         lib, pl = L.lib(), self.pool
-        n, e, d, hd = self.n, self.e, self.d, self.hd
+        n, e, d = self.n, self.e, self.d
         L.check(lib.tspm_linear_fwd(n, e, d, self.EI.data_ptr(), e, pl.proj_a.weight.data_ptr(),
                                     pl.proj_a.bias.data_ptr(), 0, None, 1.0, self.U.data_ptr(), 2 * d, sh), "proj_a")
         L.check(lib.tspm_linear_fwd(n, e, d, self.ET.data_ptr(), e, pl.proj_b.weight.data_ptr(),
                                     pl.proj_b.bias.data_ptr(), 0, None, 1.0, self.U.data_ptr() + d * 4, 2 * d, sh),
                 "proj_b")
+
+    def _pool_mix(self, sh: int, train: bool) -> None:
+        """... second half: U → tanh → dropout → max / avg / sum, or the attention / gate scoring MLP → softmax /
+        sigmoid mix."""
+        lib, pl = L.lib(), self.pool
+        n, d, hd = self.n, self.d, self.hd
         keep, scale = None, 1.0
         if train and self.pool_p > 0:
             scale = 1.0 / (1.0 - self.pool_p)
@@ -444,7 +488,7 @@ class MMIMDbEngine:
                                       self.Z.data_ptr(), d, sh), "pool mix")
 
     def _pool_bwd(self, sh: int) -> None:
-        """Backward of _pool_fwd: dZ → d[a | b] (+ the scoring MLP's gradients) → dU."""
+        """Backward of _pool_proj + _pool_mix: dZ → d[a | b] (+ the scoring MLP's gradients) → dU."""
         lib, pl = L.lib(), self.pool
         n, d, hd = self.n, self.d, self.hd
         kind, sc = pl.kind, pl.scorer()
@@ -547,6 +591,44 @@ class MMIMDbEngine:
         self._join()
 
 
+class MMIMDbEvalEngine(MMIMDbEngine):
+    """The eval-mode forward alone (running statistics, no dropout): ``MMIMDbEngine``'s ``forward_*`` parts with the
+    buffers of the parts asked for and nothing of the backward, for any ``n >= 1`` — eval mode needs no batch
+    statistics.  ``parts``: "encoders" (I, T → U), "fusion" (U → Z), "classifier" (Z → logits); the all-pattern step
+    runs the first over the B real rows and the other two over the P·B (pattern, sample) rows, on two engines."""
+
+    def __init__(self, model: "MMIMDb", n: int, device: torch.device,
+                 parts=("encoders", "fusion", "classifier")):
+        if n < 1:
+            raise L.TspmError("MMIMDbEvalEngine: at least one row")
+        self.model, self.n, self.dev = model, n, device
+        self._configure(model)
+        e, d, h, c = self.e, self.d, self.h, self.c
+        z = lambda *s: torch.zeros(*s, device=device, dtype=torch.float32)  # noqa: E731
+        self.side = None
+        if "encoders" in parts:
+            self.I, self.T = z(n, self.di), z(n, self.dt)
+            self.XnI, self.XnT, self.EI, self.ET = z(n, self.di), z(n, self.dt), z(n, e), z(n, e)
+            self._plan_encoder_splits()
+        if "encoders" in parts or "fusion" in parts:
+            self.U = z(n, 2 * d)
+        if "fusion" in parts:
+            self.H = z(n, 2 * d)
+            if self.pool is None:
+                self.gate = z(n)
+            else:
+                self.TU, self.Hpre, self.Hh, self.wts = z(n, 2 * d), z(n, self.hd), z(n, self.hd), z(n, 2)
+        if "fusion" in parts or "classifier" in parts:
+            self.Z = z(n, d)
+        if "classifier" in parts:
+            self.Zn = z(n, d)
+            self.A1, self.Y1, self.Y1n = z(n, 2 * h), z(n, h), z(n, h)
+            self.A2, self.Y2, self.Y2n = z(n, 2 * h), z(n, h), z(n, h)
+            self.logits = z(n, c)
+        self.keep_override = None
+        self.rng_ctr_ptr = None
+
+
 # ------------------------------------------------------------------------------------------------
 # the model
 # ------------------------------------------------------------------------------------------------
@@ -618,6 +700,51 @@ class MMIMDb(nn.Module):
             nbt = shared_batches_tracked(self, I.device, (nn.BatchNorm1d,))
             L.counters_add(nbt)
         return eng.logits.clone()
+
+    # -- every missing-modality pattern of a batch from one encoder pass --------------------------------
+    def _apply(self, fn, *args, **kwargs):
+        out = super()._apply(fn, *args, **kwargs)
+        # parameters moved: the zero-input projections and the steps whose graphs read them are bound to the old storage
+        self.__dict__.pop("_zero_proj", None)
+        self.__dict__.pop("_pattern_steps", None)
+        return out
+
+    def zero_projections(self, refresh: bool = True) -> torch.Tensor:
+        """``[2d]``: the fusion's projection row ``[fc_one(image) | fc_two(text)]`` (``proj_a | proj_b``) of an all-zero
+        input in eval mode — what a pattern that drops a modality feeds the fusion; with BatchNorm1d on its running
+        statistics it is the same row for every sample.  One device buffer per model with a stable address (captured
+        graphs read it), dropped when the parameters move.  ``refresh``: recompute it — the eval-mode encoders and the
+        two projections over a one-row zero batch, the engine's own launches; a new buffer is always filled.  FusedAdam
+        writes parameters through raw pointers, so nothing here can tell whether the weights changed: callers refresh
+        unless they know they did not (inside one evaluation epoch)."""
+        dev = next(self.parameters()).device
+        eng = self.__dict__.get("_zero_proj")
+        if eng is None or eng.dev != dev:
+            eng = MMIMDbEvalEngine(self, 1, dev, parts=("encoders",))  # I and T stay zero
+            self.__dict__["_zero_proj"] = eng
+            refresh = True
+        if refresh:
+            eng.forward_encoders(L.stream_handle(), False)
+        return eng.U[0]
+
+    def pattern_eval_step_for(self, loss_functions, batch: int, patterns=None,
+                              fusion: Optional[str] = None) -> "FusedMMIMDbPatternEvalStep":
+        """The cached FusedMMIMDbPatternEvalStep for (patterns, fusion leg, loss weight, batch size)."""
+        key = (norm_mmimdb_patterns(patterns), fusion or DEFAULT_PATTERN_FUSION, _bce_weight(loss_functions), batch)
+        cache = self.__dict__.setdefault("_pattern_steps", {})
+        st = cache.get(key)
+        if st is None:
+            st = cache[key] = FusedMMIMDbPatternEvalStep(self, loss_functions, batch, patterns=key[0], fusion=fusion)
+        return st
+
+    @torch.no_grad()
+    def forward_patterns(self, I: torch.Tensor, T: torch.Tensor, patterns=None) -> torch.Tensor:
+        """Eval-mode logits ``[P, B, C]`` of the batch under each of ``patterns`` (default ``("it", "i", "t")``; a subset
+        in any order) from one encoder pass, whatever the mode flag; the zero projections are refreshed first."""
+        dev = next(self.parameters()).device
+        I, T = I.to(dev, non_blocking=True).float(), T.to(dev, non_blocking=True).float()
+        st = self.pattern_eval_step_for(None, I.shape[0], patterns)
+        return st.step(I, T, None, refresh_zero=True)["logits"].clone()
 
     def train_step(self, batch: Dict[str, Any], optimizer, loss_functions, device, metric_recorder=None,
                    epoch: int = 0) -> Dict[str, Any]:
@@ -901,10 +1028,218 @@ def validation_loss(model: MMIMDb, corpus: MMIMDbCorpus, batch: int, weight: flo
     return float(np.mean([float(v) for v in torch.cat(losses).cpu()]))
 
 
+# ------------------------------------------------------------------------------------------------
+# every missing-modality pattern of a batch in one eval pass
+# ------------------------------------------------------------------------------------------------
+MMIMDB_PATTERNS = tuple(PATTERNS)  # ("it", "i", "t")
+
+
+def norm_mmimdb_patterns(patterns=None) -> Tuple[str, ...]:
+    """The patterns of a fused-pattern pass as a tuple of names: all three in ``MMIMDB_PATTERNS`` order by default, or
+    the given subset in the given order.  Unknown names raise ``ValueError``; an empty or repeating selection too."""
+    if patterns is None:
+        return MMIMDB_PATTERNS
+    pats = tuple(str(p) for p in patterns)
+    bad = set(pats) - set(MMIMDB_PATTERNS)
+    if bad:
+        raise ValueError(f"Invalid patterns: {bad}\nValid patterns are: {list(MMIMDB_PATTERNS)}")
+    if not pats or len(set(pats)) != len(pats):
+        raise ValueError(f"patterns: 1..{len(MMIMDB_PATTERNS)} distinct names among {MMIMDB_PATTERNS}, got {pats!r}")
+    return pats
+
+
+# the fusion leg of a FusedMMIMDbPatternEvalStep built without fusion=: "kernel" (tspm_gmu_pattern_fwd +
+# tspm_bce_logits_patterns) or "launches" (the same result from tspm_pattern_expand + tspm_gmu_fwd + per pattern
+# tspm_bce_logits); the leg that measured faster at batch 256 (profiles/mmimdb_patterns.json, DESIGN §3.20)
+DEFAULT_PATTERN_FUSION = "kernel"
+PATTERN_LOG_CAPACITY = 4096  # loss-log entries a step holds before reserve_log grows it
+
+
+class FusedMMIMDbPatternEvalStep(L.GraphRunner):
+    """The eval-mode forward and BCE of EVERY missing-modality pattern of a batch from one encoder pass, as one HIP graph.
+    In eval mode an encoder's output row depends on that row's input and the weights only, and the fusion's two
+    projections each act on one modality, so a zeroed modality is one constant half-row of the projection buffer
+    (``MMIMDb.zero_projections``).  The graph holds (1) the encoders and projections over the B real rows, as
+    ``MMIMDbEngine.forward(train=False)`` issues them, into ``U [B, 2d]``; (2) the fusion over the P·B (pattern, sample)
+    rows; (3) the classifier at n = P·B; (4) the loss per pattern, its F1 counts and its log entries.
+
+    ``fusion="kernel"``: ``tspm_gmu_pattern_fwd`` reads ``U`` and the zero row directly, ``tspm_bce_logits_patterns``
+    takes all patterns.  ``fusion="launches"``: ``tspm_pattern_expand`` copies the selected halves to ``[P·B, 2d]``, then
+    ``tspm_gmu_fwd`` (or the pooling launches), per pattern ``tspm_bce_logits`` and its log entry — the only leg for
+    ``multimodal_pooling`` models and for a width outside ``_lib.gmu_pattern_supported`` (``.fusion`` tells which leg
+    was built), and the A/B leg; on a GMU model the two are bitwise equal.
+
+    ``step(I, T, labels, refresh_zero=True)`` → ``{"loss": [P], "logits": [P, B, C]}`` (views of the static outputs;
+    ``labels=None`` keeps the label buffer).  ``stats [P, 3 + 3C]`` (``tspm_bce_logits``' counts, per pattern),
+    ``loss_log`` and ``counters`` (int64 ``{entries, samples}``) accumulate across steps: the caller zeroes them per
+    epoch (``reset_log``).  Any batch size >= 1."""
+
+    def __init__(self, model: "MMIMDb", loss_functions, batch: int, patterns=None, fusion: Optional[str] = None,
+                 use_graph: bool = True):
+        dev = next(model.parameters()).device
+        if dev.type != "cuda":
+            raise L.TspmError("FusedMMIMDbPatternEvalStep runs on the MI355X: move the model to cuda first")
+        self.model, self.N = model, batch
+        self.weight = _bce_weight(loss_functions)
+        self.patterns = norm_mmimdb_patterns(patterns)
+        self.P = P = len(self.patterns)
+        fusion = DEFAULT_PATTERN_FUSION if fusion is None else fusion
+        if fusion not in ("kernel", "launches"):
+            raise ValueError(f"fusion: 'kernel' or 'launches', got {fusion!r}")
+        self.enc = MMIMDbEvalEngine(model, batch, dev, parts=("encoders",))
+        d, c = self.enc.d, self.enc.c
+        if fusion == "kernel" and (self.enc.pool is not None or not L.gmu_pattern_supported(d, P)):
+            fusion = "launches"
+        self.fusion = fusion
+        self.clf = MMIMDbEvalEngine(model, P * batch, dev,
+                                    parts=("classifier",) if fusion == "kernel" else ("fusion", "classifier"))
+        self._init_graph(use_graph, dev)  # key: the zero row's and the loss log's addresses
+        self.u0 = model.zero_projections(refresh=False)
+        self.labels = torch.zeros(batch, c, device=dev, dtype=torch.float32)
+        self.loss = torch.zeros(P, device=dev, dtype=torch.float32)
+        self.stats = torch.zeros(P, 3 + 3 * c, device=dev, dtype=torch.float32)
+        self.loss_log = torch.zeros(PATTERN_LOG_CAPACITY, device=dev, dtype=torch.float32)
+        self.counters = torch.zeros(2, dtype=torch.int64, device=dev)
+        keep = [tuple(int(v != 0) for v in PATTERNS[p]) for p in self.patterns]  # (image, text) per pattern
+        # host arrays of the launch arguments (read at enqueue time only)
+        self._keep = (ctypes.c_int32 * (2 * P))(*[k for kp in keep for k in kp])
+        if fusion == "launches":
+            # tspm_pattern_expand's layout: rows [0, B) the real projections (the encoders write them), rows [B, 2B)
+            # the zero-input projections of the same rows — here one constant row, broadcast.  The entry point takes
+            # three modality widths: the text half goes in as two pieces under the same keep flag
+            self.U2 = torch.zeros(2 * batch, 2 * d, device=dev, dtype=torch.float32)
+            self.enc.U = self.U2[:batch]
+            self._widths = (d, d // 2, d - d // 2)
+            self._keep3 = (ctypes.c_int32 * (3 * P))(*[k for kp in keep for k in (kp[0], kp[1], kp[1])])
+            self._gid = (ctypes.c_int32 * P)()
+            self._row_tag = torch.zeros(batch, dtype=torch.int32, device=dev)  # the expand's label / group outputs
+            self._row_tags = torch.zeros(2, P * batch, dtype=torch.int32, device=dev)  # are scratch here
+
+    @property
+    def I(self) -> torch.Tensor:
+        return self.enc.I
+
+    @property
+    def T(self) -> torch.Tensor:
+        return self.enc.T
+
+    def reset_log(self) -> None:
+        self.stats.zero_()
+        self.counters.zero_()
+
+    def reserve_log(self, entries: int) -> None:
+        """Room for ``entries`` loss-log entries between two ``reset_log`` calls (a new buffer: the graph re-captures)."""
+        if entries > self.loss_log.numel():
+            self.loss_log = torch.zeros(entries, device=self.loss_log.device, dtype=torch.float32)
+
+    def _fusion_kernel(self, sh: int) -> None:
+        d, gmu = self.enc.d, self.model.fusion_module
+        L.check(L.lib().tspm_gmu_pattern_fwd(self.N, self.P, self._keep, d, self.enc.U.data_ptr(), 2 * d,
+                                             self.u0.data_ptr(), gmu.hidden_sigmoid.weight.data_ptr(), None, 0, None,
+                                             self.clf.Z.data_ptr(), d, sh), "gmu_pattern_fwd")
+
+    def _fusion_launches(self, sh: int) -> None:
+        B, d = self.N, self.enc.d
+        self.U2[B:].copy_(self.u0.expand(B, 2 * d))
+        wi, wt0, wt1 = self._widths
+        L.check(L.lib().tspm_pattern_expand(B, self.P, self._keep3, self._gid, wi, wt0, wt1, self.U2.data_ptr(), 2 * d,
+                                            self.clf.U.data_ptr(), 2 * d, self._row_tag.data_ptr(),
+                                            self._row_tags[0].data_ptr(), 4, self._row_tags[1].data_ptr(), sh),
+                "pattern eval expand")
+        self.clf.forward_fusion(sh, False)
+
+    def _loss_kernel(self, sh: int) -> None:
+        L.check(L.lib().tspm_bce_logits_patterns(self.N, self.P, self.clf.c, self.clf.logits.data_ptr(),
+                                                 self.labels.data_ptr(), self.weight,
+                                                 float(self.model.binary_threshold), self.loss.data_ptr(),
+                                                 self.stats.data_ptr(), self.loss_log.data_ptr(),
+                                                 self.counters.data_ptr(), self.loss_log.numel(), sh),
+                "bce_logits_patterns")
+
+    def _loss_launches(self, sh: int) -> None:
+        lib, B, c = L.lib(), self.N, self.clf.c
+        for p in range(self.P):
+            ls = self.loss[p:p + 1]
+            L.check(lib.tspm_bce_logits(B, c, self.clf.logits[p * B:(p + 1) * B].data_ptr(), self.labels.data_ptr(),
+                                        ls.data_ptr(), None, self.weight, float(self.model.binary_threshold),
+                                        self.stats[p].data_ptr(), sh), "pattern eval bce_with_logits")
+            # the log entry alone: tspm_classify_update over no rows appends *loss and advances the entry counter
+            L.check(lib.tspm_classify_update(0, c, None, None, None, 1, None, None, ls.data_ptr(),
+                                             self.loss_log.data_ptr(), self.counters.data_ptr(),
+                                             self.loss_log.numel(), sh), "pattern eval loss log")
+        L.check(lib.tspm_counters_add(self.counters[1:].data_ptr(), 1, self.P * B, sh), "pattern eval sample count")
+
+    def _enqueue(self) -> None:
+        sh = L.stream_handle()
+        self.enc.forward_encoders(sh, False)
+        if self.fusion == "kernel":
+            self._fusion_kernel(sh)
+        else:
+            self._fusion_launches(sh)
+        self.clf.forward_classifier(sh, False)
+        if self.fusion == "kernel":
+            self._loss_kernel(sh)
+        else:
+            self._loss_launches(sh)
+
+    def run(self, refresh_zero: bool = True) -> None:
+        """Evaluate the batch in the static input buffers under every pattern (logits, loss; stats and log updated)."""
+        # the graph reads the zero row by address: a model that dropped its buffer (moved) hands out another
+        self.u0 = self.model.zero_projections(refresh=refresh_zero)
+        self.replay_or_enqueue(self._enqueue, (self.u0.data_ptr(), self.loss_log.data_ptr()))
+        self.calls += 1
+
+    def step(self, I, T, labels=None, refresh_zero: bool = True) -> Dict[str, torch.Tensor]:
+        for dst, src in ((self.enc.I, I), (self.enc.T, T), (self.labels, labels)):
+            if src is not None and src.data_ptr() != dst.data_ptr():
+                dst.copy_(src.reshape(dst.shape), non_blocking=True)
+        self.run(refresh_zero)
+        return {"loss": self.loss, "logits": self.clf.logits.view(self.P, self.N, self.clf.c)}
+
+
+def evaluate_patterns(model: MMIMDb, corpus: MMIMDbCorpus, batch: int, loss_functions=None, patterns=None,
+                      fusion: Optional[str] = None) -> Dict[str, Any]:
+    """What ``validation_loss`` + one ``_evaluate`` per pattern report, from ONE pass over the validation corpus: each
+    sample is gathered once, unmasked, and a ``FusedMMIMDbPatternEvalStep`` replay evaluates its batch under every
+    pattern (a second step takes the partial last batch, of any size >= 1).  The zero projections are refreshed once
+    (weights do not change inside an evaluation) and the host reads back once, at the end.  Returns ``{"val_loss": the
+    mean of the per-(batch, pattern) fp32 losses, "<pattern>": f1_metrics(...) per pattern}``.  ``val_loss`` is
+    mathematically ``validation_loss``'s value whenever ``batch`` divides the corpus (the same rows under the same
+    patterns in equal-sized batches, grouped differently); otherwise the two differ in how the last batches are cut."""
+    import numpy as np
+    pats = norm_mmimdb_patterns(patterns)
+    P, c = len(pats), model.mm_mlp.output_size
+    sizes = [min(batch, corpus.n - s) for s in range(0, corpus.n, batch)]
+    steps = {n: model.pattern_eval_step_for(loss_functions, n, pats, fusion) for n in set(sizes)}
+    for n, st in steps.items():
+        st.reserve_log(P * sizes.count(n))
+        st.reset_log()
+    fresh = False
+    for k, n in enumerate(sizes):
+        st = steps[n]
+        idx = torch.arange(k * batch, k * batch + n, device=corpus.device)
+        corpus.gather(idx, st.I, st.T, st.labels)
+        st.run(refresh_zero=not fresh)
+        fresh = True
+    order = sorted(steps, reverse=True)
+    flat = torch.cat([t for n in order for t in (steps[n].stats.reshape(-1),
+                                                 steps[n].loss_log[:P * sizes.count(n)])]).cpu()
+    stats, losses, at = torch.zeros(P, 3 + 3 * c, dtype=torch.float64), [], 0
+    for n in order:
+        stats += flat[at:at + P * (3 + 3 * c)].double().view(P, 3 + 3 * c)
+        at += P * (3 + 3 * c)
+        losses += [float(v) for v in flat[at:at + P * sizes.count(n)]]
+        at += P * sizes.count(n)
+    out: Dict[str, Any] = {"val_loss": float(np.mean(losses))}
+    for p, name in enumerate(pats):
+        out[name] = f1_metrics(stats[p], c)
+    return out
+
+
 def fit_mmimdb(model: MMIMDb, optimizer: FusedAdam, train: MMIMDbCorpus, val: MMIMDbCorpus, batch: int,
                epochs: int, loss_functions=None, patience: int = 25, seed: int = 0,
                patterns=("it", "i", "t"), min_delta: float = 1e-3, checkpoint_dir=None,
-               scheduler=None) -> List[Dict[str, Any]]:
+               scheduler=None, fuse_patterns: bool = False) -> List[Dict[str, Any]]:
     """The epoch loop of train_multimodal.py for the MMIMDb config, every batch on the HIP path:
     shuffled train batches over every sample (the DataLoader's drop_last=False, config/data_config.py:121;
     a last batch of one row is skipped — BatchNorm1d in training mode rejects it in the reference too),
@@ -913,7 +1248,11 @@ def fit_mmimdb(model: MMIMDb, optimizer: FusedAdam, train: MMIMDbCorpus, val: MM
     reference's check (harness.check_early_stopping: patience 25 from the YAML, min_delta 1e-3 =
     TrainingConfig.early_stopping_min_delta), ``epoch_{n}.pth`` / ``best.pth`` through
     harness.CheckpointManager on improvement, and ReduceLROnPlateau on the validation loss.
-    Returns one dict per epoch: train loss / f1s, ``val_loss`` and ``val_{pattern}`` metrics."""
+    Returns one dict per epoch: train loss / f1s, ``val_loss`` and ``val_{pattern}`` metrics.
+    ``fuse_patterns=True``: ``evaluate_patterns`` replaces the ``validation_loss`` + ``_evaluate`` loops (each
+    validation sample through the encoders once per epoch instead of six times); ``val_loss`` is then the mean over
+    unshuffled per-(batch, pattern) losses — the same value whenever ``batch`` divides the validation corpus.  History
+    keys, early stopping, checkpoints and the scheduler input are the same."""
     from .harness import CheckpointManager, check_early_stopping
     weight = _bce_weight(loss_functions)
     steps: Dict[int, FusedMMIMDbStep] = {}
@@ -946,10 +1285,16 @@ def fit_mmimdb(model: MMIMDb, optimizer: FusedAdam, train: MMIMDbCorpus, val: MM
         for n, st in steps.items():
             if n != batch:
                 tot += st.eng.stats
-        rec = {"epoch": ep, "train": f1_metrics(tot, model.mm_mlp.output_size),
-               "val_loss": validation_loss(model, val, batch, weight, patterns, vgen)}
-        for p in patterns:
-            rec[f"val_{p}"] = _evaluate(model, val, batch, weight, p)
+        rec = {"epoch": ep, "train": f1_metrics(tot, model.mm_mlp.output_size)}
+        if fuse_patterns:  # one pass over the validation corpus for the monitored loss and every pattern's metrics
+            ev = evaluate_patterns(model, val, batch, loss_functions, patterns)
+            rec["val_loss"] = ev["val_loss"]
+            for p in patterns:
+                rec[f"val_{p}"] = ev[p]
+        else:
+            rec["val_loss"] = validation_loss(model, val, batch, weight, patterns, vgen)
+            for p in patterns:
+                rec[f"val_{p}"] = _evaluate(model, val, batch, weight, p)
         history.append(rec)
         vm = {"loss": rec["val_loss"]}
         is_best, cont, wait = check_early_stopping(vm, best, patience, min_delta, wait)
