@@ -753,6 +753,35 @@ int tspm_bn1d_bwd_pair(int32_t m, int32_t c0, const float* g0, const float* x0, 
                        const float* invstd0, const float* gamma0, float* dgamma0, float* dbeta0, float* dx0,
                        int32_t c1, const float* g1, const float* x1, const float* mean1, const float* invstd1,
                        const float* gamma1, float* dgamma1, float* dbeta1, float* dx1, tspm_stream_t stream);
+/* tspm_bn1d_fwd over a REPLICATED batch, from its m distinct rows (added under ABI 23) — the input BatchNorm1d of an
+ * encoder when every missing-modality pattern of a batch trains in one step: the batch the layer sees holds each row of
+ * x [m, c] `reps` times (the patterns that keep the modality, reps >= 1) and, per row of x, `zero_rows_per_row`
+ * all-zero rows (the patterns that drop it, >= 0), N = m*(reps + zero_rows_per_row) rows in all.  Per channel, with
+ * S = sum_r x[r]:
+ *   mean   = reps*S / N
+ *   M2     = reps*sum_r (x[r] - mean)^2 + zero_rows_per_row*m*mean^2
+ *   invstd = 1/sqrt(M2/N + eps)           (the biased variance normalises)
+ *   running_mean <- (1 - momentum)*running_mean + momentum*mean,  running_var likewise with M2/(N - 1)  (NULL: skipped)
+ *   y[r]   = gamma*(x[r] - mean)*invstd + beta   for r < m
+ *   y[m]   = gamma*(0 - mean)*invstd + beta      — the row every all-zero row normalises to
+ * so y has m + 1 rows ([m + 1, c]; x is read over m rows only) and save_mean / save_invstd [c] hold the replicated
+ * batch's statistics: tspm_bn1d_bwd at m + 1 rows over an input whose row m is zero, with the gradients folded onto
+ * those rows, then gives the replicated batch's dgamma / dbeta.  tspm_bn1d_fwd's kernel structure (one launch, lane =
+ * channel, 32 row groups, two-pass statistics in double, row groups combined in a fixed order, no atomics, no
+ * workspace).  With reps = 1 and zero_rows_per_row = 0, rows [0, m) of y, the saved and the running statistics are
+ * BITWISE tspm_bn1d_fwd's.  The pair form takes two layers over the same m rows in one launch, each half with its own
+ * reps / zero_rows_per_row and bitwise the single call.  TSPM_ERR_INVALID before any launch: m <= 0, c <= 0,
+ * reps < 1, zero_rows_per_row < 0, m*(reps + zero_rows_per_row) < 2, a NULL among x, gamma, beta, save_mean,
+ * save_invstd, y. */
+int tspm_bn1d_fwd_rep(int32_t m, int32_t c, const float* x, const float* gamma, const float* beta,
+                      float* running_mean, float* running_var, float momentum, float eps, float* save_mean,
+                      float* save_invstd, float* y, int32_t reps, int32_t zero_rows_per_row, tspm_stream_t stream);
+int tspm_bn1d_fwd_rep_pair(int32_t m, int32_t c0, const float* x0, const float* gamma0, const float* beta0,
+                           float* running_mean0, float* running_var0, float momentum0, float eps0, float* save_mean0,
+                           float* save_invstd0, float* y0, int32_t reps0, int32_t zero_rows_per_row0, int32_t c1,
+                           const float* x1, const float* gamma1, const float* beta1, float* running_mean1,
+                           float* running_var1, float momentum1, float eps1, float* save_mean1, float* save_invstd1,
+                           float* y1, int32_t reps1, int32_t zero_rows_per_row1, tspm_stream_t stream);
 /* BCEWithLogitsLoss (mean) — LossFunctionGroup{bce_with_logits: w} (experiment_utils/loss.py:52,
  * configs/mmimdb/centralised/mmimdb_baseline.yaml): loss[0] = grad_scale * mean((1-t)*x - logsigmoid(x)),
  * dlogits = (sigmoid(x) - t) * grad_scale / (n*classes) (nullable).  If stats != NULL (3 + 3*classes
@@ -1129,6 +1158,33 @@ int tspm_pattern_head_eval(const tspm_pattern_head_eval_desc* desc, tspm_stream_
 int tspm_gmu_pattern_fwd(int32_t batch, int32_t npat, const int32_t* keep, int32_t d, const float* u, int32_t ldu,
                          const float* u0, const float* wz, float* h, int32_t ldh, float* gate, float* z, int32_t ldz,
                          tspm_stream_t stream);
+/* The adjoint of tspm_gmu_pattern_fwd (added under ABI 23), for training every pattern of a batch in one step: the
+ * gradient of the P*batch fusion rows folded onto batch + 1 projection rows.  dz [npat*batch][lddz] is the gradient of
+ * z; h [npat*batch][ldh] and gate [npat*batch] are what tspm_gmu_pattern_fwd wrote (both required here).  Per row
+ * r = p*batch + b, with (ds_r, du_r[2d]) = what tspm_gmu_bwd computes for that row:
+ *   ds[r]                  = ds_r   (the gate weight gradient stays tspm_linear_bwd_weight over the npat*batch rows)
+ *   du[b][half]            = sum over the p that keep the half's modality of du_r[half]          (b < batch)
+ *   du[batch][half]        = sum over every b and every p that drops the half's modality of du_r[half]
+ * half = columns [0, d) (image, keep[2p]) or [d, 2d) (text, keep[2p + 1]); du [batch + 1][lddu].  Row batch is the
+ * gradient of the one projection row every all-zero input shares (tspm_gmu_pattern_fwd's u0).  A slot no pattern uses
+ * is written +0.0 (every pattern keeps both modalities: row batch is all +0.0).
+ * Two launches.  (1) One 256-thread workgroup per sample (G = min(batch, 1024) workgroups, workgroup g walking samples
+ * g, g + G, ...): per pattern tspm_gmu_bwd's per-thread fmaf chain, block sum and element expressions; a thread owns
+ * columns tid, tid + 256, ... of both halves and keeps their sums in registers.  Order of every sum, all plain fp32 adds
+ * from +0.0: du[b] over p ascending; workgroup g's zero-row partial over its samples b ascending and, within a sample,
+ * p ascending.  The partials go to workspace [G][2d].  (2) Column c of du[batch] = ((s0 + s1) + s2) + s3 with s_q the
+ * sum over g = q, q + 4, q + 8, ... ascending of partial g.  No floating-point atomics, no inter-workgroup hand-off
+ * inside a launch; two calls on the same inputs are bitwise equal; rows b < batch depend on sample b's rows, wz and
+ * keep only.  Nothing but the named elements is written (padding columns keep their content).  keep is a HOST array as
+ * in tspm_gmu_pattern_fwd.  workspace: tspm_gmu_pattern_bwd_workspace(batch, d) bytes (0 for a refused shape), fully
+ * overwritten by every call (no initialisation needed).  TSPM_ERR_INVALID before any launch: batch <= 0, npat outside
+ * 1..TSPM_MAX_PATTERNS, a pattern that keeps nothing, d outside 1..TSPM_GMU_PATTERN_MAX_D, lddz < d, ldh < 2d,
+ * lddu < 2d, a NULL among keep / dz / h / gate / wz / du / ds; a missing or short workspace with the other arguments
+ * valid: TSPM_ERR_WORKSPACE. */
+size_t tspm_gmu_pattern_bwd_workspace(int32_t batch, int32_t d);
+int tspm_gmu_pattern_bwd(int32_t batch, int32_t npat, const int32_t* keep, int32_t d, const float* dz, int32_t lddz,
+                         const float* h, int32_t ldh, const float* gate, const float* wz, float* du, int32_t lddu,
+                         float* ds, void* workspace, size_t workspace_bytes, tspm_stream_t stream);
 /* tspm_bce_logits for every pattern of a batch in one call (added under ABI 23; no gradient): logits
  * [npat*batch][classes] (row p*batch + b), targets [batch][classes] shared by the patterns (not replicated).  Workgroup
  * p runs tspm_bce_logits' code on its row slice: loss[p] and stats[p] (stats [npat][3 + 3*classes], tspm_bce_logits'

@@ -450,6 +450,15 @@ _SIGS = {
                                        _P, _P, c_int32, _P]),
     "tspm_bce_logits_patterns": (c_int32, [c_int32, c_int32, c_int32, _P, _P, c_float, c_float, _P, _P, _P, _P,
                                            c_int64, _P]),
+    # added under ABI 23: training every pattern of an MMIMDb batch in one step — the encoders' input BatchNorm1d over
+    # the replicated batch from its distinct rows, and the GMU backward folded onto batch + 1 projection rows
+    "tspm_bn1d_fwd_rep": (c_int32, [c_int32, c_int32, _P, _P, _P, _P, _P, c_float, c_float, _P, _P, _P, c_int32,
+                                    c_int32, _P]),
+    "tspm_bn1d_fwd_rep_pair": (c_int32, [c_int32] + ([c_int32, _P, _P, _P, _P, _P, c_float, c_float, _P, _P, _P,
+                                                      c_int32, c_int32] * 2) + [_P]),
+    "tspm_gmu_pattern_bwd_workspace": (c_size_t, [c_int32, c_int32]),
+    "tspm_gmu_pattern_bwd": (c_int32, [c_int32, c_int32, POINTER(c_int32), c_int32, _P, c_int32, _P, c_int32, _P, _P,
+                                       _P, c_int32, _P, _P, c_size_t, _P]),
 }
 
 EXPORTED = tuple(_SIGS)

@@ -9,7 +9,9 @@
 //     f1_{samples,macro,weighted,micro} metrics of configs/mmimdb/centralised/mmimdb_baseline.yaml
 //     (prediction = sigmoid(x) > threshold, models/mmimdb.py:236-237);
 //   * the GMU forward and that loss for every missing-modality pattern of a batch in one call each
-//     (k_gmu_pattern_fwd, k_bce_logits_patterns: bitwise the per-row / per-pattern kernels above).
+//     (k_gmu_pattern_fwd, k_bce_logits_patterns: bitwise the per-row / per-pattern kernels above);
+//   * training every pattern of a batch in one step: the encoders' input BatchNorm1d over the replicated batch from its
+//     distinct rows (k_bn1d_fwd_rep*), and the GMU backward folded onto batch + 1 projection rows (k_gmu_pattern_bwd*).
 // Every kernel is HBM/latency bound (a few hundred KB per launch); rows map to workgroups so the
 // row reductions are wave shuffles + one LDS step in a fixed order (deterministic).
 #include "common.h"
@@ -277,6 +279,96 @@ __global__ __launch_bounds__(kRowThreads) void k_gmu_pattern_fwd(int batch, int 
   }
 }
 
+// The adjoint of k_gmu_pattern_fwd, folded onto batch + 1 rows.  One workgroup per sample (walking samples above the
+// grid cap, like the forward): per pattern p it runs k_gmu_bwd's statement list on row p*batch + b — the same fmaf
+// chain over j = tid, tid + 256, ..., the same block_sum — writes ds[row], and adds the row's two du halves to the
+// sample's register accumulators (a half the pattern keeps) or to the workgroup's zero-row accumulators (a half it
+// drops), in ascending p from +0.0.  TRIPS = ceil(d / 256) elements per thread and half, a template parameter so the
+// accumulators stay in registers.  The sample's sums go to du[b]; the zero-row sums, carried across the workgroup's
+// samples b = g, g + G, ... in ascending order, go to part[g][2d] for k_gmu_pattern_bwd_zero.  No LDS beyond block_sum's.
+template <int TRIPS>
+__global__ __launch_bounds__(kRowThreads) void k_gmu_pattern_bwd(int batch, int npat, GmuPatternSet ps, int d,
+                                                                 const float* __restrict__ dz, int lddz,
+                                                                 const float* __restrict__ h, int ldh,
+                                                                 const float* __restrict__ gate,
+                                                                 const float* __restrict__ wz, float* __restrict__ du,
+                                                                 int lddu, float* __restrict__ ds,
+                                                                 float* __restrict__ part) {
+  __shared__ float red[kRowThreads / 64];
+  float zi[TRIPS], zt[TRIPS];
+#pragma unroll
+  for (int t = 0; t < TRIPS; ++t) zi[t] = zt[t] = 0.f;
+  for (int b = blockIdx.x; b < batch; b += gridDim.x) {
+    float ai[TRIPS], at[TRIPS];
+#pragma unroll
+    for (int t = 0; t < TRIPS; ++t) ai[t] = at[t] = 0.f;
+    for (int p = 0; p < npat; ++p) {
+      const long long r = (long long)p * batch + b;
+      const float* hr = h + r * ldh;
+      const float* dzr = dz + r * lddz;
+      float a = 0.f;
+#pragma unroll
+      for (int t = 0; t < TRIPS; ++t) {
+        const int j = threadIdx.x + t * kRowThreads;
+        if (j < d) a = fmaf(dzr[j], hr[j] - hr[d + j], a);
+      }
+      a = block_sum(a, red);
+      const float g = gate[r];
+      const float dsv = a * g * (1.f - g);
+      if (threadIdx.x == 0) ds[r] = dsv;
+      const bool ki = ps.keep[p] & 1, kt = ps.keep[p] & 2;  // uniform: kernel arguments
+#pragma unroll
+      for (int t = 0; t < TRIPS; ++t) {
+        const int j = threadIdx.x + t * kRowThreads;
+        if (j < d) {
+          const float h1 = hr[j], h2 = hr[d + j];
+          const float d1 = fmaf(dsv, wz[j], g * dzr[j]);
+          const float d2 = fmaf(dsv, wz[d + j], (1.f - g) * dzr[j]);
+          const float v1 = d1 * (1.f - h1 * h1), v2 = d2 * (1.f - h2 * h2);
+          if (ki) ai[t] += v1; else zi[t] += v1;
+          if (kt) at[t] += v2; else zt[t] += v2;
+        }
+      }
+    }
+    float* dur = du + (long long)b * lddu;
+#pragma unroll
+    for (int t = 0; t < TRIPS; ++t) {
+      const int j = threadIdx.x + t * kRowThreads;
+      if (j < d) {
+        dur[j] = ai[t];
+        dur[d + j] = at[t];
+      }
+    }
+  }
+  float* pr = part + (long long)blockIdx.x * 2 * d;
+#pragma unroll
+  for (int t = 0; t < TRIPS; ++t) {
+    const int j = threadIdx.x + t * kRowThreads;
+    if (j < d) {
+      pr[j] = zi[t];
+      pr[d + j] = zt[t];
+    }
+  }
+}
+
+// The zero row of tspm_gmu_pattern_bwd: column c of out = ((s0 + s1) + s2) + s3, s_q = the sum from +0.0 over the
+// workgroup partials g = q, q + 4, q + 8, ... (ascending) of part[g][c].  64 columns x 4 partial groups per workgroup;
+// a launch of its own, after k_gmu_pattern_bwd in the same stream, so it reads finished partials.
+constexpr int kGmuZeroCols = 64, kGmuZeroGroups = 4;
+__global__ __launch_bounds__(kGmuZeroCols * kGmuZeroGroups) void k_gmu_pattern_bwd_zero(int nparts, int width,
+                                                                                      const float* __restrict__ part,
+                                                                                      float* __restrict__ out) {
+  __shared__ float s[kGmuZeroGroups][kGmuZeroCols];
+  const int cl = threadIdx.x % kGmuZeroCols, q = threadIdx.x / kGmuZeroCols;
+  const int c = blockIdx.x * kGmuZeroCols + cl;
+  float v = 0.f;
+  if (c < width)
+    for (int g = q; g < nparts; g += kGmuZeroGroups) v += part[(long long)g * width + c];
+  s[q][cl] = v;
+  __syncthreads();
+  if (q == 0 && c < width) out[c] = ((s[0][cl] + s[1][cl]) + s[2][cl]) + s[3][cl];
+}
+
 // BatchNorm1d over [m, c] rows in ONE launch each way (m = the batch, at most a few thousand rows on
 // this path): one workgroup per kBnCh channels, kBnGroups row groups — lane = channel, so every row
 // read is one coalesced segment; two-pass statistics (sum, then centred squares), row groups
@@ -384,6 +476,70 @@ TSPM_DEV void bn1d_fwd_body(int m, const Bn1dFwd& p, int bid, double* red) {
     const float v = (x[i] - mean) * invstd * ga + be;
     p.y[i] = (DROP && p.keep) ? v * (p.keep[i] ? p.keep_scale : 0.f) : v;
   }
+}
+
+// BatchNorm1d over a batch that holds each of the m rows of x `reps` times and, per row of x, `zrows` all-zero rows
+// (every missing-modality pattern of a batch in one train step: the patterns that keep the modality, the patterns that
+// drop it) — the statistics of those N = m*(reps + zrows) rows from the m real rows alone, per channel with S = sum x:
+//   mean = reps*S / N,  M2 = reps*sum (x - mean)^2 + zrows*m*mean^2,  invstd = 1/sqrt(M2/N + eps),  running var <- M2/(N-1)
+// bn1d_fwd_body's structure (lane = channel, kBnGroups row groups, two passes in double, bn_group_sum's fixed order, no
+// atomics) as a body of its own, so the plain kernels compile as before.  y has m + 1 rows: row m is what every
+// all-zero row normalises to.  reps = 1, zrows = 0 forms bn1d_fwd_body's values bit for bit (1.0*S, Q + 0.0): the
+// compiler contracts nothing here, and the fmaf calls below are the contractions it makes in bn1d_fwd_body (the running
+// variance's blend and y's scale-and-shift; the running mean's blend is two products and an add there).
+TSPM_DEV void bn1d_fwd_rep_body(int m, const Bn1dFwd& p, int reps, int zrows, int bid, double* red) {
+#pragma clang fp contract(off)
+  const int c = p.c;
+  const float* __restrict__ x = p.x;
+  const float momentum = p.momentum, eps = p.eps;
+  float* __restrict__ rmean = p.rmean;
+  float* __restrict__ rvar = p.rvar;
+  const int ch = bid * kBnCh + threadIdx.x % kBnCh, grp = threadIdx.x / kBnCh;
+  const bool ok = ch < c;
+  const double nrep = (double)m * (double)(reps + zrows);
+  double s = 0.0;
+  if (ok)
+#pragma unroll 4
+    for (int r = grp; r < m; r += kBnGroups) s += (double)x[(long long)r * c + ch];
+  const double meand = (double)reps * bn_group_sum(s, red) / nrep;
+  double q = 0.0;
+  if (ok)
+#pragma unroll 4
+    for (int r = grp; r < m; r += kBnGroups) {
+      const double d = (double)x[(long long)r * c + ch] - meand;
+      q = fma(d, d, q);
+    }
+  const double m2 = (double)reps * bn_group_sum(q, red) + (double)zrows * (double)m * (meand * meand);
+  const float mean = (float)meand;
+  const float invstd = (float)(1.0 / sqrt(m2 / nrep + (double)eps));
+  if (!ok) return;
+  const float ga = p.gamma[ch], be = p.beta[ch];
+  if (grp == 0) {
+    p.smean[ch] = mean;
+    p.sinvstd[ch] = invstd;
+    if (rmean) rmean[ch] = (1.f - momentum) * rmean[ch] + momentum * mean;
+    if (rvar) rvar[ch] = fmaf(1.f - momentum, rvar[ch], momentum * (float)(m2 / (nrep - 1.0)));
+    p.y[(long long)m * c + ch] = fmaf(ga, (0.f - mean) * invstd, be);
+  }
+  for (int r = grp; r < m; r += kBnGroups) {
+    const long long i = (long long)r * c + ch;
+    p.y[i] = fmaf(ga, (x[i] - mean) * invstd, be);
+  }
+}
+
+__global__ __launch_bounds__(kBnCh * kBnGroups) void k_bn1d_fwd_rep(int m, Bn1dFwd p, int reps, int zrows) {
+  __shared__ double red[kBnCh * kBnGroups];
+  bn1d_fwd_rep_body(m, p, reps, zrows, blockIdx.x, red);
+}
+
+// Two such layers over the same m rows in one launch (k_bn1d_fwd2's split): blocks [0, nb0) take p0.
+__global__ __launch_bounds__(kBnCh * kBnGroups) void k_bn1d_fwd_rep2(int m, Bn1dFwd p0, int reps0, int zrows0,
+                                                                     Bn1dFwd p1, int reps1, int zrows1, int nb0) {
+  __shared__ double red[kBnCh * kBnGroups];
+  if ((int)blockIdx.x < nb0)
+    bn1d_fwd_rep_body(m, p0, reps0, zrows0, blockIdx.x, red);
+  else
+    bn1d_fwd_rep_body(m, p1, reps1, zrows1, blockIdx.x - nb0, red);
 }
 
 struct Bn1dBwd {
@@ -1018,6 +1174,81 @@ extern "C" int tspm_gmu_pattern_fwd(int32_t batch, int32_t npat, const int32_t* 
   const size_t lds = (size_t)(4 * d + 4) * sizeof(float);
   hipLaunchKernelGGL(k_gmu_pattern_fwd, dim3(batch < kGmuPatternGrid ? batch : kGmuPatternGrid), dim3(kRowThreads), lds,
                      static_cast<hipStream_t>(stream), batch, npat, ps, d, u, ldu, u0, wz, h, ldh, gate, z, ldz);
+  TSPM_LAUNCH_CHECK();
+  return TSPM_OK;
+}
+
+extern "C" size_t tspm_gmu_pattern_bwd_workspace(int32_t batch, int32_t d) {
+  if (batch <= 0 || d <= 0 || d > TSPM_GMU_PATTERN_MAX_D) return 0;
+  return (size_t)(batch < kGmuPatternGrid ? batch : kGmuPatternGrid) * 2 * (size_t)d * sizeof(float);
+}
+
+extern "C" int tspm_gmu_pattern_bwd(int32_t batch, int32_t npat, const int32_t* keep, int32_t d, const float* dz,
+                                    int32_t lddz, const float* h, int32_t ldh, const float* gate, const float* wz,
+                                    float* du, int32_t lddu, float* ds, void* workspace, size_t workspace_bytes,
+                                    tspm_stream_t stream) {
+  if (batch <= 0 || npat < 1 || npat > TSPM_MAX_PATTERNS || d <= 0 || d > TSPM_GMU_PATTERN_MAX_D)
+    return TSPM_ERR_INVALID;
+  if (!keep || !dz || !h || !gate || !wz || !du || !ds || lddz < d || ldh < 2 * d || lddu < 2 * d)
+    return TSPM_ERR_INVALID;
+  GmuPatternSet ps{};
+  for (int p = 0; p < npat; ++p) {
+    ps.keep[p] = (keep[2 * p] ? 1 : 0) | (keep[2 * p + 1] ? 2 : 0);
+    if (ps.keep[p] == 0) return TSPM_ERR_INVALID;
+  }
+  if (!workspace || workspace_bytes < tspm_gmu_pattern_bwd_workspace(batch, d)) return TSPM_ERR_WORKSPACE;
+  const int grid = batch < kGmuPatternGrid ? batch : kGmuPatternGrid;
+  const hipStream_t st = static_cast<hipStream_t>(stream);
+  float* part = static_cast<float*>(workspace);
+#define TSPM_GMU_PBWD(TRIPS)                                                                                          \
+  hipLaunchKernelGGL(k_gmu_pattern_bwd<TRIPS>, dim3(grid), dim3(kRowThreads), 0, st, batch, npat, ps, d, dz, lddz, h, \
+                     ldh, gate, wz, du, lddu, ds, part)
+  const int trips = cdiv(d, kRowThreads);  // 1..16 (d <= 4095)
+  if (trips <= 1) TSPM_GMU_PBWD(1);
+  else if (trips <= 2) TSPM_GMU_PBWD(2);
+  else if (trips <= 4) TSPM_GMU_PBWD(4);
+  else if (trips <= 8) TSPM_GMU_PBWD(8);
+  else TSPM_GMU_PBWD(16);
+#undef TSPM_GMU_PBWD
+  TSPM_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_gmu_pattern_bwd_zero, dim3(cdiv(2 * d, kGmuZeroCols)), dim3(kGmuZeroCols * kGmuZeroGroups), 0,
+                     st, grid, 2 * d, part, du + (long long)batch * lddu);
+  TSPM_LAUNCH_CHECK();
+  return TSPM_OK;
+}
+
+extern "C" int tspm_bn1d_fwd_rep(int32_t m, int32_t c, const float* x, const float* gamma, const float* beta,
+                                 float* running_mean, float* running_var, float momentum, float eps, float* save_mean,
+                                 float* save_invstd, float* y, int32_t reps, int32_t zero_rows_per_row,
+                                 tspm_stream_t stream) {
+  if (m <= 0 || c <= 0 || reps < 1 || zero_rows_per_row < 0 || (long long)m * (reps + (long long)zero_rows_per_row) < 2 ||
+      !x || !gamma || !beta || !save_mean || !save_invstd || !y)
+    return TSPM_ERR_INVALID;
+  const Bn1dFwd p{c, x, gamma, beta, running_mean, running_var, momentum, eps, save_mean, save_invstd, y};
+  hipLaunchKernelGGL(k_bn1d_fwd_rep, dim3(cdiv(c, kBnCh)), dim3(kBnCh * kBnGroups), 0, static_cast<hipStream_t>(stream),
+                     m, p, reps, zero_rows_per_row);
+  TSPM_LAUNCH_CHECK();
+  return TSPM_OK;
+}
+
+extern "C" int tspm_bn1d_fwd_rep_pair(int32_t m, int32_t c0, const float* x0, const float* gamma0, const float* beta0,
+                                      float* running_mean0, float* running_var0, float momentum0, float eps0,
+                                      float* save_mean0, float* save_invstd0, float* y0, int32_t reps0,
+                                      int32_t zero_rows_per_row0, int32_t c1, const float* x1, const float* gamma1,
+                                      const float* beta1, float* running_mean1, float* running_var1, float momentum1,
+                                      float eps1, float* save_mean1, float* save_invstd1, float* y1, int32_t reps1,
+                                      int32_t zero_rows_per_row1, tspm_stream_t stream) {
+  if (m <= 0 || c0 <= 0 || c1 <= 0 || reps0 < 1 || reps1 < 1 || zero_rows_per_row0 < 0 || zero_rows_per_row1 < 0 ||
+      (long long)m * (reps0 + (long long)zero_rows_per_row0) < 2 ||
+      (long long)m * (reps1 + (long long)zero_rows_per_row1) < 2 || !x0 || !gamma0 || !beta0 || !save_mean0 ||
+      !save_invstd0 || !y0 || !x1 || !gamma1 || !beta1 || !save_mean1 || !save_invstd1 || !y1)
+    return TSPM_ERR_INVALID;
+  const Bn1dFwd p0{c0, x0, gamma0, beta0, running_mean0, running_var0, momentum0, eps0, save_mean0, save_invstd0, y0};
+  const Bn1dFwd p1{c1, x1, gamma1, beta1, running_mean1, running_var1, momentum1, eps1, save_mean1, save_invstd1, y1};
+  const int nb0 = cdiv(c0, kBnCh);
+  hipLaunchKernelGGL(k_bn1d_fwd_rep2, dim3(nb0 + cdiv(c1, kBnCh)), dim3(kBnCh * kBnGroups), 0,
+                     static_cast<hipStream_t>(stream), m, p0, reps0, zero_rows_per_row0, p1, reps1, zero_rows_per_row1,
+                     nb0);
   TSPM_LAUNCH_CHECK();
   return TSPM_OK;
 }

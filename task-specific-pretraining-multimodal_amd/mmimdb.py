@@ -22,6 +22,12 @@ buffer — ``MMIMDb.zero_projections`` / ``forward_patterns``, ``FusedMMIMDbPatt
 ``tspm_bce_logits_patterns``, or the same result from existing launches), ``evaluate_patterns``,
 ``fit_mmimdb(fuse_patterns=True)``.
 
+Training every pattern of a batch in ONE step (opt-in): under batch statistics too a zeroed modality is one
+constant row — the replicated batch's BatchNorm1d statistics follow from the B real rows (``tspm_bn1d_fwd_rep_pair``) — so
+the encoders run over B + 1 rows forward and backward and only the fusion and the classifier see the P·B rows:
+``FusedMMIMDbPatternStep`` (``tspm_gmu_pattern_fwd`` + ``tspm_gmu_pattern_bwd``, or the same from existing launches),
+``MMIMDb.pattern_step_for``, an ``"all_patterns"`` batch in ``train_step``, ``fit_mmimdb(all_patterns=True)``.
+
 Supported configuration = the reference's MMIMDb configs: GMU fusion or ``multimodal_pooling``
 (``MultimodalPooling``, models/pooling.py: max / avg / sum / attention / gated; ``tspm_pool_*``),
 MaxOut with 2 units and no bias, Dropout 0.5, biasless GMU.
@@ -328,6 +334,12 @@ class MMIMDbEngine:
                      mean.data_ptr(), inv.data_ptr(), out.data_ptr()]
         L.check(L.lib().tspm_bn1d_fwd_pair(self.n, *args, sh), "bn1d_fwd_pair")
 
+    def _input_bns_train(self, sh) -> None:
+        """Both encoders' input BatchNorm1d in train mode, one launch (text first, as the separate launches ran)."""
+        m = self.model
+        self._bn_train_pair(("t", m.text_model.net[0], self.T, self.dt, self.XnT),
+                            ("i", m.image_model.net[0], self.I, self.di, self.XnI), sh)
+
     def _bn_eval(self, bn, x, width, out, sh):
         g, b, rm, rv, eps, _ = _bn(bn)
         L.check(L.lib().tspm_bn_apply_eval(self.n, width, x.data_ptr(), rm.data_ptr(), rv.data_ptr(), eps, g.data_ptr(),
@@ -374,8 +386,7 @@ class MMIMDbEngine:
         pairs = _PAIRS and self.side is None
         if pairs:  # one stream, independent pairs of launches merged (bitwise the separate launches)
             if train:
-                self._bn_train_pair(("t", te[0], self.T, self.dt, self.XnT), ("i", ie[0], self.I, self.di, self.XnI),
-                                    sh)
+                self._input_bns_train(sh)
             else:
                 bn("t", te[0], self.T, self.dt, self.XnT)
                 bn("i", ie[0], self.I, self.di, self.XnI)
@@ -530,10 +541,16 @@ class MMIMDbEngine:
 
     # -- backward -----------------------------------------------------------------------------------
     def backward(self, sh: int) -> None:
-        lib = L.lib()
-        m = self.model
-        n, e, d, h, c = self.n, self.e, self.d, self.h, self.c
-        ie, te, gmu, net = m.image_model.net, m.text_model.net, m.fusion_module, m.mm_mlp.net
+        """The whole backward: its three parts in order (the all-pattern train step runs them at different row
+        counts, on two engines)."""
+        self.backward_classifier(sh)
+        self.backward_fusion(sh)
+        self.backward_encoders(sh)
+
+    def backward_classifier(self, sh: int) -> None:
+        """dlogits → dZ, and the classifier's parameter gradients."""
+        n, d, h, c = self.n, self.d, self.h, self.c
+        net = self.model.mm_mlp.net
         scale = 1.0 / (1.0 - self.p) if self.p > 0 else 1.0
         k1 = self.keep[0].data_ptr() if self.p > 0 else None
         k2 = self.keep[1].data_ptr() if self.p > 0 else None
@@ -550,16 +567,30 @@ class MMIMDbEngine:
         linear_bwd(n, d, 2 * h, self.Zn.data_ptr(), d, self.dA1.data_ptr(), 2 * h, net[1].layers[0].weight.data_ptr(),
                    g(net[1].layers[0].weight), None, self.dZn.data_ptr(), d, sh)
         self._bn_bwd("b0", net[0], self.dZn, self.Z, d, self.dZ, sh)
+
+    def backward_fusion(self, sh: int) -> None:
+        """dZ → dU, and the gradients of the fusion's own parameters (the gate, or the pooling's scoring MLP)."""
+        lib = L.lib()
+        n, d = self.n, self.d
+        gmu = self.model.fusion_module
+        g = lambda p: p.grad.data_ptr()  # noqa: E731
         if self.pool is None:  # GMU
             L.check(lib.tspm_gmu_bwd(n, d, self.dZ.data_ptr(), d, self.H.data_ptr(), 2 * d, self.gate.data_ptr(),
                                      gmu.hidden_sigmoid.weight.data_ptr(), self.dU.data_ptr(), 2 * d,
                                      self.ds.data_ptr(), sh), "gmu bwd")
             L.check(lib.tspm_linear_bwd_weight(n, 2 * d, 1, self.H.data_ptr(), 2 * d, self.ds.data_ptr(), 1,
                                                g(gmu.hidden_sigmoid.weight), None, sh), "gmu gate dW")
-            fa, fb = gmu.fc_one, gmu.fc_two
         else:
             self._pool_bwd(sh)
-            fa, fb = self.pool.proj_a, self.pool.proj_b
+
+    def backward_encoders(self, sh: int) -> None:
+        """dU → the projections', the encoder Linears' and the input BatchNorm1ds' parameter gradients."""
+        lib = L.lib()
+        m = self.model
+        n, e, d = self.n, self.e, self.d
+        ie, te, gmu = m.image_model.net, m.text_model.net, m.fusion_module
+        g = lambda p: p.grad.data_ptr()  # noqa: E731
+        fa, fb = (gmu.fc_one, gmu.fc_two) if self.pool is None else (self.pool.proj_a, self.pool.proj_b)
         dU1, dU2 = self.dU.data_ptr(), self.dU.data_ptr() + d * 4
         if _PAIRS and self.side is None:
             # fc_two + fc_one (proj_b + proj_a) backward in one launch, then both encoder Linears, then
@@ -746,10 +777,31 @@ class MMIMDb(nn.Module):
         st = self.pattern_eval_step_for(None, I.shape[0], patterns)
         return st.step(I, T, None, refresh_zero=True)["logits"].clone()
 
+    def pattern_step_for(self, optimizer, loss_functions, batch: int, patterns=None,
+                         fusion: Optional[str] = None) -> "FusedMMIMDbPatternStep":
+        """The cached FusedMMIMDbPatternStep for (optimizer, patterns, fusion leg, loss weight, batch size)."""
+        key = ("train", id(optimizer), norm_mmimdb_patterns(patterns), fusion or DEFAULT_TRAIN_PATTERN_FUSION,
+               _bce_weight(loss_functions), batch)
+        cache = self.__dict__.setdefault("_pattern_steps", {})
+        st = cache.get(key)
+        if st is None or st.opt is not optimizer:
+            st = cache[key] = FusedMMIMDbPatternStep(self, optimizer, loss_functions, batch, patterns=key[2],
+                                                     fusion=fusion)
+        return st
+
     def train_step(self, batch: Dict[str, Any], optimizer, loss_functions, device, metric_recorder=None,
                    epoch: int = 0) -> Dict[str, Any]:
-        """models/mmimdb.py:203-245 on the fused HIP step."""
+        """models/mmimdb.py:203-245 on the fused HIP step.  A batch carrying ``"all_patterns": True`` (the samples
+        once, unmasked) and optionally ``"patterns"`` trains every row under every pattern in one step
+        (``FusedMMIMDbPatternStep``); the recorder then receives all P·B rows, pattern by pattern."""
         I, T, labels = _batch_tensors(batch, device)
+        if batch.get("all_patterns"):
+            st = self.pattern_step_for(optimizer, loss_functions, I.shape[0], batch.get("patterns"))
+            out = st.step(I, T, labels)
+            names = [p for p in st.patterns for _ in range(I.shape[0])]
+            _record(metric_recorder, out["logits"].reshape(-1, labels.shape[1]), labels.repeat(st.P, 1), names,
+                    self.binary_threshold)
+            return {"loss": out["loss"].item()}
         key = ("train", id(optimizer), id(loss_functions), I.shape[0])
         st = self._steps.get(key)
         if st is None:
@@ -1236,10 +1288,276 @@ def evaluate_patterns(model: MMIMDb, corpus: MMIMDbCorpus, batch: int, loss_func
     return out
 
 
+# ------------------------------------------------------------------------------------------------
+# every missing-modality pattern of a batch in one train step
+# ------------------------------------------------------------------------------------------------
+# the fusion leg of a FusedMMIMDbPatternStep built without fusion=: "kernel" (tspm_gmu_pattern_fwd / tspm_gmu_pattern_bwd)
+# or "launches" (tspm_pattern_expand + the engine's fusion launches at P·B rows + tspm_pattern_expand_bwd + a column
+# sum); the leg that measured faster at batch 256 (profiles/mmimdb_train_patterns.json, DESIGN §3.21: the launches leg,
+# by about 2 % of the step — unlike evaluation, training has to write h and gate, and one workgroup per sample runs the
+# patterns' reductions one after the other)
+DEFAULT_TRAIN_PATTERN_FUSION = "launches"
+
+
+class MMIMDbTrainPartsEngine(MMIMDbEngine):
+    """``MMIMDbEngine``'s train-mode ``forward_*`` / ``backward_*`` parts with the buffers of the parts asked for only —
+    the two engines of the all-pattern train step.
+
+    ``parts=("encoders",)`` with ``replication=((k_image, z_image), (k_text, z_text))``: ``n = B + 1`` rows, the B
+    distinct samples and, as row B, the one row every all-zero input shares.  The input BatchNorm1ds take the batch
+    statistics of the replicated batch (each sample k times, z all-zero rows per sample: ``tspm_bn1d_fwd_rep_pair``
+    over the B real rows, writing B + 1); the Linears and projections are row-wise and run over the B + 1 rows, and so
+    does ``backward_encoders`` once ``dU [B + 1, 2d]`` holds the folded gradient: row B of ``I`` / ``T`` stays zero,
+    which is the input of every folded zero row.  ``parts=("fusion", "classifier")``: the P·B (pattern, sample) rows;
+    ``expanded`` adds the fusion's input and input-gradient buffers ``U`` / ``dU [n, 2d]`` (the launches leg)."""
+
+    def __init__(self, model: "MMIMDb", n: int, device: torch.device, parts, replication=None, expanded: bool = False):
+        if n < 2:
+            raise L.TspmError("BatchNorm1d in training mode needs more than one sample per batch")
+        self.model, self.n, self.dev = model, n, device
+        self._configure(model)
+        e, d, h, c = self.e, self.d, self.h, self.c
+        z = lambda *s: torch.zeros(*s, device=device, dtype=torch.float32)  # noqa: E731
+        self.side = None
+        self.stat = {}
+        self.replication = replication
+        if "encoders" in parts:
+            self.I, self.T = z(n, self.di), z(n, self.dt)
+            self.XnI, self.XnT, self.EI, self.ET = z(n, self.di), z(n, self.dt), z(n, e), z(n, e)
+            self.U, self.dU = z(n, 2 * d), z(n, 2 * d)
+            self.dEI, self.dET, self.dXn, self.dXnT = z(n, e), z(n, e), z(n, self.di), z(n, self.dt)
+            self.stat.update(i=(z(self.di), z(self.di)), t=(z(self.dt), z(self.dt)))
+            self._plan_encoder_splits()
+        if "fusion" in parts:
+            self.H, self.gate, self.ds = z(n, 2 * d), z(n), z(n)
+            if expanded:
+                self.U, self.dU = z(n, 2 * d), z(n, 2 * d)
+            if self.pool is not None:
+                hd = self.hd
+                self.TU, self.Hpre, self.Hh, self.wts = z(n, 2 * d), z(n, hd), z(n, hd), z(n, 2)
+                self.dAB2, self.dS, self.dHpre = z(n, 2 * d), z(n, 2), z(n, hd)
+                self.keep_pool = torch.ones(n, 2 * d, dtype=torch.uint8, device=device)
+                self.pool_keep_override = None
+        if "fusion" in parts or "classifier" in parts:
+            self.Z, self.dZ = z(n, d), z(n, d)
+        if "classifier" in parts:
+            self.labels = z(n, c)
+            self.Zn, self.A1, self.Y1, self.Y1n = z(n, d), z(n, 2 * h), z(n, h), z(n, h)
+            self.A2, self.Y2, self.Y2n = z(n, 2 * h), z(n, h), z(n, h)
+            self.logits, self.loss, self.dlogits = z(n, c), z(1), z(n, c)
+            self.dY2n, self.dY2, self.dA2, self.dY1n, self.dY1, self.dA1 = z(n, h), z(n, h), z(n, 2 * h), z(n, h), \
+                z(n, h), z(n, 2 * h)
+            self.dZn = z(n, d)
+            self.keep = torch.ones(2, n, h, dtype=torch.uint8, device=device)
+            self.stat.update(b0=(z(d), z(d)), b1=(z(h), z(h)), b2=(z(h), z(h)))
+            self.stats = z(3 + 3 * c)
+        self.keep_override = None
+        self.rng_ctr_ptr = None
+
+    def _input_bns_train(self, sh) -> None:
+        if self.replication is None:
+            return super()._input_bns_train(sh)
+        m = self.model
+        (ki, zi), (kt, zt) = self.replication
+        args = []
+        for key, bn, x, width, out, k, zr in (("t", m.text_model.net[0], self.T, self.dt, self.XnT, kt, zt),
+                                              ("i", m.image_model.net[0], self.I, self.di, self.XnI, ki, zi)):
+            g, bb, rm, rv, eps, mom = _bn(bn)
+            mean, inv = self.stat[key]
+            args += [width, x.data_ptr(), g.data_ptr(), bb.data_ptr(), rm.data_ptr(), rv.data_ptr(), mom, eps,
+                     mean.data_ptr(), inv.data_ptr(), out.data_ptr(), k, zr]
+        L.check(L.lib().tspm_bn1d_fwd_rep_pair(self.n - 1, *args, sh), "bn1d_fwd_rep_pair")
+
+
+class FusedMMIMDbPatternStep(L.GraphRunner):
+    """One MMIMDb train step over EVERY missing-modality pattern of a batch — mathematically one ``FusedMMIMDbStep`` on
+    the P·B-row batch whose row ``p·B + b`` is sample b with the modality pattern p drops zeroed and labels ``y[b]`` —
+    with the encoders over B + 1 rows instead of P·B, as one HIP graph.  The encoders are BatchNorm1d →
+    Linear and each fusion projection acts on one modality, so even under batch statistics a zeroed modality is one
+    constant row: the replicated batch's statistics follow from the B real rows (``tspm_bn1d_fwd_rep_pair``) and every
+    all-zero row normalises to the same vector, row B of the encoder buffers.  Only the fusion and the classifier see
+    the P·B rows.  Backward, the fusion-input gradient is folded onto the B + 1 rows (row b: the patterns that keep the
+    modality; row B: every sample under every pattern that drops it) and every Linear / BatchNorm1d backward over them
+    gives the replicated batch's parameter gradients.
+
+    The graph holds: the replicated input BNs; both encoder Linears and the projections at n = B + 1 into
+    ``U [B + 1, 2d]``; the fusion over the P·B rows; the classifier in train mode at n = P·B; the labels replicated to
+    ``[P·B, C]`` and ``tspm_bce_logits`` (mean over all P·B·C elements, times the weight); ``backward_classifier``; the
+    fusion backward folded to ``dU [B + 1, 2d]`` and the fusion's own weight gradients at n = P·B; ``backward_encoders``
+    at B + 1 rows; the ``num_batches_tracked`` counters (+1); one Adam update.
+
+    ``fusion="kernel"``: ``tspm_gmu_pattern_fwd`` (u0 = ``U[B]``) and ``tspm_gmu_pattern_bwd``.  ``fusion="launches"``:
+    ``tspm_pattern_expand`` from ``[2B, 2d]`` rows (``U[B]`` broadcast into rows [B, 2B)), the engine's
+    ``forward_fusion`` / ``backward_fusion`` at n = P·B, ``tspm_pattern_expand_bwd`` and a column sum of its rows
+    [B, 2B) into row B (``tspm_reduce_slabs``, a fixed order) — the only leg for ``multimodal_pooling`` models and for a
+    width outside ``_lib.gmu_pattern_supported``, and the A/B leg; ``.fusion`` tells which leg was built.
+
+    Classifier dropout is drawn per (pattern, sample) row exactly as ``FusedMMIMDbStep`` at n = P·B draws it (the same
+    seed, counter and element index); ``keep_override [2, P·B, h]`` replaces it.  ``step(I, T, labels)`` →
+    ``{"loss": [1], "logits": [P, B, C]}``.  Any B >= 1 with P·B >= 2.  ``FusedAdam`` only; ``allreduce`` is refused:
+    data parallelism is not built for this step."""
+
+    def __init__(self, model: "MMIMDb", optimizer: FusedAdam, loss_functions, batch: int, patterns=None,
+                 fusion: Optional[str] = None, use_graph: bool = True, allreduce=None):
+        if allreduce is not None:
+            raise L.TspmError("FusedMMIMDbPatternStep: allreduce (data parallelism) is not built for the all-pattern "
+                              "step; use FusedMMIMDbStep")
+        self.patterns = norm_mmimdb_patterns(patterns)
+        self.P = P = len(self.patterns)
+        fusion = DEFAULT_TRAIN_PATTERN_FUSION if fusion is None else fusion
+        if fusion not in ("kernel", "launches"):
+            raise ValueError(f"fusion: 'kernel' or 'launches', got {fusion!r}")
+        keep = [tuple(int(v != 0) for v in PATTERNS[p]) for p in self.patterns]  # (image, text) per pattern
+        ki, kt = sum(k[0] for k in keep), sum(k[1] for k in keep)
+        for k, name in ((ki, "image"), (kt, "text")):
+            if k < 1:  # that modality's replicated batch would be all zeros: tspm_bn1d_fwd_rep takes reps >= 1
+                raise L.TspmError(f"FusedMMIMDbPatternStep: no pattern of {self.patterns} keeps the {name} modality "
+                                  "(train that selection with FusedMMIMDbStep on the masked batch)")
+        if not isinstance(optimizer, FusedAdam):
+            raise L.TspmError("FusedMMIMDbPatternStep needs FusedAdam (the flat gradient buffer the kernels write)")
+        if batch < 1 or P * batch < 2:
+            raise L.TspmError("FusedMMIMDbPatternStep: BatchNorm1d in training mode needs P·B >= 2 rows")
+        dev = next(model.parameters()).device
+        if dev.type != "cuda":
+            raise L.TspmError("FusedMMIMDbPatternStep runs on the MI355X: move the model to cuda first")
+        self.model, self.opt, self.N = model, optimizer, batch
+        self.weight = _bce_weight(loss_functions)
+        B = batch
+        self.enc = MMIMDbTrainPartsEngine(model, B + 1, dev, ("encoders",), replication=((ki, P - ki), (kt, P - kt)))
+        d, c = self.enc.d, self.enc.c
+        if fusion == "kernel" and (self.enc.pool is not None or not L.gmu_pattern_supported(d, P)):
+            fusion = "launches"
+        self.fusion = fusion
+        self.clf = MMIMDbTrainPartsEngine(model, P * B, dev, ("fusion", "classifier"), expanded=fusion == "launches")
+        self.clf.check_maxout_weights()
+        fgs = optimizer.flat_groups()
+        self.clf.rng_ctr_ptr = fgs[0].hyper.data_ptr() + L.HYPER_STEP_OFFSET
+        self.nbt = shared_batches_tracked(model, dev, (nn.BatchNorm1d,))
+        self.labels = torch.zeros(B, c, device=dev, dtype=torch.float32)
+        self._keep = (ctypes.c_int32 * (2 * P))(*[k for kp in keep for k in kp])  # host launch arguments
+        if fusion == "kernel":
+            wsb = int(L.lib().tspm_gmu_pattern_bwd_workspace(B, d))
+            self.ws = torch.zeros(max(wsb // 4, 4), device=dev, dtype=torch.float32)
+        else:
+            # tspm_pattern_expand's layout: rows [0, B) the real projections, rows [B, 2B) the zero-input projections
+            # of the same rows — here one constant row, U[B], which is the first of them already: the encoder
+            # engine's U / dU are the first B + 1 rows of the [2B, 2d] buffers.  The entry points take three modality
+            # widths: the text half goes in as two pieces under the same keep flag
+            self.U2 = torch.zeros(max(2 * B, B + 1), 2 * d, device=dev, dtype=torch.float32)
+            self.dU2 = torch.zeros_like(self.U2)
+            self.enc.U, self.enc.dU = self.U2[:B + 1], self.dU2[:B + 1]
+            self._zsum = torch.zeros(2 * d, device=dev, dtype=torch.float32)
+            self._widths = (d, d // 2, d - d // 2)
+            self._keep3 = (ctypes.c_int32 * (3 * P))(*[k for kp in keep for k in (kp[0], kp[1], kp[1])])
+            self._gid = (ctypes.c_int32 * P)()
+            self._row_tag = torch.zeros(B, dtype=torch.int32, device=dev)  # the expand's label / group outputs
+            self._row_tags = torch.zeros(2, P * B, dtype=torch.int32, device=dev)  # are scratch here
+        self._init_graph(use_graph, dev)
+        self.log_stats = False
+
+    @property
+    def I(self) -> torch.Tensor:
+        return self.enc.I[:self.N]
+
+    @property
+    def T(self) -> torch.Tensor:
+        return self.enc.T[:self.N]
+
+    @property
+    def stats(self) -> torch.Tensor:
+        """``tspm_bce_logits``' counts over all P·B rows, accumulated while ``log_stats`` is set."""
+        return self.clf.stats
+
+    @property
+    def keep(self) -> torch.Tensor:
+        """The classifier dropout masks of the last step, ``[2, P·B, h]``."""
+        return self.clf.keep
+
+    @property
+    def keep_override(self):
+        return self.clf.keep_override
+
+    @keep_override.setter
+    def keep_override(self, v):
+        self.clf.keep_override = v
+
+    def _fusion_fwd(self, sh: int) -> None:
+        lib, B, P, d, clf = L.lib(), self.N, self.P, self.enc.d, self.clf
+        if self.fusion == "kernel":
+            L.check(lib.tspm_gmu_pattern_fwd(B, P, self._keep, d, self.enc.U.data_ptr(), 2 * d,
+                                             self.enc.U[B].data_ptr(),
+                                             self.model.fusion_module.hidden_sigmoid.weight.data_ptr(),
+                                             clf.H.data_ptr(), 2 * d, clf.gate.data_ptr(), clf.Z.data_ptr(), d, sh),
+                    "gmu_pattern_fwd")
+            return
+        if B > 1:
+            self.U2[B + 1:].copy_(self.U2[B].expand(B - 1, 2 * d))
+        wi, wt0, wt1 = self._widths
+        L.check(lib.tspm_pattern_expand(B, P, self._keep3, self._gid, wi, wt0, wt1, self.U2.data_ptr(), 2 * d,
+                                        clf.U.data_ptr(), 2 * d, self._row_tag.data_ptr(),
+                                        self._row_tags[0].data_ptr(), 4, self._row_tags[1].data_ptr(), sh),
+                "pattern train expand")
+        clf.forward_fusion(sh, True)
+
+    def _fusion_bwd(self, sh: int) -> None:
+        lib, B, P, d, clf = L.lib(), self.N, self.P, self.enc.d, self.clf
+        if self.fusion == "kernel":
+            wz = self.model.fusion_module.hidden_sigmoid.weight
+            L.check(lib.tspm_gmu_pattern_bwd(B, P, self._keep, d, clf.dZ.data_ptr(), d, clf.H.data_ptr(), 2 * d,
+                                             clf.gate.data_ptr(), wz.data_ptr(), self.enc.dU.data_ptr(), 2 * d,
+                                             clf.ds.data_ptr(), self.ws.data_ptr(), self.ws.numel() * 4, sh),
+                    "gmu_pattern_bwd")
+            L.check(lib.tspm_linear_bwd_weight(P * B, 2 * d, 1, clf.H.data_ptr(), 2 * d, clf.ds.data_ptr(), 1,
+                                               wz.grad.data_ptr(), None, sh), "gmu gate dW")
+            return
+        clf.backward_fusion(sh)
+        wi, wt0, wt1 = self._widths
+        L.check(lib.tspm_pattern_expand_bwd(B, P, self._keep3, wi, wt0, wt1, clf.dU.data_ptr(), 2 * d,
+                                            self.dU2.data_ptr(), 2 * d, 7, sh), "pattern train expand bwd")
+        # the B zero-input rows were one row: its gradient is their column sum (tspm_reduce_slabs' fixed slab order)
+        L.check(lib.tspm_reduce_slabs(2 * d, B, 2 * d, self.dU2[B].data_ptr(), self._zsum.data_ptr(), sh),
+                "pattern train zero-row sum")
+        self.dU2[B].copy_(self._zsum)
+
+    def _all(self) -> None:
+        sh = L.stream_handle()
+        B, P, clf = self.N, self.P, self.clf
+        self.enc.forward_encoders(sh, True)
+        self._fusion_fwd(sh)
+        clf.forward_classifier(sh, True)
+        clf.labels.view(P, B, -1).copy_(self.labels.unsqueeze(0).expand(P, B, -1))
+        clf.loss_fn(sh, self.weight, True, self.log_stats)
+        clf.backward_classifier(sh)
+        self._fusion_bwd(sh)
+        self.enc.backward_encoders(sh)
+        L.counters_add(self.nbt)
+        self.opt.launch(sh)
+
+    def run(self) -> None:
+        """One step on the batch in the static input buffers (``I``, ``T``, ``labels``)."""
+        self.model.train()
+        self.opt.sync_hyper()
+        clf = self.clf
+        if clf.keep_override is not None:
+            clf.keep.copy_(clf.keep_override.reshape(clf.keep.shape).to(torch.uint8), non_blocking=True)
+        if clf.pool is not None and clf.pool_keep_override is not None:
+            clf.keep_pool.copy_(clf.pool_keep_override.reshape(clf.keep_pool.shape).to(torch.uint8), non_blocking=True)
+        self.replay_or_enqueue(self._all)
+        self.opt.note_steps(1)
+        self.calls += 1
+
+    def step(self, I: torch.Tensor, T: torch.Tensor, labels: torch.Tensor) -> Dict[str, torch.Tensor]:
+        for dst, src in ((self.I, I), (self.T, T), (self.labels, labels)):
+            if src.data_ptr() != dst.data_ptr():
+                dst.copy_(src.reshape(dst.shape), non_blocking=True)
+        self.run()
+        return {"loss": self.clf.loss, "logits": self.clf.logits.view(self.P, self.N, self.clf.c)}
+
+
 def fit_mmimdb(model: MMIMDb, optimizer: FusedAdam, train: MMIMDbCorpus, val: MMIMDbCorpus, batch: int,
                epochs: int, loss_functions=None, patience: int = 25, seed: int = 0,
                patterns=("it", "i", "t"), min_delta: float = 1e-3, checkpoint_dir=None,
-               scheduler=None, fuse_patterns: bool = False) -> List[Dict[str, Any]]:
+               scheduler=None, fuse_patterns: bool = False, all_patterns: bool = False) -> List[Dict[str, Any]]:
     """The epoch loop of train_multimodal.py for the MMIMDb config, every batch on the HIP path:
     shuffled train batches over every sample (the DataLoader's drop_last=False, config/data_config.py:121;
     a last batch of one row is skipped — BatchNorm1d in training mode rejects it in the reference too),
@@ -1252,18 +1570,30 @@ def fit_mmimdb(model: MMIMDb, optimizer: FusedAdam, train: MMIMDbCorpus, val: MM
     ``fuse_patterns=True``: ``evaluate_patterns`` replaces the ``validation_loss`` + ``_evaluate`` loops (each
     validation sample through the encoders once per epoch instead of six times); ``val_loss`` is then the mean over
     unshuffled per-(batch, pattern) losses — the same value whenever ``batch`` divides the validation corpus.  History
-    keys, early stopping, checkpoints and the scheduler input are the same."""
+    keys, early stopping, checkpoints and the scheduler input are the same.
+    ``all_patterns=True``: the model trains for the patterns it is scored on — each train batch is gathered once,
+    unmasked, and one ``FusedMMIMDbPatternStep`` trains its rows under every pattern of ``patterns`` (the loss and the
+    train metrics run over all P·B rows; a last batch with P·B < 2 is skipped).  History keys are the same."""
     from .harness import CheckpointManager, check_early_stopping
     weight = _bce_weight(loss_functions)
-    steps: Dict[int, FusedMMIMDbStep] = {}
+    steps: Dict[int, Any] = {}
+    min_rows = 2
+    if all_patterns:
+        min_rows = -(-2 // len(norm_mmimdb_patterns(patterns)))  # P·B >= 2
 
     def step_for(n):
         st = steps.get(n)
         if st is None:
-            st = FusedMMIMDbStep(model, optimizer, loss_functions, n)
+            if all_patterns:
+                st = FusedMMIMDbPatternStep(model, optimizer, loss_functions, n, patterns=patterns)
+            else:
+                st = FusedMMIMDbStep(model, optimizer, loss_functions, n)
             st.log_stats = True
             steps[n] = st
         return st
+
+    def bufs(st):  # the step's static (image, text, labels, stats) buffers
+        return (st.I, st.T, st.labels, st.stats) if all_patterns else (st.eng.I, st.eng.T, st.eng.labels, st.eng.stats)
     main = step_for(batch)
     gen = torch.Generator(device="cpu").manual_seed(seed)
     vgen = torch.Generator(device="cpu").manual_seed(seed + 1)
@@ -1272,19 +1602,19 @@ def fit_mmimdb(model: MMIMDb, optimizer: FusedAdam, train: MMIMDbCorpus, val: MM
     for ep in range(1, epochs + 1):
         model.train()
         for st in steps.values():
-            st.eng.stats.zero_()
+            bufs(st)[3].zero_()
         perm = torch.randperm(train.n, generator=gen).to(train.device)
         for s in range(0, train.n, batch):
             rows = perm[s:s + batch]
-            if rows.numel() < 2:
+            if rows.numel() < min_rows:
                 break
             st = step_for(rows.numel())
-            train.gather(rows, st.eng.I, st.eng.T, st.eng.labels)
+            train.gather(rows, *bufs(st)[:3])
             st.run()
-        tot = main.eng.stats.clone()
+        tot = bufs(main)[3].clone()
         for n, st in steps.items():
             if n != batch:
-                tot += st.eng.stats
+                tot += bufs(st)[3]
         rec = {"epoch": ep, "train": f1_metrics(tot, model.mm_mlp.output_size)}
         if fuse_patterns:  # one pass over the validation corpus for the monitored loss and every pattern's metrics
             ev = evaluate_patterns(model, val, batch, loss_functions, patterns)
