@@ -59,7 +59,9 @@ enum {
  * row's own windows (per-sample text lengths read on the device); tspm_adam_begin_multi / tspm_adam_step_multi /
  * tspm_grad_clip_coef_multi, the optimizer phase of a step with up to 8 FusedAdam groups in the launches one group
  * takes; tspm_lstm_bwd_seq, the backward recurrence with a gradient at every step, and tspm_attn_pool_fwd /
- * tspm_attn_pool_bwd, the attention pooling of LSTMEncoder(embd_method="attention"). */
+ * tspm_attn_pool_bwd, the attention pooling of LSTMEncoder(embd_method="attention"); tspm_pattern_head_train_step /
+ * tspm_pattern_head_train_workspace, the AVMNIST fusion head's train step (forward, dropout, cross-entropy, weight
+ * backward) over every missing-modality pattern of a batch whose encoders are frozen, in two launches. */
 #define TSPM_ABI_VERSION 23
 int tspm_abi_version(void);  /* returns TSPM_ABI_VERSION */
 /* Static string for a status code. */
@@ -1136,6 +1138,65 @@ typedef struct tspm_pattern_head_eval_desc {
 } tspm_pattern_head_eval_desc;
 size_t tspm_pattern_head_eval_workspace(int32_t batch, int32_t npat);
 int tspm_pattern_head_eval(const tspm_pattern_head_eval_desc* desc, tspm_stream_t stream);
+
+/* All-pattern head TRAIN step (added under ABI 23) — tspm_head_train_step (forward, dropout, weighted cross-entropy,
+ * the head's whole weight backward) for EVERY missing-modality pattern of a batch in one call, for the head stage on
+ * frozen encoders: an encoder on its running statistics is a per-row function, so the embedding of a zeroed modality
+ * is the constant row x0 and never changes while only the head trains.  Inputs as in tspm_pattern_head_eval (x, x0,
+ * HOST keep [npat][2], the six weights, labels [batch]) plus tspm_head_desc's dropout fields.  For p < npat and
+ * b < batch, row = p*batch + b, the head's input is x[b]'s columns per kept modality, else x0's:
+ *   logits[row]                  [npat*batch][classes]
+ *   loss[0]                      = loss_weight * mean over ALL npat*batch rows of CE(logits[row], labels[b])
+ *   stats (nullable)             stats[0] += sum CE, stats[1] += #(argmax == label), stats[2] += npat*batch
+ *   adam_step (nullable)         += 1 by launch 2, after launch 1 read `counter` (as tspm_head_desc.adam_step)
+ *   gw0 gb0 gw3 gb3 gw5 gb5      overwritten with the gradients of loss[0]
+ * There is no dx: the encoders are frozen and nobody reads it.  The per-row h1, hh, dlogits and dz3 that the
+ * weight-gradient launch reads live in the workspace.  Dropout: the mask of row p*batch + b is drawn per (pattern,
+ * sample) row; with gen_keep = 1 the bytes written to keep_mask [npat*batch][hidden] are those of
+ * tspm_dropout_mask(npat*batch*hidden, p, seed, counter); with gen_keep = 0 keep_mask is read.  Semantics: those of
+ * tspm_pattern_expand followed by tspm_head_train_step with n = npat*batch, up to summation order; an out-of-range
+ * label gives a NaN loss and NaN gradients (nothing read out of bounds) and never counts as correct.
+ * Two launches.  (1) One workgroup of 512 threads per sample (at most 256 workgroups, each walking its samples),
+ * weights staged in LDS as tspm_head_train_step stages them.  fc0 is linear in the concatenated input: the audio-half
+ * and image-half products of x0 are formed once per workgroup and those of a sample once (2 half products per sample
+ * instead of npat full ones); fc3, fc5, the cross-entropy and the backward down to dz0 run on the sample's npat rows.
+ * The same algebra runs backwards: per modality m the workgroup writes fold_m[b] = sum over the p that keep m of
+ * dz0[p*batch + b] (ascending p) and accumulates zsum_m = sum over the p that drop m and its samples b of the same (its
+ * samples in ascending b, p ascending inside), one partial row per workgroup.  (2) The weight gradients on the
+ * small-GEMM tiles — gw5 / gw3 over the npat*batch rows, and gw0[:, cols_m] = sum_b fold_m[b]^T (x) x[b, cols_m]
+ * + sum_g zsum_m[g]^T (x) x0[cols_m] as ONE product per modality whose K is batch + workgroups (not npat*batch),
+ * gb0 its row sums — plus the loss workgroup (tspm_head_train_step's fixed-order sums, in double).  No floating-point
+ * atomics; every sum has a fixed order; eager, captured and replayed calls are bitwise equal.  A sample's npat logits
+ * rows depend on x[b], x0, the weights, keep and the rows' masks only.
+ * Limits: tspm_head_train_step's (in <= 256, hidden <= 256, hidden2 <= 128, classes <= 16; in, hidden, hidden2
+ * multiples of 4; ldx >= in and a multiple of 4; x, x0, w0, w3, w5 16-byte aligned; 0 <= p < 1, keep_mask required when
+ * p > 0) plus 0 < w_audio < in, w_audio % 4 == 0, 1 <= npat <= TSPM_PATTERN_HEAD_MAX_PATTERNS; weights plus the npat
+ * row buffers within 160 KiB of LDS (tspm_pattern_head_eval's formula).  x0 may be NULL when every pattern keeps both
+ * modalities.  Anything else, or a NULL among x, keep, the six weights, labels, logits, the six gradients, loss:
+ * TSPM_ERR_INVALID; a missing, misaligned or short workspace with the other arguments valid: TSPM_ERR_WORKSPACE.
+ * Nothing is launched on error. */
+typedef struct tspm_pattern_head_train_desc {
+  int32_t batch, npat, in, w_audio, hidden, hidden2, classes, ldx;
+  int32_t gen_keep, reserved_;
+  const float* x;           /* [batch, ldx] */
+  const float* x0;          /* [in] */
+  const int32_t* keep;      /* HOST [npat][2]: (audio, image), non-zero = the real input */
+  const float *w0, *b0, *w3, *b3, *w5, *b5;
+  const int64_t* labels;    /* [batch] */
+  float p;                  /* dropout probability (0: no mask) */
+  float loss_weight;        /* the cross-entropy term's weight */
+  uint64_t seed;
+  const uint64_t* counter;  /* device step counter (fresh masks per graph replay) */
+  uint8_t* keep_mask;       /* [npat*batch, hidden] */
+  float* logits;            /* [npat*batch, classes] */
+  float *gw0, *gb0, *gw3, *gb3, *gw5, *gb5;
+  float *loss, *stats;      /* stats nullable */
+  int64_t* adam_step;       /* nullable */
+  void* workspace;          /* tspm_pattern_head_train_workspace(batch, npat) bytes, 16-byte aligned */
+  size_t workspace_bytes;
+} tspm_pattern_head_train_desc;
+size_t tspm_pattern_head_train_workspace(int32_t batch, int32_t npat);
+int tspm_pattern_head_train_step(const tspm_pattern_head_train_desc* desc, tspm_stream_t stream);
 
 /* All-pattern MMIMDb fusion (added under ABI 23) — tspm_gmu_fwd for EVERY missing-modality pattern of a batch in one
  * launch.  In eval mode an encoder's output row depends on that row's input and the weights only, and fc_one / fc_two

@@ -16,12 +16,13 @@ from ._lib import TspmError, TspmLibraryError
 from .engine import EncoderEngine, prepare_encoder_layout
 from .modules import AVMNIST, BasicBlock, ResNet18, ResNet34, ResNetEncoder, modality_key
 from .optim import FusedAdam
-from .step import FusedTrainStep
+from .step import FusedHeadStagePatternStep, FusedHeadStageStep, FusedTrainStep
 from .monomodal import FusedMonoStep, MonomodalEncoder
 from . import plugin, ddp, data, monomodal, mmimdb
 from .mmimdb import MMIMDb, FusedMMIMDbStep
 
 __all__ = ["AVMNIST", "BasicBlock", "ResNet18", "ResNet34", "ResNetEncoder", "FusedAdam", "FusedTrainStep",
+           "FusedHeadStageStep", "FusedHeadStagePatternStep",
            "EncoderEngine", "prepare_encoder_layout", "TspmError", "TspmLibraryError", "plugin", "ddp", "data",
            "modality_key", "MonomodalEncoder", "FusedMonoStep", "monomodal", "mmimdb", "MMIMDb", "FusedMMIMDbStep"]
 __version__ = "0.1.0"

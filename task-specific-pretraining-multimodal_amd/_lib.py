@@ -211,6 +211,27 @@ def pattern_head_eval_supported(in_: int, w_audio: int, hidden: int, hidden2: in
     return floats * 4 <= 160 * 1024
 
 
+class PatternHeadTrainDesc(Structure):
+    """tspm_pattern_head_train_desc (added under ABI 23): AVMNIST's fusion head train step (forward, dropout,
+    cross-entropy, weight backward) over every missing-modality pattern of a batch whose encoders are frozen, in two
+    launches; ``keep`` is a host int32 array."""
+    _fields_ = [(n, c_int32) for n in ("batch", "npat", "in_", "w_audio", "hidden", "hidden2", "classes", "ldx",
+                                       "gen_keep", "reserved_")] + \
+        [("x", c_void_p), ("x0", c_void_p), ("keep", POINTER(c_int32))] + \
+        [(n, c_void_p) for n in ("w0", "b0", "w3", "b3", "w5", "b5", "labels")] + \
+        [("p", c_float), ("loss_weight", c_float), ("seed", c_uint64)] + \
+        [(n, c_void_p) for n in ("counter", "keep_mask", "logits", "gw0", "gb0", "gw3", "gb3", "gw5", "gb5", "loss",
+                                 "stats", "adam_step", "workspace")] + [("workspace_bytes", c_size_t)]
+
+
+def pattern_head_train_supported(in_: int, w_audio: int, hidden: int, hidden2: int, classes: int, npat: int) -> bool:
+    """Python mirror of tspm_pattern_head_train_step's shape checks: tspm_head_train_step's limits, sizes % 4,
+    0 < w_audio < in, 1..8 patterns, and the weights plus the P row buffers in at most 160 KiB of LDS (the launch-1
+    kernel keeps tspm_pattern_head_eval's LDS layout).  False = the call would return TSPM_ERR_INVALID for this head
+    whatever the pointers; FusedHeadStagePatternStep then takes its ``launches`` leg."""
+    return pattern_head_eval_supported(in_, w_audio, hidden, hidden2, classes, npat)
+
+
 GMU_PATTERN_MAX_D = 4095  # TSPM_GMU_PATTERN_MAX_D: (4d + 4) floats of LDS within 64 KiB
 
 
@@ -445,6 +466,9 @@ _SIGS = {
     # added under ABI 23: AVMNIST's eval head + cross-entropy + classification log for every pattern of a batch
     "tspm_pattern_head_eval_workspace": (c_size_t, [c_int32, c_int32]),
     "tspm_pattern_head_eval": (c_int32, [POINTER(PatternHeadEvalDesc), _P]),
+    # added under ABI 23: the head's train step over every pattern of a batch on frozen encoders (the AVMNIST head stage)
+    "tspm_pattern_head_train_workspace": (c_size_t, [c_int32, c_int32]),
+    "tspm_pattern_head_train_step": (c_int32, [POINTER(PatternHeadTrainDesc), _P]),
     # added under ABI 23: MMIMDb's GMU and BCEWithLogits for every pattern of a batch
     "tspm_gmu_pattern_fwd": (c_int32, [c_int32, c_int32, POINTER(c_int32), c_int32, _P, c_int32, _P, _P, _P, c_int32,
                                        _P, _P, c_int32, _P]),

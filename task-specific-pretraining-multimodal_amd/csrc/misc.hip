@@ -1512,6 +1512,339 @@ extern "C" int tspm_pattern_head_eval(const tspm_pattern_head_eval_desc* desc, t
 }
 
 // ------------------------------------------------------------------------------------------------
+// All-pattern head train step (tspm_pattern_head_train_step, added under ABI 23): tspm_head_train_step over the
+// npat * batch (pattern, sample) rows of a batch whose encoders are frozen, without ever forming those rows' inputs.
+// Launch 1 (k_pattern_head_train_rows): k_pattern_head_rows' shape (one workgroup per sample, at most PH_MAXGRID,
+// weights in LDS, fc0 as two half products per sample) with k_head_rows' dropout, cross-entropy gradient and
+// backward down to dz0 on the sample's P rows.  dz0 leaves the workgroup folded: fold_m[b] (the patterns that keep
+// modality m) per sample, and the workgroup's running sum over the patterns that drop m as ONE extra row of the fold
+// buffer per workgroup, paired with a copy of x0 as that row's input — so fc0's weight gradient is one product per
+// modality over batch + grid rows (launch 2), and its row sums are gb0.  dx is never formed.
+// Launch 2 (k_pattern_head_wgrad): k_head_wgrad's body (a copy: sharing it would re-generate that kernel) over four
+// products, with the loss workgroup riding along.
+// The bodies below duplicate rather than parametrise the eval / train kernels' so that those keep their code.
+// ------------------------------------------------------------------------------------------------
+namespace {
+
+struct PatTrainArgs {
+  tspm_pattern_head_train_desc d;  // keep (host pointer) is not read on the device
+  int keep[PH_MAXP][2];
+  float scale;                     // 1/(1-p), or 1
+  int grid;                        // workgroups of launch 1 (= extra rows of fold / xe)
+  // workspace views
+  float *h1, *hh, *dlogits, *dz3;  // [P*B][H], [P*B][H2], [P*B][C], [P*B][H2]
+  float* row_ws;                   // [2][P*B]: per-row CE terms, correct flags
+  float* fold;                     // [2][B + grid][H]
+  float* xe;                       // [B + grid][F]: x's rows, then x0 once per workgroup
+};
+
+// the workspace's float counts for a (batch, npat) at the largest head: sized without the head's shape, laid out with it
+size_t pat_train_ws_bytes(int batch, int npat) {
+  const size_t pb = (size_t)batch * npat, r = (size_t)batch + (batch < PH_MAXGRID ? batch : PH_MAXGRID);
+  const size_t floats = pb * (HEAD_MAXH + 2 * HEAD_MAXH2 + HEAD_MAXC) + ((2 * pb + 3) & ~(size_t)3) +
+                        r * (2 * HEAD_MAXH + HEAD_MAXIN);
+  return floats * sizeof(float);
+}
+
+__global__ __launch_bounds__(PH_THREADS) void k_pattern_head_train_rows(PatTrainArgs a) {
+  const tspm_pattern_head_train_desc& d = a.d;
+  extern __shared__ float lds[];
+  const int F = d.in, H = d.hidden, H2 = d.hidden2, C = d.classes, P = d.npat, WA = d.w_audio, B = d.batch;
+  const int ldx = F + 4, ldh = H + 4, ldh2 = H2 + 4, ldc = head_ldc(C);
+  float* sw0 = lds;                 // [H][F + 4]
+  float* sw3 = sw0 + H * ldx;       // [H2][H + 4]
+  float* sw5 = sw3 + H2 * ldh;      // [C][H2 + 4]
+  float* sx = sw5 + C * ldh2;       // [2][F + 4]: the sample's row, x0
+  float* spart = sx + 2 * ldx;      // [2][2][H]: (sample | x0) x (audio half | image half) of fc0
+  float* sh1 = spart + 4 * H;       // [P][H + 4]: h1, then dz0
+  float* shh = sh1 + P * ldh;       // [P][H2 + 4]: hh, then dz3
+  float* sz = shh + P * ldh2;       // [P][ldc]: logits, then dlogits
+  float* sb0 = sz + P * ldc;        // biases [H], [H2], [C]
+  float* sb3 = sb0 + H;
+  float* sb5 = sb3 + H2;
+  const int t = threadIdx.x;
+  const long long PB = (long long)P * B;
+  const int R = B + a.grid;         // rows of a fold plane / of xe
+  uint64_t base = 0;
+  {
+    const HeadSeg g0{d.w0, sw0, H, F / 4, H, F}, g3{d.w3, sw3, H2, H / 4, H2, H}, g5{d.w5, sw5, C, H2 / 4, C, H2};
+    constexpr int U0 = (128 * 192 / 4 + PH_THREADS - 1) / PH_THREADS, U3 = (64 * 128 / 4 + PH_THREADS - 1) / PH_THREADS;
+    f32x4 v0[U0], v3[U3], v5[1];
+    const uint64_t ctr = (d.p > 0.f && d.gen_keep && d.counter) ? *d.counter : 0ULL;
+    head_load(g0, v0);
+    head_load(g3, v3);
+    head_load(g5, v5);
+    head_store(g0, v0);
+    head_store(g3, v3);
+    head_store(g5, v5);
+    for (int i = t; i < H + H2 + C; i += PH_THREADS)
+      sb0[i] = i < H ? d.b0[i] : i < H + H2 ? d.b3[i - H] : d.b5[i - H - H2];
+    for (int i = t; i < F / 4; i += PH_THREADS) {
+      const f32x4 v = d.x0 ? ld4(d.x0 + 4 * i) : f32x4{0.f, 0.f, 0.f, 0.f};
+      st4(sx + ldx + 4 * i, v);
+      st4(a.xe + (long long)(B + blockIdx.x) * F + 4 * i, v);  // this workgroup's zsum rows pair with x0
+    }
+    if (d.p > 0.f && d.gen_keep) base = tspm_dropout_base(d.seed, ctr);
+  }
+  head_sync();
+  // the two halves of fc0 on row `xr` -> dst[half * H + o]
+  auto halves = [&](const float* xr, float* dst) {
+    for (int item = t; item < 2 * H; item += PH_THREADS) {
+      const int half = item >= H ? 1 : 0, o = item - half * H;
+      const int k0 = half ? WA : 0, K = half ? F - WA : WA;
+      dst[item] = pat_dot(xr + k0, sw0 + o * ldx + k0, K);
+    }
+  };
+  halves(sx + ldx, spart + 2 * H);
+  // thread t < 2H owns unit (m, o) = (t / H, t % H) of the folds (H <= 256: 2H <= PH_THREADS)
+  const int fm = t >= H ? 1 : 0, fo = t - fm * H;
+  float zs = 0.f;  // this workgroup's zsum_m[o]
+  const float invn = 1.0f / (float)PB;
+  for (int b = blockIdx.x; b < B; b += gridDim.x) {
+    // sx row 0 was last read before the previous sample's barriers
+    for (int i = t; i < F / 4; i += PH_THREADS) {
+      const f32x4 v = ld4(d.x + (long long)b * d.ldx + 4 * i);
+      st4(sx + 4 * i, v);
+      st4(a.xe + (long long)b * F + 4 * i, v);
+    }
+    head_sync();
+    halves(sx, spart);
+    head_sync();
+    // fc0 + ReLU + dropout (tspm_linear_fwd's epilogue order: + bias, relu, * keep*scale)
+    for (int item = t; item < P * H; item += PH_THREADS) {
+      const int p = item / H, o = item - p * H;
+      const float pa = spart[(a.keep[p][0] ? 0 : 2 * H) + o], pi = spart[(a.keep[p][1] ? 0 : 2 * H) + H + o];
+      float v = relu_f((pa + pi) + sb0[o]);
+      const long long i = ((long long)p * B + b) * H + o;
+      if (d.p > 0.f) {
+        bool kp;
+        if (d.gen_keep) {
+          kp = tspm_dropout_keep(base, i, d.p);
+          d.keep_mask[i] = kp ? 1 : 0;
+        } else {
+          kp = d.keep_mask[i] != 0;
+        }
+        v *= kp ? a.scale : 0.f;
+      }
+      sh1[p * ldh + o] = v;
+      a.h1[i] = v;
+    }
+    head_sync();
+    for (int item = t; item < P * H2; item += PH_THREADS) {
+      const int p = item / H2, o = item - p * H2;
+      const float v = relu_f(pat_dot(sh1 + p * ldh, sw3 + o * ldh, H) + sb3[o]);
+      shh[p * ldh2 + o] = v;
+      a.hh[((long long)p * B + b) * H2 + o] = v;
+    }
+    head_sync();
+    for (int item = t; item < P * C; item += PH_THREADS) {
+      const int p = item / C, o = item - p * C;
+      const float v = pat_dot(shh + p * ldh2, sw5 + o * ldh2, H2) + sb5[o];
+      sz[p * ldc + o] = v;
+      d.logits[((long long)p * B + b) * C + o] = v;
+    }
+    head_sync();
+    // cross-entropy per row (k_head_rows' arithmetic): 16 lanes per row, lane k owns class k; sz becomes dlogits
+    if (t < 16 * P) {
+      const int p = t >> 4, k = t & 15, l0 = (t & 63) & ~15;
+      float* z = sz + p * ldc;
+      const bool kv = k < C;
+      float mx = z[0];
+      int am = 0;
+      for (int j = 1; j < C; ++j)
+        if (z[j] > mx) { mx = z[j]; am = j; }
+      const float e = kv ? expf(z[k] - mx) : 0.f;
+      float se = 0.f;
+      for (int j = 0; j < C; ++j) se += __shfl(e, l0 + j, 64);
+      const long long lab64 = d.labels[b];
+      const bool lok = lab64 >= 0 && lab64 < C;  // out-of-range label: NaN loss / gradients, nothing read out of bounds
+      const int lab = lok ? (int)lab64 : 0;
+      const long long row = (long long)p * B + b;
+      if (k == 0) {
+        a.row_ws[row] = lok ? logf(se) - (z[lab] - mx) : __builtin_nanf("");
+        a.row_ws[PB + row] = (lok && am == lab) ? 1.f : 0.f;  // an out-of-range label is never correct
+      }
+      const float pk = e / se;
+      const float g = lok ? (pk - (k == lab ? 1.f : 0.f)) * invn * d.loss_weight : __builtin_nanf("");
+      if (kv) {  // after every lane of the row has read z (the row's 16 lanes sit in one wave: program order)
+        z[k] = g;
+        a.dlogits[row * C + k] = g;
+      }
+    }
+    head_sync();
+    // dz3 = (dlogits w5) * (hh > 0)   (w5 is [C][H2]) -> shh; item (p, o)'s hh value is read and overwritten by its
+    // own thread only
+    for (int item = t; item < P * H2; item += PH_THREADS) {
+      const int p = item / H2, o = item - p * H2;
+      float acc = 0.f;
+      for (int k = 0; k < C; ++k) acc = fmaf(sz[p * ldc + k], sw5[k * ldh2 + o], acc);
+      const float v = shh[p * ldh2 + o] > 0.f ? acc : 0.f;
+      shh[p * ldh2 + o] = v;
+      a.dz3[((long long)p * B + b) * H2 + o] = v;
+    }
+    head_sync();
+    // dz0 = (dz3 w3) * (h1 > 0 ? scale : 0)   (w3 is [H2][H]) -> sh1
+    for (int item = t; item < P * H; item += PH_THREADS) {
+      const int p = item / H, o = item - p * H;
+      const float* zp = shh + p * ldh2;
+      float acc = 0.f;
+      for (int k = 0; k < H2; k += 4) {
+        const f32x4 z4 = ld4(zp + k);
+        acc = fmaf(z4[0], sw3[(k + 0) * ldh + o], acc);
+        acc = fmaf(z4[1], sw3[(k + 1) * ldh + o], acc);
+        acc = fmaf(z4[2], sw3[(k + 2) * ldh + o], acc);
+        acc = fmaf(z4[3], sw3[(k + 3) * ldh + o], acc);
+      }
+      sh1[p * ldh + o] = sh1[p * ldh + o] > 0.f ? acc * a.scale : 0.f;
+    }
+    head_sync();
+    // the folds of dz0 (fc0's backward in the forward's algebra): ascending p, plain adds
+    if (t < 2 * H) {
+      float fk = 0.f;
+      for (int p = 0; p < P; ++p) {
+        const float v = sh1[p * ldh + fo];
+        if (a.keep[p][fm]) fk += v;
+        else zs += v;
+      }
+      a.fold[((long long)fm * R + b) * H + fo] = fk;
+    }
+    // the next sample writes sx / spart behind this iteration's barriers and sh1 only behind two more
+  }
+  if (t < 2 * H) a.fold[((long long)fm * R + B + blockIdx.x) * H + fo] = zs;
+}
+
+template <int WK>
+__global__ __launch_bounds__(64 * WK) void k_pattern_head_wgrad(GemmMulti mp, int total, PatTrainArgs a) {
+  extern __shared__ float lds[];
+  const int b = blockIdx.x;
+  if (b < total) {
+    int i = 0;
+    while (i + 1 < mp.count && b >= mp.start[i + 1]) ++i;  // workgroup-uniform
+    gemm_body<WK>(mp.p[i], b - mp.start[i], lds);
+    return;
+  }
+  // the loss: fixed-order sums of the per-row losses / correct flags over the P*B rows, in double
+  const tspm_pattern_head_train_desc& d = a.d;
+  const int n = d.npat * d.batch;
+  double* red = reinterpret_cast<double*>(lds);
+  const int T = 64 * WK;
+  double ls = 0.0, cs = 0.0;
+  for (int r = threadIdx.x; r < n; r += T) {
+    ls += (double)a.row_ws[r];
+    cs += (double)a.row_ws[n + r];
+  }
+  red[threadIdx.x] = ls;
+  red[T + threadIdx.x] = cs;
+  __syncthreads();
+  for (int s = T / 2; s > 0; s >>= 1) {
+    if (threadIdx.x < s) {
+      red[threadIdx.x] += red[threadIdx.x + s];
+      red[T + threadIdx.x] += red[T + threadIdx.x + s];
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    const float l = (float)(red[0] / (double)n);
+    d.loss[0] = l * d.loss_weight;
+    if (d.adam_step) d.adam_step[0] += 1;  // after launch 1 read the step counter (dropout), before any Adam launch
+    if (d.stats) {
+      d.stats[0] += (float)red[0];
+      d.stats[1] += (float)red[T];
+      d.stats[2] += (float)n;
+    }
+  }
+}
+
+}  // namespace
+
+extern "C" size_t tspm_pattern_head_train_workspace(int32_t batch, int32_t npat) {
+  if (batch <= 0 || npat <= 0 || npat > PH_MAXP) return 0;
+  return pat_train_ws_bytes(batch, npat);
+}
+
+extern "C" int tspm_pattern_head_train_step(const tspm_pattern_head_train_desc* desc, tspm_stream_t stream) {
+  if (!desc) return TSPM_ERR_INVALID;
+  const tspm_pattern_head_train_desc& d = *desc;
+  if (d.batch <= 0 || d.npat <= 0 || d.npat > PH_MAXP) return TSPM_ERR_INVALID;
+  if ((long long)d.batch * d.npat > (1LL << 24)) return TSPM_ERR_INVALID;  // row indices and counts stay exact in float
+  if (d.in <= 0 || d.hidden <= 0 || d.hidden2 <= 0 || d.classes <= 0) return TSPM_ERR_INVALID;
+  if (d.in > HEAD_MAXIN || d.hidden > HEAD_MAXH || d.hidden2 > HEAD_MAXH2 || d.classes > HEAD_MAXC)
+    return TSPM_ERR_INVALID;
+  if (d.in % 4 || d.hidden % 4 || d.hidden2 % 4 || d.w_audio % 4 || d.w_audio <= 0 || d.w_audio >= d.in)
+    return TSPM_ERR_INVALID;
+  if (d.ldx < d.in || d.ldx % 4) return TSPM_ERR_INVALID;
+  if (!d.x || !d.keep || !d.w0 || !d.b0 || !d.w3 || !d.b3 || !d.w5 || !d.b5 || !d.labels || !d.logits || !d.gw0 ||
+      !d.gb0 || !d.gw3 || !d.gb3 || !d.gw5 || !d.gb5 || !d.loss)
+    return TSPM_ERR_INVALID;
+  if (!aligned16(d.x) || !aligned16(d.x0) || !aligned16(d.w0) || !aligned16(d.w3) || !aligned16(d.w5))
+    return TSPM_ERR_INVALID;
+  if (!(d.p >= 0.f && d.p < 1.f) || (d.p > 0.f && !d.keep_mask)) return TSPM_ERR_INVALID;
+  PatTrainArgs a{};
+  a.d = d;
+  bool drops = false;
+  for (int p = 0; p < d.npat; ++p) {
+    a.keep[p][0] = d.keep[2 * p] != 0;
+    a.keep[p][1] = d.keep[2 * p + 1] != 0;
+    drops = drops || !a.keep[p][0] || !a.keep[p][1];
+  }
+  if (drops && !d.x0) return TSPM_ERR_INVALID;
+  const size_t lds_rows = pat_head_lds_floats(d.in, d.hidden, d.hidden2, d.classes, d.npat) * sizeof(float);
+  if (lds_rows > 160 * 1024) return TSPM_ERR_INVALID;
+  if (!d.workspace || !aligned16(d.workspace) || d.workspace_bytes < pat_train_ws_bytes(d.batch, d.npat))
+    return TSPM_ERR_WORKSPACE;
+  const int B = d.batch, P = d.npat, F = d.in, H = d.hidden, H2 = d.hidden2, C = d.classes;
+  const int grid = B < PH_MAXGRID ? B : PH_MAXGRID, R = B + grid;
+  const size_t pb = (size_t)B * P;
+  // every view starts on a 16-byte boundary (H, H2, F are multiples of 4; the odd-sized ones are rounded up) and the
+  // sum stays below pat_train_ws_bytes' (the same terms at the largest head)
+  float* w = static_cast<float*>(d.workspace);
+  a.h1 = w;          w += pb * H;
+  a.hh = w;          w += pb * H2;
+  a.dz3 = w;         w += pb * H2;
+  a.dlogits = w;     w += (pb * C + 3) & ~(size_t)3;
+  a.row_ws = w;      w += (2 * pb + 3) & ~(size_t)3;
+  a.fold = w;        w += (size_t)2 * R * H;
+  a.xe = w;
+  a.scale = d.p > 0.f ? 1.0f / (1.0f - d.p) : 1.0f;
+  a.grid = grid;
+  a.d.keep = nullptr;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(k_pattern_head_train_rows, dim3(grid), dim3(PH_THREADS), lds_rows, st, a);
+  TSPM_LAUNCH_CHECK();
+  // weight gradients: dw[o,i] = sum_n dz[n,o] in[n,i], db[o] = sum_n dz[n,o] (tspm_linear_bwd_weight's operands).
+  // fc5 / fc3 over the P*B rows; fc0 per modality over the B sample rows and the workgroups' zsum rows, whose inputs
+  // are x's columns / x0's; gb0 = the audio product's row sums (every pattern either keeps or drops the audio input,
+  // so the audio folds cover every row exactly once)
+  const int n = (int)pb;
+  GemmMulti mp{};
+  mp.p[0] = GemmArgs{C, H2, n, a.dlogits, 1, C, a.hh, H2, 1, d.gw5, H2, nullptr, 0, nullptr, 1.f, d.gb5};
+  mp.p[1] = GemmArgs{H2, H, n, a.dz3, 1, H2, a.h1, H, 1, d.gw3, H, nullptr, 0, nullptr, 1.f, d.gb3};
+  mp.p[2] = GemmArgs{H, d.w_audio, R, a.fold, 1, H, a.xe, F, 1, d.gw0, F, nullptr, 0, nullptr, 1.f, d.gb0};
+  mp.p[3] = GemmArgs{H, F - d.w_audio, R, a.fold + (size_t)R * H, 1, H, a.xe + d.w_audio, F, 1, d.gw0 + d.w_audio, F,
+                     nullptr, 0, nullptr, 1.f, nullptr};
+  mp.count = 4;
+  int total = 0, wk = 1;
+  for (int i = 0; i < 4; ++i) {
+    const int wv = gemm_wk(mp.p[i]);
+    wk = wv > wk ? wv : wk;
+    mp.start[i] = total;
+    total += cdiv(mp.p[i].M, 32) * cdiv(mp.p[i].N, 32);
+  }
+  mp.start[4] = total;
+  // LDS: the small-GEMM combine, or 2 x threads doubles for the loss workgroup
+  const size_t lds_gemm = (size_t)(wk - 1) * (16 * 64 + 32) * sizeof(float);
+  const size_t lds_loss = (size_t)2 * 64 * wk * sizeof(double);
+  const size_t lds = lds_gemm > lds_loss ? lds_gemm : lds_loss;
+  switch (wk) {
+    case 1: hipLaunchKernelGGL(k_pattern_head_wgrad<1>, dim3(total + 1), dim3(64), lds, st, mp, total, a); break;
+    case 2: hipLaunchKernelGGL(k_pattern_head_wgrad<2>, dim3(total + 1), dim3(128), lds, st, mp, total, a); break;
+    default: hipLaunchKernelGGL(k_pattern_head_wgrad<4>, dim3(total + 1), dim3(256), lds, st, mp, total, a); break;
+  }
+  TSPM_LAUNCH_CHECK();
+  return TSPM_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
 // Monomodal head step (ABI 23): classifier Linear forward, weighted cross-entropy, argmax(logits) and the
 // Linear's whole backward in ONE launch of ONE workgroup.  The problem is launch-bound ([128,64] x [64,3] at
 // the MOSI shapes), so the rows are not spread over workgroups: the workgroup walks the batch in chunks of

@@ -541,10 +541,12 @@ class AVMNIST(torch.utils.data.Dataset):
     def device_loader(self, batch_size: int, shuffle: bool = False, drop_last: bool = False,
                       generator: Optional[torch.Generator] = None, *, rank: int = 0, world_size: int = 1,
                       distributed: Optional[bool] = None, seed: int = 0, pattern: Optional[str] = None,
-                      out=None, fuse_patterns: bool = False) -> "DeviceLoader":
-        """``fuse_patterns`` (valid / test splits of the multimodal target): see :class:`DeviceLoader`."""
+                      out=None, fuse_patterns: bool = False, all_patterns: bool = False) -> "DeviceLoader":
+        """``fuse_patterns`` (valid / test splits of the multimodal target) and ``all_patterns`` (its train split): see
+        :class:`DeviceLoader`."""
         return DeviceLoader(self, batch_size, shuffle, drop_last, generator, rank=rank, world_size=world_size,
-                            distributed=distributed, seed=seed, pattern=pattern, out=out, fuse_patterns=fuse_patterns)
+                            distributed=distributed, seed=seed, pattern=pattern, out=out, fuse_patterns=fuse_patterns,
+                            all_patterns=all_patterns)
 
     def _check_fuse_patterns(self, pattern: Optional[str] = None) -> None:
         """A fused-pattern loader yields every sample once, unmasked; the step rebuilds each selected pattern from the
@@ -555,12 +557,27 @@ class AVMNIST(torch.utils.data.Dataset):
                               f"{self.target_modality!r}")
         if pattern is not None:
             raise L.TspmError("fuse_patterns=True evaluates every selected pattern of a batch; it excludes pattern=")
+        self._check_pattern_probs("fuse_patterns=True")
+
+    def _check_pattern_probs(self, what: str) -> None:
         for p in self.selected_patterns:
             probs = self.missing_patterns[p]
             want = {m: (1.0 if m[0] in p else 0.0) for m in MODALITIES}
             if any(probs.get(m, 1.0) != want[m] for m in MODALITIES):
-                raise L.TspmError(f"fuse_patterns=True needs 0 / 1 presence probabilities that match the pattern's name; "
+                raise L.TspmError(f"{what} needs 0 / 1 presence probabilities that match the pattern's name; "
                                   f"pattern {p!r} has {probs}")
+
+    def _check_all_patterns(self, pattern: Optional[str] = None) -> None:
+        """An all-pattern train loader yields every sample once, unmasked; the head-stage step trains every selected
+        pattern of the batch from the real embedding or the zero-input one (``_check_fuse_patterns``' rules, for the
+        train split)."""
+        if self.split != "train" or self.target_modality != "multimodal":
+            raise L.TspmError(f"all_patterns=True is for the multimodal train split (every sample trained under every "
+                              f"selected pattern in one step); this dataset is split {self.split!r}, target_modality "
+                              f"{self.target_modality!r}")
+        if pattern is not None:
+            raise L.TspmError("all_patterns=True trains every selected pattern of a batch; it excludes pattern=")
+        self._check_pattern_probs("all_patterns=True")
 
     def get_split(self) -> str:
         return self.split
@@ -602,6 +619,13 @@ class DeviceLoader:
     ``pattern_name`` / ``pattern_ids`` — ``step.FusedPatternEvalStep`` evaluates every pattern of such a batch from
     one encoder pass.  ``len`` counts these batches; distributed sharding is over the N samples.
 
+    ``all_patterns=True`` (the train split of the multimodal target; refused for other splits, a single-modality target,
+    together with ``pattern=`` or ``fuse_patterns=``, and for fractional presence probabilities): each sample is yielded
+    ONCE, unmasked, in the order the loader would have drawn anyway (shuffled or not), in batches that carry
+    ``"patterns": list(selected_patterns)`` and ``"all_patterns": True`` and no ``pattern_name`` / ``pattern_ids`` —
+    ``step.FusedHeadStagePatternStep`` trains the fusion head under every pattern of such a batch in one step, on
+    frozen encoders (``AVMNIST.freeze_encoders``).
+
     ``out=(audio, image, labels)``: full batches are written into these caller-owned buffers (e.g. a
     ``FusedTrainStep``'s static inputs, so the step consumes the gather's output in place) and the
     yielded dict holds those same tensors — consume each batch before advancing the iterator."""
@@ -609,12 +633,17 @@ class DeviceLoader:
     def __init__(self, dataset: AVMNIST, batch_size: int, shuffle: bool = False, drop_last: bool = False,
                  generator: Optional[torch.Generator] = None, *, rank: int = 0, world_size: int = 1,
                  distributed: Optional[bool] = None, seed: int = 0, pattern: Optional[str] = None, out=None,
-                 fuse_patterns: bool = False):
+                 fuse_patterns: bool = False, all_patterns: bool = False):
         if batch_size <= 0:
             raise ValueError("batch_size must be positive")
         self.fuse_patterns = bool(fuse_patterns)
+        self.all_patterns = bool(all_patterns)
+        if self.fuse_patterns and self.all_patterns:
+            raise L.TspmError("fuse_patterns=True (valid / test) and all_patterns=True (train) exclude each other")
         if self.fuse_patterns:
             dataset._check_fuse_patterns(pattern)
+        if self.all_patterns:
+            dataset._check_all_patterns(pattern)
         self.out = out
         self.ds, self.batch_size, self.shuffle, self.drop_last = dataset, batch_size, shuffle, drop_last
         self.generator, self.rank, self.world_size, self.seed = generator, rank, world_size, seed
@@ -661,7 +690,7 @@ class DeviceLoader:
         if nb == 0:
             return
         order = order[:nb * self.batch_size] if self.drop_last else order
-        if self.fuse_patterns:
+        if self.fuse_patterns or self.all_patterns:
             yield from self._iter_fused(order, nb)
             return
         samples, names, am, im = self.ds._resolve(order)
@@ -678,7 +707,8 @@ class DeviceLoader:
             yield self.ds._pack(a, imt, lab, names[lo:hi], pid_d[lo:hi])
 
     def _iter_fused(self, order: np.ndarray, nb: int) -> Iterator[Dict[Any, Any]]:
-        """The fused-pattern epoch: each sample once, unmasked (null masks), with the selected patterns named."""
+        """The fused-pattern (eval) or all-pattern (train) epoch: each sample once, unmasked (null masks), with the
+        selected patterns named."""
         dc = self.ds.device_corpus
         idx_d = torch.from_numpy(np.ascontiguousarray(order, dtype=np.int64)).pin_memory().to(dc.device, non_blocking=True)
         pats = list(self.ds.selected_patterns)
@@ -686,6 +716,7 @@ class DeviceLoader:
             lo, hi = b * self.batch_size, min(len(order), (b + 1) * self.batch_size)
             out = self.out if (self.out is not None and hi - lo == self.batch_size) else None
             a, imt, lab = dc.gather(idx_d[lo:hi], None, None, out=out)
-            batch: Dict[Any, Any] = {"labels": lab, "missing_masks": {}, "patterns": list(pats), "fused_patterns": True,
+            flag = "all_patterns" if self.all_patterns else "fused_patterns"
+            batch: Dict[Any, Any] = {"labels": lab, "missing_masks": {}, "patterns": list(pats), flag: True,
                                      self.ds.keys["audio"]: a, self.ds.keys["image"]: imt}
             yield batch

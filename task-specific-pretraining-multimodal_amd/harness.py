@@ -32,7 +32,8 @@ import torch
 from . import _lib as L
 from .metrics import ClassificationLog, DeviceMetricRecorder, RegressionLog, RegressionMetricRecorder
 from .modules import modality_key
-from .step import FusedEvalStep, FusedPatternEvalStep, FusedTrainStep, norm_avmnist_patterns
+from .step import (FusedEvalStep, FusedHeadStagePatternStep, FusedHeadStageStep, FusedPatternEvalStep, FusedTrainStep,
+                   head_stage_frozen, norm_avmnist_patterns, train_step_key)
 
 # the AVMNIST YAML's metric block (configs/avmnist/centralised/train_avmnist_resnet.yaml:105-166)
 AVMNIST_METRICS = {
@@ -120,7 +121,10 @@ class EpochRunner:
     on the device (data.DeviceLoader / the drop-in DataLoader); batches of the runner's size are fed
     through the static buffers of one captured graph, a smaller last batch through a second one.  A
     ``"fused_patterns"`` batch (the samples once, unmasked) is one ``FusedPatternEvalStep`` replay that writes one loss
-    entry per pattern, in pattern order, and every row's count under its pattern."""
+    entry per pattern, in pattern order, and every row's count under its pattern.  A model with frozen encoders
+    (``AVMNIST.freeze_encoders``) trains on ``FusedHeadStageStep``, and an ``"all_patterns"`` train batch on
+    ``FusedHeadStagePatternStep`` (one loss entry per step, every row's count under its pattern); both live in
+    ``train_steps`` under ``step.train_step_key``'s keys, which for an all-trainable model are the batch sizes."""
 
     def __init__(self, model, optimizer, loss_functions, metric_config=None, device=None, log_capacity: int = 1 << 16):
         self.model, self.optimizer, self.loss_functions = model, optimizer, loss_functions
@@ -131,11 +135,28 @@ class EpochRunner:
         self.eval_steps: Dict[int, FusedEvalStep] = {}
         self.pattern_eval_steps: Dict[Tuple[Tuple[str, ...], int], FusedPatternEvalStep] = {}
 
-    def _train_step(self, n: int) -> FusedTrainStep:
-        st = self.train_steps.get(n)
+    def _train_step(self, n: int):
+        key = train_step_key(self.model, n)
+        st = self.train_steps.get(key)
         if st is None:
-            st = FusedTrainStep(self.model, self.optimizer, self.loss_functions, n)
-            self.train_steps[n] = st
+            # the flags are read (and every unsupported combination refused) before anything is built
+            cls = FusedHeadStageStep if head_stage_frozen(self.model, self.optimizer) else FusedTrainStep
+            st = cls(self.model, self.optimizer, self.loss_functions, n)
+            self.train_steps[key] = st
+        st.log = self.log
+        return st
+
+    def train_pattern_step_for(self, n: int, patterns=None) -> FusedHeadStagePatternStep:
+        """The cached FusedHeadStagePatternStep for (patterns, batch size) — every pattern of an ``"all_patterns"`` batch
+        (``data.AVMNIST.device_loader(all_patterns=True)``) trained in one step on frozen encoders; refused (with the
+        BatchNorm argument) for a model whose encoders are not frozen."""
+        pats = norm_avmnist_patterns(patterns)
+        head_stage_frozen(self.model, self.optimizer, all_patterns=True)
+        key = train_step_key(self.model, n, pats)
+        st = self.train_steps.get(key)
+        if st is None or st.eng_a is not self.model.audio_encoder.engine_for(st.A):  # the model dropped its engines
+            st = FusedHeadStagePatternStep(self.model, self.optimizer, self.loss_functions, n, patterns=pats)
+            self.train_steps[key] = st
         st.log = self.log
         return st
 
@@ -175,7 +196,14 @@ class EpochRunner:
         """→ (mean batch loss, seconds, metrics dict, batches)."""
         self.log.reset()
         t0 = time.time()
+        fresh_zero = False  # the zero-input embeddings of an all-pattern epoch: refreshed on its first batch only
         for b in loader:
+            if b.get("all_patterns"):
+                a, i = b[modality_key(b, "audio")], b[modality_key(b, "image")]
+                st = self.train_pattern_step_for(a.shape[0], b["patterns"])
+                st.step(a, i, b["labels"], refresh_zero=not fresh_zero)
+                fresh_zero = True
+                continue
             a, i, lab, g = self._unpack(b)
             self._train_step(a.shape[0]).step(a, i, lab, g)
         return self._finish(t0)

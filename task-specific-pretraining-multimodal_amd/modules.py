@@ -273,7 +273,8 @@ class _HeadFn(torch.autograd.Function):
         gw0, gb0 = torch.empty_like(w0), torch.empty(w0.shape[0], device=dev)
         dh = torch.empty(n, h2, device=dev)
         dh1 = torch.empty(n, hd, device=dev)
-        dfused = torch.empty_like(fused)
+        need_dx = ctx.needs_input_grad[0]  # False on frozen encoders (the head stage): nobody reads dfused
+        dfused = torch.empty_like(fused) if need_dx else None
         L.check(lib.tspm_linear_bwd_weight(n, h2, NUM_CLASSES, hh.data_ptr(), h2, g.data_ptr(), NUM_CLASSES,
                                            gw5.data_ptr(), gb5.data_ptr(), sh), "head fc5 wgrad")
         L.check(lib.tspm_linear_bwd_data(n, h2, NUM_CLASSES, g.data_ptr(), NUM_CLASSES, w5.data_ptr(), dh.data_ptr(), h2,
@@ -287,8 +288,9 @@ class _HeadFn(torch.autograd.Function):
         F = fused.shape[1]
         L.check(lib.tspm_linear_bwd_weight(n, F, hd, fused.data_ptr(), F, dh1.data_ptr(), hd, gw0.data_ptr(),
                                            gb0.data_ptr(), sh), "head fc0 wgrad")
-        L.check(lib.tspm_linear_bwd_data(n, F, hd, dh1.data_ptr(), hd, w0.data_ptr(), dfused.data_ptr(), F, sh),
-                "head fc0 dgrad")
+        if need_dx:
+            L.check(lib.tspm_linear_bwd_data(n, F, hd, dh1.data_ptr(), hd, w0.data_ptr(), dfused.data_ptr(), F, sh),
+                    "head fc0 dgrad")
         return dfused, None, gw0, gb0, gw3, gb3, gw5, gb5
 
 
@@ -316,6 +318,51 @@ class AVMNIST(nn.Module):
         self._rng_seed = int(torch.initial_seed()) & ((1 << 63) - 1)
         self._rng_ctr = None
         self.keep_override: Optional[torch.Tensor] = None  # parity hook: inject the dropout keep-mask
+        self._frozen_encoders: Tuple[str, ...] = ()  # freeze_encoders(): the encoders pinned to eval mode
+
+    # -- the head stage: frozen, pre-trained encoders (this project's opt-in; the reference's pretrained YAML ends up
+    #    with one all-trainable group and keeps that path) ------------------------------------------------
+    ENCODERS = ("audio_encoder", "image_encoder")
+
+    def freeze_encoders(self) -> "AVMNIST":
+        """Freeze BOTH encoders for the second training stage (the fusion head on pre-trained encoders): their
+        parameters get ``requires_grad_(False)`` and ``grad = None``, and the encoders are pinned to eval mode — a
+        frozen encoder always runs on its running statistics, whatever ``train(mode)`` says, so its parameters,
+        ``running_mean``, ``running_var`` and ``num_batches_tracked`` never change.  The head's dropout follows
+        ``mode`` as before.  Build the optimizer AFTER this call (FusedAdam's flat buffers hold the trainable
+        parameters only); ``train_step`` then runs ``step.FusedHeadStageStep``, and an ``all_patterns`` batch
+        ``step.FusedHeadStagePatternStep``."""
+        for name in self.ENCODERS:
+            enc = getattr(self, name)
+            for p in enc.parameters():
+                p.requires_grad_(False)
+                p.grad = None
+            enc.eval()
+        self._frozen_encoders = tuple(self.ENCODERS)
+        self._fused_step = None
+        return self
+
+    def unfreeze_encoders(self) -> "AVMNIST":
+        """Undo ``freeze_encoders``: every encoder parameter trainable again and the encoders back on the model's
+        mode.  An optimizer built while they were frozen does not hold them: build a new one."""
+        self._frozen_encoders = ()
+        for name in self.ENCODERS:
+            enc = getattr(self, name)
+            for p in enc.parameters():
+                p.requires_grad_(True)
+            enc.train(self.training)
+        self._fused_step = None
+        return self
+
+    def frozen_encoders(self) -> Tuple[str, ...]:
+        """Names of the encoders ``freeze_encoders`` pinned: ``()`` or ``("audio_encoder", "image_encoder")``."""
+        return getattr(self, "_frozen_encoders", ())
+
+    def train(self, mode: bool = True) -> "AVMNIST":
+        super().train(mode)
+        for name in getattr(self, "_frozen_encoders", ()):  # a frozen encoder stays on its running statistics
+            getattr(self, name).eval()
+        return self
 
     # -- dropout mask --------------------------------------------------------------------------------
     def _draw_keep(self, count: int, dev: torch.device) -> torch.Tensor:
@@ -371,11 +418,18 @@ class AVMNIST(nn.Module):
         metrics.DeviceMetricRecorder the batch's predictions are recorded on the device inside the step's
         HIP graph; with the reference's MetricRecorder they are copied to the host as the reference does."""
         from .step import FusedTrainStep, fused_step_supported
+        if batch.get("all_patterns"):
+            return self._train_step_all_patterns(batch, optimizer, loss_functions, device, metric_recorder)
         A, I, labels, miss_type = self._unpack(batch, device)
         dlog = self._device_log(metric_recorder)
         if fused_step_supported(self, optimizer, loss_functions, A, I):
             if self._fused_step is None or not self._fused_step.matches(A, I, optimizer, loss_functions):
-                self._fused_step = FusedTrainStep(self, optimizer, loss_functions, A.shape[0])
+                from .step import FusedHeadStageStep, head_stage_frozen
+                # the flags are read (and every unsupported combination refused) before anything is built
+                if head_stage_frozen(self, optimizer):
+                    self._fused_step = FusedHeadStageStep(self, optimizer, loss_functions, A.shape[0])
+                else:
+                    self._fused_step = FusedTrainStep(self, optimizer, loss_functions, A.shape[0])
             self._fused_step.log = dlog
             out = self._fused_step.step(A, I, labels, self._group_ids(batch, dlog, miss_type, device))
             logits = out["logits"]
@@ -396,6 +450,32 @@ class AVMNIST(nn.Module):
                                              m_types=np.array(miss_type if miss_type is not None else []))
         return {"loss": float(loss_t.item())}
 
+    def _train_step_all_patterns(self, batch, optimizer, loss_functions, device, metric_recorder):
+        """An ``"all_patterns"`` batch (data.AVMNIST.device_loader(all_patterns=True): the samples once, unmasked): one
+        ``FusedHeadStagePatternStep`` — the head trained under every pattern of the batch, on frozen encoders."""
+        from .step import FusedHeadStagePatternStep, fused_step_supported, head_stage_frozen, norm_avmnist_patterns
+        A, I, labels, _ = self._unpack(batch, device)
+        if not fused_step_supported(self, optimizer, loss_functions, A, I):
+            raise L.TspmError("an all_patterns batch runs on the fused head-stage step only: it needs this package's "
+                              "FusedAdam, a single cross-entropy loss term, device tensors and a fusion head within "
+                              "tspm_head_train_step's limits")
+        pats = norm_avmnist_patterns(batch["patterns"])
+        st = self.__dict__.get("_fused_pattern_step")
+        if st is None or not st.matches(A, I, optimizer, loss_functions, pats):
+            if not head_stage_frozen(self, optimizer, all_patterns=True):
+                raise AssertionError("unreachable: head_stage_frozen(all_patterns=True) refuses an unfrozen model")
+            st = FusedHeadStagePatternStep(self, optimizer, loss_functions, A.shape[0], patterns=pats)
+            self.__dict__["_fused_pattern_step"] = st
+        st.log = self._device_log(metric_recorder)
+        out = st.step(A, I, labels, refresh_zero=True)
+        if metric_recorder is not None and st.log is None:
+            P = len(pats)
+            predictions = torch.softmax(out["logits"].detach().reshape(P * A.shape[0], -1), dim=1).argmax(dim=1)
+            metric_recorder.update_group_all("classification", predictions=predictions.cpu().numpy(),
+                                             targets=np.tile(labels.detach().cpu().numpy(), P),
+                                             m_types=np.repeat(np.array(pats), A.shape[0]))
+        return {"loss": float(out["loss"].item())}
+
     def eval_step_for(self, loss_functions, batch: int, log=None):
         """The cached FusedEvalStep for this batch size (one HIP graph per size)."""
         from .step import FusedEvalStep
@@ -414,6 +494,7 @@ class AVMNIST(nn.Module):
         # whose graphs read them are bound to the old storage
         self.__dict__.pop("_zero_emb", None)
         self.__dict__.pop("_fused_pattern_eval", None)
+        self.__dict__.pop("_fused_pattern_step", None)
         return out
 
     def zero_embeddings(self, refresh: bool = True, audio_hw=(32, 94), image_hw=(28, 28)) -> torch.Tensor:

@@ -197,6 +197,9 @@ class FusedTrainStep(L.GraphRunner):
         if not head_supported(model):
             raise L.TspmError("FusedTrainStep: the fusion head's shape is outside tspm_head_train_step's limits "
                               "(use AVMNIST.train_step, which routes such heads to the autograd path)")
+        if head_stage_frozen(model):  # (refuses the unsupported flag combinations itself, naming the parameter)
+            raise L.TspmError("FusedTrainStep trains every parameter; a model with frozen encoders "
+                              f"{head_stage_frozen(model)} trains with FusedHeadStageStep (AVMNIST.train_step routes it)")
         self.N = batch
         self.allreduce = allreduce
         p0 = next(model.parameters())
@@ -837,3 +840,410 @@ class FusedPatternEvalStep(L.GraphRunner):
         self.run(refresh_zero)
         return {"loss": self.loss, "logits": self.logits.view(self.P, self.N, NUM_CLASSES),
                 "preds": self.preds.view(self.P, self.N)}
+
+
+# ------------------------------------------------------------------------------------------------------
+# The head stage: the fusion head trained on frozen, pre-trained encoders (AVMNIST.freeze_encoders)
+# ------------------------------------------------------------------------------------------------------
+ENCODER_NAMES = ("audio_encoder", "image_encoder")
+
+
+def head_stage_frozen(model, optimizer=None, allreduce=None, all_patterns: bool = False) -> Tuple[str, ...]:
+    """The model's frozen encoders as the fused steps may use them: ``()`` for an all-trainable model (the
+    ``FusedTrainStep`` path, untouched) or both encoder names for the head stage.  Everything else is refused here,
+    before anything is built, with a ``TspmError`` that names the module or parameter: mixed ``requires_grad`` flags
+    inside an encoder; exactly one encoder frozen; encoders frozen by hand (``requires_grad_(False)`` without
+    ``AVMNIST.freeze_encoders()``, which also pins them to eval mode — train-mode statistics of a frozen encoder are
+    out of scope); a head parameter that is not trainable; and, for a frozen model, ``allreduce`` and a ``FusedAdam``
+    whose flat buffers are not exactly the model's trainable parameters now.  ``all_patterns``: an all-pattern batch
+    needs the frozen encoders and is refused without them."""
+    frozen = {}
+    for name in ENCODER_NAMES:
+        enc = getattr(model, name)
+        flags = [(n, p.requires_grad) for n, p in enc.named_parameters()]
+        if flags and any(f != flags[0][1] for _, f in flags):
+            odd = next(n for n, f in flags if f != flags[0][1])
+            raise L.TspmError(f"{name}: mixed requires_grad flags inside an encoder ({name}.{flags[0][0]} is "
+                              f"{flags[0][1]}, {name}.{odd} is {not flags[0][1]}); an encoder is frozen as a whole "
+                              "(AVMNIST.freeze_encoders()) or not at all")
+        frozen[name] = bool(flags) and not flags[0][1]
+    pinned = tuple(getattr(model, "frozen_encoders", lambda: ())())
+    if sum(frozen.values()) == 1:
+        one = next(n for n in ENCODER_NAMES if frozen[n])
+        other = next(n for n in ENCODER_NAMES if not frozen[n])
+        raise L.TspmError(f"exactly one encoder is frozen ({one}; {other} is trainable): the head stage freezes both "
+                          "encoders (AVMNIST.freeze_encoders()); one frozen and one trainable encoder is not supported")
+    for name in ENCODER_NAMES:
+        enc = getattr(model, name)
+        if frozen[name] and (name not in pinned or enc.training):
+            raise L.TspmError(f"{name}: its parameters have requires_grad=False but the encoder is not pinned to eval "
+                              "mode; a frozen encoder on train-mode BatchNorm statistics is not supported - freeze with "
+                              "AVMNIST.freeze_encoders(), which pins it to its running statistics")
+        if name in pinned and not frozen[name]:
+            raise L.TspmError(f"{name}: pinned by AVMNIST.freeze_encoders() but its parameters are trainable again; "
+                              "call AVMNIST.unfreeze_encoders() to train it")
+    for n, p in model.net.named_parameters():
+        if not p.requires_grad:
+            raise L.TspmError(f"net.{n}: a head parameter that is not trainable; the fused steps train the whole head")
+    names = tuple(n for n in ENCODER_NAMES if frozen[n])
+    if not names:
+        if all_patterns:
+            raise L.TspmError(
+                "an all_patterns batch trains every missing-modality pattern of the batch in one step, which is exact "
+                "only on frozen encoders (AVMNIST.freeze_encoders()): a trainable encoder runs BatchNorm on batch "
+                "statistics, and the statistics of the B real rows are not those of the P*B replicated, masked rows "
+                "(DESIGN 3.19), so one encoder pass cannot stand for the replicated batch")
+        return ()
+    if allreduce is not None:
+        raise L.TspmError("allreduce: data parallelism for the head stage (frozen encoders) is not supported")
+    if isinstance(optimizer, FusedAdam):
+        fgs = optimizer.flat_groups()
+        if len(fgs) != 1:
+            raise L.TspmError(f"the head stage updates one FusedAdam group; the optimizer has {len(fgs)} non-empty groups")
+        have = {id(p): p for p in fgs[0].params}
+        for n, p in model.named_parameters():
+            if p.requires_grad != (id(p) in have):
+                what = "is trainable but not in" if p.requires_grad else "is frozen but still in"
+                raise L.TspmError(f"{n} {what} the FusedAdam's flat buffers: they must hold exactly the model's "
+                                  "trainable parameters (optimizer built before freeze_encoders(), or the flags changed "
+                                  "since) - build a new FusedAdam(model.parameters())")
+        if len(have) != sum(1 for p in model.parameters() if p.requires_grad):
+            raise L.TspmError("the FusedAdam holds parameters that are not the model's: build it from "
+                              "model.parameters() after freeze_encoders()")
+    return names
+
+
+def train_step_key(model, n: int, patterns=None):
+    """The cache key of a model's fused train step for batch size ``n``: ``n`` itself for an all-trainable model (every
+    existing key unchanged); with frozen encoders a tuple that ends in ``("frozen", names)``; an all-pattern step's
+    starts with ``("patterns", names)``."""
+    names = tuple(getattr(model, "frozen_encoders", lambda: ())())
+    if not names and patterns is None:
+        return n
+    key = ((("patterns", tuple(patterns)),) if patterns is not None else ()) + (n,)
+    return key + ((("frozen", names),) if names else ())
+
+
+class _HeadStageBase(L.GraphRunner):
+    """What the two head-stage steps share: the checks, the static inputs, both encoders' eval-mode forward on two
+    streams (``FusedEvalStep``'s), the head's flat gradient views, ``tspm_classify_update`` and Adam over the head's
+    one flat group (the head launch advances the step counter, so the update is one more launch)."""
+
+    def _setup(self, model, optimizer, loss_functions, batch: int, audio_hw, image_hw, use_graph: bool, what: str):
+        self.model, self.opt, self.loss_functions, self.N = model, optimizer, loss_functions, int(batch)
+        self.ce_weight = _ce_weight(loss_functions)
+        if self.ce_weight is None:
+            raise L.TspmError(f"{what}: the loss group must be a single cross-entropy term")
+        if not isinstance(optimizer, FusedAdam):
+            raise L.TspmError(f"{what}: the optimizer must be this package's FusedAdam")
+        if self.N < 1:
+            raise L.TspmError(f"{what}: batch must be >= 1")
+        self.frozen = head_stage_frozen(model, optimizer)
+        if not self.frozen:
+            raise L.TspmError(f"{what}: the model's encoders are not frozen (AVMNIST.freeze_encoders()); an all-trainable "
+                              "model trains with FusedTrainStep")
+        if not head_supported(model):
+            raise L.TspmError(f"{what}: the fusion head's shape is outside tspm_head_train_step's limits")
+        dev = next(model.parameters()).device
+        self._init_graph(use_graph, dev)
+        self.audio_hw, self.image_hw = tuple(audio_hw), tuple(image_hw)
+        f32 = dict(device=dev, dtype=torch.float32)
+        B = self.N
+        self.ea = int(model.embd_size_A)
+        self.F = self.ea + int(model.embd_size_I)
+        self.hd, self.h2 = int(model.hidden_dim), int(model.hidden_dim) // 2
+        self.A = torch.zeros(B, audio_hw[0], audio_hw[1], **f32)
+        self.I = torch.zeros(B, 1, image_hw[0], image_hw[1], **f32)
+        self.labels = torch.zeros(B, dtype=torch.int64, device=dev)
+        self.eng_a = model.audio_encoder.engine_for(self.A)
+        self.eng_i = model.image_encoder.engine_for(self.I)
+        self.loss = torch.zeros(1, **f32)
+        self.stats = torch.zeros(4, **f32)  # loss*n, correct, n (accumulated on device)
+        self.log = None
+        self.keep_override: Optional[torch.Tensor] = None
+        self.side = L.shared_streams(dev, 1)[0]
+        fg = optimizer.flat_groups()[0]
+        self.fg = fg
+        # the head's gradients go straight into FusedAdam's flat gradient buffer (its own views, whatever p.grad holds)
+        gv = {id(p): g for p, g in zip(fg.params, fg.grad_views)}
+        net = model.net
+        self.gptr = [gv[id(p)].data_ptr() for p in (net[0].weight, net[0].bias, net[3].weight, net[3].bias,
+                                                    net[5].weight, net[5].bias)]
+        # dropout RNG counter = FusedAdam's device step counter (group 0's hyper.step)
+        self._rng_ctr_ptr = fg.hyper.data_ptr() + L.HYPER_STEP_OFFSET
+        self._sig = (id(optimizer), id(loss_functions), self.N, ("frozen", self.frozen))
+
+    def _encoders(self, fused: torch.Tensor) -> int:
+        """Both encoders' eval-mode forward into ``fused [B, F]``; returns the main stream's handle."""
+        main = torch.cuda.current_stream()
+        self.side.wait_stream(main)
+        with torch.cuda.stream(self.side):
+            self.eng_i.forward(self.I, fused[:, self.ea:], self.F, train=False)
+        self.eng_a.forward(self.A, fused, self.F, train=False)
+        main.wait_stream(self.side)
+        return main.cuda_stream
+
+    def _head_bumps(self) -> bool:
+        """The head's second launch advances Adam's step counter (no clip coefficient: the range update has none)."""
+        return getattr(self.opt, "clip_coef", None) is None
+
+    def _adam(self, sh: int) -> None:
+        if self._head_bumps():
+            self.opt.launch_ranges(sh, [[(0, self.fg.numel)]])
+        else:
+            self.opt.launch(sh)
+
+    def _classify_rows(self, sh: int, n: int, logits, labels, groups) -> None:
+        log = self.log
+        if log is None:
+            return
+        L.check(L.lib().tspm_classify_update(
+            n, NUM_CLASSES, logits.data_ptr(), labels.data_ptr(), groups.data_ptr(), len(log.groups),
+            log.conf.data_ptr(), None, self.loss.data_ptr(), log.loss_log.data_ptr(), log.counters.data_ptr(),
+            log.capacity, sh), "classify_update")
+
+    def _load(self, A, I, labels) -> None:
+        for dst, src in ((self.A, A), (self.I, I), (self.labels, labels)):
+            if src.data_ptr() != dst.data_ptr():
+                dst.copy_(src.reshape(dst.shape), non_blocking=True)
+
+    def _still_frozen(self) -> None:
+        if tuple(self.model.frozen_encoders()) != self.frozen:
+            raise L.TspmError("the model's frozen encoders changed since this step was built: build a new step (and a new "
+                              "FusedAdam)")
+
+
+class FusedHeadStageStep(_HeadStageBase):
+    """AVMNIST.train_step on FROZEN encoders as one HIP graph: both encoders' eval-mode forward (running statistics,
+    two streams), ``tspm_head_train_step`` over the B rows (its dx goes to a scratch buffer nobody reads),
+    ``tspm_classify_update`` when a log is set, Adam over the head's one flat group.  The batch is what the train
+    loader yields: one random pattern per sample, masks applied to the inputs.  No encoder backward, no BatchNorm
+    statistics update: every encoder parameter and buffer is bitwise unchanged by any number of steps.  Any B >= 1."""
+
+    def __init__(self, model, optimizer: FusedAdam, loss_functions, batch: int, audio_hw=(32, 94), image_hw=(28, 28),
+                 use_graph: bool = True, allreduce=None):
+        if allreduce is not None:
+            head_stage_frozen(model, optimizer, allreduce)  # refuses it for a frozen model, naming why
+        self._setup(model, optimizer, loss_functions, batch, audio_hw, image_hw, use_graph, "FusedHeadStageStep")
+        dev, B = self.device, self.N
+        f32 = dict(device=dev, dtype=torch.float32)
+        self.groups = torch.zeros(B, dtype=torch.int32, device=dev)
+        self.fused = torch.empty(B, self.F, **f32)
+        self.h1 = torch.empty(B, self.hd, **f32)
+        self.hh = torch.empty(B, self.h2, **f32)
+        self.logits = torch.empty(B, NUM_CLASSES, **f32)
+        self.dlogits = torch.empty(B, NUM_CLASSES, **f32)
+        self.dh = torch.empty(B, self.h2, **f32)
+        self.dh1 = torch.empty(B, self.hd, **f32)
+        self.dscratch = torch.empty(B, self.F, **f32)  # the head's dx: written, never read
+        self.row_ws = torch.empty(2 * B, **f32)
+        self.keep = torch.ones(B, self.hd, dtype=torch.uint8, device=dev)
+        self.head_rows_per_block = int(os.environ.get("TSPM_HEAD_RB", "0"))
+
+    def matches(self, A, I, optimizer, loss_functions) -> bool:
+        return (self._sig == (id(optimizer), id(loss_functions), A.shape[0], ("frozen", tuple(self.model.frozen_encoders())))
+                and tuple(A.shape[1:]) == tuple(self.A.shape[1:]) and tuple(I.shape[-2:]) == tuple(self.I.shape[-2:]))
+
+    def _enqueue(self) -> None:
+        sh = self._encoders(self.fused)
+        net, g = self.model.net, (lambda t: t.data_ptr())
+        p = float(self.model.dropout_p)
+        gp = self.gptr
+        d = L.HeadDesc(n=self.N, in_=self.F, hidden=self.hd, hidden2=self.h2, classes=NUM_CLASSES, ldx=self.F,
+                       lddx=self.F, gen_keep=1 if (p > 0 and self.keep_override is None) else 0,
+                       x=g(self.fused), w0=g(net[0].weight), b0=g(net[0].bias), w3=g(net[3].weight), b3=g(net[3].bias),
+                       w5=g(net[5].weight), b5=g(net[5].bias), p=p, loss_weight=self.ce_weight,
+                       seed=int(self.model._rng_seed) if p > 0 else 0, counter=self._rng_ctr_ptr if p > 0 else None,
+                       keep=g(self.keep), labels=g(self.labels), h1=g(self.h1), hh=g(self.hh), logits=g(self.logits),
+                       dlogits=g(self.dlogits), dz3=g(self.dh), dz0=g(self.dh1), dx=g(self.dscratch),
+                       row_ws=g(self.row_ws), gw0=gp[0], gb0=gp[1], gw3=gp[2], gb3=gp[3], gw5=gp[4], gb5=gp[5],
+                       loss=g(self.loss), stats=g(self.stats),
+                       adam_step=self._rng_ctr_ptr if self._head_bumps() else None,
+                       rows_per_block=self.head_rows_per_block)
+        L.check(L.lib().tspm_head_train_step(d, sh), "head_train_step")
+        self._classify_rows(sh, self.N, self.logits, self.labels, self.groups)
+        self._adam(sh)
+
+    def load_batch(self, A, I, labels, groups=None) -> None:
+        if groups is not None and groups.data_ptr() != self.groups.data_ptr():
+            self.groups.copy_(groups.reshape(-1).to(torch.int32), non_blocking=True)
+        self._load(A, I, labels)
+
+    def run(self) -> None:
+        """One head-stage step on the batch in the static input buffers."""
+        self._still_frozen()
+        self.model.train()  # the head's dropout on; the frozen encoders stay pinned to eval
+        self.opt.sync_hyper()
+        if self.keep_override is not None:
+            self.keep.copy_(self.keep_override.reshape(self.keep.shape).to(torch.uint8), non_blocking=True)
+        self.replay_or_enqueue(self._enqueue, (self.log, self.keep_override is None, self._head_bumps()))
+        self.opt.note_steps(1)
+        self.calls += 1
+
+    def step(self, A, I, labels, groups=None) -> Dict[str, torch.Tensor]:
+        self.load_batch(A, I, labels, groups)
+        self.run()
+        return {"loss": self.loss, "logits": self.logits}
+
+
+# the head of a FusedHeadStagePatternStep built without head=: "kernel" (tspm_pattern_head_train_step) or "launches"
+# (tspm_pattern_expand + tspm_head_train_step over the P*B rows); the leg whose median measured lower at batch 128
+# (profiles/avmnist_head_stage.json, DESIGN §3.22)
+DEFAULT_HEAD_STAGE_HEAD = "kernel"
+
+
+class FusedHeadStagePatternStep(_HeadStageBase):
+    """The head stage on EVERY missing-modality pattern of a batch in one step, as one HIP graph.  A frozen encoder on
+    its running statistics is a per-row function and its weights do not move, so the embedding of a zeroed modality is
+    one constant row (``AVMNIST.zero_embeddings``) for the whole training: the graph holds both encoders' eval forward
+    over the B real, unmasked rows, then the head's forward, cross-entropy, backward over the P*B (pattern, sample)
+    rows — ``head="kernel"``: one ``tspm_pattern_head_train_step`` call (fc0 as two half products per sample, its
+    weight gradient over B + workgroups rows); ``head="launches"``: ``tspm_pattern_expand`` to ``[P*B, F]`` and
+    ``tspm_head_train_step`` with ``n = P*B`` (the A/B leg, and the fallback for a head outside the kernel's limits) —
+    then ``tspm_classify_update`` with every row under its pattern's group (ONE loss-log entry per step: the P*B-row
+    mean) and Adam.  ``loss`` is ``weight * mean CE`` over all P*B rows.
+
+    ``step(A, I, labels, refresh_zero=False)`` → ``{"loss": [1], "logits": [P, B, C]}``.  The zero embeddings are
+    computed when the step is built and again on ``refresh_zero=True`` (``EpochRunner.train_epoch`` asks once per
+    epoch; the weights that produce them are frozen)."""
+
+    def __init__(self, model, optimizer: FusedAdam, loss_functions, batch: int, patterns=None, head: Optional[str] = None,
+                 log=None, audio_hw=(32, 94), image_hw=(28, 28), use_graph: bool = True):
+        self.patterns = norm_avmnist_patterns(patterns)
+        self.P = P = len(self.patterns)
+        head_stage_frozen(model, optimizer, all_patterns=True)  # an unfrozen model: refused with the BatchNorm argument
+        self._setup(model, optimizer, loss_functions, batch, audio_hw, image_hw, use_graph, "FusedHeadStagePatternStep")
+        self.log = log
+        head = DEFAULT_HEAD_STAGE_HEAD if head is None else head
+        if head not in ("kernel", "launches"):
+            raise ValueError(f"head: 'kernel' or 'launches', got {head!r}")
+        if head == "kernel" and not L.pattern_head_train_supported(self.F, self.ea, self.hd, self.h2, NUM_CLASSES, P):
+            head = "launches"
+        dev, B = self.device, self.N
+        n = P * B
+        self.head = head
+        f32 = dict(device=dev, dtype=torch.float32)
+        self.x0 = model.zero_embeddings(refresh=True, audio_hw=self.audio_hw, image_hw=self.image_hw)
+        self.logits = torch.empty(n, NUM_CLASSES, **f32)
+        self.keep = torch.ones(n, self.hd, dtype=torch.uint8, device=dev)
+        self.labels_x = torch.zeros(n, dtype=torch.int64, device=dev)
+        self.groups = torch.zeros(n, dtype=torch.int32, device=dev)
+        self._keep2 = (ctypes.c_int32 * (2 * P))(*[k for p in self.patterns for k in PATTERN_KEEP[p]])
+        self._gid = (ctypes.c_int32 * P)()
+        if head == "kernel":
+            self.fused = torch.empty(B, self.F, **f32)
+            need = int(L.lib().tspm_pattern_head_train_workspace(B, P))
+            self.ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+        else:
+            # tspm_pattern_expand's layout (FusedPatternEvalStep's launches leg): rows [0, B) the real embeddings,
+            # rows [B, 2B) the zero-input row broadcast; the image columns go in as two halves under one keep flag
+            ei = self.F - self.ea
+            self.emb2 = torch.empty(2 * B, self.F, **f32)
+            self.fused = self.emb2[:B]
+            self._widths = (self.ea, ei // 2, ei - ei // 2)
+            self.x = torch.empty(n, self.F, **f32)
+            self.h1 = torch.empty(n, self.hd, **f32)
+            self.hh = torch.empty(n, self.h2, **f32)
+            self.dlogits = torch.empty(n, NUM_CLASSES, **f32)
+            self.dh = torch.empty(n, self.h2, **f32)
+            self.dh1 = torch.empty(n, self.hd, **f32)
+            self.dscratch = torch.empty(n, self.F, **f32)
+            self.row_ws = torch.empty(2 * n, **f32)
+            self._keep3 = (ctypes.c_int32 * (3 * P))(*[k for p in self.patterns
+                                                        for k in (PATTERN_KEEP[p][0],) + (PATTERN_KEEP[p][1],) * 2])
+        self._bound_groups = None  # the group ids last written to ``groups`` (kernel leg)
+        self._sig = self._sig + (self.patterns,)
+
+    def matches(self, A, I, optimizer, loss_functions, patterns) -> bool:
+        return (self._sig == (id(optimizer), id(loss_functions), A.shape[0],
+                              ("frozen", tuple(self.model.frozen_encoders())), tuple(patterns))
+                and tuple(A.shape[1:]) == tuple(self.A.shape[1:]) and tuple(I.shape[-2:]) == tuple(self.I.shape[-2:]))
+
+    def _group_ids(self) -> List[int]:
+        gid = self.log.gid if self.log is not None else {p: i for i, p in enumerate(AVMNIST_PATTERNS)}
+        try:
+            return [int(gid[p]) for p in self.patterns]
+        except KeyError as e:
+            raise L.TspmError(f"pattern {e} is not one of this log's groups {self.log.groups}") from None
+
+    def _enqueue(self) -> None:
+        for p, g in enumerate(self._group_ids()):
+            self._gid[p] = g
+        sh = self._encoders(self.fused)
+        self._head(sh)
+        self._classify_rows(sh, self.P * self.N, self.logits, self.labels_x, self.groups)
+        self._adam(sh)
+
+    def _head(self, sh: int) -> None:
+        """The head leg alone (forward, loss, weight backward over the P*B rows) from ``fused`` and ``x0``, either way."""
+        net, g = self.model.net, (lambda t: t.data_ptr())
+        p = float(self.model.dropout_p)
+        gp = self.gptr
+        gen_keep = 1 if (p > 0 and self.keep_override is None) else 0
+        seed = int(self.model._rng_seed) if p > 0 else 0
+        ctr = self._rng_ctr_ptr if p > 0 else None
+        bump = self._rng_ctr_ptr if self._head_bumps() else None
+        n, B, F = self.P * self.N, self.N, self.F
+        if self.head == "kernel":
+            d = L.PatternHeadTrainDesc(
+                batch=B, npat=self.P, in_=F, w_audio=self.ea, hidden=self.hd, hidden2=self.h2, classes=NUM_CLASSES,
+                ldx=F, gen_keep=gen_keep, x=g(self.fused), x0=g(self.x0), keep=self._keep2, w0=g(net[0].weight),
+                b0=g(net[0].bias), w3=g(net[3].weight), b3=g(net[3].bias), w5=g(net[5].weight), b5=g(net[5].bias),
+                labels=g(self.labels), p=p, loss_weight=self.ce_weight, seed=seed, counter=ctr, keep_mask=g(self.keep),
+                logits=g(self.logits), gw0=gp[0], gb0=gp[1], gw3=gp[2], gb3=gp[3], gw5=gp[4], gb5=gp[5],
+                loss=g(self.loss), stats=g(self.stats), adam_step=bump, workspace=g(self.ws),
+                workspace_bytes=self.ws.numel())
+            L.check(L.lib().tspm_pattern_head_train_step(d, sh), "pattern_head_train_step")
+        else:
+            # the P*B rows, their labels and their group ids in one launch
+            self.emb2[B:].copy_(self.x0.expand(B, F))
+            wa, wv, wt = self._widths
+            L.check(L.lib().tspm_pattern_expand(B, self.P, self._keep3, self._gid, wa, wv, wt, self.emb2.data_ptr(), F,
+                                                self.x.data_ptr(), F, self.labels.data_ptr(), self.labels_x.data_ptr(),
+                                                8, self.groups.data_ptr(), sh), "head stage pattern expand")
+            d = L.HeadDesc(n=n, in_=F, hidden=self.hd, hidden2=self.h2, classes=NUM_CLASSES, ldx=F, lddx=F,
+                           gen_keep=gen_keep, x=g(self.x), w0=g(net[0].weight), b0=g(net[0].bias), w3=g(net[3].weight),
+                           b3=g(net[3].bias), w5=g(net[5].weight), b5=g(net[5].bias), p=p, loss_weight=self.ce_weight,
+                           seed=seed, counter=ctr, keep=g(self.keep), labels=g(self.labels_x), h1=g(self.h1),
+                           hh=g(self.hh), logits=g(self.logits), dlogits=g(self.dlogits), dz3=g(self.dh),
+                           dz0=g(self.dh1), dx=g(self.dscratch), row_ws=g(self.row_ws), gw0=gp[0], gb0=gp[1],
+                           gw3=gp[2], gb3=gp[3], gw5=gp[4], gb5=gp[5], loss=g(self.loss), stats=g(self.stats),
+                           adam_step=bump, rows_per_block=0)
+            L.check(L.lib().tspm_head_train_step(d, sh), "head_train_step (P*B rows)")
+
+    def load_batch(self, A, I, labels) -> None:
+        """The batch into the static inputs.  The kernel leg never forms the P*B rows, so the per-row labels that
+        ``tspm_classify_update`` reads are laid out here, with the other input copies, outside the graph (the launches
+        leg's expand writes them)."""
+        self._load(A, I, labels)
+        if self.head == "kernel" and self.log is not None:
+            self.labels_x.view(self.P, self.N).copy_(self.labels.unsqueeze(0).expand(self.P, self.N), non_blocking=True)
+
+    def _bind_groups(self) -> None:
+        """Kernel leg: every row's group id for the current log (constant while the log is), written outside the graph."""
+        if self.head != "kernel" or self.log is None:
+            return
+        gids = tuple(self._group_ids())
+        if self._bound_groups != gids:
+            self.groups.copy_(torch.tensor(gids, dtype=torch.int32).repeat_interleave(self.N), non_blocking=False)
+            self._bound_groups = gids
+
+    def run(self, refresh_zero: bool = False) -> None:
+        """One head-stage step on the batch in the static input buffers, under every pattern."""
+        self._still_frozen()
+        self.model.train()
+        self.opt.sync_hyper()
+        if self.keep_override is not None:
+            self.keep.copy_(self.keep_override.reshape(self.keep.shape).to(torch.uint8), non_blocking=True)
+        # the graph reads the zero-row buffer by address: a model that dropped its buffer (moved) hands out another
+        self.x0 = self.model.zero_embeddings(refresh=refresh_zero, audio_hw=self.audio_hw, image_hw=self.image_hw)
+        self._bind_groups()
+        self.replay_or_enqueue(self._enqueue, (self.log, self.keep_override is None, self._head_bumps(),
+                                               self.x0.data_ptr()))
+        self.opt.note_steps(1)
+        self.calls += 1
+
+    def step(self, A, I, labels, refresh_zero: bool = False) -> Dict[str, torch.Tensor]:
+        self.load_batch(A, I, labels)
+        self.run(refresh_zero)
+        return {"loss": self.loss, "logits": self.logits.view(self.P, self.N, NUM_CLASSES)}
