@@ -61,7 +61,9 @@ enum {
  * takes; tspm_lstm_bwd_seq, the backward recurrence with a gradient at every step, and tspm_attn_pool_fwd /
  * tspm_attn_pool_bwd, the attention pooling of LSTMEncoder(embd_method="attention"); tspm_pattern_head_train_step /
  * tspm_pattern_head_train_workspace, the AVMNIST fusion head's train step (forward, dropout, cross-entropy, weight
- * backward) over every missing-modality pattern of a batch whose encoders are frozen, in two launches. */
+ * backward) over every missing-modality pattern of a batch whose encoders are frozen, in two launches;
+ * tspm_embed_gather and tspm_cached_head_train_step / tspm_cached_head_train_workspace, that head stage on a cache of
+ * the frozen encoders' embeddings (rows gathered by index; every pattern of the batch or one pattern per sample). */
 #define TSPM_ABI_VERSION 23
 int tspm_abi_version(void);  /* returns TSPM_ABI_VERSION */
 /* Static string for a status code. */
@@ -1197,6 +1199,78 @@ typedef struct tspm_pattern_head_train_desc {
 } tspm_pattern_head_train_desc;
 size_t tspm_pattern_head_train_workspace(int32_t batch, int32_t npat);
 int tspm_pattern_head_train_step(const tspm_pattern_head_train_desc* desc, tspm_stream_t stream);
+
+/* Cached embeddings (added under ABI 23) — the head stage without the encoders.  A frozen encoder on its running
+ * statistics is a per-row function whose weights never move, so the embedding of every corpus sample is a constant of
+ * the whole head stage: emb [n_rows][ld_emb] holds them (columns [0, w_audio) the audio encoder's, the rest the image
+ * encoder's), labels_all [n_rows] the samples' labels, x0 [in] the embeddings of zeroed inputs, and a batch is the
+ * index vector rows [batch] (int64, the loader's index dtype).
+ *
+ * tspm_embed_gather — one launch:
+ *   out[b][0:in]  = emb[rows[b]][0:in]        for b < batch
+ *   labels_out[b] = labels_all[rows[b]]       (labels_all / labels_out: both given or both NULL)
+ * With row_keep ([batch][2] uint8 on the DEVICE, audio then image) the columns of a modality whose flag is 0 come from
+ * x0 instead (w_audio splits the columns; x0 is required with row_keep).  ld_emb and ld_out are multiples of 4 and at
+ * least in; in (and w_audio with row_keep, 0 < w_audio < in) a multiple of 4; emb, x0, out 16-byte aligned: every load
+ * and store is a float4.  The padding columns of out keep their content.  An index outside [0, n_rows) writes a NaN row
+ * and label -1 and reads nothing out of bounds.  batch >= 1, n_rows >= 1; anything else, or a NULL among emb, rows,
+ * out: TSPM_ERR_INVALID, nothing launched. */
+int tspm_embed_gather(int32_t batch, int32_t in, const float* emb, int64_t n_rows, int32_t ld_emb, const int64_t* rows,
+                      const int64_t* labels_all, const uint8_t* row_keep, int32_t w_audio, const float* x0, float* out,
+                      int32_t ld_out, int64_t* labels_out, tspm_stream_t stream);
+
+/* tspm_cached_head_train_step — tspm_pattern_head_train_step reading its samples straight from the cache, with
+ * tspm_classify_update's bookkeeping folded in.  Two launches, the semantics, sums (order included), limits and status
+ * codes of tspm_pattern_head_train_step — the text above applies word for word — except:
+ *   - sample b's input row is emb[rows[b]] and its label labels_all[rows[b]]; no [batch][in] input is ever formed;
+ *   - two modes.  EVERY PATTERN OF THE BATCH: HOST keep [npat][2] as above, and HOST group_id [npat] (required when
+ *     confusion is given).  ONE PATTERN PER SAMPLE (what the default train loader draws): npat == 1, DEVICE row_keep
+ *     [batch][2] uint8 (audio, image) and DEVICE row_group [batch] int32, both given; HOST keep must be NULL, group_id
+ *     is not read and x0 is required.  Sample b's one row takes each modality from emb or from x0 by its own flags;
+ *     fold_m[b] is zero for a sample whose flag drops modality m, and the workgroup's zsum_m row accumulates those
+ *     samples' dz0 (ascending b);
+ *   - the bookkeeping of a tspm_classify_update call over the npat*batch rows (TSPM_ARGMAX_SOFTMAX: the first maximum
+ *     of the softmax values): confusion[group][label][pred] += 1 with integer atomics (a row whose label or group is out
+ *     of range is not counted), and once per call, when counters is given: loss_log[counters[0]] = loss[0] when that
+ *     index is below log_capacity (loss_log nullable), then counters[0] += 1, counters[1] += npat*batch.  confusion,
+ *     loss_log and counters are nullable; loss_log needs counters, confusion needs n_groups >= 1, log_capacity >= 0;
+ *   - an index outside [0, n_rows) behaves like an out-of-range label: NaN loss and gradients, the row is not counted,
+ *     nothing is read out of bounds (the sample's input row reads as zeros, its label as -1).
+ * Every-pattern mode is bitwise tspm_pattern_head_train_step on the explicitly gathered rows.  No floating-point
+ * atomics; eager, captured and replayed calls are bitwise equal.  In addition to tspm_pattern_head_train_step's
+ * limits: n_rows >= 1; ld_emb >= in and a multiple of 4; emb 16-byte aligned; rows, emb, labels_all given; row_keep and
+ * row_group both given or both NULL.  The workspace is tspm_cached_head_train_workspace(batch, npat) bytes. */
+typedef struct tspm_cached_head_train_desc {
+  int32_t batch, npat, in, w_audio, hidden, hidden2, classes, ld_emb;
+  int32_t gen_keep, n_groups;
+  int64_t n_rows;
+  const float* emb;            /* [n_rows, ld_emb] */
+  const float* x0;             /* [in] */
+  const int64_t* rows;         /* [batch] */
+  const int64_t* labels_all;   /* [n_rows] */
+  const int32_t* keep;         /* HOST [npat][2], every-pattern mode; NULL in per-sample mode */
+  const int32_t* group_id;     /* HOST [npat], every-pattern mode */
+  const uint8_t* row_keep;     /* DEVICE [batch][2], per-sample mode */
+  const int32_t* row_group;    /* DEVICE [batch], per-sample mode */
+  const float *w0, *b0, *w3, *b3, *w5, *b5;
+  float p;                     /* dropout probability (0: no mask) */
+  float loss_weight;
+  uint64_t seed;
+  const uint64_t* counter;
+  uint8_t* keep_mask;          /* [npat*batch, hidden] */
+  float* logits;               /* [npat*batch, classes] */
+  float *gw0, *gb0, *gw3, *gb3, *gw5, *gb5;
+  float *loss, *stats;         /* stats nullable */
+  int64_t* adam_step;          /* nullable */
+  int64_t* confusion;          /* nullable: [n_groups][classes][classes] */
+  float* loss_log;             /* nullable */
+  int64_t* counters;           /* nullable: {entries, samples} */
+  int64_t log_capacity;
+  void* workspace;             /* tspm_cached_head_train_workspace(batch, npat) bytes, 16-byte aligned */
+  size_t workspace_bytes;
+} tspm_cached_head_train_desc;
+size_t tspm_cached_head_train_workspace(int32_t batch, int32_t npat);
+int tspm_cached_head_train_step(const tspm_cached_head_train_desc* desc, tspm_stream_t stream);
 
 /* All-pattern MMIMDb fusion (added under ABI 23) — tspm_gmu_fwd for EVERY missing-modality pattern of a batch in one
  * launch.  In eval mode an encoder's output row depends on that row's input and the weights only, and fc_one / fc_two

@@ -14,15 +14,17 @@ import torch  # noqa: F401  (load torch's HIP runtime before libtspm.so binds to
 from . import _lib
 from ._lib import TspmError, TspmLibraryError
 from .engine import EncoderEngine, prepare_encoder_layout
-from .modules import AVMNIST, BasicBlock, ResNet18, ResNet34, ResNetEncoder, modality_key
+from .modules import AVMNIST, BasicBlock, EmbeddingCache, ResNet18, ResNet34, ResNetEncoder, modality_key
 from .optim import FusedAdam
-from .step import FusedHeadStagePatternStep, FusedHeadStageStep, FusedTrainStep
+from .step import (FusedCachedEvalStep, FusedCachedHeadStep, FusedHeadStagePatternStep, FusedHeadStageStep,
+                   FusedTrainStep)
 from .monomodal import FusedMonoStep, MonomodalEncoder
 from . import plugin, ddp, data, monomodal, mmimdb
 from .mmimdb import MMIMDb, FusedMMIMDbStep
 
 __all__ = ["AVMNIST", "BasicBlock", "ResNet18", "ResNet34", "ResNetEncoder", "FusedAdam", "FusedTrainStep",
-           "FusedHeadStageStep", "FusedHeadStagePatternStep",
+           "FusedHeadStageStep", "FusedHeadStagePatternStep", "FusedCachedHeadStep", "FusedCachedEvalStep",
+           "EmbeddingCache",
            "EncoderEngine", "prepare_encoder_layout", "TspmError", "TspmLibraryError", "plugin", "ddp", "data",
            "modality_key", "MonomodalEncoder", "FusedMonoStep", "monomodal", "mmimdb", "MMIMDb", "FusedMMIMDbStep"]
 __version__ = "0.1.0"

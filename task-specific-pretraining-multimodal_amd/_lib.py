@@ -232,6 +232,28 @@ def pattern_head_train_supported(in_: int, w_audio: int, hidden: int, hidden2: i
     return pattern_head_eval_supported(in_, w_audio, hidden, hidden2, classes, npat)
 
 
+class CachedHeadTrainDesc(Structure):
+    """tspm_cached_head_train_desc (added under ABI 23): the head stage's train step reading its samples from a cache
+    of the frozen encoders' embeddings by index, every pattern of the batch (host ``keep`` / ``group_id``) or one
+    pattern per sample (device ``row_keep`` / ``row_group``), with the classification log folded in."""
+    _fields_ = [(n, c_int32) for n in ("batch", "npat", "in_", "w_audio", "hidden", "hidden2", "classes", "ld_emb",
+                                       "gen_keep", "n_groups")] + [("n_rows", c_int64)] + \
+        [(n, c_void_p) for n in ("emb", "x0", "rows", "labels_all")] + \
+        [("keep", POINTER(c_int32)), ("group_id", POINTER(c_int32)), ("row_keep", c_void_p), ("row_group", c_void_p)] + \
+        [(n, c_void_p) for n in ("w0", "b0", "w3", "b3", "w5", "b5")] + \
+        [("p", c_float), ("loss_weight", c_float), ("seed", c_uint64)] + \
+        [(n, c_void_p) for n in ("counter", "keep_mask", "logits", "gw0", "gb0", "gw3", "gb3", "gw5", "gb5", "loss",
+                                 "stats", "adam_step", "confusion", "loss_log", "counters")] + \
+        [("log_capacity", c_int64), ("workspace", c_void_p), ("workspace_bytes", c_size_t)]
+
+
+def cached_head_train_supported(in_: int, w_audio: int, hidden: int, hidden2: int, classes: int, npat: int) -> bool:
+    """Python mirror of tspm_cached_head_train_step's shape checks — tspm_pattern_head_train_step's (the row kernel
+    keeps its LDS layout).  False = the call would return TSPM_ERR_INVALID for this head whatever the pointers;
+    FusedCachedHeadStep then takes its ``launches`` leg (tspm_embed_gather + the existing head launches)."""
+    return pattern_head_train_supported(in_, w_audio, hidden, hidden2, classes, npat)
+
+
 GMU_PATTERN_MAX_D = 4095  # TSPM_GMU_PATTERN_MAX_D: (4d + 4) floats of LDS within 64 KiB
 
 
@@ -469,6 +491,11 @@ _SIGS = {
     # added under ABI 23: the head's train step over every pattern of a batch on frozen encoders (the AVMNIST head stage)
     "tspm_pattern_head_train_workspace": (c_size_t, [c_int32, c_int32]),
     "tspm_pattern_head_train_step": (c_int32, [POINTER(PatternHeadTrainDesc), _P]),
+    # added under ABI 23: the head stage on a cache of the frozen encoders' embeddings (rows gathered by index)
+    "tspm_embed_gather": (c_int32, [c_int32, c_int32, _P, c_int64, c_int32, _P, _P, _P, c_int32, _P, _P, c_int32, _P,
+                                    _P]),
+    "tspm_cached_head_train_workspace": (c_size_t, [c_int32, c_int32]),
+    "tspm_cached_head_train_step": (c_int32, [POINTER(CachedHeadTrainDesc), _P]),
     # added under ABI 23: MMIMDb's GMU and BCEWithLogits for every pattern of a batch
     "tspm_gmu_pattern_fwd": (c_int32, [c_int32, c_int32, POINTER(c_int32), c_int32, _P, c_int32, _P, _P, _P, c_int32,
                                        _P, _P, c_int32, _P]),

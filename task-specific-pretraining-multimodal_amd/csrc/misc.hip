@@ -1845,6 +1845,407 @@ extern "C" int tspm_pattern_head_train_step(const tspm_pattern_head_train_desc* 
 }
 
 // ------------------------------------------------------------------------------------------------
+// The head stage on cached embeddings (tspm_embed_gather, tspm_cached_head_train_step; added under ABI 23).  A frozen
+// encoder's embedding of a corpus sample never changes, so a batch is an index vector into emb [n_rows][ld_emb].
+// k_embed_gather: a thread per float4 of out; row_keep substitutes x0's columns per modality.
+// k_cached_head_train_rows / k_cached_head_wgrad: k_pattern_head_train_rows' / k_pattern_head_wgrad's bodies (copies:
+// those kernels keep their code, and every sum here keeps their order — every-pattern mode is bitwise
+// tspm_pattern_head_train_step on the gathered rows) with (1) the sample's row read from emb[rows[b]] and its label from
+// labels_all[rows[b]] — one index, one label and, per sample mode, two flags and a group id per sample, loaded before
+// the row's staging and nothing more inside the pattern loop; (2) per-sample mode (P = 1, the keep flags and the group
+// of a row read on the device); (3) k_pattern_head_rows' prediction and confusion count per row and, in the loss
+// workgroup, tspm_classify_update's log entry and counters.
+// ------------------------------------------------------------------------------------------------
+namespace {
+
+__global__ __launch_bounds__(256) void k_embed_gather(int B, int Q, const float* __restrict__ emb, long long n_rows,
+                                                      int ld_emb, const long long* __restrict__ rows,
+                                                      const long long* __restrict__ labels_all,
+                                                      const uint8_t* __restrict__ row_keep, int w_audio,
+                                                      const float* __restrict__ x0, float* __restrict__ out, int ld_out,
+                                                      long long* __restrict__ labels_out) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (long long)B * Q) return;
+  const int b = (int)(i / Q), col = 4 * (int)(i - (long long)b * Q);
+  const long long r = rows[b];
+  const bool ok = r >= 0 && r < n_rows;
+  const float nan = __builtin_nanf("");
+  f32x4 v{nan, nan, nan, nan};
+  if (ok) {
+    const bool real = !row_keep || row_keep[2 * b + (col >= w_audio ? 1 : 0)] != 0;
+    v = real ? ld4(emb + r * ld_emb + col) : ld4(x0 + col);
+  }
+  st4(out + (long long)b * ld_out + col, v);
+  if (col == 0 && labels_out) labels_out[b] = ok ? labels_all[r] : -1;
+}
+
+struct CachedTrainArgs {
+  tspm_cached_head_train_desc d;  // keep / group_id (host pointers) are not read on the device
+  int keep[PH_MAXP][2];
+  int group[PH_MAXP];
+  int per_sample;                  // one pattern per sample: flags and group from d.row_keep / d.row_group
+  float scale;                     // 1/(1-p), or 1
+  int grid;                        // workgroups of launch 1 (= extra rows of fold / xe)
+  // workspace views (tspm_pattern_head_train_step's)
+  float *h1, *hh, *dlogits, *dz3;  // [P*B][H], [P*B][H2], [P*B][C], [P*B][H2]
+  float* row_ws;                   // [2][P*B]: per-row CE terms, correct flags
+  float* fold;                     // [2][B + grid][H]
+  float* xe;                       // [B + grid][F]: the gathered rows, then x0 once per workgroup
+};
+
+__global__ __launch_bounds__(PH_THREADS) void k_cached_head_train_rows(CachedTrainArgs a) {
+  const tspm_cached_head_train_desc& d = a.d;
+  extern __shared__ float lds[];
+  const int F = d.in, H = d.hidden, H2 = d.hidden2, C = d.classes, P = d.npat, WA = d.w_audio, B = d.batch;
+  const int ldx = F + 4, ldh = H + 4, ldh2 = H2 + 4, ldc = head_ldc(C);
+  float* sw0 = lds;                 // [H][F + 4]
+  float* sw3 = sw0 + H * ldx;       // [H2][H + 4]
+  float* sw5 = sw3 + H2 * ldh;      // [C][H2 + 4]
+  float* sx = sw5 + C * ldh2;       // [2][F + 4]: the sample's row, x0
+  float* spart = sx + 2 * ldx;      // [2][2][H]: (sample | x0) x (audio half | image half) of fc0
+  float* sh1 = spart + 4 * H;       // [P][H + 4]: h1, then dz0
+  float* shh = sh1 + P * ldh;       // [P][H2 + 4]: hh, then dz3
+  float* sz = shh + P * ldh2;       // [P][ldc]: logits, then dlogits
+  float* sb0 = sz + P * ldc;        // biases [H], [H2], [C]
+  float* sb3 = sb0 + H;
+  float* sb5 = sb3 + H2;
+  const int t = threadIdx.x;
+  const long long PB = (long long)P * B;
+  const int R = B + a.grid;         // rows of a fold plane / of xe
+  uint64_t base = 0;
+  {
+    const HeadSeg g0{d.w0, sw0, H, F / 4, H, F}, g3{d.w3, sw3, H2, H / 4, H2, H}, g5{d.w5, sw5, C, H2 / 4, C, H2};
+    constexpr int U0 = (128 * 192 / 4 + PH_THREADS - 1) / PH_THREADS, U3 = (64 * 128 / 4 + PH_THREADS - 1) / PH_THREADS;
+    f32x4 v0[U0], v3[U3], v5[1];
+    const uint64_t ctr = (d.p > 0.f && d.gen_keep && d.counter) ? *d.counter : 0ULL;
+    head_load(g0, v0);
+    head_load(g3, v3);
+    head_load(g5, v5);
+    head_store(g0, v0);
+    head_store(g3, v3);
+    head_store(g5, v5);
+    for (int i = t; i < H + H2 + C; i += PH_THREADS)
+      sb0[i] = i < H ? d.b0[i] : i < H + H2 ? d.b3[i - H] : d.b5[i - H - H2];
+    for (int i = t; i < F / 4; i += PH_THREADS) {
+      const f32x4 v = d.x0 ? ld4(d.x0 + 4 * i) : f32x4{0.f, 0.f, 0.f, 0.f};
+      st4(sx + ldx + 4 * i, v);
+      st4(a.xe + (long long)(B + blockIdx.x) * F + 4 * i, v);  // this workgroup's zsum rows pair with x0
+    }
+    if (d.p > 0.f && d.gen_keep) base = tspm_dropout_base(d.seed, ctr);
+  }
+  head_sync();
+  // the two halves of fc0 on row `xr` -> dst[half * H + o]
+  auto halves = [&](const float* xr, float* dst) {
+    for (int item = t; item < 2 * H; item += PH_THREADS) {
+      const int half = item >= H ? 1 : 0, o = item - half * H;
+      const int k0 = half ? WA : 0, K = half ? F - WA : WA;
+      dst[item] = pat_dot(xr + k0, sw0 + o * ldx + k0, K);
+    }
+  };
+  halves(sx + ldx, spart + 2 * H);
+  // thread t < 2H owns unit (m, o) = (t / H, t % H) of the folds (H <= 256: 2H <= PH_THREADS)
+  const int fm = t >= H ? 1 : 0, fo = t - fm * H;
+  float zs = 0.f;  // this workgroup's zsum_m[o]
+  const float invn = 1.0f / (float)PB;
+  for (int b = blockIdx.x; b < B; b += gridDim.x) {
+    // everything this sample takes from the cache's index: workgroup-uniform, loaded once, ahead of the row
+    const long long r = d.rows[b];
+    const bool rok = r >= 0 && r < d.n_rows;  // an index outside the cache: a zero row and label -1, nothing read
+    const long long lab64 = rok ? d.labels_all[r] : -1;
+    int ska = 1, ski = 1, sgrp = 0;
+    if (a.per_sample) {
+      ska = d.row_keep[2 * b] != 0;
+      ski = d.row_keep[2 * b + 1] != 0;
+      sgrp = d.row_group[b];
+    }
+    const float* er = d.emb + (rok ? r : 0) * d.ld_emb;
+    // sx row 0 was last read before the previous sample's barriers
+    for (int i = t; i < F / 4; i += PH_THREADS) {
+      const f32x4 v = rok ? ld4(er + 4 * i) : f32x4{0.f, 0.f, 0.f, 0.f};
+      st4(sx + 4 * i, v);
+      st4(a.xe + (long long)b * F + 4 * i, v);
+    }
+    head_sync();
+    halves(sx, spart);
+    head_sync();
+    // fc0 + ReLU + dropout (tspm_linear_fwd's epilogue order: + bias, relu, * keep*scale)
+    for (int item = t; item < P * H; item += PH_THREADS) {
+      const int p = item / H, o = item - p * H;
+      const int ka = a.per_sample ? ska : a.keep[p][0], ki = a.per_sample ? ski : a.keep[p][1];
+      const float pa = spart[(ka ? 0 : 2 * H) + o], pi = spart[(ki ? 0 : 2 * H) + H + o];
+      float v = relu_f((pa + pi) + sb0[o]);
+      const long long i = ((long long)p * B + b) * H + o;
+      if (d.p > 0.f) {
+        bool kp;
+        if (d.gen_keep) {
+          kp = tspm_dropout_keep(base, i, d.p);
+          d.keep_mask[i] = kp ? 1 : 0;
+        } else {
+          kp = d.keep_mask[i] != 0;
+        }
+        v *= kp ? a.scale : 0.f;
+      }
+      sh1[p * ldh + o] = v;
+      a.h1[i] = v;
+    }
+    head_sync();
+    for (int item = t; item < P * H2; item += PH_THREADS) {
+      const int p = item / H2, o = item - p * H2;
+      const float v = relu_f(pat_dot(sh1 + p * ldh, sw3 + o * ldh, H) + sb3[o]);
+      shh[p * ldh2 + o] = v;
+      a.hh[((long long)p * B + b) * H2 + o] = v;
+    }
+    head_sync();
+    for (int item = t; item < P * C; item += PH_THREADS) {
+      const int p = item / C, o = item - p * C;
+      const float v = pat_dot(shh + p * ldh2, sw5 + o * ldh2, H2) + sb5[o];
+      sz[p * ldc + o] = v;
+      d.logits[((long long)p * B + b) * C + o] = v;
+    }
+    head_sync();
+    // cross-entropy per row (k_head_rows' arithmetic): 16 lanes per row, lane k owns class k; sz becomes dlogits
+    if (t < 16 * P) {
+      const int p = t >> 4, k = t & 15, l0 = (t & 63) & ~15;
+      float* z = sz + p * ldc;
+      const bool kv = k < C;
+      float mx = z[0];
+      int am = 0;
+      for (int j = 1; j < C; ++j)
+        if (z[j] > mx) { mx = z[j]; am = j; }
+      const float e = kv ? expf(z[k] - mx) : 0.f;
+      float se = 0.f;
+      for (int j = 0; j < C; ++j) se += __shfl(e, l0 + j, 64);
+      const bool lok = lab64 >= 0 && lab64 < C;  // out-of-range label: NaN loss / gradients, nothing read out of bounds
+      const int lab = lok ? (int)lab64 : 0;
+      const long long row = (long long)p * B + b;
+      if (k == 0) {
+        a.row_ws[row] = lok ? logf(se) - (z[lab] - mx) : __builtin_nanf("");
+        a.row_ws[PB + row] = (lok && am == lab) ? 1.f : 0.f;  // an out-of-range label is never correct
+      }
+      const float pk = e / se;
+      if (d.confusion) {  // k_pattern_head_rows' prediction: the first maximum of the softmax values
+        float best = __shfl(pk, l0, 64);
+        int sm = 0;
+        for (int j = 1; j < C; ++j) {
+          const float pj = __shfl(pk, l0 + j, 64);
+          if (pj > best) { best = pj; sm = j; }
+        }
+        const int g = a.per_sample ? sgrp : a.group[p];
+        if (k == 0 && lok && g >= 0 && g < d.n_groups)
+          atomicAdd(reinterpret_cast<unsigned long long*>(d.confusion) + ((long long)g * C + lab) * C + sm, 1ULL);
+      }
+      const float g = lok ? (pk - (k == lab ? 1.f : 0.f)) * invn * d.loss_weight : __builtin_nanf("");
+      if (kv) {  // after every lane of the row has read z (the row's 16 lanes sit in one wave: program order)
+        z[k] = g;
+        a.dlogits[row * C + k] = g;
+      }
+    }
+    head_sync();
+    // dz3 = (dlogits w5) * (hh > 0)   (w5 is [C][H2]) -> shh; item (p, o)'s hh value is read and overwritten by its
+    // own thread only
+    for (int item = t; item < P * H2; item += PH_THREADS) {
+      const int p = item / H2, o = item - p * H2;
+      float acc = 0.f;
+      for (int k = 0; k < C; ++k) acc = fmaf(sz[p * ldc + k], sw5[k * ldh2 + o], acc);
+      const float v = shh[p * ldh2 + o] > 0.f ? acc : 0.f;
+      shh[p * ldh2 + o] = v;
+      a.dz3[((long long)p * B + b) * H2 + o] = v;
+    }
+    head_sync();
+    // dz0 = (dz3 w3) * (h1 > 0 ? scale : 0)   (w3 is [H2][H]) -> sh1
+    for (int item = t; item < P * H; item += PH_THREADS) {
+      const int p = item / H, o = item - p * H;
+      const float* zp = shh + p * ldh2;
+      float acc = 0.f;
+      for (int k = 0; k < H2; k += 4) {
+        const f32x4 z4 = ld4(zp + k);
+        acc = fmaf(z4[0], sw3[(k + 0) * ldh + o], acc);
+        acc = fmaf(z4[1], sw3[(k + 1) * ldh + o], acc);
+        acc = fmaf(z4[2], sw3[(k + 2) * ldh + o], acc);
+        acc = fmaf(z4[3], sw3[(k + 3) * ldh + o], acc);
+      }
+      sh1[p * ldh + o] = sh1[p * ldh + o] > 0.f ? acc * a.scale : 0.f;
+    }
+    head_sync();
+    // the folds of dz0 (fc0's backward in the forward's algebra): ascending p, plain adds
+    if (t < 2 * H) {
+      float fk = 0.f;
+      for (int p = 0; p < P; ++p) {
+        const float v = sh1[p * ldh + fo];
+        if (a.per_sample ? (fm ? ski : ska) : a.keep[p][fm]) fk += v;
+        else zs += v;
+      }
+      a.fold[((long long)fm * R + b) * H + fo] = fk;
+    }
+    // the next sample writes sx / spart behind this iteration's barriers and sh1 only behind two more
+  }
+  if (t < 2 * H) a.fold[((long long)fm * R + B + blockIdx.x) * H + fo] = zs;
+}
+
+template <int WK>
+__global__ __launch_bounds__(64 * WK) void k_cached_head_wgrad(GemmMulti mp, int total, CachedTrainArgs a) {
+  extern __shared__ float lds[];
+  const int b = blockIdx.x;
+  if (b < total) {
+    int i = 0;
+    while (i + 1 < mp.count && b >= mp.start[i + 1]) ++i;  // workgroup-uniform
+    gemm_body<WK>(mp.p[i], b - mp.start[i], lds);
+    return;
+  }
+  // the loss: fixed-order sums of the per-row losses / correct flags over the P*B rows, in double
+  const tspm_cached_head_train_desc& d = a.d;
+  const int n = d.npat * d.batch;
+  double* red = reinterpret_cast<double*>(lds);
+  const int T = 64 * WK;
+  double ls = 0.0, cs = 0.0;
+  for (int r = threadIdx.x; r < n; r += T) {
+    ls += (double)a.row_ws[r];
+    cs += (double)a.row_ws[n + r];
+  }
+  red[threadIdx.x] = ls;
+  red[T + threadIdx.x] = cs;
+  __syncthreads();
+  for (int s = T / 2; s > 0; s >>= 1) {
+    if (threadIdx.x < s) {
+      red[threadIdx.x] += red[threadIdx.x + s];
+      red[T + threadIdx.x] += red[T + threadIdx.x + s];
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    const float l = (float)(red[0] / (double)n);
+    const float lw = l * d.loss_weight;
+    d.loss[0] = lw;
+    if (d.adam_step) d.adam_step[0] += 1;  // after launch 1 read the step counter (dropout), before any Adam launch
+    if (d.stats) {
+      d.stats[0] += (float)red[0];
+      d.stats[1] += (float)red[T];
+      d.stats[2] += (float)n;
+    }
+    if (d.counters) {  // tspm_classify_update's log: one entry per call
+      const long long base = d.counters[0];
+      if (d.loss_log && base < d.log_capacity) d.loss_log[base] = lw;
+      d.counters[0] = base + 1;
+      d.counters[1] += (long long)n;
+    }
+  }
+}
+
+}  // namespace
+
+extern "C" int tspm_embed_gather(int32_t batch, int32_t in, const float* emb, int64_t n_rows, int32_t ld_emb,
+                                 const int64_t* rows, const int64_t* labels_all, const uint8_t* row_keep,
+                                 int32_t w_audio, const float* x0, float* out, int32_t ld_out, int64_t* labels_out,
+                                 tspm_stream_t stream) {
+  if (batch <= 0 || in <= 0 || in % 4 || n_rows <= 0) return TSPM_ERR_INVALID;
+  if (ld_emb < in || ld_emb % 4 || ld_out < in || ld_out % 4) return TSPM_ERR_INVALID;
+  if (!emb || !rows || !out || !aligned16(emb) || !aligned16(out)) return TSPM_ERR_INVALID;
+  if ((labels_all == nullptr) != (labels_out == nullptr)) return TSPM_ERR_INVALID;
+  if (row_keep && (!x0 || !aligned16(x0) || w_audio <= 0 || w_audio >= in || w_audio % 4)) return TSPM_ERR_INVALID;
+  const int q = in / 4;
+  const long long items = (long long)batch * q;
+  if (items > (1LL << 31) - 256) return TSPM_ERR_INVALID;
+  hipLaunchKernelGGL(k_embed_gather, dim3((unsigned)((items + 255) / 256)), dim3(256), 0,
+                     static_cast<hipStream_t>(stream), batch, q, emb, (long long)n_rows, ld_emb,
+                     reinterpret_cast<const long long*>(rows), reinterpret_cast<const long long*>(labels_all), row_keep,
+                     w_audio, x0, out, ld_out, reinterpret_cast<long long*>(labels_out));
+  TSPM_LAUNCH_CHECK();
+  return TSPM_OK;
+}
+
+extern "C" size_t tspm_cached_head_train_workspace(int32_t batch, int32_t npat) {
+  if (batch <= 0 || npat <= 0 || npat > PH_MAXP) return 0;
+  return pat_train_ws_bytes(batch, npat);
+}
+
+extern "C" int tspm_cached_head_train_step(const tspm_cached_head_train_desc* desc, tspm_stream_t stream) {
+  if (!desc) return TSPM_ERR_INVALID;
+  const tspm_cached_head_train_desc& d = *desc;
+  if (d.batch <= 0 || d.npat <= 0 || d.npat > PH_MAXP) return TSPM_ERR_INVALID;
+  if ((long long)d.batch * d.npat > (1LL << 24)) return TSPM_ERR_INVALID;  // row indices and counts stay exact in float
+  if (d.in <= 0 || d.hidden <= 0 || d.hidden2 <= 0 || d.classes <= 0) return TSPM_ERR_INVALID;
+  if (d.in > HEAD_MAXIN || d.hidden > HEAD_MAXH || d.hidden2 > HEAD_MAXH2 || d.classes > HEAD_MAXC)
+    return TSPM_ERR_INVALID;
+  if (d.in % 4 || d.hidden % 4 || d.hidden2 % 4 || d.w_audio % 4 || d.w_audio <= 0 || d.w_audio >= d.in)
+    return TSPM_ERR_INVALID;
+  if (d.n_rows < 1 || d.ld_emb < d.in || d.ld_emb % 4) return TSPM_ERR_INVALID;
+  if (!d.emb || !d.rows || !d.labels_all || !d.w0 || !d.b0 || !d.w3 || !d.b3 || !d.w5 || !d.b5 || !d.logits ||
+      !d.gw0 || !d.gb0 || !d.gw3 || !d.gb3 || !d.gw5 || !d.gb5 || !d.loss)
+    return TSPM_ERR_INVALID;
+  if (!aligned16(d.emb) || !aligned16(d.x0) || !aligned16(d.w0) || !aligned16(d.w3) || !aligned16(d.w5))
+    return TSPM_ERR_INVALID;
+  if (!(d.p >= 0.f && d.p < 1.f) || (d.p > 0.f && !d.keep_mask)) return TSPM_ERR_INVALID;
+  if (d.log_capacity < 0 || (d.loss_log && !d.counters) || (d.confusion && d.n_groups <= 0)) return TSPM_ERR_INVALID;
+  if ((d.row_keep == nullptr) != (d.row_group == nullptr)) return TSPM_ERR_INVALID;
+  CachedTrainArgs a{};
+  a.d = d;
+  a.per_sample = d.row_keep ? 1 : 0;
+  if (a.per_sample) {
+    if (d.npat != 1 || d.keep || !d.x0) return TSPM_ERR_INVALID;
+  } else {
+    if (!d.keep || (d.confusion && !d.group_id)) return TSPM_ERR_INVALID;
+    bool drops = false;
+    for (int p = 0; p < d.npat; ++p) {
+      a.keep[p][0] = d.keep[2 * p] != 0;
+      a.keep[p][1] = d.keep[2 * p + 1] != 0;
+      a.group[p] = d.group_id ? d.group_id[p] : 0;
+      drops = drops || !a.keep[p][0] || !a.keep[p][1];
+    }
+    if (drops && !d.x0) return TSPM_ERR_INVALID;
+  }
+  const size_t lds_rows = pat_head_lds_floats(d.in, d.hidden, d.hidden2, d.classes, d.npat) * sizeof(float);
+  if (lds_rows > 160 * 1024) return TSPM_ERR_INVALID;
+  if (!d.workspace || !aligned16(d.workspace) || d.workspace_bytes < pat_train_ws_bytes(d.batch, d.npat))
+    return TSPM_ERR_WORKSPACE;
+  const int B = d.batch, P = d.npat, F = d.in, H = d.hidden, H2 = d.hidden2, C = d.classes;
+  const int grid = B < PH_MAXGRID ? B : PH_MAXGRID, R = B + grid;
+  const size_t pb = (size_t)B * P;
+  // tspm_pattern_head_train_step's views
+  float* w = static_cast<float*>(d.workspace);
+  a.h1 = w;          w += pb * H;
+  a.hh = w;          w += pb * H2;
+  a.dz3 = w;         w += pb * H2;
+  a.dlogits = w;     w += (pb * C + 3) & ~(size_t)3;
+  a.row_ws = w;      w += (2 * pb + 3) & ~(size_t)3;
+  a.fold = w;        w += (size_t)2 * R * H;
+  a.xe = w;
+  a.scale = d.p > 0.f ? 1.0f / (1.0f - d.p) : 1.0f;
+  a.grid = grid;
+  a.d.keep = nullptr;
+  a.d.group_id = nullptr;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(k_cached_head_train_rows, dim3(grid), dim3(PH_THREADS), lds_rows, st, a);
+  TSPM_LAUNCH_CHECK();
+  // the weight gradients: tspm_pattern_head_train_step's four products, operand for operand
+  const int n = (int)pb;
+  GemmMulti mp{};
+  mp.p[0] = GemmArgs{C, H2, n, a.dlogits, 1, C, a.hh, H2, 1, d.gw5, H2, nullptr, 0, nullptr, 1.f, d.gb5};
+  mp.p[1] = GemmArgs{H2, H, n, a.dz3, 1, H2, a.h1, H, 1, d.gw3, H, nullptr, 0, nullptr, 1.f, d.gb3};
+  mp.p[2] = GemmArgs{H, d.w_audio, R, a.fold, 1, H, a.xe, F, 1, d.gw0, F, nullptr, 0, nullptr, 1.f, d.gb0};
+  mp.p[3] = GemmArgs{H, F - d.w_audio, R, a.fold + (size_t)R * H, 1, H, a.xe + d.w_audio, F, 1, d.gw0 + d.w_audio, F,
+                     nullptr, 0, nullptr, 1.f, nullptr};
+  mp.count = 4;
+  int total = 0, wk = 1;
+  for (int i = 0; i < 4; ++i) {
+    const int wv = gemm_wk(mp.p[i]);
+    wk = wv > wk ? wv : wk;
+    mp.start[i] = total;
+    total += cdiv(mp.p[i].M, 32) * cdiv(mp.p[i].N, 32);
+  }
+  mp.start[4] = total;
+  const size_t lds_gemm = (size_t)(wk - 1) * (16 * 64 + 32) * sizeof(float);
+  const size_t lds_loss = (size_t)2 * 64 * wk * sizeof(double);
+  const size_t lds = lds_gemm > lds_loss ? lds_gemm : lds_loss;
+  switch (wk) {
+    case 1: hipLaunchKernelGGL(k_cached_head_wgrad<1>, dim3(total + 1), dim3(64), lds, st, mp, total, a); break;
+    case 2: hipLaunchKernelGGL(k_cached_head_wgrad<2>, dim3(total + 1), dim3(128), lds, st, mp, total, a); break;
+    default: hipLaunchKernelGGL(k_cached_head_wgrad<4>, dim3(total + 1), dim3(256), lds, st, mp, total, a); break;
+  }
+  TSPM_LAUNCH_CHECK();
+  return TSPM_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
 // Monomodal head step (ABI 23): classifier Linear forward, weighted cross-entropy, argmax(logits) and the
 // Linear's whole backward in ONE launch of ONE workgroup.  The problem is launch-bound ([128,64] x [64,3] at
 // the MOSI shapes), so the rows are not spread over workgroups: the workgroup walks the batch in chunks of

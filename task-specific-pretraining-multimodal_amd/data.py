@@ -34,6 +34,7 @@ from __future__ import annotations
 import json
 import os
 import random
+import weakref
 from concurrent.futures import ThreadPoolExecutor
 from typing import Any, Dict, Iterator, List, Optional, Sequence, Tuple
 
@@ -541,12 +542,54 @@ class AVMNIST(torch.utils.data.Dataset):
     def device_loader(self, batch_size: int, shuffle: bool = False, drop_last: bool = False,
                       generator: Optional[torch.Generator] = None, *, rank: int = 0, world_size: int = 1,
                       distributed: Optional[bool] = None, seed: int = 0, pattern: Optional[str] = None,
-                      out=None, fuse_patterns: bool = False, all_patterns: bool = False) -> "DeviceLoader":
-        """``fuse_patterns`` (valid / test splits of the multimodal target) and ``all_patterns`` (its train split): see
+                      out=None, fuse_patterns: bool = False, all_patterns: bool = False,
+                      ids_only: bool = False) -> "DeviceLoader":
+        """``fuse_patterns`` (valid / test splits of the multimodal target), ``all_patterns`` (its train split) and
+        ``ids_only`` (batches of sample indices for the steps that read an :meth:`embedding_cache`): see
         :class:`DeviceLoader`."""
         return DeviceLoader(self, batch_size, shuffle, drop_last, generator, rank=rank, world_size=world_size,
                             distributed=distributed, seed=seed, pattern=pattern, out=out, fuse_patterns=fuse_patterns,
-                            all_patterns=all_patterns)
+                            all_patterns=all_patterns, ids_only=ids_only)
+
+    # -- the frozen encoders' embeddings of this split, computed once -----------------------------------
+    def embedding_cache(self, model, chunk: Optional[int] = None, refresh: bool = False):
+        """This split's ``modules.EmbeddingCache`` for ``model`` (one per model, built on first call): both FROZEN
+        encoders' eval-mode embeddings of every sample (``emb [num_samples][F]`` fp32 on the device, 46 MB for the
+        60,000 training samples), the labels and the model's zero-input row.  The fill runs the encoders once over the
+        device corpus in sample order, unmasked, in chunks of ``chunk`` rows (256 for a new cache; an existing cache
+        keeps its own unless one is given); ``refresh=True`` fills an existing cache again.  Refused for a model whose
+        encoders are not frozen and for a single-modality target.  A cache made stale
+        (``unfreeze_encoders()``, ``load_state_dict``, ``.to()``) is returned as it is and refused by the step that
+        reads it until ``refresh()``; weights written through raw pointers cannot be detected, so whoever changes
+        frozen weights that way refreshes."""
+        from .modules import EmbeddingCache
+        self._check_ids_only("embedding_cache")
+        caches = self.__dict__.setdefault("_emb_caches", weakref.WeakKeyDictionary())  # gone with their models
+        c = caches.get(model)
+        if c is None:
+            c = caches[model] = EmbeddingCache(model, self.device_corpus, 256 if chunk is None else chunk)
+        else:
+            if chunk is not None:
+                c.chunk = int(chunk)  # an existing cache keeps its rows; its next fill runs in chunks of ``chunk``
+            if refresh:
+                c.refresh()
+        return c
+
+    def _check_ids_only(self, what: str = "ids_only=True") -> None:
+        """Cached embeddings hold both modalities of every sample, and a pattern is rebuilt from the real embedding or
+        the zero-input one, which is exact only for 0 / 1 masks."""
+        if self.target_modality != "multimodal":
+            raise L.TspmError(f"{what} is for the multimodal target (the cache holds both encoders' embeddings); this "
+                              f"dataset's target_modality is {self.target_modality!r}")
+        self._check_pattern_probs(what)
+
+    def _ids_device(self) -> torch.device:
+        """Where an ``ids_only`` loader puts its index tensors: the corpus' device (no corpus upload is triggered)."""
+        if self._dev is not None:
+            return self._dev.device
+        if self._device is not None:
+            return torch.device(self._device)
+        return torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
 
     def _check_fuse_patterns(self, pattern: Optional[str] = None) -> None:
         """A fused-pattern loader yields every sample once, unmasked; the step rebuilds each selected pattern from the
@@ -626,6 +669,14 @@ class DeviceLoader:
     ``step.FusedHeadStagePatternStep`` trains the fusion head under every pattern of such a batch in one step, on
     frozen encoders (``AVMNIST.freeze_encoders``).
 
+    ``ids_only=True`` (the multimodal target with 0 / 1 presence probabilities; refused together with ``out=``): the
+    loader yields no audio or image tensors and runs no gather — each batch holds ``"sample_ids"`` (an int64 device
+    slice of the epoch's order), ``"cached": True``, ``"labels"`` and ``"dataset"`` (this dataset, whose
+    ``embedding_cache(model)`` the cached steps read), plus ``"patterns"`` and their flag with ``fuse_patterns`` /
+    ``all_patterns``, or ``"keep"`` (``[b][2]`` uint8 from the resolved masks: audio, image), ``"pattern_ids"`` and
+    ``"pattern_name"`` on the plain train / valid path.  Order, RNG draws and ``len`` are exactly those of the same
+    loader without the flag.  ``step.FusedCachedHeadStep`` / ``FusedCachedEvalStep`` consume such batches.
+
     ``out=(audio, image, labels)``: full batches are written into these caller-owned buffers (e.g. a
     ``FusedTrainStep``'s static inputs, so the step consumes the gather's output in place) and the
     yielded dict holds those same tensors — consume each batch before advancing the iterator."""
@@ -633,9 +684,14 @@ class DeviceLoader:
     def __init__(self, dataset: AVMNIST, batch_size: int, shuffle: bool = False, drop_last: bool = False,
                  generator: Optional[torch.Generator] = None, *, rank: int = 0, world_size: int = 1,
                  distributed: Optional[bool] = None, seed: int = 0, pattern: Optional[str] = None, out=None,
-                 fuse_patterns: bool = False, all_patterns: bool = False):
+                 fuse_patterns: bool = False, all_patterns: bool = False, ids_only: bool = False):
         if batch_size <= 0:
             raise ValueError("batch_size must be positive")
+        self.ids_only = bool(ids_only)
+        if self.ids_only:
+            if out is not None:
+                raise L.TspmError("ids_only=True yields sample indices, not input tensors: it excludes out=")
+            dataset._check_ids_only()
         self.fuse_patterns = bool(fuse_patterns)
         self.all_patterns = bool(all_patterns)
         if self.fuse_patterns and self.all_patterns:
@@ -690,6 +746,9 @@ class DeviceLoader:
         if nb == 0:
             return
         order = order[:nb * self.batch_size] if self.drop_last else order
+        if self.ids_only:
+            yield from self._iter_ids(order, nb)
+            return
         if self.fuse_patterns or self.all_patterns:
             yield from self._iter_fused(order, nb)
             return
@@ -719,4 +778,34 @@ class DeviceLoader:
             flag = "all_patterns" if self.all_patterns else "fused_patterns"
             batch: Dict[Any, Any] = {"labels": lab, "missing_masks": {}, "patterns": list(pats), flag: True,
                                      self.ds.keys["audio"]: a, self.ds.keys["image"]: imt}
+            yield batch
+
+    def _iter_ids(self, order: np.ndarray, nb: int) -> Iterator[Dict[Any, Any]]:
+        """The ``ids_only`` epoch: the same items, patterns and masks as the other paths resolve, as index tensors."""
+        ds = self.ds
+        dev = ds._ids_device()
+
+        def up(a: np.ndarray) -> torch.Tensor:
+            t = torch.from_numpy(np.ascontiguousarray(a))
+            return t.pin_memory().to(dev, non_blocking=True) if dev.type == "cuda" else t
+
+        fused = self.fuse_patterns or self.all_patterns
+        if fused:
+            samples, names = np.ascontiguousarray(order, dtype=np.int64), None
+        else:
+            samples, names, am, im = ds._resolve(order)
+            keep_d = up(np.stack([am != 0, im != 0], axis=1).astype(np.uint8))
+            pid_d = up(ds.pattern_ids(names))
+        idx_d, lab_d = up(samples.astype(np.int64)), up(ds.corpus.labels[samples])
+        for b in range(nb):
+            lo, hi = b * self.batch_size, min(len(order), (b + 1) * self.batch_size)
+            batch: Dict[Any, Any] = {"labels": lab_d[lo:hi], "missing_masks": {}, "sample_ids": idx_d[lo:hi],
+                                     "cached": True, "dataset": ds}
+            if fused:
+                batch["patterns"] = list(ds.selected_patterns)
+                batch["all_patterns" if self.all_patterns else "fused_patterns"] = True
+            else:
+                batch.update(keep=keep_d[lo:hi], pattern_ids=pid_d[lo:hi], pattern_name=list(names[lo:hi]))
+                if names:
+                    ds.current_pattern = names[hi - 1]
             yield batch

@@ -32,8 +32,8 @@ import torch
 from . import _lib as L
 from .metrics import ClassificationLog, DeviceMetricRecorder, RegressionLog, RegressionMetricRecorder
 from .modules import modality_key
-from .step import (FusedEvalStep, FusedHeadStagePatternStep, FusedHeadStageStep, FusedPatternEvalStep, FusedTrainStep,
-                   head_stage_frozen, norm_avmnist_patterns, train_step_key)
+from .step import (FusedCachedEvalStep, FusedCachedHeadStep, FusedEvalStep, FusedHeadStagePatternStep, FusedHeadStageStep,
+                   FusedPatternEvalStep, FusedTrainStep, head_stage_frozen, norm_avmnist_patterns, train_step_key)
 
 # the AVMNIST YAML's metric block (configs/avmnist/centralised/train_avmnist_resnet.yaml:105-166)
 AVMNIST_METRICS = {
@@ -124,7 +124,10 @@ class EpochRunner:
     entry per pattern, in pattern order, and every row's count under its pattern.  A model with frozen encoders
     (``AVMNIST.freeze_encoders``) trains on ``FusedHeadStageStep``, and an ``"all_patterns"`` train batch on
     ``FusedHeadStagePatternStep`` (one loss entry per step, every row's count under its pattern); both live in
-    ``train_steps`` under ``step.train_step_key``'s keys, which for an all-trainable model are the batch sizes."""
+    ``train_steps`` under ``step.train_step_key``'s keys, which for an all-trainable model are the batch sizes.  A
+    ``"cached"`` batch (``data.DeviceLoader(ids_only=True)``: sample indices, no input tensors) runs on the dataset's
+    ``embedding_cache(model)`` — ``FusedCachedHeadStep`` (keys with a trailing ``("cached",)``) or
+    ``FusedCachedEvalStep`` — with the same loss entries and counts and no encoder launch."""
 
     def __init__(self, model, optimizer, loss_functions, metric_config=None, device=None, log_capacity: int = 1 << 16):
         self.model, self.optimizer, self.loss_functions = model, optimizer, loss_functions
@@ -134,6 +137,7 @@ class EpochRunner:
         self.train_steps: Dict[int, FusedTrainStep] = {}
         self.eval_steps: Dict[int, FusedEvalStep] = {}
         self.pattern_eval_steps: Dict[Tuple[Tuple[str, ...], int], FusedPatternEvalStep] = {}
+        self._epoch_caches: Dict[int, Any] = {}  # dataset id -> its EmbeddingCache, for the running epoch
 
     def _train_step(self, n: int):
         key = train_step_key(self.model, n)
@@ -159,6 +163,49 @@ class EpochRunner:
             self.train_steps[key] = st
         st.log = self.log
         return st
+
+    def cached_train_step_for(self, n: int, cache, patterns=None) -> FusedCachedHeadStep:
+        """The FusedCachedHeadStep for (patterns, batch size) on ``cache``: every pattern of the batch when ``patterns``
+        is given (an ``"all_patterns"`` batch), else one pattern per sample.  Rebuilt for another cache."""
+        pats = norm_avmnist_patterns(patterns) if patterns is not None else None
+        key = train_step_key(self.model, n, pats, cached=True)
+        st = self.train_steps.get(key)
+        if st is None or st.cache is not cache:
+            st = FusedCachedHeadStep(self.model, self.optimizer, self.loss_functions, n, cache, patterns=pats,
+                                     per_sample=pats is None)
+            self.train_steps[key] = st
+        st.log = self.log
+        return st
+
+    def cached_eval_step_for(self, n: int, cache, patterns=None) -> FusedCachedEvalStep:
+        """The FusedCachedEvalStep for (patterns, batch size) on ``cache`` (``patterns``: a ``"fused_patterns"`` batch's;
+        None: each row under its own keep flags); kept apart from the other eval steps under a ("cached", ...) key."""
+        pats = norm_avmnist_patterns(patterns) if patterns is not None else None
+        key = (("cached",), pats, n)
+        st = self.pattern_eval_steps.get(key)
+        if st is None or st.cache is not cache:
+            st = FusedCachedEvalStep(self.model, self.loss_functions, n, cache, self.log, patterns=pats,
+                                     per_sample=pats is None)
+            self.pattern_eval_steps[key] = st
+        st.log = self.log
+        return st
+
+    def _cached(self, b, train: bool) -> None:
+        """One ``"cached"`` batch on its dataset's embedding cache of this model, looked up once per epoch and dataset.
+        A dataset that has no cache of this model yet gets one here — a fill pass over the whole split inside the
+        epoch's first batch; ``fit(cache_embeddings=True)`` and ``dataset.embedding_cache(model)`` do it beforehand."""
+        ds = b["dataset"]
+        cache = self._epoch_caches.get(id(ds))
+        if cache is None:
+            cache = self._epoch_caches[id(ds)] = ds.embedding_cache(self.model)
+        ids = b["sample_ids"]
+        pats = b["patterns"] if (b.get("all_patterns") or b.get("fused_patterns")) else None
+        st = (self.cached_train_step_for if train else self.cached_eval_step_for)(int(ids.numel()), cache, pats)
+        if pats is not None:
+            st.step(ids)
+        else:
+            g = b.get("pattern_ids")
+            st.step(ids, b["keep"], g if g is not None else self.log.group_ids(b["pattern_name"]))
 
     def _eval_step(self, n: int) -> FusedEvalStep:
         st = self.eval_steps.get(n)
@@ -195,9 +242,13 @@ class EpochRunner:
     def train_epoch(self, loader: Iterable[Dict[str, Any]]):
         """→ (mean batch loss, seconds, metrics dict, batches)."""
         self.log.reset()
+        self._epoch_caches = {}
         t0 = time.time()
         fresh_zero = False  # the zero-input embeddings of an all-pattern epoch: refreshed on its first batch only
         for b in loader:
+            if b.get("cached"):
+                self._cached(b, True)
+                continue
             if b.get("all_patterns"):
                 a, i = b[modality_key(b, "audio")], b[modality_key(b, "image")]
                 st = self.train_pattern_step_for(a.shape[0], b["patterns"])
@@ -211,10 +262,14 @@ class EpochRunner:
     @torch.no_grad()
     def validate_epoch(self, loader: Iterable[Dict[str, Any]]):
         self.log.reset()
+        self._epoch_caches = {}
         t0 = time.time()
         self.model.eval()
         fresh_zero = False  # the zero-input embeddings: refreshed once per epoch (no weight changes inside it)
         for b in loader:
+            if b.get("cached"):
+                self._cached(b, False)
+                continue
             if b.get("fused_patterns"):
                 a, i = b[modality_key(b, "audio")], b[modality_key(b, "image")]
                 st = self.pattern_eval_step_for(a.shape[0], b["patterns"])
@@ -438,15 +493,22 @@ def _epoch_block(loss: float, timing: float, n_batches: int, metrics: Dict[str, 
 def fit(model, optimizer, loss_functions, loaders: Dict[str, Any], epochs: int, *, metric_config=None,
         early_stopping: bool = True, patience: int = 10, min_delta: float = 1e-3, scheduler=None,
         checkpoint_dir=None, metrics_path=None, save_metric: str = "loss", mode: str = "minimize",
-        on_epoch=None, fail_on_nonfinite: bool = True) -> Dict[str, Any]:
+        on_epoch=None, fail_on_nonfinite: bool = True, cache_embeddings: bool = False) -> Dict[str, Any]:
     """_train_loop + test (train_multimodal.py:554-917) for the AVMNIST late-fusion model and the MOSI / MOSEI
     UTT-Fusion model (``runner_for``; its loaders: ``mosi_data.MOSI.loader(...)``).  ``loaders``:
     "train", "validation" and optionally "test" → iterables of device batches (a DeviceLoader is
     re-iterated each epoch; call ``set_epoch`` in ``on_epoch`` for DistributedSampler order).
     ``fail_on_nonfinite``: raise FloatingPointError as soon as an epoch's mean training loss is NaN / inf
     (checked at the epoch's one host synchronisation; SURVEY §5 — the reference only turns three numpy
-    RuntimeWarnings into errors, train_multimodal.py:46-60, and would keep training on NaN weights)."""
+    RuntimeWarnings into errors, train_multimodal.py:46-60, and would keep training on NaN weights).
+    ``cache_embeddings`` (AVMNIST on frozen encoders, ``data.DeviceLoader`` loaders; refused otherwise): before the
+    first epoch each split's ``embedding_cache(model)`` is filled once, and every epoch then iterates the ``ids_only``
+    twin of its loader — no encoder launch after the fill; metric keys and loss entries per epoch are unchanged.  The
+    fill times are reported once under ``history["embedding_cache"]``."""
     runner = runner_for(model, optimizer, loss_functions, metric_config)
+    cache_report = None
+    if cache_embeddings:
+        loaders, cache_report = _cached_loaders(model, optimizer, runner, loaders)
     if getattr(runner, "regression", False) and save_metric != "loss":
         raise ValueError(f"save_metric {save_metric!r}: a regression run selects its best epoch by the loss; only "
                          "save_metric='loss' is supported")
@@ -487,7 +549,39 @@ def fit(model, optimizer, loss_functions, loaders: Dict[str, Any], epochs: int, 
     if "test" in loaders:
         if ckpt is not None and (ckpt.model_dir / "best.pth").exists():
             ckpt.load_checkpoint(model, load_best=True)
+            if cache_embeddings:  # load_state_dict made the caches stale (the loaded encoders may differ)
+                loaders["test"].ds.embedding_cache(model, refresh=True)
         te_loss, te_time, te_metrics, _ = runner.validate_epoch(loaders["test"])
         history["test"] = dict(te_metrics, loss=te_loss)
     history["best"] = best
+    if cache_report is not None:
+        history["embedding_cache"] = cache_report
     return history
+
+
+def _cached_loaders(model, optimizer, runner, loaders: Dict[str, Any]):
+    """fit(cache_embeddings=True): the ``ids_only`` twin of every loader and one filled cache per split."""
+    from .data import DeviceLoader
+    if not isinstance(runner, EpochRunner):
+        raise L.TspmError("cache_embeddings=True is for the AVMNIST late-fusion model")
+    if not head_stage_frozen(model, optimizer):
+        raise L.TspmError("cache_embeddings=True needs frozen encoders (AVMNIST.freeze_encoders()): a trainable "
+                          "encoder's embeddings change every step, so there is nothing constant to cache")
+    out, report = {}, {"fill_seconds": {}, "rows": {}}
+    for name, ld in loaders.items():
+        if not isinstance(ld, DeviceLoader):
+            raise L.TspmError(f"cache_embeddings=True: loaders[{name!r}] must be a data.DeviceLoader "
+                              f"(dataset.device_loader(...)), got {type(ld).__name__}")
+        twin = ld if ld.ids_only else DeviceLoader(
+            ld.ds, ld.batch_size, ld.shuffle, ld.drop_last, ld.generator, rank=ld.rank, world_size=ld.world_size,
+            distributed=ld.distributed, seed=ld.seed, pattern=ld.pattern, fuse_patterns=ld.fuse_patterns,
+            all_patterns=ld.all_patterns, ids_only=True)
+        twin.epoch = ld.epoch
+        cache = ld.ds.embedding_cache(model)
+        if cache.stale_reason() is not None:
+            cache.refresh()
+        report["fill_seconds"][name], report["rows"][name] = cache.fill_seconds, cache.n
+        out[name] = twin
+    print("embedding cache filled: " + ", ".join(f"{k} {report['rows'][k]} rows in {v:.3f} s"
+                                                 for k, v in report["fill_seconds"].items()))
+    return out, report

@@ -16,6 +16,7 @@ are unchanged, so ``best.pth`` / ``encoder_{mod}_best.pth`` checkpoints interope
 """
 from __future__ import annotations
 
+import weakref
 from collections import defaultdict
 from functools import partial
 from typing import Any, Dict, List, Optional, Sequence, Tuple
@@ -96,6 +97,7 @@ class ResNetEncoder(nn.Module):
                     nn.init.constant_(m.bn2.weight, 0)
         self._engines: Dict[Tuple, EncoderEngine] = {}
         self._fwd_generation = 0
+        self._weights_generation = 0  # bumped by load_state_dict and by anything that moves the parameters
 
     def _make_layer(self, block, planes: int, blocks: int, stride: int = 1) -> nn.Sequential:
         norm_layer = self._norm_layer
@@ -118,7 +120,14 @@ class ResNetEncoder(nn.Module):
     def _apply(self, fn, *args, **kwargs):
         out = super()._apply(fn, *args, **kwargs)
         self._engines = {}  # parameters moved: drop plans bound to old storage
+        self._weights_generation = getattr(self, "_weights_generation", 0) + 1
         return out
+
+    def _load_from_state_dict(self, *args, **kwargs):
+        # reached by this encoder's own load_state_dict and by any parent's: what was computed from the old weights
+        # (EmbeddingCache) is stale from here on
+        self._weights_generation = getattr(self, "_weights_generation", 0) + 1
+        return super()._load_from_state_dict(*args, **kwargs)
 
     def engine_for(self, x: torch.Tensor) -> EncoderEngine:
         if x.dim() == 3:
@@ -339,6 +348,7 @@ class AVMNIST(nn.Module):
                 p.grad = None
             enc.eval()
         self._frozen_encoders = tuple(self.ENCODERS)
+        self._freeze_generation = getattr(self, "_freeze_generation", 0) + 1
         self._fused_step = None
         return self
 
@@ -346,6 +356,7 @@ class AVMNIST(nn.Module):
         """Undo ``freeze_encoders``: every encoder parameter trainable again and the encoders back on the model's
         mode.  An optimizer built while they were frozen does not hold them: build a new one."""
         self._frozen_encoders = ()
+        self._freeze_generation = getattr(self, "_freeze_generation", 0) + 1
         for name in self.ENCODERS:
             enc = getattr(self, name)
             for p in enc.parameters():
@@ -418,6 +429,8 @@ class AVMNIST(nn.Module):
         metrics.DeviceMetricRecorder the batch's predictions are recorded on the device inside the step's
         HIP graph; with the reference's MetricRecorder they are copied to the host as the reference does."""
         from .step import FusedTrainStep, fused_step_supported
+        if batch.get("cached"):
+            return self._train_step_cached(batch, optimizer, loss_functions, device, metric_recorder)
         if batch.get("all_patterns"):
             return self._train_step_all_patterns(batch, optimizer, loss_functions, device, metric_recorder)
         A, I, labels, miss_type = self._unpack(batch, device)
@@ -476,6 +489,64 @@ class AVMNIST(nn.Module):
                                              m_types=np.repeat(np.array(pats), A.shape[0]))
         return {"loss": float(out["loss"].item())}
 
+    # -- the head stage on cached embeddings (EmbeddingCache below; batches of an ``ids_only`` loader) ----------
+    def _cache_of(self, batch) -> "EmbeddingCache":
+        """The embedding cache a ``"cached"`` batch reads: its dataset's cache of this model (filled here, over the
+        whole split, if no epoch runner or ``fit`` has built it yet)."""
+        ds = batch.get("dataset")
+        if ds is None or not hasattr(ds, "embedding_cache"):
+            raise L.TspmError('a "cached" batch names its dataset under "dataset" (data.DeviceLoader(ids_only=True) does)')
+        return ds.embedding_cache(self)
+
+    def _train_step_cached(self, batch, optimizer, loss_functions, device, metric_recorder):
+        """A ``"cached"`` train batch (data.AVMNIST.device_loader(ids_only=True)): one ``FusedCachedHeadStep`` on the
+        dataset's embedding cache of this model — every pattern of the batch for an ``"all_patterns"`` batch, else one
+        pattern per sample from the batch's ``"keep"`` flags."""
+        from .step import FusedCachedHeadStep, norm_avmnist_patterns, train_step_key
+        cache = self._cache_of(batch)
+        ids = batch["sample_ids"]
+        pats = norm_avmnist_patterns(batch["patterns"]) if batch.get("all_patterns") else None
+        key = train_step_key(self, int(ids.numel()), pats, cached=True) + (id(optimizer), id(loss_functions), id(cache))
+        steps = self.__dict__.setdefault("_fused_cached_steps", {})
+        st = steps.get(key)
+        if st is None:
+            st = FusedCachedHeadStep(self, optimizer, loss_functions, int(ids.numel()), cache, patterns=pats,
+                                     per_sample=pats is None)
+            steps[key] = st
+        dlog = self._device_log(metric_recorder)
+        if metric_recorder is not None and dlog is None:
+            raise L.TspmError("a cached batch records its predictions on the device: train_step needs a "
+                              "metrics.DeviceMetricRecorder (or use the default loader)")
+        st.log = dlog
+        if pats is None:
+            out = st.step(ids, batch["keep"], batch.get("pattern_ids"))
+        else:
+            out = st.step(ids)
+        return {"loss": float(out["loss"].item())}
+
+    def _validation_step_cached(self, batch, loss_functions, device, metric_recorder):
+        """A ``"cached"`` valid / test batch: one ``FusedCachedEvalStep`` on the dataset's embedding cache."""
+        from .step import FusedCachedEvalStep, norm_avmnist_patterns
+        dlog = self._device_log(metric_recorder)
+        if dlog is None:
+            raise L.TspmError("a cached batch records its losses and predictions on the device: validation_step needs "
+                              "a metrics.DeviceMetricRecorder (or use the default loader)")
+        cache = self._cache_of(batch)
+        ids = batch["sample_ids"]
+        pats = norm_avmnist_patterns(batch["patterns"]) if batch.get("fused_patterns") else None
+        key = (pats, int(ids.numel()), id(cache), _ce_weight_of(loss_functions))
+        steps = self.__dict__.setdefault("_fused_cached_eval", {})
+        st = steps.get(key)
+        if st is None:
+            st = FusedCachedEvalStep(self, loss_functions, int(ids.numel()), cache, dlog, patterns=pats,
+                                     per_sample=pats is None)
+            steps[key] = st
+        st.log = dlog
+        self.eval()
+        with torch.no_grad():
+            out = st.step(ids) if pats is not None else st.step(ids, batch["keep"], batch.get("pattern_ids"))
+            return {"loss": float(out["loss"].mean().item())}
+
     def eval_step_for(self, loss_functions, batch: int, log=None):
         """The cached FusedEvalStep for this batch size (one HIP graph per size)."""
         from .step import FusedEvalStep
@@ -495,6 +566,8 @@ class AVMNIST(nn.Module):
         self.__dict__.pop("_zero_emb", None)
         self.__dict__.pop("_fused_pattern_eval", None)
         self.__dict__.pop("_fused_pattern_step", None)
+        self.__dict__.pop("_fused_cached_steps", None)
+        self.__dict__.pop("_fused_cached_eval", None)
         return out
 
     def zero_embeddings(self, refresh: bool = True, audio_hw=(32, 94), image_hw=(28, 28)) -> torch.Tensor:
@@ -571,6 +644,8 @@ class AVMNIST(nn.Module):
         """models/avmnist.py:312-360 (eval-mode BN running stats, dropout off).  With a single
         cross-entropy loss group the batch runs as one FusedEvalStep graph (predictions recorded on the
         device when metric_recorder is a metrics.DeviceMetricRecorder)."""
+        if batch.get("cached"):
+            return self._validation_step_cached(batch, loss_functions, device, metric_recorder)
         if batch.get("fused_patterns"):
             return self._validation_step_patterns(batch, loss_functions, device, metric_recorder)
         self.eval()
@@ -621,3 +696,118 @@ class AVMNIST(nn.Module):
         if name == "image":
             return self.image_encoder
         raise ValueError(f"Unknown modality: {modality}")
+
+
+# ------------------------------------------------------------------------------------------------
+# The frozen encoders' embeddings of a whole split, computed once (the head stage without the encoders)
+# ------------------------------------------------------------------------------------------------
+class EmbeddingCache:
+    """Both frozen encoders' eval-mode embeddings of every sample of a device corpus: ``emb [num_samples][F]`` fp32
+    (``F = embd_size_A + embd_size_I``, audio columns first; 60,000 x 192 x 4 B = 46 MB), ``labels_all [num_samples]``
+    int64 (the corpus' own label tensor) and ``x0 [F]``, the model's ``zero_embeddings(refresh=True)`` buffer — what a
+    pattern that drops a modality feeds the head.  A frozen encoder runs on its running statistics, so each row is a
+    function of that sample and of weights that never move: the cache is a constant of the whole head stage, and
+    ``step.FusedCachedHeadStep`` / ``FusedCachedEvalStep`` read it by sample index instead of running the encoders.
+
+    The fill (``refresh()``) runs both encoders' eval forward over the corpus in sample order, unmasked, in chunks of
+    ``chunk`` rows plus one shorter last chunk, the image encoder on the side stream as the head-stage steps run it,
+    writing straight into ``emb``.  It is refused for a model whose encoders are not frozen.
+
+    The cache remembers the model's frozen encoders, its freeze generation, each encoder's weights generation and the
+    identity of the encoders' engine tables.  ``unfreeze_encoders()``, ``load_state_dict`` on the model or on an
+    encoder, and anything that drops the engines (``.to()``) make it stale; a stale cache is refused at its next use
+    with a ``TspmError`` that says to call ``refresh()``.  Weights written through raw pointers (FusedAdam's flat
+    buffers, an in-place ``copy_``) cannot be detected, as ``AVMNIST.zero_embeddings`` says of itself: callers who
+    change frozen weights that way call ``refresh()``."""
+
+    def __init__(self, model: "AVMNIST", device_corpus, chunk: int = 256):
+        if int(chunk) < 1:
+            raise ValueError("chunk must be >= 1")
+        # the model is held weakly: the dataset's table of caches is keyed by the model and must not keep it alive
+        self._model_ref, self.dc, self.chunk = weakref.ref(model), device_corpus, int(chunk)
+        self.n = int(device_corpus.n)
+        self.ea = int(model.embd_size_A)
+        self.F = self.ea + int(model.embd_size_I)
+        self.audio_hw, self.image_hw = tuple(device_corpus.audio_shape), tuple(device_corpus.image_shape)
+        self.emb: Optional[torch.Tensor] = None
+        self.labels_all = device_corpus.labels
+        self.x0: Optional[torch.Tensor] = None
+        self.fill_seconds = 0.0
+        self.fills = 0
+        self._stamp = None
+        self.refresh()
+
+    @property
+    def model(self) -> "AVMNIST":
+        m = self._model_ref()
+        if m is None:
+            raise L.TspmError("this EmbeddingCache's model no longer exists")
+        return m
+
+    def _now(self):
+        m = self.model
+        return (tuple(m.frozen_encoders()), getattr(m, "_freeze_generation", 0),
+                getattr(m.audio_encoder, "_weights_generation", 0), getattr(m.image_encoder, "_weights_generation", 0),
+                m.audio_encoder._engines, m.image_encoder._engines)
+
+    def stale_reason(self) -> Optional[str]:
+        """None while the cache is current, else what changed since the fill."""
+        was, now = self._stamp, self._now()
+        if now[0] != was[0] or now[1] != was[1]:
+            return "the model's encoders were unfrozen (or frozen again) since the fill"
+        if now[2] != was[2] or now[3] != was[3] or now[4] is not was[4] or now[5] is not was[5]:
+            return "an encoder's weights were loaded or moved (load_state_dict, .to()) since the fill"
+        return None
+
+    def check(self, model=None) -> "EmbeddingCache":
+        """Refuse a cache built for another model, and a stale one."""
+        if model is not None and model is not self.model:
+            raise L.TspmError("this EmbeddingCache was built for another model: its rows are that model's encoders' "
+                              "embeddings (dataset.embedding_cache(model) builds this model's)")
+        why = self.stale_reason()
+        if why is not None:
+            raise L.TspmError(f"stale EmbeddingCache: {why}; call refresh() on it (with the encoders frozen) before "
+                              "the next use")
+        return self
+
+    def refresh(self) -> "EmbeddingCache":
+        """(Re)compute every row and the zero-input row; returns self."""
+        import time
+        from .step import head_stage_frozen
+        model, dc = self.model, self.dc
+        if not head_stage_frozen(model):
+            raise L.TspmError("EmbeddingCache: the model's encoders are not frozen (AVMNIST.freeze_encoders()); a "
+                              "trainable encoder's embeddings change every step and its BatchNorm runs on batch "
+                              "statistics, so there is nothing constant to cache")
+        dev = next(model.parameters()).device
+        if dev != dc.device:
+            raise L.TspmError(f"EmbeddingCache: the model is on {dev}, the corpus on {dc.device}")
+        f32 = dict(device=dev, dtype=torch.float32)
+        if self.emb is None or self.emb.device != dev:
+            self.emb = torch.empty(self.n, self.F, **f32)
+        n, F, ea, ch = self.n, self.F, self.ea, min(self.chunk, max(self.n, 1))
+        torch.cuda.synchronize(dev)
+        t0 = time.perf_counter()
+        main, side = torch.cuda.current_stream(), L.shared_streams(dev, 1)[0]
+        order = torch.arange(n, dtype=torch.int64, device=dev)
+        bufs = {}
+        with torch.no_grad():
+            for lo in range(0, n, ch):
+                b = min(ch, n - lo)
+                if b not in bufs:
+                    bufs[b] = (torch.empty(b, *self.audio_hw, **f32), torch.empty(b, 1, *self.image_hw, **f32),
+                               torch.empty(b, dtype=torch.int64, device=dev))
+                A, I, lab = bufs[b]
+                dc.gather(order[lo:lo + b], None, None, out=(A, I, lab))
+                rows = self.emb[lo:lo + b]
+                side.wait_stream(main)
+                with torch.cuda.stream(side):
+                    model.image_encoder.engine_for(I).forward(I, rows[:, ea:], F, train=False)
+                model.audio_encoder.engine_for(A).forward(A, rows, F, train=False)
+                main.wait_stream(side)  # the next chunk's gather overwrites I
+        self.x0 = model.zero_embeddings(refresh=True, audio_hw=self.audio_hw, image_hw=self.image_hw)
+        torch.cuda.synchronize(dev)
+        self.fill_seconds = time.perf_counter() - t0
+        self.fills += 1
+        self._stamp = self._now()
+        return self

@@ -729,6 +729,14 @@ class FusedPatternEvalStep(L.GraphRunner):
         self.eng_a = model.audio_encoder.engine_for(self.A)
         self.eng_i = model.image_encoder.engine_for(self.I)
         self.x0 = model.zero_embeddings(refresh=False, audio_hw=self.audio_hw, image_hw=self.image_hw)
+        self._alloc_head(dev, batch, head)
+        self.side = L.shared_streams(dev, 1)[0]
+
+    def _alloc_head(self, dev, batch: int, head: str) -> None:
+        """The outputs, the host arrays of the launch arguments and the buffers of the head leg ``head`` — everything
+        ``_head_kernel`` / ``_head_launches`` touch besides ``labels`` and ``x0`` (``FusedCachedEvalStep`` shares it)."""
+        P, ea, ei = self.P, self.ea, self.F - self.ea
+        f32 = dict(device=dev, dtype=torch.float32)
         self.logits = torch.empty(P * batch, NUM_CLASSES, **f32)
         self.loss = torch.zeros(P, **f32)
         self.preds = torch.zeros(P * batch, dtype=torch.int64, device=dev)
@@ -753,7 +761,6 @@ class FusedPatternEvalStep(L.GraphRunner):
             self.hh = torch.empty(P * batch, self.h2, **f32)
             self.labels_x = torch.zeros(P * batch, dtype=torch.int64, device=dev)
             self.groups = torch.zeros(P * batch, dtype=torch.int32, device=dev)
-        self.side = L.shared_streams(dev, 1)[0]
 
     def _group_ids(self) -> List[int]:
         """Each pattern's group in the log (its position among the log's groups; without a log, among all patterns)."""
@@ -913,15 +920,16 @@ def head_stage_frozen(model, optimizer=None, allreduce=None, all_patterns: bool 
     return names
 
 
-def train_step_key(model, n: int, patterns=None):
+def train_step_key(model, n: int, patterns=None, cached: bool = False):
     """The cache key of a model's fused train step for batch size ``n``: ``n`` itself for an all-trainable model (every
     existing key unchanged); with frozen encoders a tuple that ends in ``("frozen", names)``; an all-pattern step's
-    starts with ``("patterns", names)``."""
+    starts with ``("patterns", names)``.  ``cached``: the step of a ``"cached"`` batch (``FusedCachedHeadStep``) — the
+    same tuple with a trailing ``("cached",)`` element, which no other key has."""
     names = tuple(getattr(model, "frozen_encoders", lambda: ())())
-    if not names and patterns is None:
+    if not names and patterns is None and not cached:
         return n
     key = ((("patterns", tuple(patterns)),) if patterns is not None else ()) + (n,)
-    return key + ((("frozen", names),) if names else ())
+    return key + ((("frozen", names),) if names else ()) + ((("cached",),) if cached else ())
 
 
 class _HeadStageBase(L.GraphRunner):
@@ -930,6 +938,16 @@ class _HeadStageBase(L.GraphRunner):
     one flat group (the head launch advances the step counter, so the update is one more launch)."""
 
     def _setup(self, model, optimizer, loss_functions, batch: int, audio_hw, image_hw, use_graph: bool, what: str):
+        self._setup_head(model, optimizer, loss_functions, batch, audio_hw, image_hw, use_graph, what)
+        dev, B = self.device, self.N
+        f32 = dict(device=dev, dtype=torch.float32)
+        self.A = torch.zeros(B, audio_hw[0], audio_hw[1], **f32)
+        self.I = torch.zeros(B, 1, image_hw[0], image_hw[1], **f32)
+        self.eng_a = model.audio_encoder.engine_for(self.A)
+        self.eng_i = model.image_encoder.engine_for(self.I)
+
+    def _setup_head(self, model, optimizer, loss_functions, batch: int, audio_hw, image_hw, use_graph: bool, what: str):
+        """Everything of ``_setup`` but the encoders' inputs and engines (``FusedCachedHeadStep`` has neither)."""
         self.model, self.opt, self.loss_functions, self.N = model, optimizer, loss_functions, int(batch)
         self.ce_weight = _ce_weight(loss_functions)
         if self.ce_weight is None:
@@ -952,11 +970,7 @@ class _HeadStageBase(L.GraphRunner):
         self.ea = int(model.embd_size_A)
         self.F = self.ea + int(model.embd_size_I)
         self.hd, self.h2 = int(model.hidden_dim), int(model.hidden_dim) // 2
-        self.A = torch.zeros(B, audio_hw[0], audio_hw[1], **f32)
-        self.I = torch.zeros(B, 1, image_hw[0], image_hw[1], **f32)
         self.labels = torch.zeros(B, dtype=torch.int64, device=dev)
-        self.eng_a = model.audio_encoder.engine_for(self.A)
-        self.eng_i = model.image_encoder.engine_for(self.I)
         self.loss = torch.zeros(1, **f32)
         self.stats = torch.zeros(4, **f32)  # loss*n, correct, n (accumulated on device)
         self.log = None
@@ -1174,8 +1188,10 @@ class FusedHeadStagePatternStep(_HeadStageBase):
         self._classify_rows(sh, self.P * self.N, self.logits, self.labels_x, self.groups)
         self._adam(sh)
 
-    def _head(self, sh: int) -> None:
-        """The head leg alone (forward, loss, weight backward over the P*B rows) from ``fused`` and ``x0``, either way."""
+    def _head(self, sh: int, head: Optional[str] = None) -> None:
+        """The head leg alone (forward, loss, weight backward over the P*B rows) from ``fused`` and ``x0``, either way
+        (``head``: the leg, by default this step's own)."""
+        head = self.head if head is None else head
         net, g = self.model.net, (lambda t: t.data_ptr())
         p = float(self.model.dropout_p)
         gp = self.gptr
@@ -1184,7 +1200,7 @@ class FusedHeadStagePatternStep(_HeadStageBase):
         ctr = self._rng_ctr_ptr if p > 0 else None
         bump = self._rng_ctr_ptr if self._head_bumps() else None
         n, B, F = self.P * self.N, self.N, self.F
-        if self.head == "kernel":
+        if head == "kernel":
             d = L.PatternHeadTrainDesc(
                 batch=B, npat=self.P, in_=F, w_audio=self.ea, hidden=self.hd, hidden2=self.h2, classes=NUM_CLASSES,
                 ldx=F, gen_keep=gen_keep, x=g(self.fused), x0=g(self.x0), keep=self._keep2, w0=g(net[0].weight),
@@ -1247,3 +1263,332 @@ class FusedHeadStagePatternStep(_HeadStageBase):
         self.load_batch(A, I, labels)
         self.run(refresh_zero)
         return {"loss": self.loss, "logits": self.logits.view(self.P, self.N, NUM_CLASSES)}
+
+
+# ------------------------------------------------------------------------------------------------------
+# The head stage on cached embeddings (modules.EmbeddingCache): no encoder launch in a step
+# ------------------------------------------------------------------------------------------------------
+# the head of a FusedCachedHeadStep built without head=: "kernel" (one tspm_cached_head_train_step call, the log folded
+# in) or "launches" (tspm_embed_gather + the uncached head launch + tspm_classify_update); the leg whose median
+# measured lower at batch 128, for every pattern (39.4 against 43.8 us) and per sample (37.6 against 39.2 us):
+# profiles/avmnist_embedding_cache.json, DESIGN §3.23
+DEFAULT_CACHED_HEAD = "kernel"
+
+
+class FusedCachedHeadStep(_HeadStageBase):
+    """The head stage on an ``EmbeddingCache``: the head's forward, cross-entropy, weight backward and Adam over the
+    cache rows a batch names by sample index, as one HIP graph without an encoder launch.  Two modes.  Every pattern of
+    the batch (``patterns``: names, default all three; ``FusedHeadStagePatternStep``'s semantics, ``logits [P, B, C]``)
+    or one pattern per sample (``per_sample=True``: what the default train loader draws — ``FusedHeadStageStep``'s
+    semantics with the sample's dropped modality taken from ``cache.x0``, ``logits [B, C]``).
+
+    ``head="kernel"``: one ``tspm_cached_head_train_step`` call, which reads the rows and labels from the cache and
+    writes the classification log itself.  ``head="launches"``: ``tspm_embed_gather`` into the static ``fused``, then
+    the uncached launch — ``FusedHeadStagePatternStep._head`` (every pattern) or ``tspm_head_train_step`` (per sample)
+    — then ``tspm_classify_update``: the A/B leg, bitwise those steps fed ``cache.emb[ids]``, and the fallback for a
+    head outside the fused kernel's limits.  Then Adam over the head's one group (the head launch advances the step
+    counter).  The dropout seed and counter are the existing steps'.
+
+    ``step(sample_ids, keep=None, groups=None)`` → ``{"loss": [1], "logits"}``: ``sample_ids [B]`` int64, and per
+    sample ``keep [B, 2]`` (audio, image; non-zero = the real input) and ``groups [B]`` (the rows' groups in the log).
+    Refused: what ``_HeadStageBase`` refuses, a stale cache and a cache built for another model."""
+
+    def __init__(self, model, optimizer: FusedAdam, loss_functions, batch: int, cache, patterns=None,
+                 per_sample: bool = False, head: Optional[str] = None, log=None, use_graph: bool = True,
+                 allreduce=None):
+        if allreduce is not None:
+            head_stage_frozen(model, optimizer, allreduce)  # refuses it for a frozen model, naming why
+        self.per_sample = bool(per_sample)
+        if self.per_sample and patterns is not None:
+            raise ValueError("per_sample=True draws one pattern per sample from the keep flags; it excludes patterns=")
+        self.patterns = () if self.per_sample else norm_avmnist_patterns(patterns)
+        self.P = P = 1 if self.per_sample else len(self.patterns)
+        cache.check(model)
+        self.cache = cache
+        self._setup_head(model, optimizer, loss_functions, batch, cache.audio_hw, cache.image_hw, use_graph,
+                         "FusedCachedHeadStep")
+        self.log = log
+        head = DEFAULT_CACHED_HEAD if head is None else head
+        if head not in ("kernel", "launches"):
+            raise ValueError(f"head: 'kernel' or 'launches', got {head!r}")
+        fits = L.cached_head_train_supported(self.F, self.ea, self.hd, self.h2, NUM_CLASSES, P)
+        if head == "kernel" and not fits:
+            head = "launches"
+        self.head = head
+        dev, B = self.device, self.N
+        n = P * B
+        f32 = dict(device=dev, dtype=torch.float32)
+        self.x0 = cache.x0
+        self.rows = torch.zeros(B, dtype=torch.int64, device=dev)
+        self.row_keep = torch.ones(B, 2, dtype=torch.uint8, device=dev)
+        self.groups = torch.zeros(B, dtype=torch.int32, device=dev)
+        self.logits = torch.empty(n, NUM_CLASSES, **f32)
+        self.keep = torch.ones(n, self.hd, dtype=torch.uint8, device=dev)
+        self._keep2 = (ctypes.c_int32 * (2 * max(P, 1)))(*[k for p in self.patterns for k in PATTERN_KEEP[p]])
+        self._gid = (ctypes.c_int32 * max(P, 1))()
+        if head == "kernel":
+            need = int(L.lib().tspm_cached_head_train_workspace(B, P))
+            self.ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+        elif self.per_sample:
+            # FusedHeadStageStep's buffers
+            self.fused = torch.empty(B, self.F, **f32)
+            self.h1 = torch.empty(B, self.hd, **f32)
+            self.hh = torch.empty(B, self.h2, **f32)
+            self.dlogits = torch.empty(B, NUM_CLASSES, **f32)
+            self.dh = torch.empty(B, self.h2, **f32)
+            self.dh1 = torch.empty(B, self.hd, **f32)
+            self.dscratch = torch.empty(B, self.F, **f32)
+            self.row_ws = torch.empty(2 * B, **f32)
+        else:
+            # FusedHeadStagePatternStep's buffers, for the leg of its _head that fits this head
+            self._inner = "kernel" if L.pattern_head_train_supported(self.F, self.ea, self.hd, self.h2, NUM_CLASSES,
+                                                                     P) else "launches"
+            self.labels_x = torch.zeros(n, dtype=torch.int64, device=dev)
+            self.groups_x = torch.zeros(n, dtype=torch.int32, device=dev)
+            if self._inner == "kernel":
+                self.fused = torch.empty(B, self.F, **f32)
+                need = int(L.lib().tspm_pattern_head_train_workspace(B, P))
+                self.ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+            else:
+                ei = self.F - self.ea
+                self.emb2 = torch.empty(2 * B, self.F, **f32)
+                self.fused = self.emb2[:B]
+                self._widths = (self.ea, ei // 2, ei - ei // 2)
+                self.x = torch.empty(n, self.F, **f32)
+                self.h1 = torch.empty(n, self.hd, **f32)
+                self.hh = torch.empty(n, self.h2, **f32)
+                self.dlogits = torch.empty(n, NUM_CLASSES, **f32)
+                self.dh = torch.empty(n, self.h2, **f32)
+                self.dh1 = torch.empty(n, self.hd, **f32)
+                self.dscratch = torch.empty(n, self.F, **f32)
+                self.row_ws = torch.empty(2 * n, **f32)
+                self._keep3 = (ctypes.c_int32 * (3 * P))(*[k for p in self.patterns
+                                                            for k in (PATTERN_KEEP[p][0],) + (PATTERN_KEEP[p][1],) * 2])
+        self._bound_groups = None
+        self._sig = self._sig + (self.patterns, self.per_sample, id(cache))
+
+    def _group_ids(self) -> List[int]:
+        gid = self.log.gid if self.log is not None else {p: i for i, p in enumerate(AVMNIST_PATTERNS)}
+        try:
+            return [int(gid[p]) for p in self.patterns]
+        except KeyError as e:
+            raise L.TspmError(f"pattern {e} is not one of this log's groups {self.log.groups}") from None
+
+    def _dropout(self):
+        p = float(self.model.dropout_p)
+        return (p, 1 if (p > 0 and self.keep_override is None) else 0, int(self.model._rng_seed) if p > 0 else 0,
+                self._rng_ctr_ptr if p > 0 else None, self._rng_ctr_ptr if self._head_bumps() else None)
+
+    def _gather(self, sh: int, flags: bool) -> None:
+        c = self.cache
+        L.check(L.lib().tspm_embed_gather(
+            self.N, self.F, c.emb.data_ptr(), c.n, self.F, self.rows.data_ptr(), c.labels_all.data_ptr(),
+            self.row_keep.data_ptr() if flags else None, self.ea, self.x0.data_ptr() if flags else None,
+            self.fused.data_ptr(), self.F, self.labels.data_ptr(), sh), "embed_gather")
+
+    def _enqueue(self) -> None:
+        for i, gv in enumerate(self._group_ids()):
+            self._gid[i] = gv
+        sh = torch.cuda.current_stream().cuda_stream
+        net, g, c, log = self.model.net, (lambda t: t.data_ptr()), self.cache, self.log
+        p, gen_keep, seed, ctr, bump = self._dropout()
+        gp = self.gptr
+        if self.head == "kernel":
+            d = L.CachedHeadTrainDesc(
+                batch=self.N, npat=self.P, in_=self.F, w_audio=self.ea, hidden=self.hd, hidden2=self.h2,
+                classes=NUM_CLASSES, ld_emb=self.F, gen_keep=gen_keep, n_groups=len(log.groups) if log is not None else 1,
+                n_rows=c.n, emb=g(c.emb), x0=g(self.x0), rows=g(self.rows), labels_all=g(c.labels_all),
+                keep=None if self.per_sample else self._keep2, group_id=None if self.per_sample else self._gid,
+                row_keep=g(self.row_keep) if self.per_sample else None,
+                row_group=g(self.groups) if self.per_sample else None,
+                w0=g(net[0].weight), b0=g(net[0].bias), w3=g(net[3].weight), b3=g(net[3].bias), w5=g(net[5].weight),
+                b5=g(net[5].bias), p=p, loss_weight=self.ce_weight, seed=seed, counter=ctr, keep_mask=g(self.keep),
+                logits=g(self.logits), gw0=gp[0], gb0=gp[1], gw3=gp[2], gb3=gp[3], gw5=gp[4], gb5=gp[5],
+                loss=g(self.loss), stats=g(self.stats), adam_step=bump,
+                confusion=g(log.conf) if log is not None else None, loss_log=g(log.loss_log) if log is not None else None,
+                counters=g(log.counters) if log is not None else None, log_capacity=log.capacity if log is not None else 0,
+                workspace=g(self.ws), workspace_bytes=self.ws.numel())
+            L.check(L.lib().tspm_cached_head_train_step(d, sh), "cached_head_train_step")
+        elif self.per_sample:
+            self._gather(sh, True)
+            d = L.HeadDesc(n=self.N, in_=self.F, hidden=self.hd, hidden2=self.h2, classes=NUM_CLASSES, ldx=self.F,
+                           lddx=self.F, gen_keep=gen_keep, x=g(self.fused), w0=g(net[0].weight), b0=g(net[0].bias),
+                           w3=g(net[3].weight), b3=g(net[3].bias), w5=g(net[5].weight), b5=g(net[5].bias), p=p,
+                           loss_weight=self.ce_weight, seed=seed, counter=ctr, keep=g(self.keep), labels=g(self.labels),
+                           h1=g(self.h1), hh=g(self.hh), logits=g(self.logits), dlogits=g(self.dlogits), dz3=g(self.dh),
+                           dz0=g(self.dh1), dx=g(self.dscratch), row_ws=g(self.row_ws), gw0=gp[0], gb0=gp[1], gw3=gp[2],
+                           gb3=gp[3], gw5=gp[4], gb5=gp[5], loss=g(self.loss), stats=g(self.stats), adam_step=bump,
+                           rows_per_block=0)
+            L.check(L.lib().tspm_head_train_step(d, sh), "head_train_step")
+            self._classify_rows(sh, self.N, self.logits, self.labels, self.groups)
+        else:
+            self._gather(sh, False)
+            grp, self.groups = self.groups, self.groups_x  # _head's expand writes the P*B group ids (launches leg)
+            try:
+                FusedHeadStagePatternStep._head(self, sh, self._inner)
+            finally:
+                self.groups = grp
+            if log is not None:
+                if self._inner == "kernel":  # the rows' labels for tspm_classify_update (the expand writes them otherwise)
+                    self.labels_x.view(self.P, self.N).copy_(self.labels.unsqueeze(0).expand(self.P, self.N))
+                self._classify_rows(sh, self.P * self.N, self.logits, self.labels_x, self.groups_x)
+        self._adam(sh)
+
+    def load_batch(self, sample_ids: torch.Tensor, keep: Optional[torch.Tensor] = None,
+                   groups: Optional[torch.Tensor] = None) -> None:
+        if sample_ids.numel() != self.N:
+            raise L.TspmError(f"FusedCachedHeadStep: built for {self.N} samples, got {sample_ids.numel()} ids")
+        if not self.per_sample and (keep is not None or groups is not None):
+            raise L.TspmError("FusedCachedHeadStep: keep / groups are per-sample inputs; this step trains every pattern "
+                              "of the batch")
+        if sample_ids.data_ptr() != self.rows.data_ptr():
+            self.rows.copy_(sample_ids.reshape(-1), non_blocking=True)
+        if keep is not None and keep.data_ptr() != self.row_keep.data_ptr():
+            self.row_keep.copy_(keep.reshape(self.N, 2).to(torch.uint8), non_blocking=True)
+        if groups is not None and groups.data_ptr() != self.groups.data_ptr():
+            self.groups.copy_(groups.reshape(-1).to(torch.int32), non_blocking=True)
+
+    def _bind_groups(self) -> None:
+        """Every-pattern launches leg on the fused inner kernel: the P*B rows' group ids, written outside the graph."""
+        if self.per_sample or self.head == "kernel" or self._inner != "kernel" or self.log is None:
+            return
+        gids = tuple(self._group_ids())
+        if self._bound_groups != gids:
+            self.groups_x.copy_(torch.tensor(gids, dtype=torch.int32).repeat_interleave(self.N), non_blocking=False)
+            self._bound_groups = gids
+
+    def run(self) -> None:
+        """One head-stage step on the cache rows named in the static ``rows`` (and ``row_keep`` / ``groups``)."""
+        self._still_frozen()
+        self.cache.check(self.model)
+        self.model.train()
+        self.opt.sync_hyper()
+        if self.keep_override is not None:
+            self.keep.copy_(self.keep_override.reshape(self.keep.shape).to(torch.uint8), non_blocking=True)
+        self.x0 = self.cache.x0
+        self._bind_groups()
+        self.replay_or_enqueue(self._enqueue, (self.log, self.keep_override is None, self._head_bumps(),
+                                               self.x0.data_ptr(), self.cache.emb.data_ptr(),
+                                               tuple(self._group_ids())))
+        self.opt.note_steps(1)
+        self.calls += 1
+
+    def step(self, sample_ids, keep=None, groups=None) -> Dict[str, torch.Tensor]:
+        self.load_batch(sample_ids, keep, groups)
+        self.run()
+        return {"loss": self.loss, "logits": self.logits if self.per_sample else
+                self.logits.view(self.P, self.N, NUM_CLASSES)}
+
+
+class FusedCachedEvalStep(FusedPatternEvalStep):
+    """AVMNIST.validation_step on an ``EmbeddingCache``: ``tspm_embed_gather`` into the static ``fused``, then the
+    existing eval head, as one HIP graph without an encoder launch.  A fused-pattern batch (``patterns``: names, default
+    all three) runs ``FusedPatternEvalStep``'s head (``tspm_pattern_head_eval``, or its launches for a head outside the
+    kernel's limits): P loss entries per batch in pattern order and every row's count under its pattern, as that step
+    writes them.  A per-pattern batch (``per_sample=True``: each row under its own ``keep`` flags, the dropped modality
+    from ``cache.x0``) runs ``FusedEvalStep``'s head launches: one loss entry per batch, the rows under ``groups``.
+
+    ``step(sample_ids, keep=None, groups=None)`` → ``{"loss", "logits", "preds"}``."""
+
+    def __init__(self, model, loss_functions, batch: int, cache, log=None, patterns=None, per_sample: bool = False,
+                 head: Optional[str] = None, use_graph: bool = True):
+        self.model, self.N, self.log = model, int(batch), log
+        self.ce_weight = _ce_weight(loss_functions)
+        if self.ce_weight is None:
+            raise L.TspmError("FusedCachedEvalStep: the loss group must be a single cross-entropy term")
+        self.per_sample = bool(per_sample)
+        if self.per_sample and patterns is not None:
+            raise ValueError("per_sample=True evaluates each row under its own keep flags; it excludes patterns=")
+        self.patterns = () if self.per_sample else norm_avmnist_patterns(patterns)
+        self.P = P = 1 if self.per_sample else len(self.patterns)
+        cache.check(model)
+        self.cache = cache
+        ea, ei = int(model.embd_size_A), int(model.embd_size_I)
+        self.ea, self.F, self.hd, self.h2 = ea, ea + ei, int(model.hidden_dim), int(model.hidden_dim) // 2
+        head = DEFAULT_PATTERN_HEAD if head is None else head
+        if head not in ("kernel", "launches"):
+            raise ValueError(f"head: 'kernel' or 'launches', got {head!r}")
+        if self.per_sample or not L.pattern_head_eval_supported(self.F, ea, self.hd, self.h2, NUM_CLASSES, P):
+            head = "launches"
+        self.head = head
+        dev = next(model.parameters()).device
+        self._init_graph(use_graph, dev)
+        self.audio_hw, self.image_hw = cache.audio_hw, cache.image_hw
+        f32 = dict(device=dev, dtype=torch.float32)
+        B = self.N
+        self.rows = torch.zeros(B, dtype=torch.int64, device=dev)
+        self.row_keep = torch.ones(B, 2, dtype=torch.uint8, device=dev)
+        self.labels = torch.zeros(B, dtype=torch.int64, device=dev)
+        self.x0 = cache.x0
+        if self.per_sample:  # FusedEvalStep's head buffers: one row per sample, the rows' groups
+            self.logits = torch.empty(B, NUM_CLASSES, **f32)
+            self.loss = torch.zeros(1, **f32)
+            self.preds = torch.zeros(B, dtype=torch.int64, device=dev)
+            self.groups = torch.zeros(B, dtype=torch.int32, device=dev)
+            self.fused = torch.empty(B, self.F, **f32)
+            self.h1 = torch.empty(B, self.hd, **f32)
+            self.hh = torch.empty(B, self.h2, **f32)
+        else:
+            self._alloc_head(dev, B, head)
+
+    def load_batch(self, sample_ids: torch.Tensor, keep: Optional[torch.Tensor] = None,
+                   groups: Optional[torch.Tensor] = None) -> None:
+        if sample_ids.numel() != self.N:
+            raise L.TspmError(f"FusedCachedEvalStep: built for {self.N} samples, got {sample_ids.numel()} ids")
+        if not self.per_sample and (keep is not None or groups is not None):
+            raise L.TspmError("FusedCachedEvalStep: keep / groups are per-sample inputs; this step evaluates every "
+                              "pattern of the batch")
+        if sample_ids.data_ptr() != self.rows.data_ptr():
+            self.rows.copy_(sample_ids.reshape(-1), non_blocking=True)
+        if keep is not None and keep.data_ptr() != self.row_keep.data_ptr():
+            self.row_keep.copy_(keep.reshape(self.N, 2).to(torch.uint8), non_blocking=True)
+        if groups is not None and groups.data_ptr() != self.groups.data_ptr():
+            self.groups.copy_(groups.reshape(-1).to(torch.int32), non_blocking=True)
+
+    def _enqueue(self) -> None:
+        lib, c, log = L.lib(), self.cache, self.log
+        sh = torch.cuda.current_stream().cuda_stream
+        flags = self.per_sample
+        L.check(lib.tspm_embed_gather(
+            self.N, self.F, c.emb.data_ptr(), c.n, self.F, self.rows.data_ptr(), c.labels_all.data_ptr(),
+            self.row_keep.data_ptr() if flags else None, self.ea, self.x0.data_ptr() if flags else None,
+            self.fused.data_ptr(), self.F, self.labels.data_ptr(), sh), "embed_gather")
+        if not self.per_sample:
+            self._bind_log()
+            if self.head == "kernel":
+                self._head_kernel(sh)
+            else:
+                self._head_launches(sh)
+            return
+        # FusedEvalStep's head launches
+        n, F, hd, h2, net = self.N, self.F, self.hd, self.h2, self.model.net
+        L.check(lib.tspm_linear_fwd(n, F, hd, self.fused.data_ptr(), F, net[0].weight.data_ptr(),
+                                    net[0].bias.data_ptr(), 1, None, 1.0, self.h1.data_ptr(), hd, sh), "eval fc0")
+        L.check(lib.tspm_linear_fwd(n, hd, h2, self.h1.data_ptr(), hd, net[3].weight.data_ptr(),
+                                    net[3].bias.data_ptr(), 1, None, 1.0, self.hh.data_ptr(), h2, sh), "eval fc3")
+        L.check(lib.tspm_linear_fwd(n, h2, NUM_CLASSES, self.hh.data_ptr(), h2, net[5].weight.data_ptr(),
+                                    net[5].bias.data_ptr(), 0, None, 1.0, self.logits.data_ptr(), NUM_CLASSES, sh),
+                "eval fc5")
+        L.check(lib.tspm_cross_entropy(n, NUM_CLASSES, self.logits.data_ptr(), self.labels.data_ptr(),
+                                       self.loss.data_ptr(), None, self.ce_weight, None, sh), "eval cross_entropy")
+        L.check(lib.tspm_classify_update(
+            n, NUM_CLASSES, self.logits.data_ptr(), self.labels.data_ptr(), self.groups.data_ptr(),
+            len(log.groups) if log is not None else 1, log.conf.data_ptr() if log is not None else None,
+            self.preds.data_ptr(), self.loss.data_ptr(), log.loss_log.data_ptr() if log is not None else None,
+            log.counters.data_ptr() if log is not None else None, log.capacity if log is not None else 0, sh),
+            "eval classify_update")
+
+    def run(self) -> None:
+        self.cache.check(self.model)
+        self.model.eval()
+        self.x0 = self.cache.x0
+        self.replay_or_enqueue(self._enqueue, (self.log, self.x0.data_ptr(), self.cache.emb.data_ptr()))
+        self.calls += 1
+
+    def step(self, sample_ids, keep=None, groups=None) -> Dict[str, torch.Tensor]:
+        self.load_batch(sample_ids, keep, groups)
+        self.run()
+        if self.per_sample:
+            return {"loss": self.loss, "logits": self.logits, "preds": self.preds}
+        return {"loss": self.loss, "logits": self.logits.view(self.P, self.N, NUM_CLASSES),
+                "preds": self.preds.view(self.P, self.N)}
