@@ -63,7 +63,9 @@ enum {
  * tspm_pattern_head_train_workspace, the AVMNIST fusion head's train step (forward, dropout, cross-entropy, weight
  * backward) over every missing-modality pattern of a batch whose encoders are frozen, in two launches;
  * tspm_embed_gather and tspm_cached_head_train_step / tspm_cached_head_train_workspace, that head stage on a cache of
- * the frozen encoders' embeddings (rows gathered by index; every pattern of the batch or one pattern per sample). */
+ * the frozen encoders' embeddings (rows gathered by index; every pattern of the batch or one pattern per sample);
+ * tspm_cached_head_train_steps, up to 64 consecutive steps of that stage per host call with Adam applied in the
+ * weight-gradient launch. */
 #define TSPM_ABI_VERSION 23
 int tspm_abi_version(void);  /* returns TSPM_ABI_VERSION */
 /* Static string for a status code. */
@@ -474,7 +476,8 @@ typedef struct tspm_adam_hyper {
    * corrections are formed in double and rounded to fp32 once, as ATen does */
   double lr, beta1, beta2, eps, weight_decay, grad_scale; /* grad_scale multiplies g (e.g. 1/world) */
   int64_t step;                                          /* incremented on device by tspm_adam_begin */
-  int64_t pad_;
+  int64_t pad_;                                          /* device scratch: tspm_cached_head_train_steps keeps the step
+                                                          * in flight here; nothing else reads or writes it */
 } tspm_adam_hyper;
 /* hyper->step += 1 (device-side, so a captured graph advances the bias correction per replay). */
 int tspm_adam_begin(tspm_adam_hyper* hyper, tspm_stream_t stream);
@@ -1271,6 +1274,44 @@ typedef struct tspm_cached_head_train_desc {
 } tspm_cached_head_train_desc;
 size_t tspm_cached_head_train_workspace(int32_t batch, int32_t npat);
 int tspm_cached_head_train_step(const tspm_cached_head_train_desc* desc, tspm_stream_t stream);
+
+/* tspm_cached_head_train_steps (added under ABI 23) — `steps` consecutive head-stage steps of a cached epoch in one
+ * host call, Adam applied inside each step's weight-gradient launch.  For k = 0 .. steps-1 it enqueues one step that is
+ * BITWISE tspm_cached_head_train_step followed by tspm_adam_step over the head's parameters, where step k reads
+ *   rows + k*batch, and in per-sample mode row_keep + 2*k*batch and row_group + k*batch
+ * (rows [steps*batch], row_keep [steps*batch][2], row_group [steps*batch]: an epoch's device-resident order, sliced on
+ * the device) and every other field of desc is shared by all steps.  logits, loss, keep_mask and the six gradient
+ * buffers hold the last step's values afterwards; stats, confusion, loss_log and counters accumulate one entry per
+ * step, as `steps` single calls would.  The workspace is tspm_cached_head_train_workspace(batch, npat) bytes, reused
+ * step after step.
+ *
+ * Two launches per step.  Launch 1 is tspm_cached_head_train_step's, in which one thread also stores the step in
+ * flight, hyper->step + 1, to hyper->pad_ (a word nothing else in that launch touches).  Launch 2 walks the same four
+ * weight-gradient products, one 32x32 tile per workgroup; the wave that stores a tile's gradients applies Adam — the
+ * arithmetic of tspm_adam_step with the bias corrections of step hyper->pad_, formed once per workgroup — to the
+ * parameter, exp_avg and exp_avg_sq at the gradient's flat offset, bias gradients included.  The gradient is still
+ * stored.  Every element has one owner, nothing in launch 2 reads a weight or hyper->step, and the loss workgroup stores
+ * hyper->pad_ to hyper->step at its end: hyper->step == old + steps after the call, and step k's dropout counter is
+ * old + k when desc->counter is that word.  No clip coefficient.  No floating-point atomics; eager, captured and
+ * replayed calls are bitwise equal.
+ *
+ * adam names the head's one flat Adam group: the six gradients desc->gw0 .. gb5 each lie inside [grad, grad + count),
+ * and the matching desc->w0 .. b5 is param plus the same offset; desc->adam_step == &adam->hyper->step.  Refused with
+ * TSPM_ERR_INVALID before any launch, nothing written: desc or adam NULL; steps < 1 or > TSPM_CACHED_HEAD_MAX_STEPS;
+ * whatever tspm_cached_head_train_step refuses (TSPM_ERR_WORKSPACE for the workspace, as there); a NULL or
+ * 16-byte-unaligned param, grad, exp_avg or exp_avg_sq; hyper NULL; count < 1; a gradient outside the range or a weight
+ * at another offset; another adam_step. */
+typedef struct tspm_head_adam_desc {
+  float* param;
+  float* grad;
+  float* exp_avg;
+  float* exp_avg_sq;
+  int64_t count;
+  tspm_adam_hyper* hyper;      /* device; pad_ is written (the step in flight) */
+} tspm_head_adam_desc;
+#define TSPM_CACHED_HEAD_MAX_STEPS 64
+int tspm_cached_head_train_steps(const tspm_cached_head_train_desc* desc, const tspm_head_adam_desc* adam,
+                                 int32_t steps, tspm_stream_t stream);
 
 /* All-pattern MMIMDb fusion (added under ABI 23) — tspm_gmu_fwd for EVERY missing-modality pattern of a batch in one
  * launch.  In eval mode an encoder's output row depends on that row's input and the weights only, and fc_one / fc_two

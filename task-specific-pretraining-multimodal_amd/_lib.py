@@ -247,6 +247,16 @@ class CachedHeadTrainDesc(Structure):
         [("log_capacity", c_int64), ("workspace", c_void_p), ("workspace_bytes", c_size_t)]
 
 
+class HeadAdamDesc(Structure):
+    """tspm_head_adam_desc (added under ABI 23): the head's one flat FusedAdam group for tspm_cached_head_train_steps —
+    every gradient of the step's descriptor lies inside ``grad``, its parameter at the same offset of ``param``."""
+    _fields_ = [("param", c_void_p), ("grad", c_void_p), ("exp_avg", c_void_p), ("exp_avg_sq", c_void_p),
+                ("count", c_int64), ("hyper", c_void_p)]
+
+
+CACHED_HEAD_MAX_STEPS = 64  # TSPM_CACHED_HEAD_MAX_STEPS: the most steps of one tspm_cached_head_train_steps call
+
+
 def cached_head_train_supported(in_: int, w_audio: int, hidden: int, hidden2: int, classes: int, npat: int) -> bool:
     """Python mirror of tspm_cached_head_train_step's shape checks — tspm_pattern_head_train_step's (the row kernel
     keeps its LDS layout).  False = the call would return TSPM_ERR_INVALID for this head whatever the pointers;
@@ -496,6 +506,8 @@ _SIGS = {
                                     _P]),
     "tspm_cached_head_train_workspace": (c_size_t, [c_int32, c_int32]),
     "tspm_cached_head_train_step": (c_int32, [POINTER(CachedHeadTrainDesc), _P]),
+    # added under ABI 23: up to CACHED_HEAD_MAX_STEPS consecutive cached head steps per call, Adam in the second launch
+    "tspm_cached_head_train_steps": (c_int32, [POINTER(CachedHeadTrainDesc), POINTER(HeadAdamDesc), c_int32, _P]),
     # added under ABI 23: MMIMDb's GMU and BCEWithLogits for every pattern of a batch
     "tspm_gmu_pattern_fwd": (c_int32, [c_int32, c_int32, POINTER(c_int32), c_int32, _P, c_int32, _P, _P, _P, c_int32,
                                        _P, _P, c_int32, _P]),

@@ -84,8 +84,14 @@ TSPM_DEV void vec_round(const float* Ap, const float* Bp, long long sak, long lo
     }
 }
 
-template <int WK>
-TSPM_DEV void gemm_body(const GemmArgs& g, int bid, float* lds) {
+// gemm_body's hook on every element it stores to C / rowsum (the address and the value): nothing, for every product
+// but k_cached_head_wgrad_adam's, which applies Adam to the element's parameter there
+struct GemmNoEpi {
+  TSPM_DEV void operator()(float*, float) const {}
+};
+
+template <int WK, class Epi = GemmNoEpi>
+TSPM_DEV void gemm_body(const GemmArgs& g, int bid, float* lds, const Epi& epi = Epi{}) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   // quad mode (g.quad, WK == 4): a 64x64 output tile per workgroup, one 32x32 quadrant per wave over
   // the whole K — the waves sharing A rows / B columns hit each other's lines in the CU's L1 instead
@@ -200,9 +206,13 @@ TSPM_DEV void gemm_body(const GemmArgs& g, int bid, float* lds) {
       if (g.relu) v = relu_f(v);
       if (g.keep) v *= g.keep[(long long)cm * g.N + ccol] ? g.kscale : 0.f;  // x * mask (NaN stays NaN)
       g.C[(long long)cm * g.ldc + ccol] = v;
+      epi(g.C + (long long)cm * g.ldc + ccol, v);
     }
   }
-  if (want_rs && lane < 32 && mok) g.rowsum[m] = rs;
+  if (want_rs && lane < 32 && mok) {
+    g.rowsum[m] = rs;
+    epi(g.rowsum + m, rs);
+  }
 }
 
 template <int WK>
@@ -1855,6 +1865,8 @@ extern "C" int tspm_pattern_head_train_step(const tspm_pattern_head_train_desc* 
 // the row's staging and nothing more inside the pattern loop; (2) per-sample mode (P = 1, the keep flags and the group
 // of a row read on the device); (3) k_pattern_head_rows' prediction and confusion count per row and, in the loss
 // workgroup, tspm_classify_update's log entry and counters.
+// k_cached_head_steps_rows / k_cached_head_wgrad_adam (tspm_cached_head_train_steps): the same two launches for K
+// consecutive steps per host call, Adam applied by the wave that stores a gradient tile.
 // ------------------------------------------------------------------------------------------------
 namespace {
 
@@ -2082,6 +2094,199 @@ __global__ __launch_bounds__(PH_THREADS) void k_cached_head_train_rows(CachedTra
   if (t < 2 * H) a.fold[((long long)fm * R + B + blockIdx.x) * H + fo] = zs;
 }
 
+// tspm_cached_head_train_steps' launch 1: k_cached_head_train_rows (a copy: that kernel keeps its code) in which one
+// thread also stores the step this call's weight update belongs to, adam_step[0] + 1, to step_next — a word no
+// workgroup of this launch reads.
+__global__ __launch_bounds__(PH_THREADS) void k_cached_head_steps_rows(CachedTrainArgs a, long long* step_next) {
+  const tspm_cached_head_train_desc& d = a.d;
+  extern __shared__ float lds[];
+  const int F = d.in, H = d.hidden, H2 = d.hidden2, C = d.classes, P = d.npat, WA = d.w_audio, B = d.batch;
+  const int ldx = F + 4, ldh = H + 4, ldh2 = H2 + 4, ldc = head_ldc(C);
+  float* sw0 = lds;                 // [H][F + 4]
+  float* sw3 = sw0 + H * ldx;       // [H2][H + 4]
+  float* sw5 = sw3 + H2 * ldh;      // [C][H2 + 4]
+  float* sx = sw5 + C * ldh2;       // [2][F + 4]: the sample's row, x0
+  float* spart = sx + 2 * ldx;      // [2][2][H]: (sample | x0) x (audio half | image half) of fc0
+  float* sh1 = spart + 4 * H;       // [P][H + 4]: h1, then dz0
+  float* shh = sh1 + P * ldh;       // [P][H2 + 4]: hh, then dz3
+  float* sz = shh + P * ldh2;       // [P][ldc]: logits, then dlogits
+  float* sb0 = sz + P * ldc;        // biases [H], [H2], [C]
+  float* sb3 = sb0 + H;
+  float* sb5 = sb3 + H2;
+  const int t = threadIdx.x;
+  const long long PB = (long long)P * B;
+  const int R = B + a.grid;         // rows of a fold plane / of xe
+  uint64_t base = 0;
+  {
+    const HeadSeg g0{d.w0, sw0, H, F / 4, H, F}, g3{d.w3, sw3, H2, H / 4, H2, H}, g5{d.w5, sw5, C, H2 / 4, C, H2};
+    constexpr int U0 = (128 * 192 / 4 + PH_THREADS - 1) / PH_THREADS, U3 = (64 * 128 / 4 + PH_THREADS - 1) / PH_THREADS;
+    f32x4 v0[U0], v3[U3], v5[1];
+    const uint64_t ctr = (d.p > 0.f && d.gen_keep && d.counter) ? *d.counter : 0ULL;
+    head_load(g0, v0);
+    head_load(g3, v3);
+    head_load(g5, v5);
+    head_store(g0, v0);
+    head_store(g3, v3);
+    head_store(g5, v5);
+    for (int i = t; i < H + H2 + C; i += PH_THREADS)
+      sb0[i] = i < H ? d.b0[i] : i < H + H2 ? d.b3[i - H] : d.b5[i - H - H2];
+    for (int i = t; i < F / 4; i += PH_THREADS) {
+      const f32x4 v = d.x0 ? ld4(d.x0 + 4 * i) : f32x4{0.f, 0.f, 0.f, 0.f};
+      st4(sx + ldx + 4 * i, v);
+      st4(a.xe + (long long)(B + blockIdx.x) * F + 4 * i, v);  // this workgroup's zsum rows pair with x0
+    }
+    if (d.p > 0.f && d.gen_keep) base = tspm_dropout_base(d.seed, ctr);
+    if (blockIdx.x == 0 && t == 0) step_next[0] = d.adam_step[0] + 1;
+  }
+  head_sync();
+  // the two halves of fc0 on row `xr` -> dst[half * H + o]
+  auto halves = [&](const float* xr, float* dst) {
+    for (int item = t; item < 2 * H; item += PH_THREADS) {
+      const int half = item >= H ? 1 : 0, o = item - half * H;
+      const int k0 = half ? WA : 0, K = half ? F - WA : WA;
+      dst[item] = pat_dot(xr + k0, sw0 + o * ldx + k0, K);
+    }
+  };
+  halves(sx + ldx, spart + 2 * H);
+  // thread t < 2H owns unit (m, o) = (t / H, t % H) of the folds (H <= 256: 2H <= PH_THREADS)
+  const int fm = t >= H ? 1 : 0, fo = t - fm * H;
+  float zs = 0.f;  // this workgroup's zsum_m[o]
+  const float invn = 1.0f / (float)PB;
+  for (int b = blockIdx.x; b < B; b += gridDim.x) {
+    // everything this sample takes from the cache's index: workgroup-uniform, loaded once, ahead of the row
+    const long long r = d.rows[b];
+    const bool rok = r >= 0 && r < d.n_rows;  // an index outside the cache: a zero row and label -1, nothing read
+    const long long lab64 = rok ? d.labels_all[r] : -1;
+    int ska = 1, ski = 1, sgrp = 0;
+    if (a.per_sample) {
+      ska = d.row_keep[2 * b] != 0;
+      ski = d.row_keep[2 * b + 1] != 0;
+      sgrp = d.row_group[b];
+    }
+    const float* er = d.emb + (rok ? r : 0) * d.ld_emb;
+    // sx row 0 was last read before the previous sample's barriers
+    for (int i = t; i < F / 4; i += PH_THREADS) {
+      const f32x4 v = rok ? ld4(er + 4 * i) : f32x4{0.f, 0.f, 0.f, 0.f};
+      st4(sx + 4 * i, v);
+      st4(a.xe + (long long)b * F + 4 * i, v);
+    }
+    head_sync();
+    halves(sx, spart);
+    head_sync();
+    // fc0 + ReLU + dropout (tspm_linear_fwd's epilogue order: + bias, relu, * keep*scale)
+    for (int item = t; item < P * H; item += PH_THREADS) {
+      const int p = item / H, o = item - p * H;
+      const int ka = a.per_sample ? ska : a.keep[p][0], ki = a.per_sample ? ski : a.keep[p][1];
+      const float pa = spart[(ka ? 0 : 2 * H) + o], pi = spart[(ki ? 0 : 2 * H) + H + o];
+      float v = relu_f((pa + pi) + sb0[o]);
+      const long long i = ((long long)p * B + b) * H + o;
+      if (d.p > 0.f) {
+        bool kp;
+        if (d.gen_keep) {
+          kp = tspm_dropout_keep(base, i, d.p);
+          d.keep_mask[i] = kp ? 1 : 0;
+        } else {
+          kp = d.keep_mask[i] != 0;
+        }
+        v *= kp ? a.scale : 0.f;
+      }
+      sh1[p * ldh + o] = v;
+      a.h1[i] = v;
+    }
+    head_sync();
+    for (int item = t; item < P * H2; item += PH_THREADS) {
+      const int p = item / H2, o = item - p * H2;
+      const float v = relu_f(pat_dot(sh1 + p * ldh, sw3 + o * ldh, H) + sb3[o]);
+      shh[p * ldh2 + o] = v;
+      a.hh[((long long)p * B + b) * H2 + o] = v;
+    }
+    head_sync();
+    for (int item = t; item < P * C; item += PH_THREADS) {
+      const int p = item / C, o = item - p * C;
+      const float v = pat_dot(shh + p * ldh2, sw5 + o * ldh2, H2) + sb5[o];
+      sz[p * ldc + o] = v;
+      d.logits[((long long)p * B + b) * C + o] = v;
+    }
+    head_sync();
+    // cross-entropy per row (k_head_rows' arithmetic): 16 lanes per row, lane k owns class k; sz becomes dlogits
+    if (t < 16 * P) {
+      const int p = t >> 4, k = t & 15, l0 = (t & 63) & ~15;
+      float* z = sz + p * ldc;
+      const bool kv = k < C;
+      float mx = z[0];
+      int am = 0;
+      for (int j = 1; j < C; ++j)
+        if (z[j] > mx) { mx = z[j]; am = j; }
+      const float e = kv ? expf(z[k] - mx) : 0.f;
+      float se = 0.f;
+      for (int j = 0; j < C; ++j) se += __shfl(e, l0 + j, 64);
+      const bool lok = lab64 >= 0 && lab64 < C;  // out-of-range label: NaN loss / gradients, nothing read out of bounds
+      const int lab = lok ? (int)lab64 : 0;
+      const long long row = (long long)p * B + b;
+      if (k == 0) {
+        a.row_ws[row] = lok ? logf(se) - (z[lab] - mx) : __builtin_nanf("");
+        a.row_ws[PB + row] = (lok && am == lab) ? 1.f : 0.f;  // an out-of-range label is never correct
+      }
+      const float pk = e / se;
+      if (d.confusion) {  // k_pattern_head_rows' prediction: the first maximum of the softmax values
+        float best = __shfl(pk, l0, 64);
+        int sm = 0;
+        for (int j = 1; j < C; ++j) {
+          const float pj = __shfl(pk, l0 + j, 64);
+          if (pj > best) { best = pj; sm = j; }
+        }
+        const int g = a.per_sample ? sgrp : a.group[p];
+        if (k == 0 && lok && g >= 0 && g < d.n_groups)
+          atomicAdd(reinterpret_cast<unsigned long long*>(d.confusion) + ((long long)g * C + lab) * C + sm, 1ULL);
+      }
+      const float g = lok ? (pk - (k == lab ? 1.f : 0.f)) * invn * d.loss_weight : __builtin_nanf("");
+      if (kv) {  // after every lane of the row has read z (the row's 16 lanes sit in one wave: program order)
+        z[k] = g;
+        a.dlogits[row * C + k] = g;
+      }
+    }
+    head_sync();
+    // dz3 = (dlogits w5) * (hh > 0)   (w5 is [C][H2]) -> shh; item (p, o)'s hh value is read and overwritten by its
+    // own thread only
+    for (int item = t; item < P * H2; item += PH_THREADS) {
+      const int p = item / H2, o = item - p * H2;
+      float acc = 0.f;
+      for (int k = 0; k < C; ++k) acc = fmaf(sz[p * ldc + k], sw5[k * ldh2 + o], acc);
+      const float v = shh[p * ldh2 + o] > 0.f ? acc : 0.f;
+      shh[p * ldh2 + o] = v;
+      a.dz3[((long long)p * B + b) * H2 + o] = v;
+    }
+    head_sync();
+    // dz0 = (dz3 w3) * (h1 > 0 ? scale : 0)   (w3 is [H2][H]) -> sh1
+    for (int item = t; item < P * H; item += PH_THREADS) {
+      const int p = item / H, o = item - p * H;
+      const float* zp = shh + p * ldh2;
+      float acc = 0.f;
+      for (int k = 0; k < H2; k += 4) {
+        const f32x4 z4 = ld4(zp + k);
+        acc = fmaf(z4[0], sw3[(k + 0) * ldh + o], acc);
+        acc = fmaf(z4[1], sw3[(k + 1) * ldh + o], acc);
+        acc = fmaf(z4[2], sw3[(k + 2) * ldh + o], acc);
+        acc = fmaf(z4[3], sw3[(k + 3) * ldh + o], acc);
+      }
+      sh1[p * ldh + o] = sh1[p * ldh + o] > 0.f ? acc * a.scale : 0.f;
+    }
+    head_sync();
+    // the folds of dz0 (fc0's backward in the forward's algebra): ascending p, plain adds
+    if (t < 2 * H) {
+      float fk = 0.f;
+      for (int p = 0; p < P; ++p) {
+        const float v = sh1[p * ldh + fo];
+        if (a.per_sample ? (fm ? ski : ska) : a.keep[p][fm]) fk += v;
+        else zs += v;
+      }
+      a.fold[((long long)fm * R + b) * H + fo] = fk;
+    }
+    // the next sample writes sx / spart behind this iteration's barriers and sh1 only behind two more
+  }
+  if (t < 2 * H) a.fold[((long long)fm * R + B + blockIdx.x) * H + fo] = zs;
+}
+
 template <int WK>
 __global__ __launch_bounds__(64 * WK) void k_cached_head_wgrad(GemmMulti mp, int total, CachedTrainArgs a) {
   extern __shared__ float lds[];
@@ -2131,6 +2336,106 @@ __global__ __launch_bounds__(64 * WK) void k_cached_head_wgrad(GemmMulti mp, int
   }
 }
 
+// tspm_cached_head_train_steps' launch 2: k_cached_head_wgrad's tile walk with Adam in the epilogue.  The flat Adam
+// buffers of the head's group; every gradient element gemm_body stores sits at grad + off and its parameter and
+// moments at the same off.
+struct HeadAdam {
+  float *param, *grad, *exp_avg, *exp_avg_sq;
+  tspm_adam_hyper* hyper;  // pad_ holds the step in flight (launch 1 stored it); step is written by the loss workgroup
+};
+
+// adam_update without a clip coefficient, with its arithmetic pinned to what k_adam's vector body (the float4 loop
+// every element of a FusedAdam group takes: the groups are padded to 4 floats) compiles to.  Left to the compiler, the
+// update inside the GEMM epilogue came out as k_adam's scalar tail does — exp_avg_sq as a rounded product plus a
+// rounded product where the vector body has one fused multiply-add — so the fused operations are written out and
+// contraction is off for the rest.
+TSPM_DEV void head_adam_update(float& pp, float gg, float& mm, float& vv, const AdamConsts& c) {
+#pragma clang fp contract(off)
+  gg = gg * c.gs;
+  if (c.wd != 0.f) gg = __builtin_fmaf(c.wd, pp, gg);
+  mm = __builtin_fmaf(c.w1, gg - mm, mm);
+  vv = __builtin_fmaf(c.b2, vv, (c.omb2 * gg) * gg);
+  const float denom = sqrtf(vv) / c.bc2s + c.eps;
+  pp = __builtin_fmaf(-c.step_size, mm / denom, pp);
+}
+
+struct HeadAdamEpi {
+  HeadAdam ad;
+  AdamConsts c;
+  TSPM_DEV void operator()(float* gp, float gv) const {
+    const long long off = gp - ad.grad;
+    float pp = ad.param[off], mm = ad.exp_avg[off], vv = ad.exp_avg_sq[off];
+    head_adam_update(pp, gv, mm, vv, c);
+    ad.param[off] = pp;
+    ad.exp_avg[off] = mm;
+    ad.exp_avg_sq[off] = vv;
+  }
+};
+
+// Wave 0 of a tile's workgroup holds the tile's final gradients in registers when it stores them: it applies
+// adam_update (k_adam's constants, formed once per workgroup in LDS from the step launch 1 stored) to the parameter
+// and moments of every element it stores — one owner per element, the products' outputs are disjoint, and nothing in
+// this launch reads a weight.  Elements of a partial tile outside the tensor are neither loaded nor stored (gemm_body's
+// own bounds).  The loss workgroup is k_cached_head_wgrad's, except that it stores the step in flight to adam_step[0]
+// instead of incrementing it: no workgroup of this launch reads adam_step[0].
+template <int WK>
+__global__ __launch_bounds__(64 * WK) void k_cached_head_wgrad_adam(GemmMulti mp, int total, CachedTrainArgs a,
+                                                                    HeadAdam ad) {
+  extern __shared__ float lds[];
+  const int b = blockIdx.x;
+  if (b < total) {
+    __shared__ AdamConsts sh;
+    if (threadIdx.x == 0) {
+      tspm_adam_hyper h = *ad.hyper;
+      h.step = h.pad_;
+      sh = adam_consts(&h);
+    }
+    __syncthreads();
+    const HeadAdamEpi epi{ad, sh};
+    int i = 0;
+    while (i + 1 < mp.count && b >= mp.start[i + 1]) ++i;  // workgroup-uniform
+    gemm_body<WK>(mp.p[i], b - mp.start[i], lds, epi);
+    return;
+  }
+  // the loss: fixed-order sums of the per-row losses / correct flags over the P*B rows, in double
+  const tspm_cached_head_train_desc& d = a.d;
+  const int n = d.npat * d.batch;
+  double* red = reinterpret_cast<double*>(lds);
+  const int T = 64 * WK;
+  double ls = 0.0, cs = 0.0;
+  for (int r = threadIdx.x; r < n; r += T) {
+    ls += (double)a.row_ws[r];
+    cs += (double)a.row_ws[n + r];
+  }
+  red[threadIdx.x] = ls;
+  red[T + threadIdx.x] = cs;
+  __syncthreads();
+  for (int s = T / 2; s > 0; s >>= 1) {
+    if (threadIdx.x < s) {
+      red[threadIdx.x] += red[threadIdx.x + s];
+      red[T + threadIdx.x] += red[T + threadIdx.x + s];
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    const float l = (float)(red[0] / (double)n);
+    const float lw = l * d.loss_weight;
+    d.loss[0] = lw;
+    d.adam_step[0] = ad.hyper->pad_;  // the next step's launch 1 reads it as the dropout counter
+    if (d.stats) {
+      d.stats[0] += (float)red[0];
+      d.stats[1] += (float)red[T];
+      d.stats[2] += (float)n;
+    }
+    if (d.counters) {  // tspm_classify_update's log: one entry per step
+      const long long base = d.counters[0];
+      if (d.loss_log && base < d.log_capacity) d.loss_log[base] = lw;
+      d.counters[0] = base + 1;
+      d.counters[1] += (long long)n;
+    }
+  }
+}
+
 }  // namespace
 
 extern "C" int tspm_embed_gather(int32_t batch, int32_t in, const float* emb, int64_t n_rows, int32_t ld_emb,
@@ -2158,7 +2463,11 @@ extern "C" size_t tspm_cached_head_train_workspace(int32_t batch, int32_t npat) 
   return pat_train_ws_bytes(batch, npat);
 }
 
-extern "C" int tspm_cached_head_train_step(const tspm_cached_head_train_desc* desc, tspm_stream_t stream) {
+// One host path behind tspm_cached_head_train_step (adam == nullptr, steps == 1: its two launches) and
+// tspm_cached_head_train_steps (the checks once, then per step k launch 1 storing the step in flight and launch 2 with
+// Adam in its epilogue, on the descriptor's rows / row_keep / row_group advanced by k batches).
+static int cached_head_train(const tspm_cached_head_train_desc* desc, const tspm_head_adam_desc* adam, int steps,
+                             tspm_stream_t stream) {
   if (!desc) return TSPM_ERR_INVALID;
   const tspm_cached_head_train_desc& d = *desc;
   if (d.batch <= 0 || d.npat <= 0 || d.npat > PH_MAXP) return TSPM_ERR_INVALID;
@@ -2213,9 +2522,27 @@ extern "C" int tspm_cached_head_train_step(const tspm_cached_head_train_desc* de
   a.grid = grid;
   a.d.keep = nullptr;
   a.d.group_id = nullptr;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(k_cached_head_train_rows, dim3(grid), dim3(PH_THREADS), lds_rows, st, a);
-  TSPM_LAUNCH_CHECK();
+  HeadAdam ad{};
+  if (adam) {
+    // the head's six tensors inside the one flat group: each gradient in [grad, grad + count), its parameter at the
+    // same offset of param; the step counter the group's own
+    if (!adam->param || !adam->grad || !adam->exp_avg || !adam->exp_avg_sq || !adam->hyper || adam->count < 1)
+      return TSPM_ERR_INVALID;
+    if (!aligned16(adam->param) || !aligned16(adam->grad) || !aligned16(adam->exp_avg) || !aligned16(adam->exp_avg_sq))
+      return TSPM_ERR_INVALID;
+    if (d.adam_step != &adam->hyper->step) return TSPM_ERR_INVALID;
+    const float* gs[6] = {d.gw0, d.gb0, d.gw3, d.gb3, d.gw5, d.gb5};
+    const float* ws[6] = {d.w0, d.b0, d.w3, d.b3, d.w5, d.b5};
+    const long long ns[6] = {(long long)H * F, H, (long long)H2 * H, H2, (long long)C * H2, C};
+    const uintptr_t g0 = reinterpret_cast<uintptr_t>(adam->grad), gbytes = (uintptr_t)adam->count * sizeof(float);
+    for (int i = 0; i < 6; ++i) {
+      const uintptr_t gi = reinterpret_cast<uintptr_t>(gs[i]), bytes = (uintptr_t)ns[i] * sizeof(float);
+      if (gi < g0 || gi - g0 > gbytes || bytes > gbytes - (gi - g0) || (gi - g0) % sizeof(float)) return TSPM_ERR_INVALID;
+      if (reinterpret_cast<uintptr_t>(ws[i]) != reinterpret_cast<uintptr_t>(adam->param) + (gi - g0))
+        return TSPM_ERR_INVALID;
+    }
+    ad = HeadAdam{adam->param, adam->grad, adam->exp_avg, adam->exp_avg_sq, adam->hyper};
+  }
   // the weight gradients: tspm_pattern_head_train_step's four products, operand for operand
   const int n = (int)pb;
   GemmMulti mp{};
@@ -2236,13 +2563,51 @@ extern "C" int tspm_cached_head_train_step(const tspm_cached_head_train_desc* de
   const size_t lds_gemm = (size_t)(wk - 1) * (16 * 64 + 32) * sizeof(float);
   const size_t lds_loss = (size_t)2 * 64 * wk * sizeof(double);
   const size_t lds = lds_gemm > lds_loss ? lds_gemm : lds_loss;
-  switch (wk) {
-    case 1: hipLaunchKernelGGL(k_cached_head_wgrad<1>, dim3(total + 1), dim3(64), lds, st, mp, total, a); break;
-    case 2: hipLaunchKernelGGL(k_cached_head_wgrad<2>, dim3(total + 1), dim3(128), lds, st, mp, total, a); break;
-    default: hipLaunchKernelGGL(k_cached_head_wgrad<4>, dim3(total + 1), dim3(256), lds, st, mp, total, a); break;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (!adam) {
+    hipLaunchKernelGGL(k_cached_head_train_rows, dim3(grid), dim3(PH_THREADS), lds_rows, st, a);
+    TSPM_LAUNCH_CHECK();
+    switch (wk) {
+      case 1: hipLaunchKernelGGL(k_cached_head_wgrad<1>, dim3(total + 1), dim3(64), lds, st, mp, total, a); break;
+      case 2: hipLaunchKernelGGL(k_cached_head_wgrad<2>, dim3(total + 1), dim3(128), lds, st, mp, total, a); break;
+      default: hipLaunchKernelGGL(k_cached_head_wgrad<4>, dim3(total + 1), dim3(256), lds, st, mp, total, a); break;
+    }
+    TSPM_LAUNCH_CHECK();
+    return TSPM_OK;
   }
-  TSPM_LAUNCH_CHECK();
+  long long* step_next = reinterpret_cast<long long*>(&adam->hyper->pad_);
+  for (int k = 0; k < steps; ++k) {
+    a.d.rows = d.rows + (size_t)k * B;
+    if (a.per_sample) {
+      a.d.row_keep = d.row_keep + (size_t)2 * k * B;
+      a.d.row_group = d.row_group + (size_t)k * B;
+    }
+    hipLaunchKernelGGL(k_cached_head_steps_rows, dim3(grid), dim3(PH_THREADS), lds_rows, st, a, step_next);
+    TSPM_LAUNCH_CHECK();
+    switch (wk) {
+      case 1:
+        hipLaunchKernelGGL(k_cached_head_wgrad_adam<1>, dim3(total + 1), dim3(64), lds, st, mp, total, a, ad);
+        break;
+      case 2:
+        hipLaunchKernelGGL(k_cached_head_wgrad_adam<2>, dim3(total + 1), dim3(128), lds, st, mp, total, a, ad);
+        break;
+      default:
+        hipLaunchKernelGGL(k_cached_head_wgrad_adam<4>, dim3(total + 1), dim3(256), lds, st, mp, total, a, ad);
+        break;
+    }
+    TSPM_LAUNCH_CHECK();
+  }
   return TSPM_OK;
+}
+
+extern "C" int tspm_cached_head_train_step(const tspm_cached_head_train_desc* desc, tspm_stream_t stream) {
+  return cached_head_train(desc, nullptr, 1, stream);
+}
+
+extern "C" int tspm_cached_head_train_steps(const tspm_cached_head_train_desc* desc, const tspm_head_adam_desc* adam,
+                                            int32_t steps, tspm_stream_t stream) {
+  if (!desc || !adam || steps < 1 || steps > TSPM_CACHED_HEAD_MAX_STEPS) return TSPM_ERR_INVALID;
+  return cached_head_train(desc, adam, steps, stream);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -741,14 +741,14 @@ class DeviceLoader:
         return n // self.batch_size if self.drop_last else -(-n // self.batch_size)
 
     def __iter__(self) -> Iterator[Dict[Any, Any]]:
+        if self.ids_only:
+            yield from self._iter_ids()
+            return
         order = self.items()
         nb = len(self)
         if nb == 0:
             return
         order = order[:nb * self.batch_size] if self.drop_last else order
-        if self.ids_only:
-            yield from self._iter_ids(order, nb)
-            return
         if self.fuse_patterns or self.all_patterns:
             yield from self._iter_fused(order, nb)
             return
@@ -780,32 +780,62 @@ class DeviceLoader:
                                      self.ds.keys["audio"]: a, self.ds.keys["image"]: imt}
             yield batch
 
-    def _iter_ids(self, order: np.ndarray, nb: int) -> Iterator[Dict[Any, Any]]:
-        """The ``ids_only`` epoch: the same items, patterns and masks as the other paths resolve, as index tensors."""
+    def epoch_plan(self) -> Dict[str, Any]:
+        """One whole ``ids_only`` epoch as one object, for the steps that run several batches per host call: device
+        tensors ``sample_ids [n]`` (int64) and ``labels [n]`` in the epoch's order, ``batch_size``, ``n_batches``
+        (= ``len(self)``; batch b is rows ``[b * batch_size, min(n, (b + 1) * batch_size))``) and ``dataset``; with
+        ``all_patterns`` / ``fuse_patterns`` ``patterns`` and that flag, on the plain path ``keep [n, 2]`` (uint8),
+        ``pattern_ids [n]`` and ``pattern_names`` (n names).  It draws from the loader's generator and Python's RNG
+        exactly as one ``iter(loader)`` run to its end does, and leaves ``dataset.current_pattern`` as that would.
+        ``iter(loader)`` yields slices of this plan.  Refused for a loader without ``ids_only=True``."""
+        if not self.ids_only:
+            raise L.TspmError("epoch_plan() is the ids_only loader's epoch (sample indices on the device); this loader "
+                              "gathers input tensors per batch")
+        order = self.items()
+        nb = len(self)
+        order = order[:nb * self.batch_size] if (self.drop_last or nb == 0) else order
         ds = self.ds
         dev = ds._ids_device()
 
         def up(a: np.ndarray) -> torch.Tensor:
             t = torch.from_numpy(np.ascontiguousarray(a))
-            return t.pin_memory().to(dev, non_blocking=True) if dev.type == "cuda" else t
+            return t.pin_memory().to(dev, non_blocking=True) if (dev.type == "cuda" and t.numel()) else t.to(dev)
 
-        fused = self.fuse_patterns or self.all_patterns
-        if fused:
-            samples, names = np.ascontiguousarray(order, dtype=np.int64), None
+        plan: Dict[str, Any] = {"batch_size": self.batch_size, "n_batches": nb, "dataset": ds}
+        if nb == 0:  # iter(loader) resolves nothing for an empty epoch
+            samples = np.zeros(0, dtype=np.int64)
+            plan.update(sample_ids=up(samples), labels=up(ds.corpus.labels[samples]))
+            return plan
+        if self.fuse_patterns or self.all_patterns:
+            samples = np.ascontiguousarray(order, dtype=np.int64)
+            plan["patterns"] = list(ds.selected_patterns)
+            plan["all_patterns" if self.all_patterns else "fused_patterns"] = True
         else:
             samples, names, am, im = ds._resolve(order)
-            keep_d = up(np.stack([am != 0, im != 0], axis=1).astype(np.uint8))
-            pid_d = up(ds.pattern_ids(names))
-        idx_d, lab_d = up(samples.astype(np.int64)), up(ds.corpus.labels[samples])
-        for b in range(nb):
-            lo, hi = b * self.batch_size, min(len(order), (b + 1) * self.batch_size)
-            batch: Dict[Any, Any] = {"labels": lab_d[lo:hi], "missing_masks": {}, "sample_ids": idx_d[lo:hi],
-                                     "cached": True, "dataset": ds}
+            plan.update(keep=up(np.stack([am != 0, im != 0], axis=1).astype(np.uint8)),
+                        pattern_ids=up(ds.pattern_ids(names)), pattern_names=list(names))
+            if names:
+                ds.current_pattern = names[len(order) - 1]
+        plan.update(sample_ids=up(samples.astype(np.int64)), labels=up(ds.corpus.labels[samples]))
+        return plan
+
+    def _iter_ids(self) -> Iterator[Dict[Any, Any]]:
+        """The ``ids_only`` epoch: the same items, patterns and masks as the other paths resolve, as index tensors —
+        ``epoch_plan()`` in slices of one batch."""
+        plan = self.epoch_plan()
+        ds, n = self.ds, len(plan["sample_ids"])
+        fused = self.fuse_patterns or self.all_patterns
+        for b in range(plan["n_batches"]):
+            lo, hi = b * self.batch_size, min(n, (b + 1) * self.batch_size)
+            batch: Dict[Any, Any] = {"labels": plan["labels"][lo:hi], "missing_masks": {},
+                                     "sample_ids": plan["sample_ids"][lo:hi], "cached": True, "dataset": ds}
             if fused:
-                batch["patterns"] = list(ds.selected_patterns)
+                batch["patterns"] = list(plan["patterns"])
                 batch["all_patterns" if self.all_patterns else "fused_patterns"] = True
             else:
-                batch.update(keep=keep_d[lo:hi], pattern_ids=pid_d[lo:hi], pattern_name=list(names[lo:hi]))
+                names = plan["pattern_names"]
+                batch.update(keep=plan["keep"][lo:hi], pattern_ids=plan["pattern_ids"][lo:hi],
+                             pattern_name=list(names[lo:hi]))
                 if names:
                     ds.current_pattern = names[hi - 1]
             yield batch

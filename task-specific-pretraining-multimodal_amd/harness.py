@@ -24,14 +24,14 @@ from __future__ import annotations
 import json
 import time
 from pathlib import Path
-from typing import Any, Dict, Iterable, Optional, Tuple
+from typing import Any, Dict, Iterable, List, Optional, Tuple
 
 import numpy as np
 import torch
 
 from . import _lib as L
 from .metrics import ClassificationLog, DeviceMetricRecorder, RegressionLog, RegressionMetricRecorder
-from .modules import modality_key
+from .modules import NUM_CLASSES, modality_key
 from .step import (FusedCachedEvalStep, FusedCachedHeadStep, FusedEvalStep, FusedHeadStagePatternStep, FusedHeadStageStep,
                    FusedPatternEvalStep, FusedTrainStep, head_stage_frozen, norm_avmnist_patterns, train_step_key)
 
@@ -116,6 +116,22 @@ class CheckpointManager:
         return ck
 
 
+def cached_epoch_chunks(n_rows: int, batch_size: int, steps_per_call: Optional[int]) -> Tuple[List[int], int]:
+    """How an epoch of ``n_rows`` cached rows at ``batch_size`` is cut into host calls → ``(chunks, tail)``: ``chunks``
+    are the full batches in order, as calls of that many consecutive batches — ``full // K`` calls of K, then one call
+    of the remaining ``full % K`` (5 full batches, K = 4: ``[4, 1]``; K >= full: ``[full]``; K of None or 1: ``[1] *
+    full``, the per-batch epoch) — and ``tail`` is the short last batch's row count (0 = none), which always runs on
+    the single-batch step.  K is capped at ``_lib.CACHED_HEAD_MAX_STEPS``."""
+    if n_rows < 0 or batch_size < 1:
+        raise ValueError("cached_epoch_chunks: n_rows >= 0 and batch_size >= 1")
+    if steps_per_call is not None and int(steps_per_call) < 1:
+        raise ValueError(f"steps_per_call must be >= 1, got {steps_per_call}")
+    K = min(int(steps_per_call or 1), L.CACHED_HEAD_MAX_STEPS)
+    full, tail = divmod(n_rows, batch_size)
+    chunks = [K] * (full // K) + ([full % K] if full % K else [])
+    return chunks, tail
+
+
 class EpochRunner:
     """train_epoch / validate_epoch on the fused steps.  ``loader`` yields collate_fn-style batch dicts
     on the device (data.DeviceLoader / the drop-in DataLoader); batches of the runner's size are fed
@@ -127,7 +143,9 @@ class EpochRunner:
     ``train_steps`` under ``step.train_step_key``'s keys, which for an all-trainable model are the batch sizes.  A
     ``"cached"`` batch (``data.DeviceLoader(ids_only=True)``: sample indices, no input tensors) runs on the dataset's
     ``embedding_cache(model)`` — ``FusedCachedHeadStep`` (keys with a trailing ``("cached",)``) or
-    ``FusedCachedEvalStep`` — with the same loss entries and counts and no encoder launch."""
+    ``FusedCachedEvalStep`` — with the same loss entries and counts and no encoder launch.  With ``steps_per_call=K``
+    an epoch on an ``ids_only`` ``DeviceLoader`` takes the loader's ``epoch_plan()`` and runs K consecutive batches per
+    host call (``cached_epoch_chunks``): the same loss entries, order, metrics and batch count as the per-batch epoch."""
 
     def __init__(self, model, optimizer, loss_functions, metric_config=None, device=None, log_capacity: int = 1 << 16):
         self.model, self.optimizer, self.loss_functions = model, optimizer, loss_functions
@@ -164,31 +182,69 @@ class EpochRunner:
         st.log = self.log
         return st
 
-    def cached_train_step_for(self, n: int, cache, patterns=None) -> FusedCachedHeadStep:
+    def cached_train_step_for(self, n: int, cache, patterns=None, steps: int = 1) -> FusedCachedHeadStep:
         """The FusedCachedHeadStep for (patterns, batch size) on ``cache``: every pattern of the batch when ``patterns``
-        is given (an ``"all_patterns"`` batch), else one pattern per sample.  Rebuilt for another cache."""
+        is given (an ``"all_patterns"`` batch), else one pattern per sample.  Rebuilt for another cache.  ``steps=K >
+        1``: the step that runs K batches of ``n`` per call, under its own key (the single step's plus ``("steps", K)``)."""
         pats = norm_avmnist_patterns(patterns) if patterns is not None else None
         key = train_step_key(self.model, n, pats, cached=True)
+        if steps > 1:
+            key = key + (("steps", int(steps)),)
         st = self.train_steps.get(key)
         if st is None or st.cache is not cache:
             st = FusedCachedHeadStep(self.model, self.optimizer, self.loss_functions, n, cache, patterns=pats,
-                                     per_sample=pats is None)
+                                     per_sample=pats is None, steps=steps)
             self.train_steps[key] = st
         st.log = self.log
         return st
 
-    def cached_eval_step_for(self, n: int, cache, patterns=None) -> FusedCachedEvalStep:
+    def cached_eval_step_for(self, n: int, cache, patterns=None, steps: int = 1) -> FusedCachedEvalStep:
         """The FusedCachedEvalStep for (patterns, batch size) on ``cache`` (``patterns``: a ``"fused_patterns"`` batch's;
-        None: each row under its own keep flags); kept apart from the other eval steps under a ("cached", ...) key."""
+        None: each row under its own keep flags); kept apart from the other eval steps under a ("cached", ...) key
+        (``steps=K > 1``: K batches of ``n`` per call, the key plus ``("steps", K)``)."""
         pats = norm_avmnist_patterns(patterns) if patterns is not None else None
-        key = (("cached",), pats, n)
+        key = (("cached",), pats, n) + ((("steps", int(steps)),) if steps > 1 else ())
         st = self.pattern_eval_steps.get(key)
         if st is None or st.cache is not cache:
             st = FusedCachedEvalStep(self.model, self.loss_functions, n, cache, self.log, patterns=pats,
-                                     per_sample=pats is None)
+                                     per_sample=pats is None, steps=steps)
             self.pattern_eval_steps[key] = st
         st.log = self.log
         return st
+
+    def _multi_step_ok(self, npat: int) -> bool:
+        """Whether ``FusedCachedHeadStep(steps > 1)`` takes this model and optimizer (else the epoch runs per batch)."""
+        m = self.model
+        ea, hd = int(m.embd_size_A), int(m.hidden_dim)
+        return (getattr(self.optimizer, "clip_coef", None) is None and
+                L.cached_head_train_supported(ea + int(m.embd_size_I), ea, hd, hd // 2, NUM_CLASSES, npat))
+
+    def _cached_epoch(self, loader, steps_per_call: int, train: bool) -> None:
+        """A whole ``ids_only`` epoch from the loader's ``epoch_plan()``: ``cached_epoch_chunks``' calls of K batches
+        (and of the remaining full batches) on the multi-step steps, the short last batch on the single step."""
+        from .data import DeviceLoader
+        if not (isinstance(loader, DeviceLoader) and loader.ids_only):
+            raise L.TspmError("steps_per_call needs an ids_only data.DeviceLoader (dataset.device_loader(..., "
+                              "ids_only=True)): the epoch's sample order must be on the device as one plan")
+        plan = loader.epoch_plan()
+        if plan["n_batches"] == 0:
+            return
+        ds, B, ids = plan["dataset"], plan["batch_size"], plan["sample_ids"]
+        cache = self._epoch_caches[id(ds)] = ds.embedding_cache(self.model)
+        pats = plan.get("patterns")
+        npat = len(norm_avmnist_patterns(pats)) if pats is not None else 1
+        K = steps_per_call if (not train or self._multi_step_ok(npat)) else 1
+        chunks, tail = cached_epoch_chunks(len(ids), B, K)
+        step_for = self.cached_train_step_for if train else self.cached_eval_step_for
+        at = 0
+        for n, k in [(B, c) for c in chunks] + ([(tail, 1)] if tail else []):
+            rows = slice(at, at + n * k)
+            st = step_for(n, cache, pats, steps=k)
+            if pats is not None:
+                st.step(ids[rows])
+            else:
+                st.step(ids[rows], plan["keep"][rows], plan["pattern_ids"][rows])
+            at += n * k
 
     def _cached(self, b, train: bool) -> None:
         """One ``"cached"`` batch on its dataset's embedding cache of this model, looked up once per epoch and dataset.
@@ -239,11 +295,14 @@ class EpochRunner:
         metrics = self.recorder.calculate_metrics_for_group("classification", loss=mean, conf=conf)
         return mean, time.time() - t0, metrics, len(losses)
 
-    def train_epoch(self, loader: Iterable[Dict[str, Any]]):
-        """→ (mean batch loss, seconds, metrics dict, batches)."""
+    def train_epoch(self, loader: Iterable[Dict[str, Any]], steps_per_call: Optional[int] = None):
+        """→ (mean batch loss, seconds, metrics dict, batches).  ``steps_per_call=K > 1``: ``_cached_epoch``."""
         self.log.reset()
         self._epoch_caches = {}
         t0 = time.time()
+        if steps_per_call is not None and int(steps_per_call) > 1:
+            self._cached_epoch(loader, int(steps_per_call), True)
+            return self._finish(t0)
         fresh_zero = False  # the zero-input embeddings of an all-pattern epoch: refreshed on its first batch only
         for b in loader:
             if b.get("cached"):
@@ -260,11 +319,14 @@ class EpochRunner:
         return self._finish(t0)
 
     @torch.no_grad()
-    def validate_epoch(self, loader: Iterable[Dict[str, Any]]):
+    def validate_epoch(self, loader: Iterable[Dict[str, Any]], steps_per_call: Optional[int] = None):
         self.log.reset()
         self._epoch_caches = {}
         t0 = time.time()
         self.model.eval()
+        if steps_per_call is not None and int(steps_per_call) > 1:
+            self._cached_epoch(loader, int(steps_per_call), False)
+            return self._finish(t0)
         fresh_zero = False  # the zero-input embeddings: refreshed once per epoch (no weight changes inside it)
         for b in loader:
             if b.get("cached"):
@@ -493,7 +555,8 @@ def _epoch_block(loss: float, timing: float, n_batches: int, metrics: Dict[str, 
 def fit(model, optimizer, loss_functions, loaders: Dict[str, Any], epochs: int, *, metric_config=None,
         early_stopping: bool = True, patience: int = 10, min_delta: float = 1e-3, scheduler=None,
         checkpoint_dir=None, metrics_path=None, save_metric: str = "loss", mode: str = "minimize",
-        on_epoch=None, fail_on_nonfinite: bool = True, cache_embeddings: bool = False) -> Dict[str, Any]:
+        on_epoch=None, fail_on_nonfinite: bool = True, cache_embeddings: bool = False,
+        steps_per_call: Optional[int] = None) -> Dict[str, Any]:
     """_train_loop + test (train_multimodal.py:554-917) for the AVMNIST late-fusion model and the MOSI / MOSEI
     UTT-Fusion model (``runner_for``; its loaders: ``mosi_data.MOSI.loader(...)``).  ``loaders``:
     "train", "validation" and optionally "test" → iterables of device batches (a DeviceLoader is
@@ -504,9 +567,14 @@ def fit(model, optimizer, loss_functions, loaders: Dict[str, Any], epochs: int, 
     ``cache_embeddings`` (AVMNIST on frozen encoders, ``data.DeviceLoader`` loaders; refused otherwise): before the
     first epoch each split's ``embedding_cache(model)`` is filled once, and every epoch then iterates the ``ids_only``
     twin of its loader — no encoder launch after the fill; metric keys and loss entries per epoch are unchanged.  The
-    fill times are reported once under ``history["embedding_cache"]``."""
+    fill times are reported once under ``history["embedding_cache"]``.
+    ``steps_per_call=K`` (with ``cache_embeddings`` only; refused without): every train, validation and test epoch runs
+    K consecutive batches per host call (``EpochRunner.train_epoch(loader, steps_per_call=K)``) — the same history."""
+    if steps_per_call is not None and not cache_embeddings:
+        raise L.TspmError("steps_per_call runs several cached batches per host call: it needs cache_embeddings=True")
     runner = runner_for(model, optimizer, loss_functions, metric_config)
     cache_report = None
+    spc = {"steps_per_call": steps_per_call} if steps_per_call is not None else {}
     if cache_embeddings:
         loaders, cache_report = _cached_loaders(model, optimizer, runner, loaders)
     if getattr(runner, "regression", False) and save_metric != "loss":
@@ -521,11 +589,11 @@ def fit(model, optimizer, loss_functions, loaders: Dict[str, Any], epochs: int, 
     for epoch in range(1, epochs + 1):
         if on_epoch is not None:
             on_epoch(epoch)
-        tr_loss, tr_time, tr_metrics, tr_n = runner.train_epoch(loaders["train"])
+        tr_loss, tr_time, tr_metrics, tr_n = runner.train_epoch(loaders["train"], **spc)
         if fail_on_nonfinite and not np.isfinite(tr_loss):
             raise FloatingPointError(f"non-finite mean training loss {tr_loss} at epoch {epoch}")
         tr_metrics = dict(tr_metrics, loss=tr_loss)
-        va_loss, va_time, va_metrics, va_n = runner.validate_epoch(loaders["validation"])
+        va_loss, va_time, va_metrics, va_n = runner.validate_epoch(loaders["validation"], **spc)
         va_metrics = dict(va_metrics, loss=va_loss)
         history["train"].append(tr_metrics)
         history["validation"].append(va_metrics)
@@ -551,7 +619,7 @@ def fit(model, optimizer, loss_functions, loaders: Dict[str, Any], epochs: int, 
             ckpt.load_checkpoint(model, load_best=True)
             if cache_embeddings:  # load_state_dict made the caches stale (the loaded encoders may differ)
                 loaders["test"].ds.embedding_cache(model, refresh=True)
-        te_loss, te_time, te_metrics, _ = runner.validate_epoch(loaders["test"])
+        te_loss, te_time, te_metrics, _ = runner.validate_epoch(loaders["test"], **spc)
         history["test"] = dict(te_metrics, loss=te_loss)
     history["best"] = best
     if cache_report is not None:

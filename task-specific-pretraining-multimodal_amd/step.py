@@ -1291,11 +1291,22 @@ class FusedCachedHeadStep(_HeadStageBase):
 
     ``step(sample_ids, keep=None, groups=None)`` → ``{"loss": [1], "logits"}``: ``sample_ids [B]`` int64, and per
     sample ``keep [B, 2]`` (audio, image; non-zero = the real input) and ``groups [B]`` (the rows' groups in the log).
-    Refused: what ``_HeadStageBase`` refuses, a stale cache and a cache built for another model."""
+    Refused: what ``_HeadStageBase`` refuses, a stale cache and a cache built for another model.
+
+    ``steps=K > 1`` (at most ``_lib.CACHED_HEAD_MAX_STEPS``): one call runs K consecutive steps on K batches — the
+    static inputs are ``rows [K*B]``, ``row_keep [K*B, 2]`` and ``groups [K*B]``, ``step`` takes ``sample_ids [K*B]``
+    (batch k is rows ``[k*B, (k+1)*B)``), and the graph is one ``tspm_cached_head_train_steps`` call: two launches per
+    step, Adam applied in the second, no separate Adam launch.  Parameters, moments, log and step counter are bitwise
+    those of K ``steps=1`` steps; ``loss`` and ``logits`` are the last step's.  Refused with ``steps > 1``, by name:
+    ``head="launches"``, a head outside ``cached_head_train_supported``, a ``keep_override`` and an optimizer with a
+    clip coefficient (the fused update has none).  ``steps=1`` is the step described above, launch for launch."""
 
     def __init__(self, model, optimizer: FusedAdam, loss_functions, batch: int, cache, patterns=None,
                  per_sample: bool = False, head: Optional[str] = None, log=None, use_graph: bool = True,
-                 allreduce=None):
+                 allreduce=None, steps: int = 1):
+        self.steps = K = int(steps)
+        if not 1 <= K <= L.CACHED_HEAD_MAX_STEPS:
+            raise L.TspmError(f"FusedCachedHeadStep: steps must be 1 .. {L.CACHED_HEAD_MAX_STEPS}, got {steps}")
         if allreduce is not None:
             head_stage_frozen(model, optimizer, allreduce)  # refuses it for a frozen model, naming why
         self.per_sample = bool(per_sample)
@@ -1312,6 +1323,14 @@ class FusedCachedHeadStep(_HeadStageBase):
         if head not in ("kernel", "launches"):
             raise ValueError(f"head: 'kernel' or 'launches', got {head!r}")
         fits = L.cached_head_train_supported(self.F, self.ea, self.hd, self.h2, NUM_CLASSES, P)
+        if K > 1:
+            if head == "launches":
+                raise L.TspmError('FusedCachedHeadStep: steps > 1 runs tspm_cached_head_train_steps; head="launches" '
+                                  "has no multi-step form")
+            if not fits:
+                raise L.TspmError("FusedCachedHeadStep: steps > 1 needs a fusion head inside "
+                                  "cached_head_train_supported's limits; this head runs one step per call")
+            self._refuse_clip()
         if head == "kernel" and not fits:
             head = "launches"
         self.head = head
@@ -1319,9 +1338,9 @@ class FusedCachedHeadStep(_HeadStageBase):
         n = P * B
         f32 = dict(device=dev, dtype=torch.float32)
         self.x0 = cache.x0
-        self.rows = torch.zeros(B, dtype=torch.int64, device=dev)
-        self.row_keep = torch.ones(B, 2, dtype=torch.uint8, device=dev)
-        self.groups = torch.zeros(B, dtype=torch.int32, device=dev)
+        self.rows = torch.zeros(K * B, dtype=torch.int64, device=dev)
+        self.row_keep = torch.ones(K * B, 2, dtype=torch.uint8, device=dev)
+        self.groups = torch.zeros(K * B, dtype=torch.int32, device=dev)
         self.logits = torch.empty(n, NUM_CLASSES, **f32)
         self.keep = torch.ones(n, self.hd, dtype=torch.uint8, device=dev)
         self._keep2 = (ctypes.c_int32 * (2 * max(P, 1)))(*[k for p in self.patterns for k in PATTERN_KEEP[p]])
@@ -1365,7 +1384,12 @@ class FusedCachedHeadStep(_HeadStageBase):
                 self._keep3 = (ctypes.c_int32 * (3 * P))(*[k for p in self.patterns
                                                             for k in (PATTERN_KEEP[p][0],) + (PATTERN_KEEP[p][1],) * 2])
         self._bound_groups = None
-        self._sig = self._sig + (self.patterns, self.per_sample, id(cache))
+        self._sig = self._sig + (self.patterns, self.per_sample, id(cache)) + ((("steps", K),) if K > 1 else ())
+
+    def _refuse_clip(self) -> None:
+        if not self._head_bumps():
+            raise L.TspmError("FusedCachedHeadStep: steps > 1 applies Adam inside the weight-gradient launch, which has "
+                              "no clip coefficient; this optimizer has one set (clip_coef)")
 
     def _group_ids(self) -> List[int]:
         gid = self.log.gid if self.log is not None else {p: i for i, p in enumerate(AVMNIST_PATTERNS)}
@@ -1408,6 +1432,12 @@ class FusedCachedHeadStep(_HeadStageBase):
                 confusion=g(log.conf) if log is not None else None, loss_log=g(log.loss_log) if log is not None else None,
                 counters=g(log.counters) if log is not None else None, log_capacity=log.capacity if log is not None else 0,
                 workspace=g(self.ws), workspace_bytes=self.ws.numel())
+            if self.steps > 1:
+                fg = self.fg
+                ad = L.HeadAdamDesc(param=g(fg.param), grad=g(fg.grad), exp_avg=g(fg.exp_avg),
+                                    exp_avg_sq=g(fg.exp_avg_sq), count=fg.numel, hyper=g(fg.hyper))
+                L.check(L.lib().tspm_cached_head_train_steps(d, ad, self.steps, sh), "cached_head_train_steps")
+                return  # Adam ran in every step's second launch
             L.check(L.lib().tspm_cached_head_train_step(d, sh), "cached_head_train_step")
         elif self.per_sample:
             self._gather(sh, True)
@@ -1436,15 +1466,16 @@ class FusedCachedHeadStep(_HeadStageBase):
 
     def load_batch(self, sample_ids: torch.Tensor, keep: Optional[torch.Tensor] = None,
                    groups: Optional[torch.Tensor] = None) -> None:
-        if sample_ids.numel() != self.N:
-            raise L.TspmError(f"FusedCachedHeadStep: built for {self.N} samples, got {sample_ids.numel()} ids")
+        if sample_ids.numel() != self.steps * self.N:
+            raise L.TspmError(f"FusedCachedHeadStep: built for {self.steps * self.N} samples, got {sample_ids.numel()} "
+                              "ids")
         if not self.per_sample and (keep is not None or groups is not None):
             raise L.TspmError("FusedCachedHeadStep: keep / groups are per-sample inputs; this step trains every pattern "
                               "of the batch")
         if sample_ids.data_ptr() != self.rows.data_ptr():
             self.rows.copy_(sample_ids.reshape(-1), non_blocking=True)
         if keep is not None and keep.data_ptr() != self.row_keep.data_ptr():
-            self.row_keep.copy_(keep.reshape(self.N, 2).to(torch.uint8), non_blocking=True)
+            self.row_keep.copy_(keep.reshape(self.steps * self.N, 2).to(torch.uint8), non_blocking=True)
         if groups is not None and groups.data_ptr() != self.groups.data_ptr():
             self.groups.copy_(groups.reshape(-1).to(torch.int32), non_blocking=True)
 
@@ -1458,10 +1489,15 @@ class FusedCachedHeadStep(_HeadStageBase):
             self._bound_groups = gids
 
     def run(self) -> None:
-        """One head-stage step on the cache rows named in the static ``rows`` (and ``row_keep`` / ``groups``)."""
+        """``steps`` head-stage steps on the cache rows named in the static ``rows`` (and ``row_keep`` / ``groups``)."""
         self._still_frozen()
         self.cache.check(self.model)
         self.model.train()
+        if self.steps > 1:
+            if self.keep_override is not None:
+                raise L.TspmError("FusedCachedHeadStep: steps > 1 draws every step's dropout mask on the device; a "
+                                  "keep_override holds one step's mask")
+            self._refuse_clip()
         self.opt.sync_hyper()
         if self.keep_override is not None:
             self.keep.copy_(self.keep_override.reshape(self.keep.shape).to(torch.uint8), non_blocking=True)
@@ -1469,8 +1505,9 @@ class FusedCachedHeadStep(_HeadStageBase):
         self._bind_groups()
         self.replay_or_enqueue(self._enqueue, (self.log, self.keep_override is None, self._head_bumps(),
                                                self.x0.data_ptr(), self.cache.emb.data_ptr(),
-                                               tuple(self._group_ids())))
-        self.opt.note_steps(1)
+                                               tuple(self._group_ids())) + ((("steps", self.steps),)
+                                                                             if self.steps > 1 else ()))
+        self.opt.note_steps(self.steps)
         self.calls += 1
 
     def step(self, sample_ids, keep=None, groups=None) -> Dict[str, torch.Tensor]:
@@ -1488,10 +1525,18 @@ class FusedCachedEvalStep(FusedPatternEvalStep):
     writes them.  A per-pattern batch (``per_sample=True``: each row under its own ``keep`` flags, the dropped modality
     from ``cache.x0``) runs ``FusedEvalStep``'s head launches: one loss entry per batch, the rows under ``groups``.
 
-    ``step(sample_ids, keep=None, groups=None)`` → ``{"loss", "logits", "preds"}``."""
+    ``step(sample_ids, keep=None, groups=None)`` → ``{"loss", "logits", "preds"}``.
+
+    ``steps=K > 1``: one call evaluates K consecutive batches — static ``rows [K*B]``, ``row_keep [K*B, 2]`` and
+    ``groups [K*B]``, and the graph holds the launches above K times, the k-th gather reading ``rows[k*B:(k+1)*B]``:
+    the log takes the same entries, in batch order, as K single steps; ``loss``, ``logits`` and ``preds`` are the last
+    batch's."""
 
     def __init__(self, model, loss_functions, batch: int, cache, log=None, patterns=None, per_sample: bool = False,
-                 head: Optional[str] = None, use_graph: bool = True):
+                 head: Optional[str] = None, use_graph: bool = True, steps: int = 1):
+        self.steps = K = int(steps)
+        if not 1 <= K <= L.CACHED_HEAD_MAX_STEPS:
+            raise L.TspmError(f"FusedCachedEvalStep: steps must be 1 .. {L.CACHED_HEAD_MAX_STEPS}, got {steps}")
         self.model, self.N, self.log = model, int(batch), log
         self.ce_weight = _ce_weight(loss_functions)
         if self.ce_weight is None:
@@ -1516,15 +1561,15 @@ class FusedCachedEvalStep(FusedPatternEvalStep):
         self.audio_hw, self.image_hw = cache.audio_hw, cache.image_hw
         f32 = dict(device=dev, dtype=torch.float32)
         B = self.N
-        self.rows = torch.zeros(B, dtype=torch.int64, device=dev)
-        self.row_keep = torch.ones(B, 2, dtype=torch.uint8, device=dev)
+        self.rows = torch.zeros(K * B, dtype=torch.int64, device=dev)
+        self.row_keep = torch.ones(K * B, 2, dtype=torch.uint8, device=dev)
         self.labels = torch.zeros(B, dtype=torch.int64, device=dev)
         self.x0 = cache.x0
         if self.per_sample:  # FusedEvalStep's head buffers: one row per sample, the rows' groups
             self.logits = torch.empty(B, NUM_CLASSES, **f32)
             self.loss = torch.zeros(1, **f32)
             self.preds = torch.zeros(B, dtype=torch.int64, device=dev)
-            self.groups = torch.zeros(B, dtype=torch.int32, device=dev)
+            self.groups = torch.zeros(K * B, dtype=torch.int32, device=dev)
             self.fused = torch.empty(B, self.F, **f32)
             self.h1 = torch.empty(B, self.hd, **f32)
             self.hh = torch.empty(B, self.h2, **f32)
@@ -1533,25 +1578,32 @@ class FusedCachedEvalStep(FusedPatternEvalStep):
 
     def load_batch(self, sample_ids: torch.Tensor, keep: Optional[torch.Tensor] = None,
                    groups: Optional[torch.Tensor] = None) -> None:
-        if sample_ids.numel() != self.N:
-            raise L.TspmError(f"FusedCachedEvalStep: built for {self.N} samples, got {sample_ids.numel()} ids")
+        if sample_ids.numel() != self.steps * self.N:
+            raise L.TspmError(f"FusedCachedEvalStep: built for {self.steps * self.N} samples, got {sample_ids.numel()} "
+                              "ids")
         if not self.per_sample and (keep is not None or groups is not None):
             raise L.TspmError("FusedCachedEvalStep: keep / groups are per-sample inputs; this step evaluates every "
                               "pattern of the batch")
         if sample_ids.data_ptr() != self.rows.data_ptr():
             self.rows.copy_(sample_ids.reshape(-1), non_blocking=True)
         if keep is not None and keep.data_ptr() != self.row_keep.data_ptr():
-            self.row_keep.copy_(keep.reshape(self.N, 2).to(torch.uint8), non_blocking=True)
+            self.row_keep.copy_(keep.reshape(self.steps * self.N, 2).to(torch.uint8), non_blocking=True)
         if groups is not None and groups.data_ptr() != self.groups.data_ptr():
             self.groups.copy_(groups.reshape(-1).to(torch.int32), non_blocking=True)
 
     def _enqueue(self) -> None:
+        for k in range(self.steps):
+            self._enqueue_batch(k)
+
+    def _enqueue_batch(self, k: int) -> None:
+        """The step's launches on batch k of the static inputs (rows, flags and groups ``[k*B, (k+1)*B)``)."""
         lib, c, log = L.lib(), self.cache, self.log
         sh = torch.cuda.current_stream().cuda_stream
         flags = self.per_sample
+        at = k * self.N
         L.check(lib.tspm_embed_gather(
-            self.N, self.F, c.emb.data_ptr(), c.n, self.F, self.rows.data_ptr(), c.labels_all.data_ptr(),
-            self.row_keep.data_ptr() if flags else None, self.ea, self.x0.data_ptr() if flags else None,
+            self.N, self.F, c.emb.data_ptr(), c.n, self.F, self.rows[at:].data_ptr(), c.labels_all.data_ptr(),
+            self.row_keep[at:].data_ptr() if flags else None, self.ea, self.x0.data_ptr() if flags else None,
             self.fused.data_ptr(), self.F, self.labels.data_ptr(), sh), "embed_gather")
         if not self.per_sample:
             self._bind_log()
@@ -1572,7 +1624,7 @@ class FusedCachedEvalStep(FusedPatternEvalStep):
         L.check(lib.tspm_cross_entropy(n, NUM_CLASSES, self.logits.data_ptr(), self.labels.data_ptr(),
                                        self.loss.data_ptr(), None, self.ce_weight, None, sh), "eval cross_entropy")
         L.check(lib.tspm_classify_update(
-            n, NUM_CLASSES, self.logits.data_ptr(), self.labels.data_ptr(), self.groups.data_ptr(),
+            n, NUM_CLASSES, self.logits.data_ptr(), self.labels.data_ptr(), self.groups[at:].data_ptr(),
             len(log.groups) if log is not None else 1, log.conf.data_ptr() if log is not None else None,
             self.preds.data_ptr(), self.loss.data_ptr(), log.loss_log.data_ptr() if log is not None else None,
             log.counters.data_ptr() if log is not None else None, log.capacity if log is not None else 0, sh),
@@ -1582,7 +1634,8 @@ class FusedCachedEvalStep(FusedPatternEvalStep):
         self.cache.check(self.model)
         self.model.eval()
         self.x0 = self.cache.x0
-        self.replay_or_enqueue(self._enqueue, (self.log, self.x0.data_ptr(), self.cache.emb.data_ptr()))
+        self.replay_or_enqueue(self._enqueue, (self.log, self.x0.data_ptr(), self.cache.emb.data_ptr()) +
+                               ((("steps", self.steps),) if self.steps > 1 else ()))
         self.calls += 1
 
     def step(self, sample_ids, keep=None, groups=None) -> Dict[str, torch.Tensor]:
