@@ -65,7 +65,8 @@ enum {
  * tspm_embed_gather and tspm_cached_head_train_step / tspm_cached_head_train_workspace, that head stage on a cache of
  * the frozen encoders' embeddings (rows gathered by index; every pattern of the batch or one pattern per sample);
  * tspm_cached_head_train_steps, up to 64 consecutive steps of that stage per host call with Adam applied in the
- * weight-gradient launch. */
+ * weight-gradient launch; tspm_utt_cache_rows, the UTT-Fusion encoder half read from a cache of the frozen encoders'
+ * embeddings and pooled TextCNN features. */
 #define TSPM_ABI_VERSION 23
 int tspm_abi_version(void);  /* returns TSPM_ABI_VERSION */
 /* Static string for a status code. */
@@ -1087,6 +1088,46 @@ int tspm_pattern_expand(int32_t batch, int32_t npat, const int32_t* keep, const 
 int tspm_pattern_expand_bwd(int32_t batch, int32_t npat, const int32_t* keep, int32_t w_audio, int32_t w_video,
                             int32_t w_text, const float* dout, int64_t ld_dout, float* demb, int64_t ld_demb,
                             int32_t modalities, tspm_stream_t stream);
+
+/* The UTT-Fusion encoder half read from a cache (added under ABI 23) — the head stage on frozen encoders without the
+ * encoders.  With all three encoders frozen, everything up to the TextCNN's dropout is a per-sample constant: cache
+ * row i of emb [n_rows][ld_cache] is [ eA(i) | eV(i) | pooled(i) ] (w_audio + w_video + w_pool fp32 columns: the two
+ * LSTM embeddings and the TextCNN's time-max output BEFORE its dropout), and zero [n_zero][ld_cache] holds the same
+ * for the zeroed inputs — one row for the whole split (n_zero == 1) or one per sample (n_zero == n_rows: with
+ * per-sample lengths a zero row's embedding depends on its own lengths).  One launch; with R = halves*batch, for
+ * r < R, b = r mod batch and each modality m (audio, video, text):
+ *   source row = emb[rows[b]]                       when r < batch and (row_keep == NULL or row_keep[3b + m] != 0)
+ *              = zero[n_zero == 1 ? 0 : rows[b]]    otherwise
+ *   av_out[r*ld_av + c]     = source[c]                                  for c < w_audio + w_video (m by column)
+ *   pool_out[r*ld_pool + j] = keep ? v * (keep[r*w_pool + j] ? scale : 0.f) : v,   v = source[w_audio + w_video + j]
+ *   labels_out[b]           = labels_all[rows[b]]                        for r < batch only
+ * halves == 2 is the all-pattern layout tspm_pattern_expand reads (the batch in rows [0, batch), its zero rows in
+ * [batch, 2*batch)); halves == 1 with row_keep (uint8 [batch][3] on the DEVICE) gives each row its own pattern.  The
+ * pool_out expression is tspm_textcnn_pool_fwd's store: with the same mask bytes the output is bitwise the fc_in the
+ * TextCNN would have written from those pooled values.  keep (uint8 [R][w_pool], nullable) is read, never drawn here.
+ * label_bytes = 8: int64 labels, 4: float32 scores.  An index outside [0, n_rows) gives a NaN row and label -1 (NaN
+ * for float32 labels) and reads nothing out of bounds.  Every load and store of a float is a float4; no LDS, no
+ * atomics; padding columns of av_out / pool_out keep their content.  TSPM_ERR_INVALID, nothing launched: a NULL among
+ * emb, zero, rows, av_out, pool_out; a width or leading dimension that is not a positive multiple of 4, or a leading
+ * dimension below its width (ld_cache below the width sum); emb, zero, av_out, pool_out or keep not 16-byte aligned;
+ * halves outside {1, 2}; row_keep with halves == 2; n_zero not in {1, n_rows}; label_bytes not in {4, 8}; only one of
+ * labels_all / labels_out; batch < 1 or n_rows < 1. */
+typedef struct tspm_utt_cache_rows_desc {
+  int32_t batch, halves, w_audio, w_video, w_pool, ld_cache, ld_av, ld_pool;
+  int64_t n_rows, n_zero;
+  const float* emb;            /* [n_rows, ld_cache] */
+  const float* zero;           /* [n_zero, ld_cache] */
+  const int64_t* rows;         /* [batch] */
+  const uint8_t* row_keep;     /* DEVICE [batch][3] (audio, video, text); nullable, halves == 1 only */
+  const void* labels_all;      /* [n_rows] int64 or float32; nullable with labels_out */
+  void* labels_out;            /* [batch] */
+  int32_t label_bytes;         /* 8 or 4 */
+  float scale;                 /* the dropout's 1 / (1 - p) */
+  const uint8_t* keep;         /* [R, w_pool]; nullable */
+  float* av_out;               /* [R, ld_av] */
+  float* pool_out;             /* [R, ld_pool] */
+} tspm_utt_cache_rows_desc;
+int tspm_utt_cache_rows(const tspm_utt_cache_rows_desc* desc, tspm_stream_t stream);
 
 /* All-pattern evaluation head (added under ABI 23) — AVMNIST's classifier `net` (tspm_head_train_step's three Linears,
  * no dropout), the loss group's weighted cross-entropy and tspm_classify_update's bookkeeping for EVERY missing-modality

@@ -264,6 +264,16 @@ def cached_head_train_supported(in_: int, w_audio: int, hidden: int, hidden2: in
     return pattern_head_train_supported(in_, w_audio, hidden, hidden2, classes, npat)
 
 
+class UttCacheRowsDesc(Structure):
+    """tspm_utt_cache_rows_desc (added under ABI 23): the UTT-Fusion encoder half read from a cache of the frozen
+    encoders' embeddings and pooled TextCNN features, by sample index (``halves`` 2: the all-pattern 2B-row layout;
+    1 with the device ``row_keep``: one pattern per row)."""
+    _fields_ = [(n, c_int32) for n in ("batch", "halves", "w_audio", "w_video", "w_pool", "ld_cache", "ld_av",
+                                       "ld_pool")] + [("n_rows", c_int64), ("n_zero", c_int64)] + \
+        [(n, c_void_p) for n in ("emb", "zero", "rows", "row_keep", "labels_all", "labels_out")] + \
+        [("label_bytes", c_int32), ("scale", c_float)] + [(n, c_void_p) for n in ("keep", "av_out", "pool_out")]
+
+
 GMU_PATTERN_MAX_D = 4095  # TSPM_GMU_PATTERN_MAX_D: (4d + 4) floats of LDS within 64 KiB
 
 
@@ -495,6 +505,8 @@ _SIGS = {
                                       _P, c_int64, _P, c_int64, _P, _P, c_int32, _P, _P]),
     "tspm_pattern_expand_bwd": (c_int32, [c_int32, c_int32, POINTER(c_int32), c_int32, c_int32, c_int32,
                                           _P, c_int64, _P, c_int64, c_int32, _P]),
+    # added under ABI 23: the UTT-Fusion encoder half read from a cache of the frozen encoders' outputs
+    "tspm_utt_cache_rows": (c_int32, [POINTER(UttCacheRowsDesc), _P]),
     # added under ABI 23: AVMNIST's eval head + cross-entropy + classification log for every pattern of a batch
     "tspm_pattern_head_eval_workspace": (c_size_t, [c_int32, c_int32]),
     "tspm_pattern_head_eval": (c_int32, [POINTER(PatternHeadEvalDesc), _P]),

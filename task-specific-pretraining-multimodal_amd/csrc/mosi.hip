@@ -854,6 +854,58 @@ __global__ __launch_bounds__(256) void k_pattern_expand_bwd(int B, int npat, Pat
 }
 
 // ------------------------------------------------------------------------------------------------
+// The encoder half of the UTT-Fusion head stage read from a cache (tspm_utt_cache_rows): cache row i is
+// [eA(i) | eV(i) | pooled(i)], `zero` the same for the zeroed inputs (one row, or one per sample).  Output row r < R =
+// halves*B serves sample rows[r mod B]: a modality comes from emb when r < B and the row keeps it (row_keep NULL: every
+// modality), else from zero.  A thread moves one float4: an audio / video unit to av_out, a pooled unit through the
+// dropout of k_textcnn_pool's store (the same expression, so the same mask bytes give the same fc_in bits) to pool_out.
+// The first unit of a row r < B carries the row's label.  Memory bound: no LDS, no atomics.
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_utt_cache_rows(tspm_utt_cache_rows_desc d) {
+  const int B = d.batch, R = d.halves * d.batch;
+  const int uav = (d.w_audio + d.w_video) / 4, ua = d.w_audio / 4, upr = uav + d.w_pool / 4;
+  const float4* __restrict__ emb = static_cast<const float4*>(static_cast<const void*>(d.emb));
+  const float4* __restrict__ zero = static_cast<const float4*>(static_cast<const void*>(d.zero));
+  const long long ldc = d.ld_cache / 4, total = (long long)R * upr;
+  for (long long e = blockIdx.x * 256LL + threadIdx.x; e < total; e += (long long)gridDim.x * 256) {
+    const int u = (int)(e % upr), r = (int)(e / upr);
+    const int b = r % B;
+    const long long s = d.rows[b];
+    const bool valid = s >= 0 && s < d.n_rows;
+    const int m = u < ua ? 0 : (u < uav ? 1 : 2);
+    const bool real = r < B && (!d.row_keep || d.row_keep[3 * b + m] != 0);
+    float4 v;
+    if (!valid) {
+      const float q = __builtin_nanf("");
+      v = make_float4(q, q, q, q);
+    } else {
+      v = real ? emb[s * ldc + u] : zero[(d.n_zero == 1 ? 0 : s) * ldc + u];
+    }
+    if (m < 2) {
+      reinterpret_cast<float4*>(d.av_out + (long long)r * d.ld_av)[u] = v;
+    } else {
+      const int j = (u - uav) * 4;
+      if (d.keep) {
+        const uchar4 k = *reinterpret_cast<const uchar4*>(d.keep + (long long)r * d.w_pool + j);
+        const float sc = d.scale;
+        v.x = v.x * (k.x ? sc : 0.f);
+        v.y = v.y * (k.y ? sc : 0.f);
+        v.z = v.z * (k.z ? sc : 0.f);
+        v.w = v.w * (k.w ? sc : 0.f);
+      }
+      *reinterpret_cast<float4*>(d.pool_out + (long long)r * d.ld_pool + j) = v;
+    }
+    if (u == 0 && r < B && d.labels_out) {
+      if (d.label_bytes == 8) {
+        static_cast<long long*>(d.labels_out)[b] = valid ? static_cast<const long long*>(d.labels_all)[s] : -1LL;
+      } else {
+        static_cast<float*>(d.labels_out)[b] = valid ? static_cast<const float*>(d.labels_all)[s] : __builtin_nanf("");
+      }
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
 // LSTM host path: each of the nine entry points fills one LstmProb per descriptor, validates it against the entry
 // point's rules and hands the problems to lstm_dispatch.
 // ------------------------------------------------------------------------------------------------
@@ -1256,6 +1308,30 @@ extern "C" int tspm_pattern_expand_bwd(int32_t batch, int32_t npat, const int32_
   hipLaunchKernelGGL(k_pattern_expand_bwd, dim3(grid_for(2LL * batch * upr)), dim3(256), 0,
                      static_cast<hipStream_t>(stream), batch, npat, ps, dout, (long long)ld_dout, demb,
                      (long long)ld_demb, modalities);
+  TSPM_LAUNCH_CHECK();
+  return TSPM_OK;
+}
+
+extern "C" int tspm_utt_cache_rows(const tspm_utt_cache_rows_desc* desc, tspm_stream_t stream) {
+  if (!desc) return TSPM_ERR_INVALID;
+  const tspm_utt_cache_rows_desc& d = *desc;
+  if (d.batch < 1 || d.n_rows < 1 || (d.halves != 1 && d.halves != 2)) return TSPM_ERR_INVALID;
+  if (!d.emb || !d.zero || !d.rows || !d.av_out || !d.pool_out) return TSPM_ERR_INVALID;
+  const int dims[6] = {d.w_audio, d.w_video, d.w_pool, d.ld_cache, d.ld_av, d.ld_pool};
+  for (int v : dims)
+    if (v < 4 || v % 4 != 0) return TSPM_ERR_INVALID;
+  const long long wav = (long long)d.w_audio + d.w_video;
+  if (d.ld_cache < wav + d.w_pool || d.ld_av < wav || d.ld_pool < d.w_pool) return TSPM_ERR_INVALID;
+  const void* aligned[5] = {d.emb, d.zero, d.av_out, d.pool_out, d.keep};
+  for (const void* p : aligned)
+    if (reinterpret_cast<uintptr_t>(p) & 15) return TSPM_ERR_INVALID;
+  if (d.row_keep && d.halves == 2) return TSPM_ERR_INVALID;
+  if (d.n_zero != 1 && d.n_zero != d.n_rows) return TSPM_ERR_INVALID;
+  if ((d.labels_all == nullptr) != (d.labels_out == nullptr)) return TSPM_ERR_INVALID;
+  if (d.label_bytes != 4 && d.label_bytes != 8) return TSPM_ERR_INVALID;
+  if ((long long)d.halves * d.batch > INT32_MAX) return TSPM_ERR_INVALID;
+  const long long units = (long long)d.halves * d.batch * ((wav + d.w_pool) / 4);
+  hipLaunchKernelGGL(k_utt_cache_rows, dim3(grid_for(units)), dim3(256), 0, static_cast<hipStream_t>(stream), d);
   TSPM_LAUNCH_CHECK();
   return TSPM_OK;
 }

@@ -350,7 +350,9 @@ class MosiEpochRunner:
     (``MosiDeviceLoader`` with ``step_for`` pointed here by ``loader_for``) — or, for valid / test, the
     pattern-grouped ``{pattern: sub-batch}`` of data/mosi.py:236-251; each group is one ``validation_step`` (one
     ``FusedMosiEvalStep`` replay: its loss is one entry of the epoch's loss log, its rows go to the confusion
-    counts of their pattern).  A ``"fused_patterns"`` batch (``MOSI.loader(fuse_patterns=True)``: the samples once,
+    counts of their pattern).  An ``"ids_only"`` batch (``MOSI.loader(ids_only=True)``: sample indices, no input
+    tensors) runs on its dataset's ``embedding_cache(model)`` — ``FusedMosiCachedStep`` / ``FusedMosiCachedEvalStep``,
+    the same loss entries and counts with no encoder launch.  A ``"fused_patterns"`` batch (``MOSI.loader(fuse_patterns=True)``: the samples once,
     unmasked) is one ``FusedMosiPatternEvalStep`` replay that writes the same per-pattern entries and counts from one
     encoder pass.  Per-pattern metrics come from ``DeviceMetricRecorder`` with the YAML's MSA and
     confusion-matrix functions (keys ``MSA_Has0_Accuracy_ATV`` ...; metric_recorder.py:147-209)."""
@@ -373,6 +375,8 @@ class MosiEpochRunner:
         self.ragged = False  # the loader's dataset carries per-sample lengths (mosi_data.MOSI(use_lengths=True))
         self.text_lengths = False  # ... and the text lengths too (mosi_data.MOSI(text_lengths=True))
         self.patterns = None  # the selected patterns of a fuse_patterns loader (loader_for)
+        self.cached_steps: Dict[Any, Any] = {}  # the steps on a UttEmbeddingCache (ids_only batches)
+        self._epoch_caches: Dict[Any, Any] = {}  # (dataset id, steps) -> its cache, for the running epoch
 
     def train_step_for(self, b: int, t, ragged: Optional[bool] = None, text_lengths: Optional[bool] = None):
         """The model's cached FusedMosiStep for (b, t); ``t`` an ``int`` or a triple (Ta, Tv, Tt) (``mosi.norm_steps``).
@@ -447,20 +451,74 @@ class MosiEpochRunner:
                                self.pattern_eval_step_for if fused else self.eval_step_for)
         return loader
 
+    def cached_train_step_for(self, n: int, cache, patterns=None):
+        """The ``FusedMosiCachedStep`` for (patterns, batch size) on ``cache`` (a ``mosi.UttEmbeddingCache``): every
+        pattern of the batch when ``patterns`` is given (an ``"all_patterns"`` batch), else one pattern per sample.
+        Kept in ``cached_steps``; rebuilt for another cache, optimizer or set of flags."""
+        from .mosi import FusedMosiCachedStep, norm_patterns
+        pats = norm_patterns(patterns) if patterns is not None else None
+        key = ("train", pats, int(n), id(self.optimizer), self.model.flag_state()[0])
+        st = self.cached_steps.get(key)
+        if st is None or st.cache is not cache:
+            st = self.cached_steps[key] = FusedMosiCachedStep(self.model, self.optimizer, self.loss_functions, n, cache,
+                                                              patterns=pats, per_sample=pats is None)
+        if st.log is not self.log:
+            st.log, st.graph = self.log, None
+        return st
+
+    def cached_eval_step_for(self, n: int, cache, patterns=None):
+        """The ``FusedMosiCachedEvalStep`` for (patterns, batch size) on ``cache`` (``patterns``: a ``"fused_patterns"``
+        batch's; None: each row under its own keep flags)."""
+        from .mosi import FusedMosiCachedEvalStep, norm_patterns
+        pats = norm_patterns(patterns) if patterns is not None else None
+        key = ("eval", pats, int(n))
+        st = self.cached_steps.get(key)
+        if st is None or st.cache is not cache:
+            st = self.cached_steps[key] = FusedMosiCachedEvalStep(self.model, self.loss_functions, n, cache, self.log,
+                                                                  patterns=pats, per_sample=pats is None)
+        st.log = self.log
+        return st
+
+    def _cache_of(self, b: Dict[str, Any]):
+        """An ``ids_only`` batch's cache: its dataset's ``embedding_cache(model, pad_to)``, looked up once per epoch
+        (a dataset without one gets it here, a fill pass inside the epoch's first batch)."""
+        ds = b["dataset"]
+        key = (id(ds), b["steps"])
+        cache = self._epoch_caches.get(key)
+        if cache is None:
+            cache = self._epoch_caches[key] = ds.embedding_cache(self.model, pad_to=b["pad_to"])
+        return cache
+
+    def _cached_step_of(self, b: Dict[str, Any], train: bool):
+        pats = b["patterns"] if (b.get("all_patterns") or b.get("fused_patterns")) else None
+        step_for = self.cached_train_step_for if train else self.cached_eval_step_for
+        return step_for(int(b["rows"].numel()), self._cache_of(b), pats)
+
     def _train_step_of(self, b: Dict[str, Any]):
-        """The train step a batch asks for: the all-pattern step for an ``"all_patterns"`` batch, else the plain one."""
+        """The train step a batch asks for: the cached step for an ``"ids_only"`` batch, the all-pattern step for an
+        ``"all_patterns"`` batch, else the plain one."""
+        if b.get("ids_only"):
+            return self._cached_step_of(b, True)
         if b.get("all_patterns"):
             return self.train_pattern_step_for(*self._shape(b), patterns=b["patterns"], **self._modes(b))
         return self.train_step_for(*self._shape(b), **self._modes(b))
 
     def _eval_step_of(self, b: Dict[str, Any]):
-        """The eval step a batch asks for: the fused-pattern step for a ``"fused_patterns"`` batch, else the per-pattern
-        one."""
+        """The eval step a batch asks for: the cached step for an ``"ids_only"`` batch, the fused-pattern step for a
+        ``"fused_patterns"`` batch, else the per-pattern one."""
+        if b.get("ids_only"):
+            return self._cached_step_of(b, False)
         if b.get("fused_patterns"):
             return self.pattern_eval_step_for(*self._shape(b), patterns=b["patterns"], **self._modes(b))
         return self.eval_step_for(*self._shape(b), **self._modes(b))
 
     def _run(self, st, b: Dict[str, Any]) -> None:
+        if b.get("ids_only"):  # sample indices on a UttEmbeddingCache: no inputs, no lengths
+            if st.per_sample:
+                st.step(b["rows"], b["row_keep"], self.log.group_ids(b["pattern_name"]))
+            else:
+                st.step(b["rows"])
+            return
         if b.get("fused_patterns") or b.get("all_patterns"):  # the step expands labels and group ids on the device
             if b.get("time_major") and b["audio"] is st.eng.A:
                 st.run()
@@ -491,7 +549,7 @@ class MosiEpochRunner:
 
     @staticmethod
     def _groups(b: Dict[str, Any]):
-        if "label" in b:
+        if "label" in b or b.get("ids_only"):
             return [b]
         return list(b.values())  # {pattern: sub-batch}
 
@@ -507,6 +565,7 @@ class MosiEpochRunner:
     def train_epoch(self, loader: Iterable[Dict[str, Any]]):
         """→ (mean batch loss, seconds, metrics dict, batches)."""
         self.log.reset()
+        self._epoch_caches = {}
         t0 = time.time()
         for b in self.loader_for(loader, True):
             for g in self._groups(b):
@@ -516,6 +575,7 @@ class MosiEpochRunner:
     @torch.no_grad()
     def validate_epoch(self, loader: Iterable[Dict[str, Any]]):
         self.log.reset()
+        self._epoch_caches = {}
         t0 = time.time()
         self.model.eval()
         try:
@@ -525,6 +585,34 @@ class MosiEpochRunner:
         finally:
             self.model.train()
         return self._finish(t0)
+
+
+def _cached_mosi_loaders(model, loaders: Dict[str, Any]):
+    """fit(cache_embeddings=True) on a UTT-Fusion model: the ``ids_only`` twin of every ``MosiDeviceLoader`` (the same
+    ``epoch`` counter, hence the same shuffles) and one filled ``UttEmbeddingCache`` per split."""
+    from .mosi import ALL_FROZEN, frozen_encoders
+    from .mosi_data import MosiDeviceLoader
+    if frozen_encoders(model) != ALL_FROZEN:
+        raise L.TspmError("cache_embeddings=True needs frozen encoders - all of netA, netV and netT (finetune_param_groups("
+                          "..., freeze=('audio', 'video', 'text'))): a trainable encoder's outputs change every step, so "
+                          "there is nothing constant to cache")
+    out, report = {}, {"fill_seconds": {}, "rows": {}}
+    for name, ld in loaders.items():
+        if not isinstance(ld, MosiDeviceLoader):
+            raise L.TspmError(f"cache_embeddings=True: loaders[{name!r}] must be a mosi_data.MosiDeviceLoader "
+                              f"(dataset.loader(...)), got {type(ld).__name__}")
+        twin = ld if ld.ids_only else MosiDeviceLoader(ld.ds, ld.batch_size, ld.shuffle, ld.drop_last, ld.seed, None,
+                                                      ld.pad_to, ld.group_patterns, ld.fuse_patterns, ld.all_patterns,
+                                                      ids_only=True)
+        twin.epoch = ld.epoch
+        cache = ld.ds.embedding_cache(model, pad_to=ld.pad_to)
+        if cache.stale_reason() is not None:
+            cache.refresh()
+        report["fill_seconds"][name], report["rows"][name] = cache.fill_seconds, cache.n
+        out[name] = twin
+    print("embedding cache filled: " + ", ".join(f"{k} {report['rows'][k]} rows in {v:.3f} s"
+                                                 for k, v in report["fill_seconds"].items()))
+    return out, report
 
 
 def runner_for(model, optimizer, loss_functions, metric_config=None):
@@ -564,15 +652,21 @@ def fit(model, optimizer, loss_functions, loaders: Dict[str, Any], epochs: int, 
     ``fail_on_nonfinite``: raise FloatingPointError as soon as an epoch's mean training loss is NaN / inf
     (checked at the epoch's one host synchronisation; SURVEY §5 — the reference only turns three numpy
     RuntimeWarnings into errors, train_multimodal.py:46-60, and would keep training on NaN weights).
-    ``cache_embeddings`` (AVMNIST on frozen encoders, ``data.DeviceLoader`` loaders; refused otherwise): before the
+    ``cache_embeddings`` (AVMNIST on frozen encoders with ``data.DeviceLoader`` loaders, or UTT-Fusion with all three
+    encoders frozen and ``mosi_data.MosiDeviceLoader`` loaders - ``steps_per_call`` is not built for it; refused otherwise): before the
     first epoch each split's ``embedding_cache(model)`` is filled once, and every epoch then iterates the ``ids_only``
     twin of its loader — no encoder launch after the fill; metric keys and loss entries per epoch are unchanged.  The
-    fill times are reported once under ``history["embedding_cache"]``.
+    fill times are reported once under ``history["embedding_cache"]``.  When the best checkpoint is reloaded for the test
+    split only the test split's cache is refreshed: the train and validation caches are left stale, and whoever reuses
+    those datasets with the model afterwards calls ``refresh()`` on them (``embedding_cache(model, refresh=True)``).
     ``steps_per_call=K`` (with ``cache_embeddings`` only; refused without): every train, validation and test epoch runs
     K consecutive batches per host call (``EpochRunner.train_epoch(loader, steps_per_call=K)``) — the same history."""
     if steps_per_call is not None and not cache_embeddings:
         raise L.TspmError("steps_per_call runs several cached batches per host call: it needs cache_embeddings=True")
     runner = runner_for(model, optimizer, loss_functions, metric_config)
+    if steps_per_call is not None and isinstance(runner, MosiEpochRunner):
+        raise L.TspmError("steps_per_call is not built for the UTT-Fusion model: its cached head stage runs one step per "
+                          "graph replay")
     cache_report = None
     spc = {"steps_per_call": steps_per_call} if steps_per_call is not None else {}
     if cache_embeddings:
@@ -618,7 +712,11 @@ def fit(model, optimizer, loss_functions, loaders: Dict[str, Any], epochs: int, 
         if ckpt is not None and (ckpt.model_dir / "best.pth").exists():
             ckpt.load_checkpoint(model, load_best=True)
             if cache_embeddings:  # load_state_dict made the caches stale (the loaded encoders may differ)
-                loaders["test"].ds.embedding_cache(model, refresh=True)
+                ld = loaders["test"]
+                if isinstance(runner, MosiEpochRunner):  # a UTT-Fusion cache is per (model, steps): the loader's pad_to
+                    ld.ds.embedding_cache(model, pad_to=ld.pad_to, refresh=True)
+                else:
+                    ld.ds.embedding_cache(model, refresh=True)
         te_loss, te_time, te_metrics, _ = runner.validate_epoch(loaders["test"], **spc)
         history["test"] = dict(te_metrics, loss=te_loss)
     history["best"] = best
@@ -630,6 +728,8 @@ def fit(model, optimizer, loss_functions, loaders: Dict[str, Any], epochs: int, 
 def _cached_loaders(model, optimizer, runner, loaders: Dict[str, Any]):
     """fit(cache_embeddings=True): the ``ids_only`` twin of every loader and one filled cache per split."""
     from .data import DeviceLoader
+    if isinstance(runner, MosiEpochRunner):
+        return _cached_mosi_loaders(model, loaders)
     if not isinstance(runner, EpochRunner):
         raise L.TspmError("cache_embeddings=True is for the AVMNIST late-fusion model")
     if not head_stage_frozen(model, optimizer):

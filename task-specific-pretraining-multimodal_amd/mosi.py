@@ -193,6 +193,17 @@ class LSTMEncoder(nn.Module):
                     -bound, bound, generator=torch.Generator().manual_seed(_ATTENTION_VECTOR_SEED))
         self.embd_method = embd_method
         self.attention_norm = attention_norm
+        self._weights_generation = 0  # bumped by load_state_dict and by anything that moves the parameters
+
+    def _apply(self, fn, *args, **kwargs):
+        out = super()._apply(fn, *args, **kwargs)
+        self._weights_generation = getattr(self, "_weights_generation", 0) + 1
+        return out
+
+    def _load_from_state_dict(self, *args, **kwargs):
+        # reached by this encoder's own load_state_dict and by any parent's: a UttEmbeddingCache is stale from here on
+        self._weights_generation = getattr(self, "_weights_generation", 0) + 1
+        return super()._load_from_state_dict(*args, **kwargs)
 
     def forward(self, x: torch.Tensor, lengths: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Inference embedding h_T of x [B, T, input] (gradients flow through UttFusionModel only).  ``lengths`` (int
@@ -221,6 +232,7 @@ class TextCNN(nn.Module):
         self.out_channels = out_channels
         self.input_size = input_size
         self._engines: Dict[Any, "MosiEncoderEngine"] = {}
+        self._weights_generation = 0  # as LSTMEncoder's
 
     def convs(self):
         return [self.conv1, self.conv2, self.conv3]
@@ -228,7 +240,12 @@ class TextCNN(nn.Module):
     def _apply(self, fn, *args, **kwargs):
         out = super()._apply(fn, *args, **kwargs)
         self._engines = {}
+        self._weights_generation = getattr(self, "_weights_generation", 0) + 1
         return out
+
+    def _load_from_state_dict(self, *args, **kwargs):
+        self._weights_generation = getattr(self, "_weights_generation", 0) + 1
+        return super()._load_from_state_dict(*args, **kwargs)
 
     def forward(self, x: torch.Tensor, lengths: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Inference embedding of x [B, T, input] (no dropout; gradients flow through UttFusionModel or
@@ -773,9 +790,16 @@ def _text_forward(o, t: "TextCNN", sh: int, keep: Optional[int], out: int, ld_ou
     else:
         L.check(lib.tspm_textcnn_pool_fwd(B, T, 3, heights, o.C, outs, biases, keep, scale, o.pooled.data_ptr(),
                                           o.argmax.data_ptr(), o.fc_in.data_ptr(), o.nc, sh), "textcnn pool")
+    _text_embed(o, t, sh, out, ld_out)
+
+
+def _text_embed(o, t: "TextCNN", sh: int, out: int, ld_out: int) -> None:
+    """The TextCNN's tail on owner `o`: the embedding Linear + ReLU over ``o.fc_in`` [B, nc] (the pooled, dropped-out
+    features) written to `out` (row stride ld_out).  ``_text_forward`` ends with it; the cached head stage
+    (``MosiCachedEngine``) starts with it, on an ``fc_in`` that ``tspm_utt_cache_rows`` wrote."""
     emb = t.embd[0]
-    L.check(lib.tspm_linear_fwd(B, o.nc, emb.out_features, o.fc_in.data_ptr(), o.nc, emb.weight.data_ptr(),
-                                emb.bias.data_ptr(), 1, None, 1.0, out, ld_out, sh),
+    L.check(L.lib().tspm_linear_fwd(o.B, o.nc, emb.out_features, o.fc_in.data_ptr(), o.nc, emb.weight.data_ptr(),
+                                    emb.bias.data_ptr(), 1, None, 1.0, out, ld_out, sh),
             "textcnn embd")
 
 
@@ -1706,8 +1730,7 @@ class MosiPatternEngine:
         self.ragged, self.text_lengths = bool(ragged), bool(text_lengths)
         B = self.B
         self.trainable = bool(backward)
-        self.enc = MosiEngine(model, 2 * B, steps, device, ragged=ragged, text_lengths=text_lengths, classifier=False,
-                              backward=self.trainable)
+        self.enc = self._build_enc(steps)
         self.cls = MosiEngine(model, P * B, steps, device, encoders=False, backward=self.trainable)
         self.keep_override: Optional[Dict[str, torch.Tensor]] = None
         self.rng_ctr_ptr: Optional[int] = None
@@ -1715,9 +1738,23 @@ class MosiPatternEngine:
         if self.trainable:  # the clip buffers live on the classifier half
             self.clip, self.clip_coef, self.total_norm = self.cls.clip, self.cls.clip_coef, self.cls.total_norm
         self.Ts, self.E = self.enc.Ts, self.enc.E
-        self.A, self.V, self.X = self.enc.A, self.enc.V, self.enc.X   # [T_m, 2B, F]: the batch in rows [0, B)
         self.labels = torch.zeros(B, dtype=torch.int64, device=device)
         self.labels_f = torch.zeros(B, dtype=torch.float32, device=device)
+        self.logits = self.cls.logits.view(P, B, -1)
+        self.losses = torch.zeros(P, dtype=torch.float32, device=device)  # one loss per pattern, in pattern order
+        self._keep = (ctypes.c_int32 * (3 * P))(*[int(ch in p) for p in self.patterns for ch in "avt"])
+        self.set_groups(groups)
+        self._plan_inputs()
+
+    def _build_enc(self, steps):
+        """The encoder half at 2B rows (``MosiCachedPatternEngine`` puts its cache reader here)."""
+        return MosiEngine(self.m, 2 * self.B, steps, self.device, ragged=self.ragged, text_lengths=self.text_lengths,
+                          classifier=False, backward=self.trainable)
+
+    def _plan_inputs(self) -> None:
+        """What ``load`` / ``set_lengths`` and the loader's gather write: views of the encoder half's inputs."""
+        B, device = self.B, self.device
+        self.A, self.V, self.X = self.enc.A, self.enc.V, self.enc.X   # [T_m, 2B, F]: the batch in rows [0, B)
         # the first halves of the 2B-long length buffers: what set_lengths and the loader's gather write
         self._len_bufs = ([(self.enc.lens["a"], "audio", self.Ts[0]), (self.enc.lens["v"], "video", self.Ts[1])]
                           if self.ragged else [])
@@ -1725,10 +1762,6 @@ class MosiPatternEngine:
             self._len_bufs.append((self.enc.text_lens, "text", self.Ts[2]))
         self.lens = {"a": self.enc.lens["a"][:B], "v": self.enc.lens["v"][:B]} if self.ragged else None
         self.text_lens = self.enc.text_lens[:B] if self.text_lengths else None
-        self.logits = self.cls.logits.view(P, B, -1)
-        self.losses = torch.zeros(P, dtype=torch.float32, device=device)  # one loss per pattern, in pattern order
-        self._keep = (ctypes.c_int32 * (3 * P))(*[int(ch in p) for p in self.patterns for ch in "avt"])
-        self.set_groups(groups)
         eng = self.enc
         self._index = torch.arange(B, dtype=torch.int64, device=device)
         self._lens = {T_m: eng._lens[T_m][:B] for T_m in eng._lens}
@@ -1875,6 +1908,354 @@ class FusedMosiPatternEvalStep(FusedMosiEvalStep):
 
 
 # ------------------------------------------------------------------------------------------------
+# the head stage on cached encoder features
+# ------------------------------------------------------------------------------------------------
+ALL_FROZEN = tuple(nm for nm, _ in ENCODER_MODULES)
+
+
+class UttEmbeddingCache:
+    """What the three FROZEN encoders of a ``UttFusionModel`` compute for every sample of one ``mosi_data.MOSI`` split,
+    computed once: ``emb [n][W]`` fp32 with row i = ``[ eA(i) | eV(i) | pooled(i) ]``, ``W = ha + hv + nc`` — the two
+    LSTM embeddings (any ``embd_method``) and the TextCNN's time-max output (``nc = 3 * out_channels``) BEFORE its
+    dropout — ``zero [n_zero][W]``, the same for the zeroed inputs a dropped modality feeds its encoder (one row for the
+    split; with ``use_lengths`` one per sample, as a zero row's embedding depends on its own lengths), and
+    ``labels_all``, the device corpus's own label tensor (int64, or float32 scores).  A frozen ``netT`` in a train-mode
+    model still applies its dropout, so the dropout, the embedding ``Linear nc -> ht`` + ReLU and everything from
+    ``fused`` on stay in the step (``FusedMosiCachedStep`` / ``FusedMosiCachedEvalStep``, which read the cache by sample
+    index through ``tspm_utt_cache_rows``).  16k rows x 512 columns x 4 B = 33 MB at MOSEI's default widths, twice that
+    with per-sample zero rows.
+
+    Without lengths an embedding depends on the padded length (the LSTM runs through the padding), so the cache is
+    built for ONE ``steps`` value, the split's corpus-wide padded lengths under the caller's ``pad_to``
+    (``DeviceMosiCorpus.batch_steps(arange(n), pad_to)``), and remembers it: its semantics are those of the uncached
+    loader with a ``pad_to`` that covers the corpus (one step shape for the epoch), or of the ragged path under any
+    padding.
+
+    The fill (``refresh()``) runs forward-only encoder halves ``MosiEngine(model, 2c, steps, classifier=False,
+    backward=False)`` exactly as ``MosiPatternEngine.forward`` runs its own: the chunk gathered into rows [0, c), rows
+    [c, 2c) left zero, lengths mirrored, ``_forward_encoders(sh, train=False)`` — in sample order, in chunks of
+    ``chunk`` rows plus one engine for the short last chunk; no new launch.  It is refused unless all three encoders are
+    frozen.  The cache remembers the model's ``flag_state()``, each encoder's weights generation and the generation of
+    the model's engine table: a changed flag, ``load_state_dict`` on the model or an encoder (``load_pretrained()``) and
+    anything that drops the engines (``.to()``) make it stale, and a stale cache, or another model's, is refused with a
+    ``TspmError`` that says to call ``refresh()``.  Weights written through raw pointers (an in-place ``copy_``) cannot
+    be detected: whoever changes frozen weights that way calls ``refresh()``."""
+
+    def __init__(self, model: "UttFusionModel", dataset, steps, chunk: int = 128):
+        import weakref
+        if int(chunk) < 1:
+            raise ValueError("chunk must be >= 1")
+        # the model is held weakly: the dataset's table of caches is keyed by the model and must not keep it alive
+        self._model_ref, self.ds, self.chunk = weakref.ref(model), dataset, int(chunk)
+        self.dc = dataset.device_corpus
+        self.n, self.steps = int(self.dc.n), norm_steps(steps)
+        self.ha, self.hv, self.nc = model.netA.hidden_size, model.netV.hidden_size, 3 * model.netT.out_channels
+        self.W = self.ha + self.hv + self.nc
+        self.per_sample_zero = bool(dataset.use_lengths)
+        self.n_zero = self.n if self.per_sample_zero else 1
+        self.emb: Optional[torch.Tensor] = None
+        self.zero: Optional[torch.Tensor] = None
+        self.labels_all = self.dc.labels
+        self.fill_seconds, self.fills, self._stamp = 0.0, 0, None
+        self.refresh()
+
+    @property
+    def model(self) -> "UttFusionModel":
+        m = self._model_ref()
+        if m is None:
+            raise L.TspmError("this UttEmbeddingCache's model no longer exists")
+        return m
+
+    def _now(self):
+        m = self.model
+        return (m.flag_state()[0], tuple(getattr(getattr(m, attr), "_weights_generation", 0)
+                                         for _, attr in ENCODER_MODULES), m._engines_generation)
+
+    def stale_reason(self) -> Optional[str]:
+        """None while the cache is current, else what changed since the fill."""
+        was, now = self._stamp, self._now()
+        if now[0] != was[0]:
+            return "the model's requires_grad flags (its frozen encoders) changed since the fill"
+        if now[1] != was[1] or now[2] != was[2]:
+            return "an encoder's weights were loaded or moved (load_state_dict, load_pretrained, .to()) since the fill"
+        return None
+
+    def check(self, model=None) -> "UttEmbeddingCache":
+        """Refuse a cache built for another model, and a stale one."""
+        if model is not None and model is not self.model:
+            raise L.TspmError("this UttEmbeddingCache was built for another model: its rows are that model's encoders' "
+                              "outputs (dataset.embedding_cache(model) builds this model's)")
+        why = self.stale_reason()
+        if why is not None:
+            raise L.TspmError(f"stale UttEmbeddingCache: {why}; call refresh() on it (with all three encoders frozen) "
+                              "before the next use")
+        return self
+
+    def refresh(self) -> "UttEmbeddingCache":
+        """(Re)compute every row and the zero rows, into the same storage; returns self."""
+        import time
+        model, dc, ds = self.model, self.dc, self.ds
+        if frozen_encoders(model) != ALL_FROZEN:
+            raise L.TspmError("UttEmbeddingCache needs frozen encoders - all of netA, netV and netT (finetune_param_groups("
+                              "..., freeze=('audio', 'video', 'text'))): a trainable encoder's outputs change every "
+                              "step, so there is nothing constant to cache")
+        dev = next(model.parameters()).device
+        if dev.type != "cuda" or dev != dc.device:
+            raise L.TspmError(f"UttEmbeddingCache: the model is on {dev}, the corpus on {dc.device} (both on the ROCm "
+                              f"device)")
+        if self.nc % 4 or (self.ha + self.hv) % 4:
+            raise L.TspmError("UttEmbeddingCache: the cache rows are moved 16 bytes at a time - TextCNN out_channels and "
+                              "the LSTM widths must be multiples of 4")
+        f32 = dict(device=dev, dtype=torch.float32)
+        if self.emb is None or self.emb.device != dev:
+            self.emb = torch.empty(self.n, self.W, **f32)
+            self.zero = torch.empty(self.n_zero, self.W, **f32)
+        n, hav, ch = self.n, self.ha + self.hv, min(self.chunk, max(self.n, 1))
+        torch.cuda.synchronize(dev)
+        t0 = time.perf_counter()
+        sh = L.stream_handle()
+        order = torch.arange(n, dtype=torch.int64, device=dev)
+        engines: Dict[int, MosiEngine] = {}
+        with torch.no_grad():
+            for lo in range(0, n, ch):
+                c = min(ch, n - lo)
+                eng = engines.get(c)
+                if eng is None:
+                    eng = engines[c] = MosiEngine(model, 2 * c, self.steps, dev, ragged=ds.use_lengths,
+                                                  text_lengths=ds.text_lengths, classifier=False, backward=False)
+                    eng.lab = torch.empty(c, dtype=dc.label_dtype, device=dev)
+                bufs = ([("audio", eng.lens["a"]), ("video", eng.lens["v"])] if ds.use_lengths else []) + \
+                       ([("text", eng.text_lens)] if ds.text_lengths else [])
+                dc.gather(order[lo:lo + c], self.steps, {"audio": eng.A, "video": eng.V, "text": eng.X}, True, None,
+                          eng.lab, {m: buf[:c] for m, buf in bufs} or None, rows=2 * c)
+                for _, buf in bufs:
+                    buf[c:].copy_(buf[:c])  # a zero row runs exactly as long as its real row
+                eng._forward_encoders(sh, False)
+                self.emb[lo:lo + c, :hav].copy_(eng.fused[:c, :hav])
+                self.emb[lo:lo + c, hav:].copy_(eng.pooled[:c])
+                if self.per_sample_zero:
+                    self.zero[lo:lo + c, :hav].copy_(eng.fused[c:, :hav])
+                    self.zero[lo:lo + c, hav:].copy_(eng.pooled[c:])
+                elif lo == 0:
+                    self.zero[0, :hav].copy_(eng.fused[c, :hav])
+                    self.zero[0, hav:].copy_(eng.pooled[c])
+        torch.cuda.synchronize(dev)
+        self.fill_seconds = time.perf_counter() - t0
+        self.fills += 1
+        self._stamp = self._now()
+        return self
+
+
+class MosiCachedEngine(MosiEngine):
+    """``MosiEngine`` whose encoder half is a stand-in that reads a ``UttEmbeddingCache``: it owns ``fused``, ``fc_in``
+    and (a training engine) ``keeps[0]`` — no ``A`` / ``V`` / ``X``, ``lstm`` or ``conv_out`` buffer — and its
+    ``_forward_encoders`` is ONE ``tspm_utt_cache_rows`` launch (the cached LSTM embeddings into ``fused``, the cached
+    pooled features through the TextCNN's dropout into ``fc_in``, the labels) followed by the TextCNN's embedding Linear
+    (``_text_embed``).  Everything else — masks, classifier, loss, log, backward, clip — is ``MosiEngine``'s own code.
+    ``halves=1`` (``batch`` sample rows, with a classifier half): row b takes each modality from the cache or from the
+    zero rows by ``row_keep[b]`` (uint8 [batch][3], written before each run).  ``halves=2`` (``batch`` = 2B rows, no
+    classifier): the all-pattern layout ``MosiPatternEngine`` expands, the batch in rows [0, B), its zero rows in
+    [B, 2B).  ``rows`` (int64 [B]) are the batch's sample indices.  Refused unless all three encoders are frozen."""
+
+    def __init__(self, model: "UttFusionModel", batch: int, cache: UttEmbeddingCache, device, halves: int = 1, *,
+                 classifier: bool = True, backward: bool = True):
+        if _frozen_state(model)[0] != ALL_FROZEN:
+            raise L.TspmError("the cached UTT-Fusion steps need frozen encoders - all of netA, netV and netT: a trainable "
+                              "encoder's outputs change every step, so the cache cannot stand in for it")
+        if model.netT.hidden_size % 4:
+            raise L.TspmError("the cached UTT-Fusion steps move rows 16 bytes at a time: the TextCNN embd_size must be a "
+                              "multiple of 4")
+        self.cache, self.halves = cache, int(halves)
+        self.rows = torch.zeros(int(batch) // self.halves, dtype=torch.int64, device=device)
+        self.row_keep = (torch.ones(int(batch), 3, dtype=torch.uint8, device=device) if self.halves == 1 else None)
+        self.label_dst: Optional[torch.Tensor] = None  # halves == 2: the pattern engine's label buffer
+        super().__init__(model, batch, cache.steps, device, encoders=True, classifier=classifier, backward=backward)
+
+    def _plan_encoders(self) -> None:
+        """The stand-in's plan: the embedding Linear's input, nothing else."""
+        t = self.m.netT
+        self.C, self.nc = t.out_channels, 3 * t.out_channels
+        self.fc_in = torch.empty(self.B, self.nc, device=self.device, dtype=torch.float32)
+        self.lens = self.text_lens = None
+
+    def _plan_backward(self) -> None:
+        super()._plan_backward()
+        if not self.has_classifier:
+            del self.dfused  # nothing is trainable below the expansion: no adjoint is ever launched
+
+    def set_lengths(self, lengths) -> None:
+        if lengths is not None:
+            raise L.TspmError("MosiCachedEngine: the cache holds the lengths' effect already; no lengths are taken")
+
+    def _forward_encoders(self, sh: int, train: bool) -> None:
+        m, t, cache = self.m, self.m.netT, self.cache
+        tp = float(t.dropout.p)
+        use_keep = train and tp > 0
+        float_labels = cache.labels_all.dtype == torch.float32
+        dst = self.label_dst if self.halves == 2 else (self.labels_f if float_labels else self.labels)
+        d = L.UttCacheRowsDesc(batch=self.B // self.halves, halves=self.halves, w_audio=cache.ha, w_video=cache.hv,
+                               w_pool=cache.nc, ld_cache=cache.W, ld_av=self.E, ld_pool=self.nc, n_rows=cache.n,
+                               n_zero=cache.n_zero, label_bytes=4 if float_labels else 8,
+                               scale=(1.0 / (1.0 - tp) if tp < 1 else 0.0) if use_keep else 1.0)
+        d.emb, d.zero, d.rows = cache.emb.data_ptr(), cache.zero.data_ptr(), self.rows.data_ptr()
+        d.row_keep = L.ptr(self.row_keep)
+        if dst is not None:
+            d.labels_all, d.labels_out = cache.labels_all.data_ptr(), dst.data_ptr()
+        d.keep = self.keeps[0].data_ptr() if use_keep else None
+        d.av_out, d.pool_out = self.fused.data_ptr(), self.fc_in.data_ptr()
+        L.check(L.lib().tspm_utt_cache_rows(ctypes.byref(d), sh), "utt_cache_rows")
+        _text_embed(self, t, sh, self.fused.data_ptr() + (cache.ha + cache.hv) * 4, self.E)
+
+
+class MosiCachedPatternEngine(MosiPatternEngine):
+    """``MosiPatternEngine`` on a ``UttEmbeddingCache``: ``enc`` is a ``MosiCachedEngine(halves=2)`` at 2B rows in
+    place of the encoder half, ``cls`` the same classifier half at P*B rows; ``forward`` / ``backward`` /
+    ``_keep_masks`` / ``apply_keep_override`` are the parent's, so the mask layout is its own (``"text"`` [2B, nc],
+    ``"cls{j}"`` [P*B, w_j]).  The batch is ``rows`` (int64 [B] sample indices); there are no inputs and no lengths."""
+
+    def __init__(self, model: "UttFusionModel", batch: int, cache: UttEmbeddingCache, device, patterns=None,
+                 groups: Optional[Sequence[str]] = None, backward: bool = False):
+        self.cache = cache
+        super().__init__(model, batch, cache.steps, device, patterns, groups=groups, backward=backward)
+
+    def _build_enc(self, steps):
+        return MosiCachedEngine(self.m, 2 * self.B, self.cache, self.device, halves=2, classifier=False,
+                                backward=self.trainable)
+
+    def _plan_inputs(self) -> None:
+        """No inputs and no lengths: the batch is ``rows``, and the cache reader writes this engine's labels."""
+        self.rows = self.enc.rows
+        self.enc.label_dst = self.labels_f if self.cache.labels_all.dtype == torch.float32 else self.labels
+        self._len_bufs, self.lens, self.text_lens = [], None, None
+
+
+def _cache_for_step(who: str, model: "UttFusionModel", cache, regress) -> UttEmbeddingCache:
+    if not isinstance(cache, UttEmbeddingCache):
+        raise L.TspmError(f"{who}: cache is a UttEmbeddingCache (mosi_data.MOSI.embedding_cache(model))")
+    cache.check(model)
+    if (regress is not None) != (cache.labels_all.dtype == torch.float32):
+        raise L.TspmError(f"{who}: the regression head goes with float32 labels (regression_labels), cross-entropy with "
+                          f"int64 class labels; the cache's corpus carries {cache.labels_all.dtype}")
+    return cache
+
+
+def _load_cached_batch(st, rows: torch.Tensor, row_keep, groups) -> None:
+    """A cached step's batch into its engine's index buffers (device-to-device, outside any captured graph)."""
+    e = st.eng
+    if not torch.is_tensor(rows) or rows.dtype != torch.int64 or rows.numel() != st.N:
+        raise L.TspmError(f"{type(st).__name__}: rows is an int64 tensor of {st.N} sample indices")
+    e.rows.copy_(rows.reshape(-1), non_blocking=True)
+    if st.per_sample:
+        if row_keep is None or groups is None:
+            raise L.TspmError(f"{type(st).__name__}(per_sample=True): step(rows, row_keep, groups) - uint8 [B][3] keep "
+                              f"flags (audio, video, text) and int32 [B] group ids")
+        e.row_keep.copy_(row_keep.reshape(st.N, 3).to(torch.uint8), non_blocking=True)
+        e.groups.copy_(groups.reshape(-1).to(torch.int32), non_blocking=True)
+    elif row_keep is not None or groups is not None:
+        raise L.TspmError(f"{type(st).__name__}: row_keep / groups go with per_sample=True (this step runs every pattern)")
+
+
+class FusedMosiCachedStep(FusedMosiPatternStep):
+    """The UTT-Fusion train step of the head stage on a ``UttEmbeddingCache`` (all three encoders frozen): the batch is
+    ``rows``, int64 [B] sample indices, and no encoder runs.  EVERY PATTERN (default; ``patterns``: a subset) is
+    ``FusedMosiPatternStep``'s schedule with its ``_forward_encoders`` replaced — the two mask draws,
+    ``tspm_utt_cache_rows`` (``halves = 2``), the embedding Linear over 2B rows, ``tspm_pattern_expand``, the
+    classifier, the loss, ``tspm_classify_update`` or ``head_regress``, the classifier's backward with no ``dx`` at
+    layer 0, clip and Adam — with its mask layout (``keep_override``: ``"text"`` [2B, nc], ``"cls{j}"`` [P*B, w_j]).
+    ``per_sample=True`` is ``FusedMosiStep``'s schedule and mask layout at B rows: ``tspm_utt_cache_rows`` (``halves =
+    1``) writes each row under its own ``row_keep`` flags straight into the classifier half's ``fused``;
+    ``step(rows, row_keep, groups)`` takes uint8 [B][3] flags (audio, video, text) and int32 [B] group ids.  With the
+    same mask bytes either form is bitwise the uncached step whose encoder leg returns the cache's rows.  Refused, with
+    the reason: a trainable encoder, more than one ``FusedAdam`` group, ``allreduce``, a non-``FusedAdam`` optimizer, a
+    cache that is stale, another model's or (a regression model on int64 labels, or the reverse) of the wrong labels.
+    ``step`` returns ``{"loss", "logits"}``, logits [P, B, C] or [B, C]."""
+
+    def __init__(self, model: "UttFusionModel", optimizer: FusedAdam, loss_functions, batch: int, cache, patterns=None,
+                 per_sample: bool = False, use_graph: bool = True, allreduce=None):
+        if allreduce is not None:
+            raise L.TspmError("FusedMosiCachedStep: allreduce (data parallelism) is not built for the cached head stage")
+        if not isinstance(optimizer, FusedAdam):
+            raise L.TspmError("FusedMosiCachedStep needs FusedAdam (the flat gradient buffer the kernels write)")
+        if frozen_encoders(model) != ALL_FROZEN:
+            raise L.TspmError("FusedMosiCachedStep needs frozen encoders - all of netA, netV and netT; with a trainable "
+                              "encoder take FusedMosiStep / FusedMosiPatternStep")
+        if len(optimizer.flat_groups()) > 1:
+            raise L.TspmError("FusedMosiCachedStep: one FusedAdam parameter group (only the classifier trains)")
+        self.per_sample = bool(per_sample)
+        if self.per_sample and patterns is not None:
+            raise L.TspmError("FusedMosiCachedStep: patterns go with the every-pattern form, not per_sample=True")
+        self.patterns = None if self.per_sample else norm_patterns(patterns)
+        self.cache = _cache_for_step("FusedMosiCachedStep", model, cache, _regress_mode(model, loss_functions))
+        FusedMosiStep.__init__(self, model, optimizer, loss_functions, int(batch), cache.steps, use_graph=use_graph)
+
+    def _head_rows(self, batch: int) -> int:
+        return batch if self.per_sample else len(self.patterns) * batch
+
+    def _build_engine(self, dev, steps):
+        if self.per_sample:
+            return MosiCachedEngine(self.model, self.N, self.cache, dev, halves=1)
+        return MosiCachedPatternEngine(self.model, self.N, self.cache, dev, self.patterns, backward=True)
+
+    def _fwd_bwd(self) -> None:
+        (FusedMosiStep if self.per_sample else FusedMosiPatternStep)._fwd_bwd(self)
+
+    def _bind_log(self) -> tuple:
+        key = (FusedMosiStep if self.per_sample else FusedMosiPatternStep)._bind_log(self)
+        return key + (self.cache.emb.data_ptr(), self.cache.zero.data_ptr())
+
+    def step(self, rows: torch.Tensor, row_keep: Optional[torch.Tensor] = None,
+             groups: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+        _load_cached_batch(self, rows, row_keep, groups)
+        self.run()
+        e = self.eng
+        return {"loss": e.loss if self.per_sample else e.cls.loss, "logits": e.logits}
+
+    def run(self) -> None:
+        self.cache.check(self.model)
+        super().run()
+
+
+class FusedMosiCachedEvalStep(FusedMosiPatternEvalStep):
+    """``FusedMosiPatternEvalStep`` (default; ``patterns``: a subset) or, with ``per_sample=True``,
+    ``FusedMosiEvalStep`` on a ``UttEmbeddingCache``: the same loss and log launches, hence the same loss entries in the
+    same order and the same counts, behind ``tspm_utt_cache_rows`` and the embedding Linear in place of the encoders; no
+    dropout.  ``step(rows[, row_keep, groups])`` as ``FusedMosiCachedStep.step``; the loss returned is the per-pattern
+    ``losses`` [P], or the batch's [1]."""
+
+    def __init__(self, model: "UttFusionModel", loss_functions, batch: int, cache, log, patterns=None,
+                 per_sample: bool = False, use_graph: bool = True):
+        self.per_sample = bool(per_sample)
+        if self.per_sample and patterns is not None:
+            raise L.TspmError("FusedMosiCachedEvalStep: patterns go with the every-pattern form, not per_sample=True")
+        self.patterns = None if self.per_sample else norm_patterns(patterns)
+        self.cache = _cache_for_step("FusedMosiCachedEvalStep", model, cache, _regress_mode(model, loss_functions))
+        FusedMosiEvalStep.__init__(self, model, loss_functions, int(batch), cache.steps, log, use_graph=use_graph)
+
+    def _build_engine(self, dev, steps):
+        if self.per_sample:
+            return MosiCachedEngine(self.model, self.N, self.cache, dev, halves=1, backward=False)
+        return MosiCachedPatternEngine(self.model, self.N, self.cache, dev, self.patterns)
+
+    def _bind_log(self) -> tuple:
+        key = (FusedMosiEvalStep if self.per_sample else FusedMosiPatternEvalStep)._bind_log(self)
+        return key + (self.cache.emb.data_ptr(), self.cache.zero.data_ptr())
+
+    def _all(self) -> None:
+        (FusedMosiEvalStep if self.per_sample else FusedMosiPatternEvalStep)._all(self)
+
+    def step(self, rows: torch.Tensor, row_keep: Optional[torch.Tensor] = None,
+             groups: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+        _load_cached_batch(self, rows, row_keep, groups)
+        self.run()
+        e = self.eng
+        return {"loss": e.loss if self.per_sample else e.losses, "logits": e.logits}
+
+    def run(self) -> None:
+        self.cache.check(self.model)
+        super().run()
+
+
+# ------------------------------------------------------------------------------------------------
 # the model
 # ------------------------------------------------------------------------------------------------
 def _modality(batch: Dict[Any, Any], name: str):
@@ -1950,10 +2331,12 @@ class UttFusionModel(nn.Module):
         self._steps: Dict[Any, FusedMosiStep] = {}
         self._fwd_generation = 0
         self._flag_cache = None
+        self._engines_generation = 0  # bumped whenever the engines are dropped (a UttEmbeddingCache's stamp reads it)
 
     def _apply(self, fn, *args, **kwargs):
         out = super()._apply(fn, *args, **kwargs)
         self._engines, self._steps, self._flag_cache = {}, {}, None
+        self._engines_generation = getattr(self, "_engines_generation", 0) + 1
         return out
 
     def flag_state(self):

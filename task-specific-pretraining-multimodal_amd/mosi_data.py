@@ -472,7 +472,8 @@ class MOSI(torch.utils.data.Dataset):
     def device_loader(self, batch_size: int, shuffle: bool = False, drop_last: bool = False,
                       generator: Optional[torch.Generator] = None, step_for=None,
                       pad_to: int = 0, group_patterns: Optional[bool] = None,
-                      fuse_patterns: bool = False, all_patterns: bool = False) -> Iterator[Dict[str, Any]]:
+                      fuse_patterns: bool = False, all_patterns: bool = False,
+                      ids_only: bool = False) -> Iterator[Dict[str, Any]]:
         """One epoch of batches gathered on device.  ``step_for(B, T) -> FusedMosiStep`` (or
         ``FusedMosiEvalStep``): gather each batch time-major straight into that step's input buffers.
         ``pad_to``: pad every batch to at least this many steps (the aligned length, e.g. 50 for aligned_50:
@@ -491,7 +492,16 @@ class MOSI(torch.utils.data.Dataset):
         ``all_patterns`` (the multimodal train split only; not with ``fuse_patterns``): the train form of the same — each
         sample ONCE per epoch, unmasked, in the loader's usual (shuffled) order, in batches that carry ``"patterns"`` and
         ``"all_patterns": True`` and neither ``pattern_name`` nor ``fused_patterns``; ``step_for(B, T)`` then returns a
-        ``FusedMosiPatternStep``, which trains every pattern of the batch in one step."""
+        ``FusedMosiPatternStep``, which trains every pattern of the batch in one step.
+        ``ids_only`` (the multimodal target only; for the steps that read an :meth:`embedding_cache`): the same order,
+        the same RNG draws and the same number of batches, but no input tensor is gathered and ``step_for`` is not used
+        — every batch carries ``"ids_only": True``, ``"rows"`` (int64 [b] sample indices on the device), ``"steps"``
+        (the split's corpus-wide padded lengths under ``pad_to``: the cache's), ``"dataset"`` and ``"pad_to"``; an
+        ``all_patterns`` / ``fuse_patterns`` batch adds ``"patterns"`` and its flag as above, a plain train batch
+        ``"row_keep"`` (uint8 [b][3] on the device: each row's (audio, video, text) keep flags) and ``"pattern_name"``,
+        and a grouped valid / test batch is ``{pattern: such a sub-batch}``."""
+        if ids_only:
+            self._check_ids_only()
         if all_patterns:
             self._check_all_patterns(fuse_patterns)
         if fuse_patterns or all_patterns:
@@ -503,6 +513,10 @@ class MOSI(torch.utils.data.Dataset):
                 rows = order[s:s + batch_size].astype(np.int64)
                 if drop_last and len(rows) < batch_size:
                     break
+                if ids_only:
+                    yield {**self._collate_ids(rows, None, pad_to), "patterns": list(self.selected_patterns),
+                           ("all_patterns" if all_patterns else "fused_patterns"): True}
+                    continue
                 step = step_for(len(rows), self.device_corpus.batch_steps(rows, pad_to)) if step_for is not None else None
                 yield (self._collate_all if all_patterns else self._collate_fused)(rows, step, pad_to)
             return
@@ -520,7 +534,9 @@ class MOSI(torch.utils.data.Dataset):
             out = {}
             for name, sel in parts:
                 r, q = rows[sel], pid[sel]
-                if step_for is not None:
+                if ids_only:
+                    out[name] = self._collate_ids(r, q, pad_to)
+                elif step_for is not None:
                     want = self._want()
                     t = (self.device_corpus.batch_steps(r, pad_to) if len(want) > 1
                          else self.device_corpus.steps_for(r, pad_of(pad_to, want[0]), want))
@@ -535,15 +551,72 @@ class MOSI(torch.utils.data.Dataset):
 
     def loader(self, batch_size: int, shuffle: bool = False, drop_last: bool = False, seed: Optional[int] = None,
                step_for=None, pad_to: int = 0, group_patterns: Optional[bool] = None,
-               fuse_patterns: bool = False, all_patterns: bool = False) -> "MosiDeviceLoader":
+               fuse_patterns: bool = False, all_patterns: bool = False, ids_only: bool = False) -> "MosiDeviceLoader":
         """A re-iterable epoch loader (one ``device_loader`` pass per ``iter``), as a DataLoader is.  ``fuse_patterns`` /
-        ``all_patterns``: see ``device_loader`` (refused here already for a dataset they are not for)."""
+        ``all_patterns`` / ``ids_only``: see ``device_loader`` (refused here already for a dataset they are not for)."""
+        if ids_only:
+            self._check_ids_only()
         if all_patterns:
             self._check_all_patterns(fuse_patterns)
         if fuse_patterns:
             self._check_fuse_patterns()
         return MosiDeviceLoader(self, batch_size, shuffle, drop_last, seed, step_for, pad_to, group_patterns,
-                                fuse_patterns, all_patterns)
+                                fuse_patterns, all_patterns, ids_only)
+
+    # -- the frozen encoders' outputs of this split, computed once ---------------------------------------
+    def _check_ids_only(self, what: str = "ids_only=True") -> None:
+        if self.target_modality != "multimodal":
+            raise L.TspmError(f"{what} is for the multimodal target (the cache holds all three encoders' outputs); this "
+                              f"dataset's target_modality is {self.target_modality!r}")
+
+    def corpus_steps(self, pad_to=0):
+        """The split's corpus-wide padded lengths under ``pad_to`` — ``batch_steps`` of every sample at once: the
+        ``steps`` an :meth:`embedding_cache` is built for and an ``ids_only`` batch carries.  A constant of (corpus,
+        ``pad_to``), computed once per ``pad_to``: every ``ids_only`` batch asks for it."""
+        from .mosi import norm_steps
+        memo = self.__dict__.setdefault("_corpus_steps", {})
+        key = repr(pad_to)
+        if key not in memo:
+            memo[key] = norm_steps(self.device_corpus.batch_steps(np.arange(self.num_samples), pad_to))
+        return memo[key]
+
+    def _collate_ids(self, rows: np.ndarray, pid: Optional[np.ndarray], pad_to) -> Dict[str, Any]:
+        """An ``ids_only`` batch: the sample indices on the device and, with ``pid`` (one pattern per row), the rows'
+        keep flags and pattern names.  Nothing is gathered."""
+        out = {"ids_only": True, "rows": torch.from_numpy(np.ascontiguousarray(rows, dtype=np.int64)).to(self.device),
+               "steps": self.corpus_steps(pad_to), "dataset": self, "pad_to": pad_to}
+        if pid is not None:
+            k = self._keep[[PATTERNS.index(self.selected_patterns[p]) for p in pid]]
+            out["row_keep"] = (k != 0).to(torch.uint8).contiguous().to(self.device)
+            out["pattern_name"] = [self.selected_patterns[p] for p in pid]
+        return out
+
+    def embedding_cache(self, model, pad_to=0, chunk: Optional[int] = None, refresh: bool = False):
+        """This split's ``mosi.UttEmbeddingCache`` for ``model`` — one per (model, steps), built on first call: the
+        three FROZEN encoders' outputs of every sample (the LSTM embeddings and the TextCNN's pooled features before its
+        dropout) and of the zeroed inputs, for ``steps`` = :meth:`corpus_steps` of ``pad_to`` (without ``use_lengths``
+        an embedding depends on the padded length, so the cache is that of the uncached loader under a ``pad_to`` that
+        covers the corpus).  The fill runs the encoders once over the device corpus in sample order, in chunks of
+        ``chunk`` rows (128 for a new cache; an existing cache keeps its own unless one is given); ``refresh=True``
+        fills an existing cache again.  Refused unless all three encoders are frozen, and for a single-modality
+        target.  A cache made stale (a ``requires_grad`` flag, ``load_state_dict``, ``.to()``) is returned as it is and
+        refused by the step that reads it until ``refresh()``; weights written through raw pointers cannot be detected,
+        so whoever changes frozen weights that way refreshes."""
+        import weakref
+        from .mosi import UttEmbeddingCache
+        self._check_ids_only("embedding_cache")
+        steps = self.corpus_steps(pad_to)
+        caches = self.__dict__.setdefault("_emb_caches", weakref.WeakKeyDictionary())  # gone with their models
+        table = caches.setdefault(model, {})
+        c = table.get(steps)
+        if c is None:
+            c = table[steps] = UttEmbeddingCache(model, self, steps, 128 if chunk is None else chunk)
+        else:
+            if chunk is not None:
+                c.chunk = int(chunk)
+            if refresh:
+                c.refresh()
+        return c
 
     def get_split(self) -> str:
         return self.split
@@ -570,11 +643,13 @@ class MosiDeviceLoader:
     (the harness points it at its own train / eval steps)."""
 
     def __init__(self, ds: MOSI, batch_size: int, shuffle: bool, drop_last: bool, seed: Optional[int], step_for,
-                 pad_to: int, group_patterns: Optional[bool], fuse_patterns: bool = False, all_patterns: bool = False):
+                 pad_to: int, group_patterns: Optional[bool], fuse_patterns: bool = False, all_patterns: bool = False,
+                 ids_only: bool = False):
         self.ds, self.batch_size, self.shuffle, self.drop_last = ds, batch_size, shuffle, drop_last
         self.seed, self.step_for, self.pad_to, self.group_patterns = seed, step_for, pad_to, group_patterns
         self.fuse_patterns = bool(fuse_patterns)
         self.all_patterns = bool(all_patterns)
+        self.ids_only = bool(ids_only)
         self.epoch = 0
 
     def __len__(self) -> int:
@@ -588,4 +663,4 @@ class MosiDeviceLoader:
             gen.manual_seed((self.seed if self.seed is not None else 0) + self.epoch)
         self.epoch += 1
         return self.ds.device_loader(self.batch_size, self.shuffle, self.drop_last, gen, self.step_for, self.pad_to,
-                                     self.group_patterns, self.fuse_patterns, self.all_patterns)
+                                     self.group_patterns, self.fuse_patterns, self.all_patterns, self.ids_only)
